@@ -13,7 +13,12 @@ per-GPU batch (weak scaling) on its own shard of global sample indices and the m
 with ONE RCCL all-reduce per step.  torch.distributed (gloo, CPU) is used only as the launcher's
 rendezvous/barrier; no torch.cuda object is ever created - the compute path is ctypes -> C ABI -> HIP.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the line (`value`,
+`ms_per_step`, and the roofline of the dominant pass from the timed steps' own HIP events).  `--full` adds what takes runs
+of its own: the per-kernel timing steps behind the timed region, the f32-input-MFMA engine, the oracle's parity check of
+the last timed step, the CPU baseline and, with several ranks, the sharded config-5 leg.  `--dump-outputs DIR` writes
+what the last timed step computed (moments, samples, local energies) as DIR/<name>.npy; with several ranks, rank 0 writes
+the global moments and its own shard.
 """
 import argparse
 import json
@@ -209,12 +214,50 @@ PARITY_SAMPLES = {"cfg1": 500, "cfg2": 10000, "cfg3": 2048, "cfg4": 256, "cfg5":
                   "cfg2_parity": 256, "cfg2_l2": 256, "cfg2_l3": 192, "cfg3_l2": 512}
 
 
-def parity_leg(workload, wl, wf, prm, couplings, step_index, offset, timed_moments):
-    """Validates the timed path's own output: the LAST timed step is run once more with its samples and local energies
-    returned (same seed / step / offset -> the same batch; its moments must reproduce the timed step's bit for bit), and
-    the oracle scores a spread subset (config 2: all) of that very sample matrix."""
+def last_step_outputs(wf, wl, couplings, step_index, offset, reduce_moments):
+    """The LAST timed step run once more with its samples and local energies returned (same seed / step / offset -> the
+    same batch; its moments must reproduce the timed step's bit for bit).  Every rank calls it: the moments are all-reduced
+    as in the timed steps."""
+    out = wf.vmc_step(wl["ns"], seed=111, step=step_index, couplings=couplings, sample_offset=offset, want_samples=True, want_eloc=True)
+    out["moments"] = reduce_moments(wf, out["moments"])
+    return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, out, timed_moments, limit=DUMP_LIMIT_BYTES):
+    """What the last timed step computed, as float32 / float64 .npy files under `dirname`: `moments` (sum E, sum E^2, n,
+    sum Im E; what the timed step returned), `samples` (0/1 spins, exact in float32) and `eloc` (float64; the complex RNN's
+    complex64 local energies as `eloc_real` / `eloc_imag` in float32).  If the batch exceeds `limit` bytes, a fixed
+    (RandomState(0)) subset of its rows is written, sorted, and `sample_rows` holds their indices."""
+    samples = np.asarray(out["samples"])
+    eloc = np.asarray(out["eloc"])
+    per_row = int(np.prod(samples.shape[1:], dtype=np.int64)) * 4 + 8 + 8      # spins, local energy, row index
+    ns = samples.shape[0]
+    keep = max(1, (limit - 4096) // per_row)
+    arrays = {"moments": np.asarray(timed_moments, dtype=np.float64)}
+    if ns > keep:
+        rows = np.sort(np.random.RandomState(0).choice(ns, keep, replace=False))
+        samples, eloc = samples[rows], eloc[rows]
+        arrays["sample_rows"] = rows.astype(np.float64)
+    arrays["samples"] = samples.astype(np.float32)
+    if np.iscomplexobj(eloc):
+        arrays["eloc_real"] = np.ascontiguousarray(eloc.real, dtype=np.float32)
+        arrays["eloc_imag"] = np.ascontiguousarray(eloc.imag, dtype=np.float32)
+    else:
+        arrays["eloc"] = eloc.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return {"dir": dirname, "files": sorted(n + ".npy" for n in arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "rows": int(samples.shape[0]), "of": int(ns)}
+
+
+def parity_leg(workload, wl, prm, couplings, out, step_index, timed_moments):
+    """Validates the timed path's own output: the oracle scores a spread subset (config 2: all) of the sample matrix of the
+    last timed step (`out`, from last_step_outputs)."""
     ns, N = wl["ns"], wl["N"]
-    out = wf.vmc_step(ns, seed=111, step=step_index, couplings=couplings, sample_offset=offset, want_samples=True, want_eloc=True)
     n = min(ns, PARITY_SAMPLES.get(workload, 256))
     sub = np.unique(np.linspace(0, ns - 1, n).astype(np.int64))
     t0 = time.perf_counter()
@@ -360,8 +403,9 @@ def assemble_record(*, args, wl, world, dt, step_ms, per_rank_ms, infos, moments
                      "mfma_flops_issued_per_launch": issued,
                      "launches_per_step": flip["launches"] / max(args.steps, 1),
                      "avg_launch_ms": flip_ms,
-                     "base_pass_ms": base["total_ms"] / max(base["launches"], 1),
-                     "assembly_ms": asm["total_ms"] / 3.0},            # per step (the three extra steps behind the timed region)
+                     # --full only: per step, from the three extra steps behind the timed region
+                     "base_pass_ms": base["total_ms"] / max(base["launches"], 1) if base else None,
+                     "assembly_ms": asm["total_ms"] / 3.0 if asm else None},
     }
     if cfg5 is not None:
         rec["cfg5_sharded"] = cfg5
@@ -378,6 +422,9 @@ def exit_status(rec, allow_fallback=False):
                 par.get("max_abs_dE_per_site", float("nan")), par.get("d_meanE_per_site", float("nan")), par.get("tolerance_per_site", 0.0))
         if not par.get("reproduces_timed_step"):
             return 2, "parity leg: the re-run of the last timed step did not reproduce its moments bit for bit"
+    dump = rec.get("dump_outputs")
+    if dump is not None and not dump.get("reproduces_timed_step"):
+        return 2, "--dump-outputs: the re-run of the last timed step did not reproduce its moments bit for bit"
     if rec.get("transport_fallback") and not allow_fallback:
         return 3, "RCCL communicator could not be created; the moments went over gloo (pass --allow-fallback to accept): " + rec["transport_fallback"]
     if rec.get("n_gpus", 1) > 1 and rec.get("rccl_nranks") is not None and rec["rccl_nranks"] != rec["n_gpus"]:
@@ -426,13 +473,18 @@ def main():
     ap.add_argument("--numsamples", type=int, default=0, help="per-GPU batch override")
     ap.add_argument("--weights", default="init", choices=("init", "trained"),
                     help="init: glorot-uniform as initialised; trained: kernels x 3 (sharper conditionals)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt-engine", action="store_true", help="skip the extra f32-input-MFMA timing")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle check of the last timed step's output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: per-kernel timing steps, the f32-input-MFMA engine, the oracle's "
+                         "parity check, the CPU baseline and (several ranks) the sharded config-5 leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-alt-engine", action="store_true", help="--full: skip the extra f32-input-MFMA timing")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the oracle check of the last timed step's output")
     ap.add_argument("--train", type=int, default=0, metavar="K",
                     help="also time K training iterations' gradient (rnnwf_vmc_gradient) behind the timed region")
     ap.add_argument("--no-cfg5", action="store_true",
-                    help="multi-GPU runs: skip the extra north-star config 5 leg (N=200, 100 units, 32768 samples per GPU)")
+                    help="--full, multi-GPU runs: skip the extra north-star config 5 leg (N=200, 100 units, 32768 samples per GPU)")
     ap.add_argument("--transport", default="rccl", choices=("rccl", "gloo"),
                     help="all-reduce of the moments: RCCL over xGMI (default) or the launcher's gloo group (rehearsal of "
                          "the multi-rank control flow on a box whose GPUs cannot host one rank each)")
@@ -441,6 +493,8 @@ def main():
                     help="multi-GPU runs: exit 0 even if the RCCL communicator could not be created and the moments went over gloo "
                          "(without this flag such a run exits 3: a scaling number that silently measured gloo is worse than none)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -533,11 +587,15 @@ def main():
     step_ms = np.diff(marks) * 1e3
     last_step = args.warmup + args.steps - 1
     flip = wf.timing_get(1)
-    wf.timing_enable(1)
-    wf.timing_reset()
-    for it in range(3):
-        step(args.warmup + args.steps + it)
-    barrier(wf)
+    base = asm = None
+    if args.full:
+        wf.timing_enable(1)
+        wf.timing_reset()
+        for it in range(3):
+            step(args.warmup + args.steps + it)
+        barrier(wf)
+        base = wf.timing_get(0)
+        asm = wf.timing_get(2)
 
     def max_over_ranks(x):
         if dist is None:
@@ -561,10 +619,8 @@ def main():
         infos = [None] * world
         dist.all_gather_object(infos, info)
 
-    base = wf.timing_get(0)
-    asm = wf.timing_get(2)
     cfg5 = None
-    if world > 1 and not args.no_cfg5 and args.workload == "cfg2" and not args.numsamples:
+    if args.full and world > 1 and not args.no_cfg5 and args.workload == "cfg2" and not args.numsamples:
         def factory(w5):
             w5["weights"] = args.weights
             made = make_wavefunction(w5, device=device)
@@ -577,18 +633,26 @@ def main():
                 "global_numsamples": world * wl5["ns"], "mean_E": m5[0] / m5[2],
                 "note": "north-star config 5 (sharded over the ranks of this job, one RCCL all-reduce per step), "
                         "reported beside `value`, which stays on the metric's own workload so that it is comparable across N"}
+    want_parity = args.full and world == 1 and not args.no_parity
+    last = None
+    if args.dump_outputs or want_parity:        # every rank: the re-run all-reduces its moments like the timed steps
+        last = last_step_outputs(wf, wl, couplings, last_step, offset, reduce_moments)
     rc = 0
     if rank == 0:
         rec = assemble_record(args=args, wl=wl, world=world, dt=dt, step_ms=step_ms, per_rank_ms=per_rank_ms, infos=infos, moments=m,
                               flip=flip, base=base, asm=asm, engine=wf.engine_name(), transport_fallback=transport_note["fallback"],
                               cfg5=cfg5, traffic=load_traffic(args.workload), last_step=last_step)
-        if rec["roofline"]["engine_is_bf16x3"] and world == 1 and not args.no_alt_engine:
+        if args.dump_outputs:
+            rec["dump_outputs"] = dict(dump_outputs(args.dump_outputs, last, m), step=int(last_step), rank=rank,
+                                       reproduces_timed_step=bool(np.array_equal(np.asarray(last["moments"]), np.asarray(m))))
+        if args.full and rec["roofline"]["engine_is_bf16x3"] and world == 1 and not args.no_alt_engine:
             rec["f32mfma_engine"] = alt_engine_run(wl, couplings, args.warmup, max(args.steps // 2, 3), last_step)
         # the oracle as CHECKER of the timed path's own output (outside the timed region, like the cpu_baseline leg)
-        rec["parity"] = parity_leg(args.workload, wl, wf, prm, couplings, last_step, offset, m) if world == 1 and not args.no_parity else None
+        rec["parity"] = parity_leg(args.workload, wl, prm, couplings, last, last_step, m) if want_parity else None
         if args.train and world == 1:
             rec["train"] = train_leg(wl, wf, prm, couplings, args.train, offset)
-        if not args.no_cpu_baseline and world == 1 and wl["kind"] == "tfim1d" and wl.get("layers", 1) == 1 and not wl.get("parity"):
+        if args.full and not args.no_cpu_baseline and world == 1 and wl["kind"] == "tfim1d" and wl.get("layers", 1) == 1 \
+                and not wl.get("parity"):
             rec["cpu_baseline"] = cpu_baseline(wl, prm)
         else:
             rec["cpu_baseline"] = None

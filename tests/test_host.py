@@ -430,6 +430,31 @@ def test_bench_rank0_record_assembles_for_every_rank_count(world):
     assert bench.exit_status(d) == (0, None)
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: float32 / float64 files only; a batch over the byte limit is cut to a fixed, sorted subset of rows
+    whose indices are written beside it; the complex RNN's local energies as real and imaginary parts."""
+    import bench
+    rng = np.random.RandomState(1)
+    s = rng.randint(0, 2, (300, 12)).astype(np.int32)
+    e = rng.randn(300)
+    m = np.array([e.sum(), (e * e).sum(), 300.0, 0.0])
+    info = bench.dump_outputs(str(tmp_path / "a"), {"samples": s, "eloc": e, "moments": m}, m)
+    got = {f: np.load(tmp_path / "a" / f) for f in info["files"]}
+    assert sorted(got) == ["eloc.npy", "moments.npy", "samples.npy"] and info["rows"] == info["of"] == 300
+    assert got["samples.npy"].dtype == np.float32 and np.array_equal(got["samples.npy"], s)
+    assert got["eloc.npy"].dtype == np.float64 and np.array_equal(got["eloc.npy"], e) and np.array_equal(got["moments.npy"], m)
+    ec = (rng.randn(300) + 1j * rng.randn(300)).astype(np.complex64)
+    limit = 4096 + 100 * (12 * 4 + 16)
+    infos = [bench.dump_outputs(str(tmp_path / k), {"samples": s, "eloc": ec}, m, limit=limit) for k in ("b", "c")]
+    assert infos[0]["rows"] == 100 and infos[0]["bytes"] <= limit
+    rows = np.load(tmp_path / "b" / "sample_rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "sample_rows.npy")) and np.all(np.diff(rows) > 0)
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "b" / "samples.npy"), s[r])
+    assert np.load(tmp_path / "b" / "eloc_real.npy").dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / "b" / "eloc_real.npy") + 1j * np.load(tmp_path / "b" / "eloc_imag.npy"), ec[r])
+
+
 def test_bench_exit_status_is_nonzero_on_red_parity_or_silent_fallback():
     """a red parity leg or a gloo fallback must not hand the driver an rc-0 number."""
     import bench

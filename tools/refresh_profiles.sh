@@ -13,18 +13,18 @@ if [ $part = all ] || [ $part = bench ]; then
 for w in cfg1 cfg2 cfg3 cfg4 cfg5; do
   extra="--no-cpu-baseline"; [ $w = cfg2 ] && extra=""
   steps=20; [ $w = cfg5 ] && steps=5; [ $w = cfg4 ] && steps=10
-  timeout -k 10 300 python bench.py --workload $w --steps $steps --warmup 3 $extra > $out/${tag}_bench_$w.json 2> $out/${tag}_bench_$w.err || { echo "bench $w failed"; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload $w --steps $steps --warmup 3 $extra > $out/${tag}_bench_$w.json 2> $out/${tag}_bench_$w.err || { echo "bench $w failed"; exit 1; }
   echo "bench $w done"
 done
 # SURVEY 8 rows f4 / f1 "at speed": the parity-symmetric model, stacked layers, and the gradient leg (--train) of every config
 for w in cfg2_parity cfg2_l2 cfg2_l3 cfg3_l2; do
-  timeout -k 10 300 python bench.py --workload $w --steps 10 --warmup 2 --train 5 > $out/${tag}_bench_$w.json 2> $out/${tag}_bench_$w.err || { echo "bench $w failed"; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload $w --steps 10 --warmup 2 --train 5 > $out/${tag}_bench_$w.json 2> $out/${tag}_bench_$w.err || { echo "bench $w failed"; exit 1; }
 done
 for w in cfg2 cfg3 cfg4 cfg5; do
   timeout -k 10 300 python bench.py --workload $w --steps 5 --warmup 2 --train 10 --no-cpu-baseline --no-alt-engine --no-parity > $out/${tag}_train_$w.json 2> $out/${tag}_train_$w.err || { echo "train $w failed"; exit 1; }
 done
 for w in cfg2 cfg3; do
-  RNNWF_ENGINE=f32 timeout -k 10 200 python bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline --no-alt-engine > $out/${tag}_bench_${w}_engine_f32.json 2>/dev/null || exit 1
+  RNNWF_ENGINE=f32 timeout -k 10 200 python bench.py --full --workload $w --steps 10 --warmup 2 --no-cpu-baseline --no-alt-engine > $out/${tag}_bench_${w}_engine_f32.json 2>/dev/null || exit 1
 done
 echo "bench part done"
 fi
