@@ -47,7 +47,9 @@ typedef enum {
     RNNWF_MODEL_GRU1D_PARITY = 1,/* 1DTFIM/RNNwavefunction_paritysym.py:7-145 same sampler, symmetrised P   */
     RNNWF_MODEL_CRNN_U1 = 2,     /* J1J2/ComplexRNNwavefunction.py:15-169    cRNN, f32/complex64, U(1) mask */
     RNNWF_MODEL_GRU1D_F64 = 3,   /* 2DTFIM_1DRNN/RNNwavefunction.py:8-130    pRNN over a raster path, f64   */
-    RNNWF_MODEL_MDRNN2D = 4      /* 2DTFIM_2DRNN/RNNwavefunction.py:5-200 + MDRNNcell.py:6-66, f64          */
+    RNNWF_MODEL_MDRNN2D = 4,     /* 2DTFIM_2DRNN/RNNwavefunction.py:5-200 + MDRNNcell.py:6-66, f64          */
+    RNNWF_MODEL_LSTM1D_F64 = 5   /* 2DTFIM_1DRNN/RNNwavefunction.py:9,37 with its default cell=LSTMCell:    */
+                                 /* one LSTM layer over the raster path, f64; evaluation only (no gradient) */
 } rnnwf_model;
 
 typedef enum { RNNWF_F32 = 0, RNNWF_F64 = 1 } rnnwf_dtype;
@@ -63,7 +65,8 @@ typedef struct {
                                       /* <= 100 units, float64: <= 68) for the GRU models          */
     int32_t units[RNNWF_MAX_LAYERS];  /* units[n]: one layer <= 260 (float GRU models; above 100 the */
                                       /* weight image is read through L2), <= 100 (float64 GRU;   */
-                                      /* above 68 likewise), <= 84 (2D RNN)                       */
+                                      /* above 68 likewise), <= 84 (2D RNN), <= 68 (LSTM, one     */
+                                      /* layer only)                                              */
     int32_t device;                   /* HIP device ordinal                                       */
     int32_t reserved[6];
 } rnnwf_config;
@@ -134,7 +137,7 @@ int rnnwf_tfim_eloc(rnnwf_handle* h, const int32_t* samples, int64_t numsamples,
 
 /* rnnwf_tfim2d_eloc <- Ising2D_local_energies(Jz, Bx, Nx, Ny, samples, ...)
  *   (2DTFIM_2DRNN/Training2DRNN_2DTFIM.py:13-83 for RNNWF_MODEL_MDRNN2D, samples (ns, Nx, Ny);
- *    2DTFIM_1DRNN/Training1DRNN_2DTFIM.py:13-81 for RNNWF_MODEL_GRU1D_F64, samples (ns, Nx*Ny)).
+ *    2DTFIM_1DRNN/Training1DRNN_2DTFIM.py:13-81 for RNNWF_MODEL_GRU1D_F64 and RNNWF_MODEL_LSTM1D_F64, samples (ns, Nx*Ny)).
  *   Jz: (Nx, Ny) f64 row-major.                                                                */
 int rnnwf_tfim2d_eloc(rnnwf_handle* h, const int32_t* samples, int64_t numsamples, const double* Jz, double Bx,
                       double* eloc, double* log_probs);
@@ -164,6 +167,7 @@ int rnnwf_vmc_step(rnnwf_handle* h, int64_t numsamples, uint64_t seed, uint64_t 
                    double* moments);
 
 /* ---- gradient of the VMC cost (models GRU1D, GRU1D_PARITY, CRNN_U1 (f32), GRU1D_F64, MDRNN2D (f64)) ----
+ * (RNNWF_MODEL_LSTM1D_F64 has no gradient: these four and rnnwf_load_batch return RNNWF_ERR_INVALID for it.)
  * rnnwf_vmc_gradient <- optimizer.compute_gradients(cost) with
  *   cost = mean(log_probs * Eloc) - mean(Eloc) * mean(log_probs)      (1DTFIM/TrainingRNN_1DTFIM.py:151-162)
  *   evaluated on the batch of the LAST rnnwf_vmc_step (its samples, per-site hidden states and E_loc are still

@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librnnwf_hip.so")
 
-MODEL_GRU1D, MODEL_GRU1D_PARITY, MODEL_CRNN_U1, MODEL_GRU1D_F64, MODEL_MDRNN2D = range(5)
+MODEL_GRU1D, MODEL_GRU1D_PARITY, MODEL_CRNN_U1, MODEL_GRU1D_F64, MODEL_MDRNN2D, MODEL_LSTM1D_F64 = range(6)
 F32, F64 = 0, 1
 ABI_VERSION = 1
 MAX_LAYERS = 4
@@ -254,7 +254,7 @@ class NativeWavefunction:
             if log_probs.dtype != np.float64 or not log_probs.flags.c_contiguous or log_probs.size < (self.N + 1) * ns:
                 raise ValueError("log_probs must be a contiguous float64 array of (N+1)*numsamples entries")
             lpp = log_probs.ctypes.data_as(_F64P)
-        two_d = self.model in (MODEL_GRU1D_F64, MODEL_MDRNN2D)
+        two_d = self.model in (MODEL_GRU1D_F64, MODEL_MDRNN2D, MODEL_LSTM1D_F64)
         fn = self.lib.rnnwf_tfim2d_eloc if two_d else self.lib.rnnwf_tfim_eloc
         self._check(fn(self.h, sp, ns, jzp, float(Bx), e.ctypes.data_as(_F64P), lpp))
         return e

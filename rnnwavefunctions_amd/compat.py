@@ -211,15 +211,32 @@ class CudnnCompatibleGRUCell:
         self.num_units = num_units
 
 
+class LSTMCell:
+    """Sentinel for ``tf.contrib.rnn.LSTMCell`` / ``tf.nn.rnn_cell.LSTMCell``, the default cell of
+    2DTFIM_1DRNN/RNNwavefunction.py:9 (TF 1.x defaults: forget_bias 1, tanh, no peepholes): the arithmetic lives in
+    the HIP kernels (csrc/lstm_core.h)."""
+
+    def __init__(self, num_units=None, *args, **kwargs):
+        self.num_units = num_units
+
+
+def relu(x, *args, **kwargs):
+    """Sentinel for ``tf.nn.relu``: the reference's 2D wave function takes ``activation=tf.nn.relu`` (:9) and never
+    passes it to its cell (:37); the facade accepts it and ignores it likewise."""
+    raise TypeError("tf.nn.relu is only an argument sentinel here: nothing is evaluated symbolically")
+
+
 class _Namespace:
     def __init__(self, **kw):
         self.__dict__.update(kw)
 
 
 # tf.contrib.cudnn_rnn.CudnnCompatibleGRUCell, the cell every run script of the reference passes
-# (1DTFIM/TrainingRNN_1DTFIM.py:103, J1J2/TrainingRNN_J1J2.py:153, 2DTFIM_1DRNN/Training1DRNN_2DTFIM.py:104)
+# (1DTFIM/TrainingRNN_1DTFIM.py:103, J1J2/TrainingRNN_J1J2.py:153, 2DTFIM_1DRNN/Training1DRNN_2DTFIM.py:104),
+# and tf.contrib.rnn.LSTMCell, the default cell of 2DTFIM_1DRNN/RNNwavefunction.py:9
 contrib = _Namespace(cudnn_rnn=_Namespace(CudnnCompatibleGRUCell=CudnnCompatibleGRUCell),
-                     rnn=_Namespace(GRUCell=CudnnCompatibleGRUCell))
+                     rnn=_Namespace(GRUCell=CudnnCompatibleGRUCell, LSTMCell=LSTMCell))
+nn = _Namespace(rnn_cell=_Namespace(LSTMCell=LSTMCell), relu=relu)
 AUTO_REUSE = "AUTO_REUSE"
 
 
@@ -380,6 +397,10 @@ class _Train:
                 raise NotImplementedError("compute_gradients: expected ONE log-probability op of a placeholder and ONE energy placeholder")
             if (sig == _COST_COMPLEX) != (ops[0].kind == "log_amp"):
                 raise NotImplementedError("compute_gradients: the complex cost goes with log_amplitude, the real one with log_probability")
+            from . import _lib
+            if getattr(ops[0].wf, "_model", None) == _lib.MODEL_LSTM1D_F64:
+                raise NotImplementedError("compute_gradients: no gradient for the LSTM cell (the LSTM wave function "
+                                          "evaluates only: sampling, log-probabilities, local energies)")
             plan = _CostPlan(ops[0].wf, ops[0].source, phs[0], sig == _COST_COMPLEX)
             return [(_Gradient(plan, v), v) for v in (var_list or [VariableRef(plan.wf, k) for k in plan.wf.params])]
 
@@ -446,6 +467,15 @@ class _Train:
 
 train = _Train()
 compat = _Namespace(v1=_Namespace(logging=logging, Session=None, placeholder=None))
+
+
+def is_lstm_cell(cell):
+    if cell is LSTMCell or isinstance(cell, LSTMCell):
+        return True
+    if cell is None:
+        return False
+    name = cell if isinstance(cell, str) else getattr(cell, "__name__", type(cell).__name__)
+    return "LSTM" in str(name).upper()
 
 
 def is_gru_cell(cell):

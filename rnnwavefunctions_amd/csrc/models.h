@@ -25,6 +25,7 @@ int model_pack_image(rnnwf_handle* h, std::vector<char>& img);  // dispatches to
 int prnn_pack_image(rnnwf_handle* h, std::vector<char>& img);
 int crnn_pack_image(rnnwf_handle* h, std::vector<char>& img);
 int mdrnn_pack_image(rnnwf_handle* h, std::vector<char>& img);
+int lstm_pack_image(rnnwf_handle* h, std::vector<char>& img);
 
 // ---- positive GRU RNN (prnn.hip): models GRU1D, GRU1D_PARITY, GRU1D_F64 ---------------------------
 int prnn_sample(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, int32_t* out, double* out_log);
@@ -32,6 +33,14 @@ int prnn_log_prob(rnnwf_handle* h, const int32_t* samples, int64_t B, double* ou
 int prnn_tfim_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, int Nx, int Ny, const double* Jz, double Bx,
                    double* eloc, double* log_probs);
 int prnn_vmc_step(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, const double* couplings,
+                  int32_t* out_samples, double* out_eloc, double* moments);
+
+// ---- LSTM over the raster path (lstm.hip): model LSTM1D_F64 -----------------------------------------
+int lstm_sample(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, int32_t* out, double* out_log);
+int lstm_log_prob(rnnwf_handle* h, const int32_t* samples, int64_t B, double* out);
+int lstm_tfim_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* Jz, double Bx, double* eloc,
+                   double* log_probs);
+int lstm_vmc_step(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, const double* couplings,
                   int32_t* out_samples, double* out_eloc, double* moments);
 
 // ---- complex GRU RNN with U(1) mask (crnn.hip) -----------------------------------------------------

@@ -53,6 +53,13 @@ static void declare_params(rnnwf_handle* h) {
         declare(h, "wf_dense/bias", {2});
         return;
     }
+    if (h->model == RNNWF_MODEL_LSTM1D_F64) {              // tf.nn.rnn_cell.LSTMCell(H) in MultiRNNCell + Dense(2)
+        declare(h, "multi_rnn_cell/cell_0/lstm_cell/kernel", {2 + H, 4 * H});
+        declare(h, "multi_rnn_cell/cell_0/lstm_cell/bias", {4 * H});
+        declare(h, "wf_dense/kernel", {H, 2});
+        declare(h, "wf_dense/bias", {2});
+        return;
+    }
     // layer l of width w_l (input width d_l: 2 for the first layer, w_{l-1} above), everything padded to H = max w
     for (int l = 0; l < h->NL; ++l) {
         const std::string pl = "multi_rnn_cell/cell_" + std::to_string(l) + "/cudnn_compatible_gru_cell/";
@@ -148,11 +155,15 @@ extern "C" int rnnwf_create(const rnnwf_config* cfg, rnnwf_handle** out) {
     if (!cfg || !out) return bad("rnnwf_create: null argument");
     *out = nullptr;
     if (cfg->abi_version != RNNWF_ABI_VERSION) return bad("rnnwf_create: ABI version mismatch");
-    if (cfg->model < 0 || cfg->model > RNNWF_MODEL_MDRNN2D) return bad("rnnwf_create: unknown model");
+    if (cfg->model < 0 || cfg->model > RNNWF_MODEL_LSTM1D_F64) return bad("rnnwf_create: unknown model");
     if (cfg->nx < 1 || cfg->ny < 1) return bad("rnnwf_create: system size must be positive");
     if (cfg->num_layers < 1 || cfg->num_layers > RNNWF_MAX_LAYERS)
         return bad("rnnwf_create: len(units) must be 1.." + std::to_string(RNNWF_MAX_LAYERS));
     if (cfg->units[0] < 1) return bad("rnnwf_create: units[0] must be positive");
+    if (cfg->model == RNNWF_MODEL_LSTM1D_F64) {            // its weight image fits the 160 KiB of LDS up to 68 units (lstm_core.h)
+        if (cfg->num_layers > 1) return bad("rnnwf_create: the LSTM wave function has one layer (stacked LSTM layers are not implemented)");
+        if (cfg->units[0] > 68) return bad("rnnwf_create: the LSTM cell needs num_units <= 68");
+    }
     if (cfg->num_layers > 1) {
         // MultiRNNCell stacks (1DTFIM/RNNwavefunction.py:32, J1J2/ComplexRNNwavefunction.py:40,
         // 2DTFIM_1DRNN/RNNwavefunction.py): GRU models, equal widths, the images of all layers must fit LDS
@@ -170,7 +181,7 @@ extern "C" int rnnwf_create(const rnnwf_config* cfg, rnnwf_handle** out) {
             return bad("rnnwf_create: stacked layers: num_units <= 100");
         }
     }
-    const bool two_d = cfg->model == RNNWF_MODEL_MDRNN2D || cfg->model == RNNWF_MODEL_GRU1D_F64;
+    const bool two_d = cfg->model == RNNWF_MODEL_MDRNN2D || cfg->model == RNNWF_MODEL_GRU1D_F64 || cfg->model == RNNWF_MODEL_LSTM1D_F64;
     if (!two_d && cfg->ny != 1) return bad("rnnwf_create: ny must be 1 for the 1D models");
     if (cfg->model == RNNWF_MODEL_CRNN_U1 && (cfg->nx % 2)) return bad("rnnwf_create: the U(1) cRNN needs an even number of sites");
 
@@ -185,7 +196,7 @@ extern "C" int rnnwf_create(const rnnwf_config* cfg, rnnwf_handle** out) {
     rnnwf_handle* h = new rnnwf_handle();
     h->cfg = *cfg;
     h->model = cfg->model;
-    h->f64 = cfg->model == RNNWF_MODEL_GRU1D_F64 || cfg->model == RNNWF_MODEL_MDRNN2D;
+    h->f64 = cfg->model == RNNWF_MODEL_GRU1D_F64 || cfg->model == RNNWF_MODEL_MDRNN2D || cfg->model == RNNWF_MODEL_LSTM1D_F64;
     h->H = *std::max_element(cfg->units, cfg->units + cfg->num_layers);      // layers of unequal width are padded to the widest (handle.h: ParamSpec)
     h->Nx = cfg->nx;
     h->Ny = cfg->ny;
@@ -362,6 +373,11 @@ extern "C" int rnnwf_init_params(rnnwf_handle* h, uint64_t seed) {
         draw("b_rnn_0", 1, H, true);
         draw("wf_dense/kernel", H, 2);
         constant("wf_dense/bias", 0.0);
+    } else if (h->model == RNNWF_MODEL_LSTM1D_F64) {       // params.init_lstm_params: glorot kernels, zero biases
+        draw("multi_rnn_cell/cell_0/lstm_cell/kernel", 2 + H, 4 * H);
+        constant("multi_rnn_cell/cell_0/lstm_cell/bias", 0.0);
+        draw("wf_dense/kernel", H, 2);
+        constant("wf_dense/bias", 0.0);
     } else {                                               // params.init_gru_params
         int64_t d = 2, w = H;
         for (int l = 0; l < h->NL; ++l) {
@@ -506,6 +522,7 @@ int rnnwf::run_parity_share(rnnwf_handle* h, double* lpF, double* lpR, int64_t n
 int rnnwf::model_pack_image(rnnwf_handle* h, std::vector<char>& img) {
     if (h->model == RNNWF_MODEL_MDRNN2D) return mdrnn_pack_image(h, img);
     if (h->model == RNNWF_MODEL_CRNN_U1) return crnn_pack_image(h, img);
+    if (h->model == RNNWF_MODEL_LSTM1D_F64) return lstm_pack_image(h, img);
     return prnn_pack_image(h, img);
 }
 
@@ -522,7 +539,9 @@ extern "C" int rnnwf_sample(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t
     if (ns < 1 || !out_samples) return h->fail(RNNWF_ERR_INVALID, "rnnwf_sample: numsamples must be >= 1 and out_samples non-null");
     if (is_prnn(h)) return prnn_sample(h, ns, seed, step, offset, out_samples, out_log);
     if (h->model == RNNWF_MODEL_CRNN_U1) return crnn_sample(h, ns, seed, step, offset, out_samples, out_log);
-    return mdrnn_sample(h, ns, seed, step, offset, out_samples, out_log);
+    if (h->model == RNNWF_MODEL_LSTM1D_F64) return lstm_sample(h, ns, seed, step, offset, out_samples, out_log);
+    if (h->model == RNNWF_MODEL_MDRNN2D) return mdrnn_sample(h, ns, seed, step, offset, out_samples, out_log);
+    return h->fail(RNNWF_ERR_INVALID, "rnnwf_sample: unknown model %d", h->model);
 }
 
 extern "C" int rnnwf_log_prob(rnnwf_handle* h, const int32_t* samples, int64_t B, double* out) {
@@ -531,7 +550,9 @@ extern "C" int rnnwf_log_prob(rnnwf_handle* h, const int32_t* samples, int64_t B
     if (B == 0) return RNNWF_OK;
     if (is_prnn(h)) return prnn_log_prob(h, samples, B, out);
     if (h->model == RNNWF_MODEL_CRNN_U1) return crnn_log_amp(h, samples, B, nullptr, out);
-    return mdrnn_log_prob(h, samples, B, out);
+    if (h->model == RNNWF_MODEL_LSTM1D_F64) return lstm_log_prob(h, samples, B, out);
+    if (h->model == RNNWF_MODEL_MDRNN2D) return mdrnn_log_prob(h, samples, B, out);
+    return h->fail(RNNWF_ERR_INVALID, "rnnwf_log_prob: unknown model %d", h->model);
 }
 
 extern "C" int rnnwf_log_amp(rnnwf_handle* h, const int32_t* samples, int64_t B, float* out_re_im) {
@@ -557,7 +578,8 @@ extern "C" int rnnwf_tfim2d_eloc(rnnwf_handle* h, const int32_t* samples, int64_
     if (ns < 1 || !samples || !Jz || !eloc) return h->fail(RNNWF_ERR_INVALID, "rnnwf_tfim2d_eloc: bad arguments");
     if (h->model == RNNWF_MODEL_GRU1D_F64) return prnn_tfim_eloc(h, samples, ns, h->Nx, h->Ny, Jz, Bx, eloc, log_probs);
     if (h->model == RNNWF_MODEL_MDRNN2D) return mdrnn_tfim_eloc(h, samples, ns, Jz, Bx, eloc, log_probs);
-    return h->fail(RNNWF_ERR_INVALID, "rnnwf_tfim2d_eloc: needs a 2D handle (GRU1D_F64 or MDRNN2D)");
+    if (h->model == RNNWF_MODEL_LSTM1D_F64) return lstm_tfim_eloc(h, samples, ns, Jz, Bx, eloc, log_probs);
+    return h->fail(RNNWF_ERR_INVALID, "rnnwf_tfim2d_eloc: needs a 2D handle (GRU1D_F64, MDRNN2D or LSTM1D_F64)");
 }
 
 extern "C" int rnnwf_j1j2_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* J1, const double* J2,
@@ -581,18 +603,25 @@ extern "C" int rnnwf_vmc_step(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64
         if (n_couplings != h->N + 1) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_step: TFIM needs Nx*Ny+1 couplings (Jz, Bx)");
         return mdrnn_vmc_step(h, ns, seed, step, offset, couplings, out_samples, (double*)out_eloc, moments);
     }
+    if (h->model == RNNWF_MODEL_LSTM1D_F64) {
+        if (n_couplings != h->N + 1) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_step: TFIM needs Nx*Ny+1 couplings (Jz, Bx)");
+        return lstm_vmc_step(h, ns, seed, step, offset, couplings, out_samples, (double*)out_eloc, moments);
+    }
+    if (h->model != RNNWF_MODEL_CRNN_U1) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_step: unknown model %d", h->model);
     if (n_couplings != 3 * h->N + 2) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_step: J1J2 needs 3N+2 couplings");
     return crnn_vmc_step(h, ns, seed, step, offset, couplings, out_samples, (float*)out_eloc, moments);
 }
 
 extern "C" int rnnwf_load_batch(rnnwf_handle* h, const int32_t* samples, int64_t ns, const void* eloc) {
     if (int rc = check_ready(h)) return rc;
+    if (h->model == RNNWF_MODEL_LSTM1D_F64) return h->fail(RNNWF_ERR_INVALID, "rnnwf_load_batch: no gradient for the LSTM cell");
     if (ns < 1 || !samples || !eloc) return h->fail(RNNWF_ERR_INVALID, "rnnwf_load_batch: bad arguments");
     h->last_ns = 0;
     int rc;
     if (is_prnn(h)) rc = prnn_load_batch(h, samples, ns);
     else if (h->model == RNNWF_MODEL_CRNN_U1) rc = crnn_load_batch(h, samples, ns);
-    else rc = mdrnn_load_batch(h, samples, ns);
+    else if (h->model == RNNWF_MODEL_MDRNN2D) rc = mdrnn_load_batch(h, samples, ns);
+    else return h->fail(RNNWF_ERR_INVALID, "rnnwf_load_batch: unknown model %d", h->model);
     if (rc) return rc;
     const size_t bytes = (size_t)ns * 8;                  // float64 per sample, or complex64 = two float32 per sample
     RNNWF_HIP(h, hipMemcpyAsync(h->eloc.p, eloc, bytes, hipMemcpyHostToDevice, h->stream));

@@ -173,6 +173,7 @@ int add_image(rnnwf_handle* h, DevBuf* target, Fn&& run_packer) {
 
 int build(rnnwf_handle* h) {
     TrainState& t = h->train;
+    if (h->model == RNNWF_MODEL_LSTM1D_F64) return h->fail(RNNWF_ERR_INVALID, "device-resident training: no gradient for the LSTM cell");
     if (t.built) return t.supported ? 0 : h->fail(RNNWF_ERR_INVALID, "device-resident training is not available for this model: %s", t.why.c_str());
     t.built = true;
     const bool md = h->model == RNNWF_MODEL_MDRNN2D;
@@ -363,7 +364,7 @@ int rnnwf::train_sync_params_to_host(rnnwf_handle* h) {
 }
 
 extern "C" int rnnwf_device_training_supported(rnnwf_handle* h) {
-    if (!h || !h->committed) return 0;
+    if (!h || !h->committed || h->model == RNNWF_MODEL_LSTM1D_F64) return 0;
     if (hipSetDevice(h->cfg.device) != hipSuccess) return 0;
     return build(h) == 0 ? 1 : 0;
 }
@@ -401,6 +402,7 @@ extern "C" int rnnwf_adam_get_state(rnnwf_handle* h, double* m_flat, double* v_f
 // One optimizer step from the gradient rnnwf_vmc_gradient left on the device (its dW image), then the images' re-pack: what
 // `sess.run(optstep)` does behind the gradient (1DTFIM/TrainingRNN_1DTFIM.py:221).
 extern "C" int rnnwf_adam_step(rnnwf_handle* h, double learning_rate, double beta1, double beta2, double epsilon) {
+    if (h && h->model == RNNWF_MODEL_LSTM1D_F64) return h->fail(RNNWF_ERR_INVALID, "rnnwf_adam_step: no gradient for the LSTM cell");
     if (!h || !h->committed) return RNNWF_ERR_INVALID;
     RNNWF_HIP(h, hipSetDevice(h->cfg.device));
     if (int rc = build(h)) return rc;
@@ -421,6 +423,7 @@ extern "C" int rnnwf_adam_step(rnnwf_handle* h, double learning_rate, double bet
 extern "C" int rnnwf_train_steps(rnnwf_handle* h, int32_t K, int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset,
                                  const double* couplings, int64_t n_couplings, const double* learning_rates, double beta1, double beta2,
                                  double epsilon, double* moments) {
+    if (h && h->model == RNNWF_MODEL_LSTM1D_F64) return h->fail(RNNWF_ERR_INVALID, "rnnwf_train_steps: no gradient for the LSTM cell");
     if (!h || !h->committed) return RNNWF_ERR_INVALID;
     if (K < 1 || K > kMaxSteps || numsamples < 1 || !couplings || !learning_rates || !moments)
         return h->fail(RNNWF_ERR_INVALID, "rnnwf_train_steps: bad arguments (1 <= K <= %d)", kMaxSteps);

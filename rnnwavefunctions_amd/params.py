@@ -16,6 +16,7 @@ from collections import OrderedDict
 import numpy as np
 
 GRU_PREFIX = "multi_rnn_cell/cell_%d/cudnn_compatible_gru_cell/"
+LSTM_PREFIX = "multi_rnn_cell/cell_0/lstm_cell/"
 
 
 def _glorot(rng, shape, dtype):
@@ -50,6 +51,23 @@ def init_gru_params(units, seed=111, scope="RNNwavefunction", dtype=np.float32, 
     for head in heads:
         p[scope + "/" + head + "/kernel"] = _glorot(rng, (d, 2), dtype)
         p[scope + "/" + head + "/bias"] = np.zeros(2, dtype=dtype)
+    return p
+
+
+def init_lstm_params(units, seed=111, scope="RNNwavefunction", dtype=np.float64, inputdim=2):
+    """Parameters of ``MultiRNNCell([LSTMCell(units[0])])`` + ``Dense(2)``, the default cell of
+    2DTFIM_1DRNN/RNNwavefunction.py:9,37 (one layer).  TF's LSTMCell keeps one kernel [inputdim + H, 4H] (gate
+    columns i | j | f | o) and a zero-initialised bias [4H]; the forget bias 1.0 is added at run time, not stored."""
+    units = list(units)
+    if len(units) != 1:
+        raise ValueError("the LSTM wave function has one layer (got units=%r)" % (units,))
+    rng = np.random.RandomState(seed)
+    h = units[0]
+    p = OrderedDict()
+    p[scope + "/" + LSTM_PREFIX + "kernel"] = _glorot(rng, (inputdim + h, 4 * h), dtype)
+    p[scope + "/" + LSTM_PREFIX + "bias"] = np.zeros(4 * h, dtype=dtype)
+    p[scope + "/wf_dense/kernel"] = _glorot(rng, (h, 2), dtype)
+    p[scope + "/wf_dense/bias"] = np.zeros(2, dtype=dtype)
     return p
 
 

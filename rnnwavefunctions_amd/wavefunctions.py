@@ -6,7 +6,7 @@ import numpy as np
 from . import _lib
 from . import params as P
 from . import tf_checkpoint as T
-from .compat import EvalOp, Graph, Placeholder, SampleOp, is_gru_cell
+from .compat import EvalOp, Graph, Placeholder, SampleOp, is_gru_cell, is_lstm_cell
 
 
 class _NativeWF:
@@ -208,19 +208,30 @@ class ComplexGRUWavefunction1D(GRUWavefunction1D):
 
 
 class GRUWavefunction2DRaster(GRUWavefunction1D):
-    """2DTFIM_1DRNN/RNNwavefunction.py:8-130 - float64 GRU run over the flattened lattice."""
+    """2DTFIM_1DRNN/RNNwavefunction.py:8-130 - float64 GRU or LSTM run over the flattened lattice.
+
+    The reference's constructor defaults to cell=tf.contrib.rnn.LSTMCell (:9) while its training script passes the GRU
+    (Training1DRNN_2DTFIM.py:104).  Here cell=None keeps meaning the GRU, as it always has in this package; pass
+    cell=tf.contrib.rnn.LSTMCell (or tf.nn.rnn_cell.LSTMCell) for the LSTM wave function (one layer, <= 68 units,
+    evaluation only: sampling, log-probabilities and local energies, no gradient).  `activation` is accepted and
+    ignored, as the reference never hands it to the cell (:37)."""
 
     _model = _lib.MODEL_GRU1D_F64
     _dtype = np.float64
 
     def __init__(self, systemsize_x, systemsize_y, cell=None, units=[10], scope="RNNwavefunction", seed=111,
                  activation=None, device=0):
-        if not is_gru_cell(cell):
-            raise ValueError("only the GRU cell the reference's training script passes is implemented "
-                             "(got cell=%r)" % (cell,))
+        lstm = is_lstm_cell(cell)
+        if not lstm and not is_gru_cell(cell):
+            raise ValueError("only the GRU cell the reference's training script passes and the LSTM cell of the "
+                             "reference's default are implemented (got cell=%r)" % (cell,))
         self.Nx, self.Ny = systemsize_x, systemsize_y
         self.N = systemsize_x * systemsize_y
-        prm = P.init_gru_params(units, seed=seed, scope=scope, dtype=np.float64)
+        if lstm:
+            self._model = _lib.MODEL_LSTM1D_F64
+            prm = P.init_lstm_params(units, seed=seed, scope=scope, dtype=np.float64)
+        else:
+            prm = P.init_gru_params(units, seed=seed, scope=scope, dtype=np.float64)
         self._setup(systemsize_x, systemsize_y, units, scope, seed, device, prm)
         self._layer_views()
 
