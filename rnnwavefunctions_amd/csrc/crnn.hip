@@ -1,5 +1,5 @@
-// crnn.hip - host side of the complex GRU RNN wave function with the U(1) mask (model CRNN_U1):
-// sample / log_amplitude / fused J1-J2 local energies / fused VMC step.
+// crnn.hip - host side of the complex GRU RNN wave function with the U(1) mask (model CRNN_U1): weight image, base pass,
+// log_amplitude, fused J1-J2 local energies (the VMC step and sampling are rnnwf_api.hip's driver, through crnn_family).
 #include <algorithm>
 
 #include <cstdlib>
@@ -292,9 +292,26 @@ int64_t collect_totals(rnnwf_handle* h, int64_t ns) {
     return t[0] + ns;   // + one diagonal configuration per sample
 }
 
-}  // namespace
+// base pass alone: 2 Re log psi of every chain -> h->out_lp (the spins drawn into h->bits when `d`)
+int log_prob_pass(rnnwf_handle* h, int64_t ns, const Draw* d) {
+    if (int rc = ensure(h, h->out_lp, (size_t)ns * 8)) return rc;
+    CrnnArgs a = base_args(h, ns);
+    a.bits = (uint32_t*)h->bits.p;
+    a.out_logp = (double*)h->out_lp.p;
+    if (d) { a.sampling = 1; a.seed = d->seed; a.step = d->step; a.sample_offset = d->offset; }
+    return launch_base(h, a);
+}
 
-int rnnwf::crnn_pack_image(rnnwf_handle* h, std::vector<char>& img) {
+// couplings: J1, J2, Bz (N each, on the device in h->coupl), then the periodic and Marshall flags
+int energy(rnnwf_handle* h, int64_t ns, const Draw* d, const double* couplings) {
+    const int N = h->N;
+    return j1j2_on_device(h, ns, d != nullptr, d ? d->seed : 0, d ? d->step : 0, d ? d->offset : 0, (const double*)h->coupl.p,
+                          couplings[3 * N] != 0.0, couplings[3 * N + 1] != 0.0);
+}
+
+void count_work(rnnwf_handle* h, int64_t ns) { collect_totals(h, ns); }
+
+int pack_image(rnnwf_handle* h, std::vector<char>& img) {
     // swap-pass engine: bf16x3 on the matrix core (RNNWF_ENGINE=f32: f32-input MFMA everywhere; above 68 units the w3
     // fragments are read through L2, split_stream.hip)
     // stacked layers of 37..50 units: a pipeline of bf16x3 kernels, one per layer (split.hip: crnn_stack_swap); other stacks and
@@ -313,23 +330,7 @@ int rnnwf::crnn_pack_image(rnnwf_handle* h, std::vector<char>& img) {
     return h->fail(RNNWF_ERR_INVALID, "no cRNN kernel for NFULL=%d", h->NFULL);
 }
 
-int rnnwf::crnn_sample(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, int32_t* out,
-                       double* out_log) {
-    const int W = (h->N + 31) / 32;
-    h->last_ns = 0;
-    if (int rc = ensure(h, h->bits, (size_t)W * ns * 4)) return rc;
-    if (int rc = ensure(h, h->out_lp, (size_t)ns * 8)) return rc;
-    CrnnArgs a = base_args(h, ns);
-    a.bits = (uint32_t*)h->bits.p;
-    a.out_logp = (double*)h->out_lp.p;
-    a.sampling = 1;
-    a.seed = seed; a.step = step; a.sample_offset = offset;
-    if (int rc = launch_base(h, a)) return rc;
-    if (int rc = unpack_and_download(h, h->bits, ns, out, nullptr)) return rc;
-    if (out_log) RNNWF_HIP(h, hipMemcpyAsync(out_log, h->out_lp.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream));
-    RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    return RNNWF_OK;
-}
+}  // namespace
 
 int rnnwf::crnn_log_amp(rnnwf_handle* h, const int32_t* samples, int64_t B, float* out_re_im, double* out_logp) {
     const int N = h->N;
@@ -378,32 +379,11 @@ int rnnwf::crnn_j1j2_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, c
     return RNNWF_OK;
 }
 
-int rnnwf::crnn_load_batch(rnnwf_handle* h, const int32_t* samples, int64_t ns) {
-    const int N = h->N;
-    if (ns > max_chains_per_pass(h))
-        return h->fail(RNNWF_ERR_NOMEM, "rnnwf_load_batch: %lld samples exceed the checkpoint budget; split the batch", (long long)ns);
-    const std::vector<double> zeros((size_t)3 * N, 0.0);              // no bonds: base pass + checkpoints only
-    if (int rc = upload_couplings(h, zeros.data(), zeros.size())) return rc;
-    if (int rc = upload_and_pack(h, samples, ns, h->bits, 0, nullptr)) return rc;
-    return j1j2_on_device(h, ns, false, 0, 0, 0, (const double*)h->coupl.p, 0, 0);
-}
-
-int rnnwf::crnn_vmc_step(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset,
-                         const double* couplings, int32_t* out_samples, float* out_eloc, double* moments) {
-    const int N = h->N;
-    const int W = (N + 31) / 32;
-    if (ns > max_chains_per_pass(h))
-        return h->fail(RNNWF_ERR_NOMEM, "rnnwf_vmc_step: %lld samples exceed the checkpoint budget; split the batch",
-                       (long long)ns);
-    if (int rc = ensure(h, h->bits, (size_t)W * ns * 4)) return rc;
-    if (int rc = upload_couplings(h, couplings, (size_t)3 * N)) return rc;
-    const int periodic = couplings[3 * N] != 0.0, marshall = couplings[3 * N + 1] != 0.0;
-    if (int rc = j1j2_on_device(h, ns, true, seed, step, offset, (const double*)h->coupl.p, periodic, marshall)) return rc;
-    if (out_samples) if (int rc = unpack_and_download(h, h->bits, ns, out_samples, nullptr)) return rc;
-    if (out_eloc) RNNWF_HIP(h, hipMemcpyAsync(out_eloc, h->eloc.p, (size_t)ns * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
-    h->last_ns = ns;                  // bits, hck and eloc stay resident for rnnwf_vmc_gradient
-    h->last_has_ckpt = true;
-    if (int rc = run_moments(h, h->eloc.p, ns, true, moments)) return rc;   // syncs the stream (moments == nullptr, device-resident training: it does not)
-    if (moments) collect_totals(h, ns);
-    return RNNWF_OK;
+const Family* rnnwf::crnn_family() {
+    static const Family f = {
+        "complex RNN", pack_image, log_prob_pass, nullptr, energy, max_chains_per_pass, nullptr, count_work,
+        3, 2,               // J1, J2, Bz per site; periodic, marshall
+        true, false, true,  // complex64 E_loc; the base pass alone keeps no states; has a gradient
+    };
+    return &f;
 }

@@ -533,7 +533,7 @@ struct MLGrad {
 
 extern "C" int rnnwf_vmc_gradient(rnnwf_handle* h, double mean_energy, double mean_energy_im, double norm) {
     if (!h) return RNNWF_ERR_INVALID;
-    if (h->model == RNNWF_MODEL_LSTM1D_F64) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: no gradient for the LSTM cell");
+    if (int rc = require_gradient(h, "rnnwf_vmc_gradient")) return rc;
     if (!h->committed) return h->fail(RNNWF_ERR_STATE, "parameters not committed");
     if (h->model == RNNWF_MODEL_MDRNN2D) return mdrnn_vmc_gradient(h, mean_energy, norm);
     if (h->NL != 1) {

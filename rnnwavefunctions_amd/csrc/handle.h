@@ -15,6 +15,8 @@
 
 namespace rnnwf {
 
+struct Family;   // models.h
+
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
@@ -78,6 +80,7 @@ struct ParamSpec {
 struct rnnwf_handle {
     rnnwf_config cfg{};
     int model = 0;
+    const rnnwf::Family* family = nullptr;   // the model's table of host hooks (models.h)
     bool f64 = false;
     int H = 0;       // num_units
     int NFULL = 0;   // padded hidden size = 16 NFULL + 4

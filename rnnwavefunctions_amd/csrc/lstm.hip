@@ -1,5 +1,5 @@
 // lstm.hip - host side of the LSTM wave function over the raster path (model LSTM1D_F64, one layer, 1..68 units, float64):
-// weight image, sample / log_probability / fused 2D TFIM local energies / fused VMC step.  The kernels are lstm_kernels.h;
+// weight image, base pass, fused 2D TFIM local energies (driven through lstm_family by rnnwf_api.hip).  The kernels are lstm_kernels.h;
 // everything downstream of them (bit packing, local-energy assembly, moments) is shared with the GRU models.
 #include <algorithm>
 #include <cstdlib>
@@ -13,7 +13,6 @@ using namespace rnnwf;
 namespace {
 
 constexpr size_t kHckBudget = (size_t)48 << 30;  // bytes of (h, c) checkpoints per pass (prnn.hip's budget)
-constexpr int64_t kLogProbChunk = (int64_t)1 << 20;
 const char* kLstmPre = "multi_rnn_cell/cell_0/lstm_cell/";
 
 // Packs LSTMCell + Dense(2) into LstmLayout<NFULL>.  TF's kernel is [2 + H, 4H]: rows 0..1 the one-hot input, rows 2.. the
@@ -142,12 +141,12 @@ int64_t max_chains_per_pass(rnnwf_handle* h) {
     return blocks * kChains;
 }
 
-// Fused local energies of ns chains whose packed spins are in h->bits (or are drawn into it): base pass with checkpoints
+// Fused local energies of ns chains whose packed spins are in h->bits (drawn into it when `d`): base pass with checkpoints
 // -> flip pass -> assembly.  Leaves E_loc in h->eloc and the log-prob queue in h->lpq.
-int eloc_on_device(rnnwf_handle* h, int64_t ns, bool sampling, uint64_t seed, uint64_t step, int64_t offset, const double* Jz_dev,
-                   double Bx) {
+int eloc_on_device(rnnwf_handle* h, int64_t ns, const Draw* d, const double* couplings) {
     const int N = h->N;
     const int64_t nsb = (ns + kChains - 1) / kChains;
+    const double Bx = couplings[N];
     if (int rc = ensure(h, h->lpq, (size_t)(N + 1) * ns * 8)) return rc;
     if (int rc = ensure(h, h->eloc, (size_t)ns * 8)) return rc;
     if (int rc = ensure(h, h->hck, (size_t)std::max(N - 1, 1) * nsb * hck_bytes_per_block(h))) return rc;
@@ -155,8 +154,7 @@ int eloc_on_device(rnnwf_handle* h, int64_t ns, bool sampling, uint64_t seed, ui
     a.bits = (uint32_t*)h->bits.p;
     a.hck = (double*)h->hck.p;
     a.lpq = (double*)h->lpq.p;
-    a.sampling = sampling ? 1 : 0;
-    a.seed = seed; a.step = step; a.sample_offset = offset;
+    if (d) { a.sampling = 1; a.seed = d->seed; a.step = d->step; a.sample_offset = d->offset; }
     if (int rc = launch_base(h, a)) return rc;
     if (Bx != 0.0 && N > 1) {
         a.ntiles = (int64_t)(N - 1) * nsb;
@@ -165,81 +163,32 @@ int eloc_on_device(rnnwf_handle* h, int64_t ns, bool sampling, uint64_t seed, ui
         h->work[0] += (double)ns * N * (N - 1) / 2.0;
         h->work[1] += (double)nsb * N * (N - 1) / 2.0 * mfma_flops_per_step(h);
     }
-    return run_tfim_eloc(h, (const uint32_t*)h->bits.p, (const double*)h->lpq.p, ns, h->Nx, h->Ny, nullptr, Jz_dev, Bx,
-                         (double*)h->eloc.p);
+    return run_tfim_eloc(h, (const uint32_t*)h->bits.p, (const double*)h->lpq.p, ns, h->Nx, h->Ny, nullptr, (const double*)h->coupl.p,
+                         Bx, (double*)h->eloc.p);
 }
 
-}  // namespace
-
-int rnnwf::lstm_pack_image(rnnwf_handle* h, std::vector<char>& img) {
-    LSTM_DISPATCH(h, { img = K::pack(h); return 0; });
-    return no_kernel(h);
-}
-
-int rnnwf::lstm_log_prob(rnnwf_handle* h, const int32_t* samples, int64_t B, double* out) {
-    const int N = h->N;
-    h->last_ns = 0;
-    for (int64_t off = 0; off < B; off += kLogProbChunk) {
-        const int64_t nb = std::min(kLogProbChunk, B - off);
-        if (int rc = upload_and_pack(h, samples + off * N, nb, h->bits, 0, nullptr)) return rc;
-        if (int rc = ensure(h, h->out_lp, (size_t)nb * 8)) return rc;
-        LstmArgs a = base_args(h, nb);
-        a.bits = (uint32_t*)h->bits.p;
-        a.out_lp = (double*)h->out_lp.p;
-        if (int rc = launch_base(h, a)) return rc;
-        RNNWF_HIP(h, hipMemcpyAsync(out + off, h->out_lp.p, (size_t)nb * 8, hipMemcpyDeviceToHost, h->stream));
-        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return RNNWF_OK;
-}
-
-int rnnwf::lstm_sample(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, int32_t* out, double* out_log) {
-    const int W = (h->N + 31) / 32;
-    h->last_ns = 0;
-    if (int rc = ensure(h, h->bits, (size_t)W * ns * 4)) return rc;
+// base pass alone: log P of every chain -> h->out_lp (the spins drawn into h->bits when `d`)
+int log_prob_pass(rnnwf_handle* h, int64_t ns, const Draw* d) {
     if (int rc = ensure(h, h->out_lp, (size_t)ns * 8)) return rc;
     LstmArgs a = base_args(h, ns);
     a.bits = (uint32_t*)h->bits.p;
     a.out_lp = (double*)h->out_lp.p;
-    a.sampling = 1;
-    a.seed = seed; a.step = step; a.sample_offset = offset;
-    if (int rc = launch_base(h, a)) return rc;
-    if (int rc = unpack_and_download(h, h->bits, ns, out, nullptr)) return rc;
-    if (out_log) RNNWF_HIP(h, hipMemcpyAsync(out_log, h->out_lp.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream));
-    RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    return RNNWF_OK;
+    if (d) { a.sampling = 1; a.seed = d->seed; a.step = d->step; a.sample_offset = d->offset; }
+    return launch_base(h, a);
 }
 
-int rnnwf::lstm_tfim_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* Jz, double Bx, double* eloc,
-                          double* log_probs) {
-    const int N = h->N;
-    h->last_ns = 0;
-    if (int rc = upload_couplings(h, Jz, (size_t)N)) return rc;
-    const int64_t chunk = max_chains_per_pass(h);
-    for (int64_t off = 0; off < ns; off += chunk) {
-        const int64_t nb = std::min(chunk, ns - off);
-        if (int rc = upload_and_pack(h, samples + off * N, nb, h->bits, 0, nullptr)) return rc;
-        if (int rc = eloc_on_device(h, nb, false, 0, 0, 0, (const double*)h->coupl.p, Bx)) return rc;
-        RNNWF_HIP(h, hipMemcpyAsync(eloc + off, h->eloc.p, (size_t)nb * 8, hipMemcpyDeviceToHost, h->stream));
-        if (log_probs)
-            RNNWF_HIP(h, hipMemcpy2DAsync(log_probs + off, (size_t)ns * 8, h->lpq.p, (size_t)nb * 8, (size_t)nb * 8,
-                                          (size_t)N + 1, hipMemcpyDeviceToHost, h->stream));
-        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return RNNWF_OK;
+int pack_image(rnnwf_handle* h, std::vector<char>& img) {
+    LSTM_DISPATCH(h, { img = K::pack(h); return 0; });
+    return no_kernel(h);
 }
 
-int rnnwf::lstm_vmc_step(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, const double* couplings,
-                         int32_t* out_samples, double* out_eloc, double* moments) {
-    const int N = h->N;
-    const int W = (N + 31) / 32;
-    h->last_ns = 0;
-    if (ns > max_chains_per_pass(h))
-        return h->fail(RNNWF_ERR_NOMEM, "rnnwf_vmc_step: %lld samples exceed the checkpoint budget; split the batch", (long long)ns);
-    if (int rc = ensure(h, h->bits, (size_t)W * ns * 4)) return rc;
-    if (int rc = upload_couplings(h, couplings, (size_t)N)) return rc;
-    if (int rc = eloc_on_device(h, ns, true, seed, step, offset, (const double*)h->coupl.p, couplings[N])) return rc;
-    if (out_samples) if (int rc = unpack_and_download(h, h->bits, ns, out_samples, nullptr)) return rc;
-    if (out_eloc) RNNWF_HIP(h, hipMemcpyAsync(out_eloc, h->eloc.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream));
-    return run_moments(h, h->eloc.p, ns, false, moments);
+}  // namespace
+
+const Family* rnnwf::lstm_family() {
+    static const Family f = {
+        "LSTM cell", pack_image, log_prob_pass, nullptr, eloc_on_device, max_chains_per_pass, nullptr, nullptr,
+        1, 1,                 // Jz per site; Bx
+        false, false, false,  // float64 E_loc; the base pass alone keeps no states; no gradient (nothing stays resident)
+    };
+    return &f;
 }

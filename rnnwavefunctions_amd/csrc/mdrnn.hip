@@ -1,5 +1,5 @@
-// mdrnn.hip - host side of the 2D MDRNN wave function (model MDRNN2D, float64):
-// sample / log_probability / fused 2D-TFIM local energies / fused VMC step.
+// mdrnn.hip - host side of the 2D MDRNN wave function (model MDRNN2D, float64): weight image, base pass, fused 2D-TFIM local
+// energies (driven through mdrnn_family by rnnwf_api.hip) and the gradient.
 #include <algorithm>
 
 #include "grad_kernels.h"
@@ -238,10 +238,14 @@ MdArgs base_args(rnnwf_handle* h, int64_t ns, const Maps& m) {
     return a;
 }
 
-int eloc_on_device(rnnwf_handle* h, int64_t ns, const Maps& m, bool sampling, uint64_t seed, uint64_t step,
-                   int64_t offset, const double* Jz_dev, double Bx) {
+// Fused local energies of ns chains whose packed spins are in h->bits (drawn into it when `d`): base pass keeping every site's
+// state -> flip pass -> assembly.  Leaves E_loc in h->eloc and the log-prob queue in h->lpq.
+int eloc_on_device(rnnwf_handle* h, int64_t ns, const Draw* d, const double* couplings) {
     const int N = h->N;
     const int64_t nsb = (ns + kChains - 1) / kChains;
+    const double Bx = couplings[N];
+    Maps m;
+    if (int rc = get_maps(h, &m)) return rc;
     if (int rc = ensure(h, h->hck, (size_t)N * nsb * hs_bytes_per_block(h))) return rc;
     if (int rc = ensure(h, h->lpq, (size_t)(N + 1) * ns * 8)) return rc;
     if (int rc = ensure(h, h->eloc, (size_t)ns * 8)) return rc;
@@ -249,8 +253,7 @@ int eloc_on_device(rnnwf_handle* h, int64_t ns, const Maps& m, bool sampling, ui
     a.bits = (uint32_t*)h->bits.p;
     a.hs = (double*)h->hck.p;
     a.lpq = (double*)h->lpq.p;
-    a.sampling = sampling ? 1 : 0;
-    a.seed = seed; a.step = step; a.sample_offset = offset;
+    if (d) { a.sampling = 1; a.seed = d->seed; a.step = d->step; a.sample_offset = d->offset; }
     if (int rc = launch_base(h, a)) return rc;
     if (Bx != 0.0 && N > 1) {
         a.sampling = 0;
@@ -259,116 +262,50 @@ int eloc_on_device(rnnwf_handle* h, int64_t ns, const Maps& m, bool sampling, ui
         h->work[0] += (double)ns * N * (N - 1) / 2.0;
         h->work[1] += (double)nsb * N * (N - 1) / 2.0 * mfma_flops_per_step(h);
     }
-    return run_tfim_eloc(h, (const uint32_t*)h->bits.p, (const double*)h->lpq.p, ns, h->Nx, h->Ny, m.pos_of_site, Jz_dev,
-                         Bx, (double*)h->eloc.p);
+    return run_tfim_eloc(h, (const uint32_t*)h->bits.p, (const double*)h->lpq.p, ns, h->Nx, h->Ny, m.pos_of_site,
+                         (const double*)h->coupl.p, Bx, (double*)h->eloc.p);
 }
 
-}  // namespace
+// base pass alone (it, too, keeps every site's state in h->hck): log P of every chain -> h->out_lp (the spins drawn into h->bits
+// when `d`)
+int log_prob_pass(rnnwf_handle* h, int64_t ns, const Draw* d) {
+    const int64_t nsb = (ns + kChains - 1) / kChains;
+    Maps m;
+    if (int rc = get_maps(h, &m)) return rc;
+    if (int rc = ensure(h, h->out_lp, (size_t)ns * 8)) return rc;
+    if (int rc = ensure(h, h->hck, (size_t)h->N * nsb * hs_bytes_per_block(h))) return rc;
+    MdArgs a = base_args(h, ns, m);
+    a.bits = (uint32_t*)h->bits.p;
+    a.hs = (double*)h->hck.p;
+    a.out_lp = (double*)h->out_lp.p;
+    if (d) { a.sampling = 1; a.seed = d->seed; a.step = d->step; a.sample_offset = d->offset; }
+    return launch_base(h, a);
+}
 
-int rnnwf::mdrnn_pack_image(rnnwf_handle* h, std::vector<char>& img) {
+// the packed bits follow the snake path: samples[b, nx, ny] is bit col_of_pos[p] of position p
+int site_maps(rnnwf_handle* h, const int32_t** col_of_pos, const int32_t** pos_of_site) {
+    Maps m;
+    if (int rc = get_maps(h, &m)) return rc;
+    *col_of_pos = m.col_of_pos;
+    *pos_of_site = m.pos_of_site;
+    return 0;
+}
+
+int pack_image(rnnwf_handle* h, std::vector<char>& img) {
     if (h->N > 256) return h->fail(RNNWF_ERR_INVALID, "MDRNN: lattices above 256 sites are not implemented");
     MD_DISPATCH(h, { img = K::template pack<double>(h); return 0; });
     return h->fail(RNNWF_ERR_INVALID, "MDRNN: num_units > 84 is not implemented on gfx950 yet");
 }
 
-int rnnwf::mdrnn_log_prob(rnnwf_handle* h, const int32_t* samples, int64_t B, double* out) {
-    const int N = h->N;
-    h->last_ns = 0;
-    Maps m;
-    if (int rc = get_maps(h, &m)) return rc;
-    const int64_t chunk = max_chains_per_pass(h);
-    for (int64_t off = 0; off < B; off += chunk) {
-        const int64_t nb = std::min(chunk, B - off);
-        const int64_t nsb = (nb + kChains - 1) / kChains;
-        if (int rc = upload_and_pack(h, samples + off * N, nb, h->bits, 0, m.col_of_pos)) return rc;
-        if (int rc = ensure(h, h->out_lp, (size_t)nb * 8)) return rc;
-        if (int rc = ensure(h, h->hck, (size_t)N * nsb * hs_bytes_per_block(h))) return rc;
-        MdArgs a = base_args(h, nb, m);
-        a.bits = (uint32_t*)h->bits.p;
-        a.hs = (double*)h->hck.p;
-        a.out_lp = (double*)h->out_lp.p;
-        if (int rc = launch_base(h, a)) return rc;
-        RNNWF_HIP(h, hipMemcpyAsync(out + off, h->out_lp.p, (size_t)nb * 8, hipMemcpyDeviceToHost, h->stream));
-        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return RNNWF_OK;
-}
+}  // namespace
 
-int rnnwf::mdrnn_sample(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, int32_t* out,
-                        double* out_log) {
-    const int N = h->N;
-    h->last_ns = 0;
-    const int W = (N + 31) / 32;
-    Maps m;
-    if (int rc = get_maps(h, &m)) return rc;
-    if (ns > max_chains_per_pass(h)) return h->fail(RNNWF_ERR_NOMEM, "rnnwf_sample: batch too large for one pass; split it");
-    const int64_t nsb = (ns + kChains - 1) / kChains;
-    if (int rc = ensure(h, h->bits, (size_t)W * ns * 4)) return rc;
-    if (int rc = ensure(h, h->out_lp, (size_t)ns * 8)) return rc;
-    if (int rc = ensure(h, h->hck, (size_t)N * nsb * hs_bytes_per_block(h))) return rc;
-    MdArgs a = base_args(h, ns, m);
-    a.bits = (uint32_t*)h->bits.p;
-    a.hs = (double*)h->hck.p;
-    a.out_lp = (double*)h->out_lp.p;
-    a.sampling = 1;
-    a.seed = seed; a.step = step; a.sample_offset = offset;
-    if (int rc = launch_base(h, a)) return rc;
-    if (int rc = unpack_and_download(h, h->bits, ns, out, m.pos_of_site)) return rc;
-    if (out_log) RNNWF_HIP(h, hipMemcpyAsync(out_log, h->out_lp.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream));
-    RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    return RNNWF_OK;
-}
-
-int rnnwf::mdrnn_tfim_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* Jz, double Bx,
-                           double* eloc, double* log_probs) {
-    const int N = h->N;
-    h->last_ns = 0;
-    Maps m;
-    if (int rc = get_maps(h, &m)) return rc;
-    if (int rc = upload_couplings(h, Jz, (size_t)N)) return rc;
-    const int64_t chunk = max_chains_per_pass(h);
-    for (int64_t off = 0; off < ns; off += chunk) {
-        const int64_t nb = std::min(chunk, ns - off);
-        if (int rc = upload_and_pack(h, samples + off * N, nb, h->bits, 0, m.col_of_pos)) return rc;
-        if (int rc = eloc_on_device(h, nb, m, false, 0, 0, 0, (const double*)h->coupl.p, Bx)) return rc;
-        RNNWF_HIP(h, hipMemcpyAsync(eloc + off, h->eloc.p, (size_t)nb * 8, hipMemcpyDeviceToHost, h->stream));
-        if (log_probs)
-            RNNWF_HIP(h, hipMemcpy2DAsync(log_probs + off, (size_t)ns * 8, h->lpq.p, (size_t)nb * 8, (size_t)nb * 8,
-                                          (size_t)N + 1, hipMemcpyDeviceToHost, h->stream));
-        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return RNNWF_OK;
-}
-
-int rnnwf::mdrnn_load_batch(rnnwf_handle* h, const int32_t* samples, int64_t ns) {
-    const int N = h->N;
-    Maps m;
-    if (int rc = get_maps(h, &m)) return rc;
-    if (ns > max_chains_per_pass(h))
-        return h->fail(RNNWF_ERR_NOMEM, "rnnwf_load_batch: %lld samples exceed the hidden-state budget; split the batch", (long long)ns);
-    const std::vector<double> zeros((size_t)N, 0.0);
-    if (int rc = upload_couplings(h, zeros.data(), (size_t)N)) return rc;
-    if (int rc = upload_and_pack(h, samples, ns, h->bits, 0, m.col_of_pos)) return rc;
-    return eloc_on_device(h, ns, m, false, 0, 0, 0, (const double*)h->coupl.p, 0.0);
-}
-
-int rnnwf::mdrnn_vmc_step(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset,
-                          const double* couplings, int32_t* out_samples, double* out_eloc, double* moments) {
-    const int N = h->N;
-    const int W = (N + 31) / 32;
-    Maps m;
-    if (int rc = get_maps(h, &m)) return rc;
-    if (ns > max_chains_per_pass(h))
-        return h->fail(RNNWF_ERR_NOMEM, "rnnwf_vmc_step: %lld samples exceed the hidden-state budget; split the batch",
-                       (long long)ns);
-    if (int rc = ensure(h, h->bits, (size_t)W * ns * 4)) return rc;
-    if (int rc = upload_couplings(h, couplings, (size_t)N)) return rc;
-    if (int rc = eloc_on_device(h, ns, m, true, seed, step, offset, (const double*)h->coupl.p, couplings[N])) return rc;
-    if (out_samples) if (int rc = unpack_and_download(h, h->bits, ns, out_samples, m.pos_of_site)) return rc;
-    if (out_eloc) RNNWF_HIP(h, hipMemcpyAsync(out_eloc, h->eloc.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream));
-    h->last_ns = ns;              // bits, hs and eloc stay resident for rnnwf_vmc_gradient
-    h->last_has_ckpt = true;
-    return run_moments(h, h->eloc.p, ns, false, moments);
+const Family* rnnwf::mdrnn_family() {
+    static const Family f = {
+        "2D RNN", pack_image, log_prob_pass, nullptr, eloc_on_device, max_chains_per_pass, site_maps, nullptr,
+        1, 1,               // Jz per site; Bx
+        false, true, true,  // float64 E_loc; the base pass alone keeps every site's state; has a gradient
+    };
+    return &f;
 }
 
 // ---- gradient of the VMC cost (2DTFIM_2DRNN/Training2DRNN_2DTFIM.py:163-170) ----

@@ -20,44 +20,47 @@ int run_tfim_eloc(rnnwf_handle* h, const uint32_t* bits, const double* lpq, int6
 int run_parity_combine(rnnwf_handle* h, const double* a, const double* b, int64_t n, double* out);
 int run_parity_share(rnnwf_handle* h, double* lpF, double* lpR, int64_t n);      // in place: P_F / (P_F + P_R), P_R / (P_F + P_R)
 
-// ---- weight image ---------------------------------------------------------------------------------
-int model_pack_image(rnnwf_handle* h, std::vector<char>& img);  // dispatches to the family below
-int prnn_pack_image(rnnwf_handle* h, std::vector<char>& img);
-int crnn_pack_image(rnnwf_handle* h, std::vector<char>& img);
-int mdrnn_pack_image(rnnwf_handle* h, std::vector<char>& img);
-int lstm_pack_image(rnnwf_handle* h, std::vector<char>& img);
+// ---- one table per wave-function family -------------------------------------------------------------
+// What the families' host code does differently.  The public compute entry points (rnnwf_api.hip) run one driver
+// against it: chunk loop, copies back to the host, budget refusals and the resident-batch rule live there.
+struct Draw { uint64_t seed, step; int64_t offset; };     // where an entry point takes a Draw, nullptr = teacher-forced
+                                                          // on the spins the driver packed into h->bits
+struct Family {
+    const char* name;
+    int (*pack_image)(rnnwf_handle* h, std::vector<char>& img);
+    // base pass alone: log P of ns chains -> h->out_lp (spins drawn into h->bits when `draw`)
+    int (*base)(rnnwf_handle* h, int64_t ns, const Draw* draw);
+    // parity model: h->out_lp <- log P symmetrised over the reversed chains of the spins in h->samples_i32; nullptr for the others
+    int (*symmetrise)(rnnwf_handle* h, int64_t ns);
+    // checkpointed base pass -> flip / swap pass -> assembly: E_loc -> h->eloc (TFIM also the log-prob queue -> h->lpq).
+    // couplings: the caller's whole vector; its per-site part is already on the device (h->coupl)
+    int (*energy)(rnnwf_handle* h, int64_t ns, const Draw* draw, const double* couplings);
+    int64_t (*max_chains_per_pass)(rnnwf_handle* h);
+    // site order of the packed bits when it is not the caller's (MDRNN: the snake path); nullptr: the same
+    int (*site_maps)(rnnwf_handle* h, const int32_t** col_of_pos, const int32_t** pos_of_site);
+    void (*after_sync)(rnnwf_handle* h, int64_t ns);    // reads what the kernels left in pinned memory (cRNN: work totals); may be nullptr
+    int coupl_per_site;        // couplings per site held on the device (TFIM: Jz; J1-J2: J1, J2, Bz) ...
+    int coupl_tail;            // ... followed by this many scalars read on the host (TFIM: Bx; J1-J2: periodic, marshall)
+    bool complex_eloc;         // complex64 E_loc (else float64)
+    bool base_keeps_states;    // the base pass alone needs the state budget: log_prob runs in passes, sample refuses past it
+    bool has_gradient;         // rnnwf_vmc_step leaves its batch resident for rnnwf_vmc_gradient
+};
+// the tables are static locals of host functions: hipcc would emit a namespace-scope const table for the device as well
+const Family* gru_family();     // prnn.hip: GRU1D, GRU1D_PARITY, GRU1D_F64
+const Family* crnn_family();    // crnn.hip: CRNN_U1
+const Family* mdrnn_family();   // mdrnn.hip: MDRNN2D
+const Family* lstm_family();    // lstm.hip: LSTM1D_F64
 
-// ---- positive GRU RNN (prnn.hip): models GRU1D, GRU1D_PARITY, GRU1D_F64 ---------------------------
-int prnn_sample(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, int32_t* out, double* out_log);
-int prnn_log_prob(rnnwf_handle* h, const int32_t* samples, int64_t B, double* out);
-int prnn_tfim_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, int Nx, int Ny, const double* Jz, double Bx,
-                   double* eloc, double* log_probs);
-int prnn_vmc_step(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, const double* couplings,
-                  int32_t* out_samples, double* out_eloc, double* moments);
+// the fused VMC step behind rnnwf_vmc_step and rnnwf_train_steps (rnnwf_api.hip); out_samples, out_eloc, moments may be nullptr
+int vmc_step(rnnwf_handle* h, int64_t ns, const Draw& draw, const double* couplings, int32_t* out_samples, void* out_eloc,
+             double* moments);
+// RNNWF_ERR_INVALID ("<what>: no gradient for the ...") for a family without one
+int require_gradient(rnnwf_handle* h, const char* what);
 
-// ---- LSTM over the raster path (lstm.hip): model LSTM1D_F64 -----------------------------------------
-int lstm_sample(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, int32_t* out, double* out_log);
-int lstm_log_prob(rnnwf_handle* h, const int32_t* samples, int64_t B, double* out);
-int lstm_tfim_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* Jz, double Bx, double* eloc,
-                   double* log_probs);
-int lstm_vmc_step(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, const double* couplings,
-                  int32_t* out_samples, double* out_eloc, double* moments);
-
-// ---- complex GRU RNN with U(1) mask (crnn.hip) -----------------------------------------------------
-int crnn_sample(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, int32_t* out, double* out_log);
+// complex RNN only (crnn.hip): amplitudes and J1-J2 local energies on caller-supplied samples
 int crnn_log_amp(rnnwf_handle* h, const int32_t* samples, int64_t B, float* out_re_im, double* out_logp);
 int crnn_j1j2_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* J1, const double* J2,
                    const double* Bz, int periodic, int marshall, float* eloc, int64_t* ncon);
-int crnn_vmc_step(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, const double* couplings,
-                  int32_t* out_samples, float* out_eloc, double* moments);
-
-// ---- 2D MDRNN (mdrnn.hip) ---------------------------------------------------------------------------
-int mdrnn_sample(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, int32_t* out, double* out_log);
-int mdrnn_log_prob(rnnwf_handle* h, const int32_t* samples, int64_t B, double* out);
-int mdrnn_tfim_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* Jz, double Bx, double* eloc,
-                    double* log_probs);
-int mdrnn_vmc_step(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, const double* couplings,
-                   int32_t* out_samples, double* out_eloc, double* moments);
 
 // ---- bf16x3 engine (split.hip; compiled without SLP packing) -----------------------------------------
 struct PrnnArgs;
@@ -95,11 +98,6 @@ bool base_bf_available(const rnnwf_handle* h);
 int base_bf_pack(rnnwf_handle* h);
 int prnn_base_coop_bf(rnnwf_handle* h, const PrnnArgs& a);
 int crnn_base_coop_bf(rnnwf_handle* h, const CrnnArgs& a);
-
-// teacher-forced base pass with checkpoints on caller-supplied samples (rnnwf_load_batch)
-int prnn_load_batch(rnnwf_handle* h, const int32_t* samples, int64_t ns);
-int crnn_load_batch(rnnwf_handle* h, const int32_t* samples, int64_t ns);
-int mdrnn_load_batch(rnnwf_handle* h, const int32_t* samples, int64_t ns);
 
 // ---- gradient (grad.hip) ---------------------------------------------------------------------------
 int mdrnn_vmc_gradient(rnnwf_handle* h, double mean_energy, double norm);

@@ -1,5 +1,5 @@
-// prnn.hip - host side of the positive GRU RNN wave function (models GRU1D, GRU1D_PARITY, GRU1D_F64):
-// sample / log_probability / fused TFIM local energies / fused VMC step.
+// prnn.hip - host side of the positive GRU RNN wave function (models GRU1D, GRU1D_PARITY, GRU1D_F64): weight image, base pass,
+// fused TFIM local energies (the driver of the entry points is rnnwf_api.hip's, through gru_family).
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -14,7 +14,6 @@ using namespace rnnwf;
 namespace {
 
 constexpr size_t kHckBudget = (size_t)48 << 30;  // bytes of hidden-state checkpoints per pass
-constexpr int64_t kLogProbChunk = (int64_t)1 << 20;
 
 template <typename T, int NFULL, int WAVES>
 struct Launch {
@@ -267,14 +266,15 @@ int flip_pass(rnnwf_handle* h, const PrnnArgs& a, int64_t ns) {
     return 0;
 }
 
-// Fused local energies of ns chains whose packed spins are already in h->bits (and, for the parity
-// model, reversed in h->bits2): base pass with checkpoints -> flip pass -> assembly.  Leaves E_loc in
-// h->eloc and the log-prob queue in h->lpq.
-int eloc_on_device(rnnwf_handle* h, int64_t ns, bool sampling, uint64_t seed, uint64_t step, int64_t offset,
-                   int Nx, int Ny, const double* Jz_dev, double Bx) {
+// Fused local energies of ns chains whose packed spins are in h->bits (drawn into it when `d`): base pass with checkpoints ->
+// flip pass -> assembly.  Leaves E_loc in h->eloc and the log-prob queue in h->lpq.  The parity model also runs the reversed chains,
+// packed into h->bits2 from h->samples_i32 (the caller's upload, or the drawn spins unpacked there).
+int eloc_on_device(rnnwf_handle* h, int64_t ns, const Draw* d, const double* couplings) {
     const int N = h->N;
     const int64_t nsb = (ns + kChains - 1) / kChains;
     const bool parity = h->model == RNNWF_MODEL_GRU1D_PARITY;
+    const bool raster = h->model == RNNWF_MODEL_GRU1D_F64;     // the 1D models' handles hold (Nx, Ny) = (N, 1); the assembly takes (1, N)
+    const double Bx = couplings[N];
     const size_t hck_bytes = (size_t)(h->NL > 1 ? N : std::max(N - 1, 1)) * nsb * hck_bytes_per_block(h);
     if (int rc = ensure(h, h->lpq, (size_t)(N + 1) * ns * 8)) return rc;
     if (int rc = ensure(h, h->eloc, (size_t)ns * 8)) return rc;
@@ -284,8 +284,7 @@ int eloc_on_device(rnnwf_handle* h, int64_t ns, bool sampling, uint64_t seed, ui
     a.bits = (uint32_t*)h->bits.p;
     a.hck = h->hck.p;
     a.lpq = (double*)h->lpq.p;
-    a.sampling = sampling ? 1 : 0;
-    a.seed = seed; a.step = step; a.sample_offset = offset;
+    if (d) { a.sampling = 1; a.seed = d->seed; a.step = d->step; a.sample_offset = d->offset; }
     if (int rc = launch_base(h, a)) return rc;
     if (Bx != 0.0 && N > 1) {
         a.ntiles = (int64_t)(N - 1) * nsb;
@@ -295,10 +294,9 @@ int eloc_on_device(rnnwf_handle* h, int64_t ns, bool sampling, uint64_t seed, ui
     }
     if (parity) {
         // second direction on the reversed chains, then log(0.5 (e^a + e^b)) row by row
-        if (sampling) {  // reversed bits from the freshly drawn spins
+        if (d)
             if (int rc = unpack_device(h, h->bits, ns, nullptr)) return rc;
-            if (int rc = pack_device(h, ns, h->bits2, 1, nullptr)) return rc;
-        }
+        if (int rc = pack_device(h, ns, h->bits2, 1, nullptr)) return rc;
         if (int rc = ensure_reverse_map(h)) return rc;
         if (int rc = ensure(h, h->lpq2, (size_t)(N + 1) * ns * 8)) return rc;
         PrnnArgs b = base_args(h, ns);
@@ -314,8 +312,30 @@ int eloc_on_device(rnnwf_handle* h, int64_t ns, bool sampling, uint64_t seed, ui
         if (int rc = run_parity_combine(h, (const double*)h->lpq.p, (const double*)h->lpq2.p, (int64_t)(N + 1) * ns,
                                         (double*)h->lpq.p)) return rc;
     }
-    return run_tfim_eloc(h, (const uint32_t*)h->bits.p, (const double*)h->lpq.p, ns, Nx, Ny, nullptr, Jz_dev, Bx,
-                         (double*)h->eloc.p);
+    return run_tfim_eloc(h, (const uint32_t*)h->bits.p, (const double*)h->lpq.p, ns, raster ? h->Nx : 1, raster ? h->Ny : N,
+                         nullptr, (const double*)h->coupl.p, Bx, (double*)h->eloc.p);
+}
+
+// base pass alone: log P of every chain -> h->out_lp (the spins drawn into h->bits when `d`)
+int log_prob_pass(rnnwf_handle* h, int64_t ns, const Draw* d) {
+    if (int rc = ensure(h, h->out_lp, (size_t)ns * 8)) return rc;
+    PrnnArgs a = base_args(h, ns);
+    a.bits = (uint32_t*)h->bits.p;
+    a.out_lp = (double*)h->out_lp.p;
+    if (d) { a.sampling = 1; a.seed = d->seed; a.step = d->step; a.sample_offset = d->offset; }
+    return launch_base(h, a);
+}
+
+// parity model: log P of the reversed chains of the spins in h->samples_i32, combined with h->out_lp into the symmetrised one
+int symmetrise(rnnwf_handle* h, int64_t ns) {
+    if (h->model != RNNWF_MODEL_GRU1D_PARITY) return 0;
+    if (int rc = pack_device(h, ns, h->bits2, 1, nullptr)) return rc;
+    if (int rc = ensure(h, h->out_lp2, (size_t)ns * 8)) return rc;
+    PrnnArgs b = base_args(h, ns);
+    b.bits = (uint32_t*)h->bits2.p;
+    b.out_lp = (double*)h->out_lp2.p;
+    if (int rc = launch_base(h, b)) return rc;
+    return run_parity_combine(h, (const double*)h->out_lp.p, (const double*)h->out_lp2.p, ns, (double*)h->out_lp.p);
 }
 
 int64_t max_chains_per_pass(rnnwf_handle* h) {
@@ -326,19 +346,7 @@ int64_t max_chains_per_pass(rnnwf_handle* h) {
     return blocks * kChains;
 }
 
-}  // namespace
-
-// Teacher-forced base pass with checkpoints over the resident spins (h->bits, or the reversed ones in h->bits2), log P of every
-// chain to out_lp: what a backward pass of the parity-symmetric model needs per direction (grad.hip).
-int rnnwf::prnn_teacher_base(rnnwf_handle* h, int64_t ns, bool reversed, double* out_lp) {
-    PrnnArgs a = base_args(h, ns);
-    a.bits = (uint32_t*)(reversed ? h->bits2.p : h->bits.p);
-    a.hck = h->hck.p;
-    a.out_lp = out_lp;
-    return launch_base(h, a);
-}
-
-int rnnwf::prnn_pack_image(rnnwf_handle* h, std::vector<char>& img) {
+int pack_image(rnnwf_handle* h, std::vector<char>& img) {
     // flip-pass engine: bf16x3 on the matrix core for the f32 models (RNNWF_ENGINE=f32 keeps the f32-input MFMA
     // everywhere; above 68 units the w3 fragments of the image are read through L2, split_stream.hip); the base pass, sampling and log_probability always run the f32-MFMA kernels
     // stacked layers: 37..50 units run as a pipeline of bf16x3 kernels, one per layer (split.hip: prnn_stack_flip); other widths
@@ -358,120 +366,23 @@ int rnnwf::prnn_pack_image(rnnwf_handle* h, std::vector<char>& img) {
     return h->fail(RNNWF_ERR_INVALID, "no pRNN kernel for NFULL=%d f64=%d", h->NFULL, (int)h->f64);
 }
 
-int rnnwf::prnn_log_prob(rnnwf_handle* h, const int32_t* samples, int64_t B, double* out) {
-    const int N = h->N;
-    h->last_ns = 0;
-    const bool parity = h->model == RNNWF_MODEL_GRU1D_PARITY;
-    for (int64_t off = 0; off < B; off += kLogProbChunk) {
-        const int64_t nb = std::min(kLogProbChunk, B - off);
-        if (int rc = upload_and_pack(h, samples + off * N, nb, h->bits, 0, nullptr)) return rc;
-        if (int rc = ensure(h, h->out_lp, (size_t)nb * 8)) return rc;
-        PrnnArgs a = base_args(h, nb);
-        a.bits = (uint32_t*)h->bits.p;
-        a.out_lp = (double*)h->out_lp.p;
-        if (int rc = launch_base(h, a)) return rc;
-        if (parity) {
-            if (int rc = pack_device(h, nb, h->bits2, 1, nullptr)) return rc;
-            if (int rc = ensure(h, h->out_lp2, (size_t)nb * 8)) return rc;
-            a.bits = (uint32_t*)h->bits2.p;
-            a.out_lp = (double*)h->out_lp2.p;
-            if (int rc = launch_base(h, a)) return rc;
-            if (int rc = run_parity_combine(h, (const double*)h->out_lp.p, (const double*)h->out_lp2.p, nb,
-                                            (double*)h->out_lp.p)) return rc;
-        }
-        RNNWF_HIP(h, hipMemcpyAsync(out + off, h->out_lp.p, (size_t)nb * 8, hipMemcpyDeviceToHost, h->stream));
-        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return RNNWF_OK;
-}
+}  // namespace
 
-int rnnwf::prnn_sample(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset, int32_t* out,
-                       double* out_log) {
-    const int N = h->N;
-    const int W = (N + 31) / 32;
-    h->last_ns = 0;
-    if (int rc = ensure(h, h->bits, (size_t)W * ns * 4)) return rc;
-    if (int rc = ensure(h, h->out_lp, (size_t)ns * 8)) return rc;
+// Teacher-forced base pass with checkpoints over the resident spins (h->bits, or the reversed ones in h->bits2), log P of every
+// chain to out_lp: what a backward pass of the parity-symmetric model needs per direction (grad.hip).
+int rnnwf::prnn_teacher_base(rnnwf_handle* h, int64_t ns, bool reversed, double* out_lp) {
     PrnnArgs a = base_args(h, ns);
-    a.bits = (uint32_t*)h->bits.p;
-    a.out_lp = (double*)h->out_lp.p;
-    a.sampling = 1;
-    a.seed = seed; a.step = step; a.sample_offset = offset;
-    if (int rc = launch_base(h, a)) return rc;
-    if (int rc = unpack_and_download(h, h->bits, ns, out, nullptr)) return rc;
-    if (out_log) {
-        if (h->model == RNNWF_MODEL_GRU1D_PARITY) {  // symmetrised probability of the drawn configurations
-            if (int rc = pack_device(h, ns, h->bits2, 1, nullptr)) return rc;
-            if (int rc = ensure(h, h->out_lp2, (size_t)ns * 8)) return rc;
-            PrnnArgs b = base_args(h, ns);
-            b.bits = (uint32_t*)h->bits2.p;
-            b.out_lp = (double*)h->out_lp2.p;
-            if (int rc = launch_base(h, b)) return rc;
-            if (int rc = run_parity_combine(h, (const double*)h->out_lp.p, (const double*)h->out_lp2.p, ns,
-                                            (double*)h->out_lp.p)) return rc;
-        }
-        RNNWF_HIP(h, hipMemcpyAsync(out_log, h->out_lp.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream));
-    }
-    RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    return RNNWF_OK;
+    a.bits = (uint32_t*)(reversed ? h->bits2.p : h->bits.p);
+    a.hck = h->hck.p;
+    a.out_lp = out_lp;
+    return launch_base(h, a);
 }
 
-int rnnwf::prnn_tfim_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, int Nx, int Ny, const double* Jz,
-                          double Bx, double* eloc, double* log_probs) {
-    const int N = h->N;
-    h->last_ns = 0;
-    h->call_ns = ns;
-    if (int rc = upload_couplings(h, Jz, (size_t)N)) return rc;
-    const int64_t chunk = max_chains_per_pass(h);
-    for (int64_t off = 0; off < ns; off += chunk) {
-        const int64_t nb = std::min(chunk, ns - off);
-        if (int rc = upload_and_pack(h, samples + off * N, nb, h->bits, 0, nullptr)) return rc;
-        if (h->model == RNNWF_MODEL_GRU1D_PARITY)
-            if (int rc = pack_device(h, nb, h->bits2, 1, nullptr)) return rc;
-        if (int rc = eloc_on_device(h, nb, false, 0, 0, 0, Nx, Ny, (const double*)h->coupl.p, Bx)) return rc;
-        RNNWF_HIP(h, hipMemcpyAsync(eloc + off, h->eloc.p, (size_t)nb * 8, hipMemcpyDeviceToHost, h->stream));
-        if (log_probs)
-            RNNWF_HIP(h, hipMemcpy2DAsync(log_probs + off, (size_t)ns * 8, h->lpq.p, (size_t)nb * 8, (size_t)nb * 8,
-                                          (size_t)N + 1, hipMemcpyDeviceToHost, h->stream));
-        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    return RNNWF_OK;
-}
-
-// Teacher-forced base pass with checkpoints on caller-supplied samples (no flips, no energies): what the gradient needs
-// resident besides E_loc, which rnnwf_load_batch uploads afterwards.
-int rnnwf::prnn_load_batch(rnnwf_handle* h, const int32_t* samples, int64_t ns) {
-    const int N = h->N;
-    if (ns > max_chains_per_pass(h))
-        return h->fail(RNNWF_ERR_NOMEM, "rnnwf_load_batch: %lld samples exceed the checkpoint budget; split the batch", (long long)ns);
-    h->call_ns = ns;
-    const std::vector<double> zeros((size_t)N, 0.0);
-    if (int rc = upload_couplings(h, zeros.data(), (size_t)N)) return rc;
-    if (int rc = upload_and_pack(h, samples, ns, h->bits, 0, nullptr)) return rc;
-    if (h->model == RNNWF_MODEL_GRU1D_PARITY)
-        if (int rc = pack_device(h, ns, h->bits2, 1, nullptr)) return rc;
-    const int Nx = h->model == RNNWF_MODEL_GRU1D_F64 ? h->Nx : 1;
-    const int Ny = h->model == RNNWF_MODEL_GRU1D_F64 ? h->Ny : N;
-    return eloc_on_device(h, ns, false, 0, 0, 0, Nx, Ny, (const double*)h->coupl.p, 0.0);
-}
-
-int rnnwf::prnn_vmc_step(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset,
-                         const double* couplings, int32_t* out_samples, double* out_eloc, double* moments) {
-    const int N = h->N;
-    const int W = (N + 31) / 32;
-    if (ns > max_chains_per_pass(h))
-        return h->fail(RNNWF_ERR_NOMEM, "rnnwf_vmc_step: %lld samples exceed the checkpoint budget; split the batch",
-                       (long long)ns);
-    h->call_ns = ns;
-    if (int rc = ensure(h, h->bits, (size_t)W * ns * 4)) return rc;
-    if (int rc = upload_couplings(h, couplings, (size_t)N)) return rc;
-    const double Bx = couplings[N];
-    const int Nx = h->model == RNNWF_MODEL_GRU1D_F64 ? h->Nx : 1;
-    const int Ny = h->model == RNNWF_MODEL_GRU1D_F64 ? h->Ny : N;
-    if (int rc = eloc_on_device(h, ns, true, seed, step, offset, Nx, Ny, (const double*)h->coupl.p, Bx)) return rc;
-    if (out_samples) if (int rc = unpack_and_download(h, h->bits, ns, out_samples, nullptr)) return rc;
-    if (out_eloc) RNNWF_HIP(h, hipMemcpyAsync(out_eloc, h->eloc.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream));
-    h->last_ns = ns;              // bits, hck and eloc stay resident for rnnwf_vmc_gradient
-    h->last_has_ckpt = true;
-    return run_moments(h, h->eloc.p, ns, false, moments);
+const Family* rnnwf::gru_family() {
+    static const Family f = {
+        "GRU cell", pack_image, log_prob_pass, symmetrise, eloc_on_device, max_chains_per_pass, nullptr, nullptr,
+        1, 1,                // Jz per site; Bx
+        false, false, true,  // float64 E_loc; the base pass alone keeps no states; has a gradient
+    };
+    return &f;
 }

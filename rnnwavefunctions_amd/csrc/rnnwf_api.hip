@@ -1,5 +1,5 @@
-// rnnwf_api.hip - C ABI (include/rnnwf.h) over the gfx950 kernels: handle life cycle, parameters,
-// pRNN sample / log_prob / TFIM local energies, fused VMC step, timing.
+// rnnwf_api.hip - C ABI (include/rnnwf.h) over the gfx950 kernels: handle life cycle, parameters, the one driver of
+// sample / log_prob / TFIM local energies / fused VMC step / load_batch over every family's hooks (models.h), timing.
 #include <cstdlib>
 #include <algorithm>
 #include <cmath>
@@ -196,6 +196,8 @@ extern "C" int rnnwf_create(const rnnwf_config* cfg, rnnwf_handle** out) {
     rnnwf_handle* h = new rnnwf_handle();
     h->cfg = *cfg;
     h->model = cfg->model;
+    h->family = cfg->model == RNNWF_MODEL_MDRNN2D ? mdrnn_family() : cfg->model == RNNWF_MODEL_CRNN_U1 ? crnn_family()
+              : cfg->model == RNNWF_MODEL_LSTM1D_F64 ? lstm_family() : gru_family();
     h->f64 = cfg->model == RNNWF_MODEL_GRU1D_F64 || cfg->model == RNNWF_MODEL_MDRNN2D || cfg->model == RNNWF_MODEL_LSTM1D_F64;
     h->H = *std::max_element(cfg->units, cfg->units + cfg->num_layers);      // layers of unequal width are padded to the widest (handle.h: ParamSpec)
     h->Nx = cfg->nx;
@@ -413,7 +415,7 @@ extern "C" int rnnwf_commit_params(rnnwf_handle* h) {
     RNNWF_HIP(h, hipSetDevice(h->cfg.device));
     if (int rc = upload_reset(h)) return rc;      // the images travel through one pinned buffer, asynchronously (handle.h: upload)
     std::vector<char> img;
-    if (int rc = model_pack_image(h, img)) return rc;
+    if (int rc = h->family->pack_image(h, img)) return rc;
     if (int rc = ensure(h, h->wimg, img.size())) return rc;
     if (int rc = upload(h, h->wimg.p, img.data(), img.size())) return rc;
     h->committed = true;
@@ -519,40 +521,80 @@ int rnnwf::run_parity_share(rnnwf_handle* h, double* lpF, double* lpR, int64_t n
     return 0;
 }
 
-int rnnwf::model_pack_image(rnnwf_handle* h, std::vector<char>& img) {
-    if (h->model == RNNWF_MODEL_MDRNN2D) return mdrnn_pack_image(h, img);
-    if (h->model == RNNWF_MODEL_CRNN_U1) return crnn_pack_image(h, img);
-    if (h->model == RNNWF_MODEL_LSTM1D_F64) return lstm_pack_image(h, img);
-    return prnn_pack_image(h, img);
+// -------------------------------------------------------------------------------------------------
+// public compute entry points: one driver over the family's hooks (models.h)
+// -------------------------------------------------------------------------------------------------
+// Resident batch (h->last_ns): what rnnwf_vmc_gradient reuses.  An entry point validates first, so that a refused call leaves an
+// earlier batch usable; it clears h->last_ns before it starts overwriting h->bits / h->hck / h->eloc and sets it again only once
+// the new batch is complete.
+constexpr int64_t kLogProbChunk = (int64_t)1 << 20;   // chains per base pass where the pass keeps no states
+
+int rnnwf::require_gradient(rnnwf_handle* h, const char* what) {
+    if (h->family->has_gradient) return 0;
+    return h->fail(RNNWF_ERR_INVALID, "%s: no gradient for the %s", what, h->family->name);
 }
 
-// -------------------------------------------------------------------------------------------------
-// public compute entry points: dispatch on the model
-// -------------------------------------------------------------------------------------------------
-static bool is_prnn(const rnnwf_handle* h) {
-    return h->model == RNNWF_MODEL_GRU1D || h->model == RNNWF_MODEL_GRU1D_PARITY || h->model == RNNWF_MODEL_GRU1D_F64;
+static int site_maps(rnnwf_handle* h, const int32_t** col_of_pos, const int32_t** pos_of_site) {
+    *col_of_pos = *pos_of_site = nullptr;
+    return h->family->site_maps ? h->family->site_maps(h, col_of_pos, pos_of_site) : 0;
+}
+
+static int64_t n_couplings(const rnnwf_handle* h) { return (int64_t)h->family->coupl_per_site * h->N + h->family->coupl_tail; }
+
+// the batch just computed stays on the device (h->bits, h->hck, h->eloc) for rnnwf_vmc_gradient
+static void keep_resident(rnnwf_handle* h, int64_t ns) {
+    if (!h->family->has_gradient) return;
+    h->last_ns = ns;
+    h->last_has_ckpt = true;
+}
+
+static int refuse_past_budget(rnnwf_handle* h, int64_t ns, const char* what) {
+    if (ns <= h->family->max_chains_per_pass(h)) return 0;
+    return h->fail(RNNWF_ERR_NOMEM, "%s: %lld samples exceed the state budget of one pass; split the batch", what, (long long)ns);
 }
 
 extern "C" int rnnwf_sample(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset,
                             int32_t* out_samples, double* out_log) {
     if (int rc = check_ready(h)) return rc;
     if (ns < 1 || !out_samples) return h->fail(RNNWF_ERR_INVALID, "rnnwf_sample: numsamples must be >= 1 and out_samples non-null");
-    if (is_prnn(h)) return prnn_sample(h, ns, seed, step, offset, out_samples, out_log);
-    if (h->model == RNNWF_MODEL_CRNN_U1) return crnn_sample(h, ns, seed, step, offset, out_samples, out_log);
-    if (h->model == RNNWF_MODEL_LSTM1D_F64) return lstm_sample(h, ns, seed, step, offset, out_samples, out_log);
-    if (h->model == RNNWF_MODEL_MDRNN2D) return mdrnn_sample(h, ns, seed, step, offset, out_samples, out_log);
-    return h->fail(RNNWF_ERR_INVALID, "rnnwf_sample: unknown model %d", h->model);
+    const Family& f = *h->family;
+    if (f.base_keeps_states)
+        if (int rc = refuse_past_budget(h, ns, "rnnwf_sample")) return rc;
+    h->last_ns = 0;
+    const int32_t *col_of_pos, *pos_of_site;
+    if (int rc = site_maps(h, &col_of_pos, &pos_of_site)) return rc;
+    if (int rc = ensure(h, h->bits, (size_t)(h->N + 31) / 32 * ns * 4)) return rc;
+    const Draw d{seed, step, offset};
+    if (int rc = f.base(h, ns, &d)) return rc;
+    if (int rc = unpack_and_download(h, h->bits, ns, out_samples, pos_of_site)) return rc;
+    if (out_log) {
+        if (f.symmetrise)
+            if (int rc = f.symmetrise(h, ns)) return rc;
+        RNNWF_HIP(h, hipMemcpyAsync(out_log, h->out_lp.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    RNNWF_HIP(h, hipStreamSynchronize(h->stream));
+    return RNNWF_OK;
 }
 
 extern "C" int rnnwf_log_prob(rnnwf_handle* h, const int32_t* samples, int64_t B, double* out) {
     if (int rc = check_ready(h)) return rc;
     if (B < 0 || (B > 0 && (!samples || !out))) return h->fail(RNNWF_ERR_INVALID, "rnnwf_log_prob: bad arguments");
     if (B == 0) return RNNWF_OK;
-    if (is_prnn(h)) return prnn_log_prob(h, samples, B, out);
-    if (h->model == RNNWF_MODEL_CRNN_U1) return crnn_log_amp(h, samples, B, nullptr, out);
-    if (h->model == RNNWF_MODEL_LSTM1D_F64) return lstm_log_prob(h, samples, B, out);
-    if (h->model == RNNWF_MODEL_MDRNN2D) return mdrnn_log_prob(h, samples, B, out);
-    return h->fail(RNNWF_ERR_INVALID, "rnnwf_log_prob: unknown model %d", h->model);
+    const Family& f = *h->family;
+    h->last_ns = 0;
+    const int32_t *col_of_pos, *pos_of_site;
+    if (int rc = site_maps(h, &col_of_pos, &pos_of_site)) return rc;
+    const int64_t chunk = f.base_keeps_states ? f.max_chains_per_pass(h) : kLogProbChunk;
+    for (int64_t off = 0; off < B; off += chunk) {
+        const int64_t nb = std::min(chunk, B - off);
+        if (int rc = upload_and_pack(h, samples + off * h->N, nb, h->bits, 0, col_of_pos)) return rc;
+        if (int rc = f.base(h, nb, nullptr)) return rc;
+        if (f.symmetrise)
+            if (int rc = f.symmetrise(h, nb)) return rc;
+        RNNWF_HIP(h, hipMemcpyAsync(out + off, h->out_lp.p, (size_t)nb * 8, hipMemcpyDeviceToHost, h->stream));
+        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return RNNWF_OK;
 }
 
 extern "C" int rnnwf_log_amp(rnnwf_handle* h, const int32_t* samples, int64_t B, float* out_re_im) {
@@ -563,23 +605,47 @@ extern "C" int rnnwf_log_amp(rnnwf_handle* h, const int32_t* samples, int64_t B,
     return crnn_log_amp(h, samples, B, out_re_im, nullptr);
 }
 
+// TFIM local energies (and optionally the (N + 1) x ns log-prob queue) of caller-supplied samples, in passes under the state budget
+static int tfim_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* Jz, double Bx, double* eloc,
+                     double* log_probs) {
+    const int N = h->N;
+    std::vector<double> couplings(Jz, Jz + N);
+    couplings.push_back(Bx);
+    h->last_ns = 0;
+    h->call_ns = ns;
+    const int32_t *col_of_pos, *pos_of_site;
+    if (int rc = site_maps(h, &col_of_pos, &pos_of_site)) return rc;
+    if (int rc = upload_couplings(h, Jz, (size_t)N)) return rc;
+    const int64_t chunk = h->family->max_chains_per_pass(h);
+    for (int64_t off = 0; off < ns; off += chunk) {
+        const int64_t nb = std::min(chunk, ns - off);
+        if (int rc = upload_and_pack(h, samples + off * N, nb, h->bits, 0, col_of_pos)) return rc;
+        if (int rc = h->family->energy(h, nb, nullptr, couplings.data())) return rc;
+        RNNWF_HIP(h, hipMemcpyAsync(eloc + off, h->eloc.p, (size_t)nb * 8, hipMemcpyDeviceToHost, h->stream));
+        if (log_probs)
+            RNNWF_HIP(h, hipMemcpy2DAsync(log_probs + off, (size_t)ns * 8, h->lpq.p, (size_t)nb * 8, (size_t)nb * 8,
+                                          (size_t)N + 1, hipMemcpyDeviceToHost, h->stream));
+        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    return RNNWF_OK;
+}
+
 extern "C" int rnnwf_tfim_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* Jz, double Bx,
                                double* eloc, double* log_probs) {
     if (int rc = check_ready(h)) return rc;
     if (h->model != RNNWF_MODEL_GRU1D && h->model != RNNWF_MODEL_GRU1D_PARITY)
         return h->fail(RNNWF_ERR_INVALID, "rnnwf_tfim_eloc: needs a 1D positive RNN handle");
     if (ns < 1 || !samples || !Jz || !eloc) return h->fail(RNNWF_ERR_INVALID, "rnnwf_tfim_eloc: bad arguments");
-    return prnn_tfim_eloc(h, samples, ns, 1, h->N, Jz, Bx, eloc, log_probs);
+    return tfim_eloc(h, samples, ns, Jz, Bx, eloc, log_probs);
 }
 
 extern "C" int rnnwf_tfim2d_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* Jz, double Bx,
                                  double* eloc, double* log_probs) {
     if (int rc = check_ready(h)) return rc;
     if (ns < 1 || !samples || !Jz || !eloc) return h->fail(RNNWF_ERR_INVALID, "rnnwf_tfim2d_eloc: bad arguments");
-    if (h->model == RNNWF_MODEL_GRU1D_F64) return prnn_tfim_eloc(h, samples, ns, h->Nx, h->Ny, Jz, Bx, eloc, log_probs);
-    if (h->model == RNNWF_MODEL_MDRNN2D) return mdrnn_tfim_eloc(h, samples, ns, Jz, Bx, eloc, log_probs);
-    if (h->model == RNNWF_MODEL_LSTM1D_F64) return lstm_tfim_eloc(h, samples, ns, Jz, Bx, eloc, log_probs);
-    return h->fail(RNNWF_ERR_INVALID, "rnnwf_tfim2d_eloc: needs a 2D handle (GRU1D_F64, MDRNN2D or LSTM1D_F64)");
+    if (h->model != RNNWF_MODEL_GRU1D_F64 && h->model != RNNWF_MODEL_MDRNN2D && h->model != RNNWF_MODEL_LSTM1D_F64)
+        return h->fail(RNNWF_ERR_INVALID, "rnnwf_tfim2d_eloc: needs a 2D handle (GRU1D_F64, MDRNN2D or LSTM1D_F64)");
+    return tfim_eloc(h, samples, ns, Jz, Bx, eloc, log_probs);
 }
 
 extern "C" int rnnwf_j1j2_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* J1, const double* J2,
@@ -590,44 +656,59 @@ extern "C" int rnnwf_j1j2_eloc(rnnwf_handle* h, const int32_t* samples, int64_t 
     return crnn_j1j2_eloc(h, samples, ns, J1, J2, Bz, periodic, marshall, eloc, ncon);
 }
 
+// moments == nullptr (device-resident training, train.hip): nothing synchronises, the moments stay on the device
+int rnnwf::vmc_step(rnnwf_handle* h, int64_t ns, const Draw& draw, const double* couplings, int32_t* out_samples, void* out_eloc,
+                    double* moments) {
+    const Family& f = *h->family;
+    if (int rc = refuse_past_budget(h, ns, "rnnwf_vmc_step")) return rc;
+    h->last_ns = 0;
+    h->call_ns = ns;
+    const int32_t *col_of_pos, *pos_of_site;
+    if (int rc = site_maps(h, &col_of_pos, &pos_of_site)) return rc;
+    if (int rc = ensure(h, h->bits, (size_t)(h->N + 31) / 32 * ns * 4)) return rc;
+    if (int rc = upload_couplings(h, couplings, (size_t)f.coupl_per_site * h->N)) return rc;
+    if (int rc = f.energy(h, ns, &draw, couplings)) return rc;
+    if (out_samples)
+        if (int rc = unpack_and_download(h, h->bits, ns, out_samples, pos_of_site)) return rc;
+    if (out_eloc)                                         // float64 or complex64: 8 bytes per sample
+        RNNWF_HIP(h, hipMemcpyAsync(out_eloc, h->eloc.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream));
+    if (int rc = run_moments(h, h->eloc.p, ns, f.complex_eloc, moments)) return rc;
+    if (moments && f.after_sync) f.after_sync(h, ns);
+    keep_resident(h, ns);
+    return RNNWF_OK;
+}
+
 extern "C" int rnnwf_vmc_step(rnnwf_handle* h, int64_t ns, uint64_t seed, uint64_t step, int64_t offset,
-                              const double* couplings, int64_t n_couplings, int32_t* out_samples, void* out_eloc,
+                              const double* couplings, int64_t n_coupl, int32_t* out_samples, void* out_eloc,
                               double* moments) {
     if (int rc = check_ready(h)) return rc;
     if (ns < 1 || !couplings || !moments) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_step: bad arguments");
-    if (is_prnn(h)) {
-        if (n_couplings != h->N + 1) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_step: TFIM needs N+1 couplings (Jz, Bx)");
-        return prnn_vmc_step(h, ns, seed, step, offset, couplings, out_samples, (double*)out_eloc, moments);
-    }
-    if (h->model == RNNWF_MODEL_MDRNN2D) {
-        if (n_couplings != h->N + 1) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_step: TFIM needs Nx*Ny+1 couplings (Jz, Bx)");
-        return mdrnn_vmc_step(h, ns, seed, step, offset, couplings, out_samples, (double*)out_eloc, moments);
-    }
-    if (h->model == RNNWF_MODEL_LSTM1D_F64) {
-        if (n_couplings != h->N + 1) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_step: TFIM needs Nx*Ny+1 couplings (Jz, Bx)");
-        return lstm_vmc_step(h, ns, seed, step, offset, couplings, out_samples, (double*)out_eloc, moments);
-    }
-    if (h->model != RNNWF_MODEL_CRNN_U1) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_step: unknown model %d", h->model);
-    if (n_couplings != 3 * h->N + 2) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_step: J1J2 needs 3N+2 couplings");
-    return crnn_vmc_step(h, ns, seed, step, offset, couplings, out_samples, (float*)out_eloc, moments);
+    if (n_coupl != n_couplings(h))
+        return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_step: the %s takes %lld couplings, not %lld", h->family->name,
+                       (long long)n_couplings(h), (long long)n_coupl);
+    return vmc_step(h, ns, Draw{seed, step, offset}, couplings, out_samples, out_eloc, moments);
 }
 
+// Teacher-forced base pass with checkpoints on caller-supplied samples (no bonds, no flips) plus the caller's E_loc: the batch
+// the gradient reuses.
 extern "C" int rnnwf_load_batch(rnnwf_handle* h, const int32_t* samples, int64_t ns, const void* eloc) {
     if (int rc = check_ready(h)) return rc;
-    if (h->model == RNNWF_MODEL_LSTM1D_F64) return h->fail(RNNWF_ERR_INVALID, "rnnwf_load_batch: no gradient for the LSTM cell");
+    if (int rc = require_gradient(h, "rnnwf_load_batch")) return rc;
     if (ns < 1 || !samples || !eloc) return h->fail(RNNWF_ERR_INVALID, "rnnwf_load_batch: bad arguments");
+    if (int rc = refuse_past_budget(h, ns, "rnnwf_load_batch")) return rc;
     h->last_ns = 0;
-    int rc;
-    if (is_prnn(h)) rc = prnn_load_batch(h, samples, ns);
-    else if (h->model == RNNWF_MODEL_CRNN_U1) rc = crnn_load_batch(h, samples, ns);
-    else if (h->model == RNNWF_MODEL_MDRNN2D) rc = mdrnn_load_batch(h, samples, ns);
-    else return h->fail(RNNWF_ERR_INVALID, "rnnwf_load_batch: unknown model %d", h->model);
-    if (rc) return rc;
+    h->call_ns = ns;
+    const Family& f = *h->family;
+    const std::vector<double> zeros((size_t)n_couplings(h), 0.0);
+    if (int rc = upload_couplings(h, zeros.data(), (size_t)f.coupl_per_site * h->N)) return rc;
+    const int32_t *col_of_pos, *pos_of_site;
+    if (int rc = site_maps(h, &col_of_pos, &pos_of_site)) return rc;
+    if (int rc = upload_and_pack(h, samples, ns, h->bits, 0, col_of_pos)) return rc;
+    if (int rc = f.energy(h, ns, nullptr, zeros.data())) return rc;
     const size_t bytes = (size_t)ns * 8;                  // float64 per sample, or complex64 = two float32 per sample
     RNNWF_HIP(h, hipMemcpyAsync(h->eloc.p, eloc, bytes, hipMemcpyHostToDevice, h->stream));
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    h->last_ns = ns;
-    h->last_has_ckpt = true;
+    keep_resident(h, ns);
     return RNNWF_OK;
 }
 

@@ -173,7 +173,7 @@ int add_image(rnnwf_handle* h, DevBuf* target, Fn&& run_packer) {
 
 int build(rnnwf_handle* h) {
     TrainState& t = h->train;
-    if (h->model == RNNWF_MODEL_LSTM1D_F64) return h->fail(RNNWF_ERR_INVALID, "device-resident training: no gradient for the LSTM cell");
+    if (int rc = require_gradient(h, "device-resident training")) return rc;
     if (t.built) return t.supported ? 0 : h->fail(RNNWF_ERR_INVALID, "device-resident training is not available for this model: %s", t.why.c_str());
     t.built = true;
     const bool md = h->model == RNNWF_MODEL_MDRNN2D;
@@ -364,7 +364,7 @@ int rnnwf::train_sync_params_to_host(rnnwf_handle* h) {
 }
 
 extern "C" int rnnwf_device_training_supported(rnnwf_handle* h) {
-    if (!h || !h->committed || h->model == RNNWF_MODEL_LSTM1D_F64) return 0;
+    if (!h || !h->committed) return 0;
     if (hipSetDevice(h->cfg.device) != hipSuccess) return 0;
     return build(h) == 0 ? 1 : 0;
 }
@@ -402,7 +402,6 @@ extern "C" int rnnwf_adam_get_state(rnnwf_handle* h, double* m_flat, double* v_f
 // One optimizer step from the gradient rnnwf_vmc_gradient left on the device (its dW image), then the images' re-pack: what
 // `sess.run(optstep)` does behind the gradient (1DTFIM/TrainingRNN_1DTFIM.py:221).
 extern "C" int rnnwf_adam_step(rnnwf_handle* h, double learning_rate, double beta1, double beta2, double epsilon) {
-    if (h && h->model == RNNWF_MODEL_LSTM1D_F64) return h->fail(RNNWF_ERR_INVALID, "rnnwf_adam_step: no gradient for the LSTM cell");
     if (!h || !h->committed) return RNNWF_ERR_INVALID;
     RNNWF_HIP(h, hipSetDevice(h->cfg.device));
     if (int rc = build(h)) return rc;
@@ -423,23 +422,20 @@ extern "C" int rnnwf_adam_step(rnnwf_handle* h, double learning_rate, double bet
 extern "C" int rnnwf_train_steps(rnnwf_handle* h, int32_t K, int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset,
                                  const double* couplings, int64_t n_couplings, const double* learning_rates, double beta1, double beta2,
                                  double epsilon, double* moments) {
-    if (h && h->model == RNNWF_MODEL_LSTM1D_F64) return h->fail(RNNWF_ERR_INVALID, "rnnwf_train_steps: no gradient for the LSTM cell");
     if (!h || !h->committed) return RNNWF_ERR_INVALID;
     if (K < 1 || K > kMaxSteps || numsamples < 1 || !couplings || !learning_rates || !moments)
         return h->fail(RNNWF_ERR_INVALID, "rnnwf_train_steps: bad arguments (1 <= K <= %d)", kMaxSteps);
     RNNWF_HIP(h, hipSetDevice(h->cfg.device));
     if (int rc = build(h)) return rc;
     TrainState& t = h->train;
-    const bool cplx = h->model == RNNWF_MODEL_CRNN_U1, md = h->model == RNNWF_MODEL_MDRNN2D;
-    if (n_couplings != (cplx ? 3 * h->N + 2 : h->N + 1)) return h->fail(RNNWF_ERR_INVALID, "rnnwf_train_steps: wrong number of couplings");
+    const bool md = h->model == RNNWF_MODEL_MDRNN2D;
+    if (n_couplings != (int64_t)h->family->coupl_per_site * h->N + h->family->coupl_tail)
+        return h->fail(RNNWF_ERR_INVALID, "rnnwf_train_steps: wrong number of couplings");
     if (int rc = params_to_device(h)) return rc;
     for (int k = 0; k < K; ++k) {
-        int rc;
         // single rank: the moments kernel writes iteration k's row of the pinned table itself (no copy launch per iteration)
         h->moments_direct = h->reduce_in_step ? nullptr : (double*)t.mom_host_dev + 4 * k;
-        if (cplx) rc = crnn_vmc_step(h, numsamples, seed, step0 + (uint64_t)k, sample_offset, couplings, nullptr, nullptr, nullptr);
-        else if (md) rc = mdrnn_vmc_step(h, numsamples, seed, step0 + (uint64_t)k, sample_offset, couplings, nullptr, nullptr, nullptr);
-        else rc = prnn_vmc_step(h, numsamples, seed, step0 + (uint64_t)k, sample_offset, couplings, nullptr, nullptr, nullptr);
+        const int rc = vmc_step(h, numsamples, Draw{seed, step0 + (uint64_t)k, sample_offset}, couplings, nullptr, nullptr, nullptr);
         h->moments_direct = nullptr;
         if (rc) return rc;
         if (h->reduce_in_step)

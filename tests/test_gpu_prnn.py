@@ -712,21 +712,30 @@ def test_multi_pass_estimators_equal_the_single_pass(monkeypatch):
         monkeypatch.delenv("RNNWF_STATE_BUDGET_MB")
         lp2 = np.zeros((N + 1) * ns)
         e2 = wf.tfim_eloc(s, np.ones(N), 1.0, log_probs=lp2)
+        out = wf.vmc_step(100, seed=1, step=0, couplings=np.append(np.ones(N), 1.0), want_eloc=True)
+        shapes = {"wf_dense/kernel": (H, 2), "wf_dense/bias": (2,)}
+        g1 = wf.vmc_gradient(out["eloc"].mean(), 100, shapes)
         with pytest.raises(_lib.RnnwfError, match="split the batch"):
             wf.vmc_step(ns, seed=1, step=0, couplings=np.append(np.ones(N), 1.0))
+        g2 = wf.vmc_gradient(out["eloc"].mean(), 100, shapes)      # the refused step left the batch before it resident
         assert np.array_equal(e1, e2) and np.array_equal(lp1, lp2)
+        assert all(np.array_equal(g1[nm], g2[nm]) for nm in shapes)
     # 2D MDRNN and the complex RNN take the same route
     from rnnwavefunctions_amd import params as PP
     wf = _lib.NativeWavefunction(_lib.MODEL_MDRNN2D, 4, 4, (20,))
     wf.set_params(PP.init_mdrnn_params(20, seed=3), scope=SCOPE)
     s2 = rng.randint(0, 2, (2000, 4, 4)).astype(np.int32)
     e1 = wf.tfim_eloc(s2, np.ones((4, 4)), 2.0)
-    monkeypatch.setenv("RNNWF_STATE_BUDGET_MB", "1")
+    lp1 = wf.log_prob(s2)
+    monkeypatch.setenv("RNNWF_STATE_BUDGET_MB", "1")                 # 16 sites x 3 KB per 16 chains: 336 chains per pass
     wf = _lib.NativeWavefunction(_lib.MODEL_MDRNN2D, 4, 4, (20,))
     monkeypatch.delenv("RNNWF_STATE_BUDGET_MB")
     wf.set_params(PP.init_mdrnn_params(20, seed=3), scope=SCOPE)
     e2 = wf.tfim_eloc(s2, np.ones((4, 4)), 2.0)
-    assert np.array_equal(e1, e2)
+    lp2 = wf.log_prob(s2)                                             # its base pass keeps the states too: several passes
+    assert np.array_equal(e1, e2) and np.array_equal(lp1, lp2)
+    with pytest.raises(_lib.RnnwfError, match="split"):
+        wf.sample(2000, seed=1)
     wfc = _lib.NativeWavefunction(_lib.MODEL_CRNN_U1, 12, 1, (20,))
     prmc = trained_like(20, seed=5, heads=("wf_dense_ampl", "wf_dense_phase"))
     wfc.set_params(prmc, scope=SCOPE)
