@@ -225,6 +225,23 @@ int rnnwf_train_steps(rnnwf_handle* h, int32_t K, int64_t numsamples, uint64_t s
 int rnnwf_adam_get_state(rnnwf_handle* h, double* m_flat, double* v_flat, int64_t count, int64_t* t_steps);
 int rnnwf_adam_set_state(rnnwf_handle* h, const double* m_flat, const double* v_flat, int64_t count, int64_t t_steps);
 
+/* ---- entanglement: second Renyi entropy ------------------------------------------------------------
+ * The reference README's "entanglement entropies", by the replica swap estimator (Hastings, Gonzalez, Kallin, Melko,
+ * PRL 104, 157201 (2010)) on pairs (sigma, tau) drawn independently from |psi|^2 = P:
+ *   r_l(sigma, tau) = psi(tau_A sigma_B) psi(sigma_A tau_B) / (psi(sigma) psi(tau)),   exp(-S2(l)) = E[r_l],
+ * psi = sqrt(P).  Models GRU1D and GRU1D_F64, one layer; every other model and stacked layers: RNNWF_ERR_INVALID.
+ * Swapped chains restart from the partner's hidden-state checkpoint at the cut: N (N - 1) cell evaluations per pair for
+ * all cuts together (docs/renyi.md).  Runs in passes under the state budget (whole pairs per pass).  The sums of each
+ * pass are reduced in a fixed order: a repeated call returns the same bits.  A pair with log r > 709 makes its cut's
+ * sums +inf.  Overwrites the batch an earlier rnnwf_vmc_step left for rnnwf_vmc_gradient (a refused call does not).  */
+/* Second Renyi entropy by the swap trick, cuts l = 0..N (A = first l sites; raster order for GRU1D_F64).
+ *   samples      (2*npairs, N) int32, pair p = rows (2p, 2p+1); nullptr: draw them on the device exactly as
+ *                rnnwf_sample(h, 2*npairs, seed, step, 2*pair_offset, ...) would (pair_offset ignored otherwise)
+ *   sums         (N+1, 2) f64: sum_p r_l, sum_p r_l^2  (additive over shards)
+ *   out_log_ratio(N+1, npairs) f64 or nullptr;  out_samples (2*npairs, N) int32 or nullptr (drawn chains)      */
+int rnnwf_renyi2_swap(rnnwf_handle* h, const int32_t* samples, int64_t npairs, uint64_t seed, uint64_t step,
+                      int64_t pair_offset, double* sums, double* out_log_ratio, int32_t* out_samples);
+
 /* ---- multi-GPU: one RCCL all-reduce of the energy moments -------------------------------------
  * The reference is single-process; these add the one data-parallel collective of SURVEY.md 8e.
  * One process per GPU: rank 0 calls rnnwf_comm_unique_id and ships the 128 bytes to the other
@@ -250,7 +267,8 @@ int rnnwf_comm_destroy(rnnwf_handle* h);
 /* ---- measurement ------------------------------------------------------------------------------
  * HIP-event timing of the kernels on the handle's stream (bench.py's roofline leg).
  * kernel ids: 0 = base pass (sample / teacher-forced + checkpoints), 1 = flip pass (dominant),
- *             2 = local-energy assembly + moments, 3 = back-propagation through time of rnnwf_vmc_gradient,
+ *             2 = local-energy assembly + moments (rnnwf_renyi2_swap: 0 = base pass + site-term replay,
+ *             1 = swap pass, 2 = log-ratio assembly + sums), 3 = back-propagation through time of rnnwf_vmc_gradient,
  *             4 = its weight-gradient GEMM.  total_ms / launches accumulate since the
  *             last rnnwf_timing_reset.  Stacked layers on the bf16x3 engine: id 1 brackets the whole
  *             pipeline of per-layer kernels as ONE launch.  work[] is the same for every id: work[0] =

@@ -66,6 +66,7 @@ PROTOTYPES = {
     "rnnwf_train_steps": (C.c_int, [_P, _I32, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _I64, _F64P, _F64, _F64, _F64, _F64P]),
     "rnnwf_adam_get_state": (C.c_int, [_P, _F64P, _F64P, _I64, C.POINTER(_I64)]),
     "rnnwf_adam_set_state": (C.c_int, [_P, _F64P, _F64P, _I64, _I64]),
+    "rnnwf_renyi2_swap": (C.c_int, [_P, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _I32P]),
     "rnnwf_timing_enable": (C.c_int, [_P, _I32]),
     "rnnwf_timing_reset": (C.c_int, [_P]),
     "rnnwf_timing_get": (C.c_int, [_P, _I32, _F64P, C.POINTER(_I64), _F64P]),
@@ -370,6 +371,30 @@ class NativeWavefunction:
         for k, v in like.items():
             nm = k[len(pre):] if pre and k.startswith(pre) else k
             out[k] = self.get_param(nm, v.shape, v.dtype)
+        return out
+
+    # -- entanglement -----------------------------------------------------------------------------
+    def renyi2_swap(self, npairs, samples=None, seed=0, step=0, pair_offset=0, want_log_ratio=False, want_samples=False):
+        """Swap-trick sums of the second Renyi entropy for every cut l = 0..N (rnnwf_renyi2_swap).  samples: (2 npairs, N)
+        int32, pair p = rows 2p, 2p + 1; None: drawn on the device as sample(2 npairs, seed, step, 2 pair_offset) draws them.
+        Returns dict(sums=(N+1, 2) [sum r_l, sum r_l^2], log_ratio=(N+1, npairs)?, samples=(2 npairs, N)?)."""
+        npairs = int(npairs)
+        sp = None
+        if samples is not None:
+            s, sp = _i32(samples)
+            if s.ndim < 2 or s.shape[0] != 2 * npairs or int(np.prod(s.shape[1:])) != self.N:
+                raise ValueError("samples must have shape (2*npairs, %d) = (%d, %d), got %r" % (self.N, 2 * npairs, self.N, s.shape))
+        sums = np.empty((self.N + 1, 2), dtype=np.float64)
+        lr = np.empty((self.N + 1, max(npairs, 0)), dtype=np.float64) if want_log_ratio else None
+        smp = np.empty((2 * max(npairs, 0), self.N), dtype=np.int32) if want_samples and samples is None else None
+        self._check(self.lib.rnnwf_renyi2_swap(self.h, sp, npairs, int(seed), int(step), int(pair_offset), sums.ctypes.data_as(_F64P),
+                                               lr.ctypes.data_as(_F64P) if lr is not None else None,
+                                               smp.ctypes.data_as(_I32P) if smp is not None else None))
+        out = {"sums": sums}
+        if want_log_ratio:
+            out["log_ratio"] = lr
+        if want_samples:
+            out["samples"] = smp if smp is not None else s
         return out
 
     # -- multi-GPU --------------------------------------------------------------------------------

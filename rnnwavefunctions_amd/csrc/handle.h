@@ -131,6 +131,7 @@ struct rnnwf_handle {
     void* upbuf = nullptr;   // pinned buffer the weight images travel through on their way to the device (upload(), below)
     size_t upbuf_cap = 0, upbuf_off = 0;
     rnnwf::DevBuf reduce_scratch;
+    rnnwf::DevBuf renyi;          // rnnwf_renyi2_swap: per-site terms, swap tails, log-ratios and partial sums of one pass (renyi.hip)
 
     bool timing_on = false;
     int timing_mask = 31;    // which kernel ids get HIP events (rnnwf_timing_enable: 1 = all, 2 = the dominant pass only)

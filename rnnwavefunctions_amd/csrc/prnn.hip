@@ -39,6 +39,10 @@ struct Launch {
         if (std::is_same<T, float>::value && NFULL <= 3 && base_bf_available(h)) return prnn_base_coop_bf(h, a);
         if (std::is_same<T, float>::value && NFULL <= 4 && a.nsb <= (int64_t)4 * h->cu_count && !h->knobs.no_coop)
             return base_coop(h, a);
+        return plain(h, a);
+    }
+    // the one-wave-per-block kernel whatever the batch size
+    static int plain(rnnwf_handle* h, const PrnnArgs& a) {
         const void* fn = (const void*)prnn_base_kernel<T, NFULL, WAVES>;
         int bpc = 0;
         if (int rc = blocks_per_cu(h, fn, &bpc)) return rc;
@@ -112,6 +116,7 @@ struct MLaunchL {
         RNNWF_HIP(h, hipGetLastError());
         return 0;
     }
+    static int plain(rnnwf_handle* h, const PrnnArgs&) { return h->fail(RNNWF_ERR_INVALID, "stacked layers: no one-wave base pass"); }
     static std::vector<char> pack(const rnnwf_handle* h) {
         std::vector<char> img = pack_gru_image<T, NFULL, 1>(h);
         for (int l = 1; l < NL; ++l) {
@@ -377,6 +382,15 @@ int rnnwf::prnn_teacher_base(rnnwf_handle* h, int64_t ns, bool reversed, double*
     a.out_lp = out_lp;
     return launch_base(h, a);
 }
+
+// The base pass on the one-wave-per-block kernel for every batch size (never the cooperative or bf16x3 kernels): the swap pass of
+// renyi.hip restarts from its checkpoints and must repeat its arithmetic step for step.
+int rnnwf::prnn_plain_base(rnnwf_handle* h, const PrnnArgs& a) {
+    PRNN_DISPATCH(h, return K::plain(h, a));
+    return h->fail(RNNWF_ERR_INVALID, "no pRNN kernel for NFULL=%d f64=%d", h->NFULL, (int)h->f64);
+}
+PrnnArgs rnnwf::prnn_base_args(rnnwf_handle* h, int64_t ns) { return base_args(h, ns); }
+size_t rnnwf::prnn_hck_bytes_per_block(rnnwf_handle* h) { return hck_bytes_per_block(h); }
 
 const Family* rnnwf::gru_family() {
     static const Family f = {
