@@ -383,7 +383,7 @@ const Family* rnnwf::crnn_family() {
     static const Family f = {
         "complex RNN", pack_image, log_prob_pass, nullptr, energy, max_chains_per_pass, nullptr, count_work,
         3, 2,               // J1, J2, Bz per site; periodic, marshall
-        true, false, true,  // complex64 E_loc; the base pass alone keeps no states; has a gradient
+        true, false, gru_gradient(),    // complex64 E_loc; the base pass alone keeps no states
     };
     return &f;
 }

@@ -1,5 +1,6 @@
-// grad.hip - host side of the VMC-cost gradient for the GRU RNNs (f32 1D positive / complex, f64 2D-lattice GRU):
-// rnnwf_vmc_gradient / rnnwf_get_grad / rnnwf_allreduce_grads.
+// grad.hip - host side of the VMC-cost gradient: the shared driver (grad_device), rnnwf_vmc_gradient,
+// the flat-gradient probe, rnnwf_get_grad / rnnwf_get_grads_flat, and the gradient hooks (models.h: Gradient) of the GRU RNNs
+// (f32 1D positive / parity / complex, f64 2D-lattice GRU; one layer or a stack).  The 2D RNN's hooks live in mdrnn.hip.
 #include <algorithm>
 
 #include "grad_kernels.h"
@@ -185,44 +186,10 @@ struct GLaunch {
     }
 };
 
-#define GRAD_DISPATCH(h, EXPR)                                          \
-    do {                                                                \
-        if ((h)->model == RNNWF_MODEL_CRNN_U1) {                        \
-            switch ((h)->NFULL) {                                       \
-                case 1: { using K = GLaunch<float, 1, 4, 3>; EXPR; }    \
-                case 2: { using K = GLaunch<float, 2, 4, 3>; EXPR; }    \
-                case 3: { using K = GLaunch<float, 3, 4, 3>; EXPR; }    \
-                case 4: { using K = GLaunch<float, 4, 4, 3>; EXPR; }    \
-                case 6: { using K = GLaunch<float, 6, 4, 3>; EXPR; }    \
-                case 8: { using K = GLaunch<float, 8, 4, 3>; EXPR; }    /* these two and the float64 GRU's widest: the      */ \
-                case 12: { using K = GLaunch<float, 12, 4, 3>; EXPR; }  /* kernels live in grad_wide.hip (GLaunch::WIDE)    */ \
-                case 16: { using K = GLaunch<float, 16, 4, 3>; EXPR; }  \
-            }                                                           \
-        } else if ((h)->model == RNNWF_MODEL_GRU1D_F64) {               \
-            switch ((h)->NFULL) {                                       \
-                case 1: { using K = GLaunch<double, 1, 4, 1>; EXPR; }   \
-                case 2: { using K = GLaunch<double, 2, 4, 1>; EXPR; }   \
-                case 3: { using K = GLaunch<double, 3, 4, 1>; EXPR; }   \
-                case 4: { using K = GLaunch<double, 4, 4, 1>; EXPR; }   \
-                case 6: { using K = GLaunch<double, 6, 4, 1>; EXPR; }   /* kernel in grad_wide.hip */ \
-            }                                                           \
-        } else {                                                        \
-            switch ((h)->NFULL) {                                       \
-                case 1: { using K = GLaunch<float, 1, 4, 1>; EXPR; }    \
-                case 2: { using K = GLaunch<float, 2, 4, 1>; EXPR; }    \
-                case 3: { using K = GLaunch<float, 3, 4, 1>; EXPR; }    \
-                case 4: { using K = GLaunch<float, 4, 4, 1>; EXPR; }    \
-                case 6: { using K = GLaunch<float, 6, 4, 1>; EXPR; }    \
-                case 8: { using K = GLaunch<float, 8, 4, 1>; EXPR; }    \
-                case 12: { using K = GLaunch<float, 12, 4, 1>; EXPR; }  \
-                case 16: { using K = GLaunch<float, 16, 4, 1>; EXPR; }  \
-            }                                                           \
-        }                                                               \
-    } while (0)
-
-// ---- stacked layers: one backward pass per layer, top first (ml_grad_kernels.h) ---------------------------------
+// ---- the GRU's gradient: one backward pass per layer, top first (ml_grad_kernels.h); one layer is a stack of one -------------
 // NOUT = 1: positive RNN; NOUT = 3: complex RNN (heads on the top layer, complex weights w_s as in gru_bwd_kernel).
-// T = float, or double for the 2D-lattice GRU (NOUT = 1).
+// T = float, or double for the 2D-lattice GRU (NOUT = 1).  The upper layers' code is compiled for NL > 1 only: no upper-layer
+// kernel at a width that has no stack.
 template <int NFULL, int NL, int WAVES, int NOUT = 1, typename T = float>
 struct MLGrad {
     using G0 = GLaunch<T, NFULL, WAVES, NOUT>;
@@ -234,6 +201,10 @@ struct MLGrad {
     static constexpr size_t HEAD = (size_t)NOUT * G0::G::HEAD_ROW;
     static constexpr size_t DWU = (size_t)GU::PCOLS * GU::QCOLS;
     static constexpr size_t DW_FLOATS = DW0 + HEAD + (NL - 1) * DWU;       // [dW layer 0 | head | dW layer 1 | ...]
+    // a stack's layer-0 pass has no head term: it adds its zeros into a scratch head row past the result
+    static constexpr size_t DW_ALLOC = DW_FLOATS + (NL > 1 ? HEAD : 0);
+
+    static GradImage layout() { return {std::is_same<T, double>::value, DW_FLOATS, DW_ALLOC}; }
 
     template <class S = double>
     static std::vector<char> pack_upper_bwd(const rnnwf_handle* h, int layer) {
@@ -273,16 +244,17 @@ struct MLGrad {
         return img;
     }
 
-    static std::vector<char> pack_all(const rnnwf_handle* h) {
-        std::vector<char> img = G0::template pack_bwd<double>(h);
-        for (int l = 1; l < NL; ++l) {
-            const std::vector<char> up = pack_upper_bwd<double>(h, l);
-            img.insert(img.end(), up.begin(), up.end());
+    // the backward buffer [layer 0 | upper layers]; img == nullptr: the same images once more over Lin, the table of the whole
+    // buffer (pack_value.h; the active PackTrace's shift moves along)
+    static void pack(const rnnwf_handle* h, std::vector<char>* img) {
+        if (img) {
+            *img = G0::template pack_bwd<double>(h);
+            for (int l = 1; l < NL; ++l) {
+                const std::vector<char> up = pack_upper_bwd<double>(h, l);
+                img->insert(img->end(), up.begin(), up.end());
+            }
+            return;
         }
-        return img;
-    }
-    // the same images once more over Lin: the table of the whole backward buffer (pack_value.h; the active PackTrace's shift moves along)
-    static void pack_all_table(const rnnwf_handle* h) {
         const size_t base = pack_trace().shift;
         G0::template pack_bwd<Lin>(h);
         for (int l = 1; l < NL; ++l) {
@@ -291,7 +263,7 @@ struct MLGrad {
         }
         pack_trace().shift = base;
     }
-    // and of the forward buffer [layer 0 | upper layers]
+    // the table of a stack's forward buffer [layer 0 | upper layers] (grad_stack_forward_table)
     static void pack_forward_table(const rnnwf_handle* h) {
         const size_t base = pack_trace().shift;
         pack_gru_image<T, NFULL, NOUT, Lin>(h);
@@ -301,12 +273,11 @@ struct MLGrad {
         }
         pack_trace().shift = base;
     }
-    static void probe_unpack(rnnwf_handle* h, size_t* count) {
-        std::vector<T> img(DW_FLOATS);
-        for (size_t k = 0; k < DW_FLOATS; ++k) img[k] = (T)(k + 1);
-        G0::unpack(h, img.data(), DW0);
-        for (int l = 1; l < NL; ++l) unpack_upper(h, img.data() + DW0 + HEAD + (size_t)(l - 1) * DWU, l);
-        *count = DW_FLOATS;
+    // dW image + head rows (host copy of h->gradW) -> TF-named gradient arrays
+    static void unpack(rnnwf_handle* h, const void* img) {
+        const T* dW = (const T*)img;
+        G0::unpack(h, dW, DW0);                                // layer 0 + head (written by the top layer's pass)
+        for (int l = 1; l < NL; ++l) unpack_upper(h, dW + DW0 + HEAD + (size_t)(l - 1) * DWU, l);
     }
 
     template <bool TOP>
@@ -333,110 +304,85 @@ struct MLGrad {
         return 0;
     }
 
-    static int gemm(rnnwf_handle* h, const T* P, const T* Q, int64_t R, T* dW, bool upper) {
-        if (upper) return tn_gemm_launch<T, GU::PCOLS / 16, GU::QCOLS / 16>(h, P, Q, R, dW);
-        return tn_gemm_launch<T, G0::G::PCOLS / 16, G0::G::QCOLS / 16>(h, P, Q, R, dW);
-    }
-
-    static int run(rnnwf_handle* h, double mean_energy, double mean_energy_im, double norm) {
-        if (int rc = run_device(h, mean_energy, mean_energy_im, norm, nullptr)) return rc;
-        if (int rc = ensure_staging(h, DW_FLOATS * ES)) return rc;
-        const T* host = (const T*)h->staging;
-        RNNWF_HIP(h, hipMemcpyAsync(h->staging, h->gradW.p, DW_FLOATS * ES, hipMemcpyDeviceToHost, h->stream));
-        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-        G0::unpack(h, host, DW0);                              // layer 0 + head (written by the top layer's pass)
-        for (int l = 1; l < NL; ++l) unpack_upper(h, host + DW0 + HEAD + (size_t)(l - 1) * DWU, l);
-        return RNNWF_OK;
-    }
-
-    // every kernel of the stacked gradient, result left in h->gradW; mom_dev != nullptr: device-resident training (grad_single_layer_device)
-    static int run_device(rnnwf_handle* h, double mean_energy, double mean_energy_im, double norm, const double* mom_dev) {
+    // every kernel of the gradient on the resident batch, added into the cleared h->gradW
+    static int launch(rnnwf_handle* h, const GradCost& c) {
         const int N = h->N;
         const int64_t ns = h->last_ns, R = ns * N, nsb = (ns + kChains - 1) / kChains;
-        const double inv_norm = mom_dev ? (NOUT == 3 ? 2.0 : 1.0) : (NOUT == 3 ? 2.0 : 1.0) / norm;     // the complex cost carries a factor 2 (TrainingRNN_J1J2.py:197)
-        const bool parity = h->model == RNNWF_MODEL_GRU1D_PARITY;
-        if (!h->wbwd_valid) {
-            const std::vector<char> img = pack_all(h);
-            if (int rc = ensure(h, h->wbwd, img.size())) return rc;
-            if (int rc = upload(h, h->wbwd.p, img.data(), img.size())) return rc;
-            h->wbwd_valid = true;
-        }
-        if (int rc = ensure(h, h->gradP, (size_t)R * GU::PCOLS * ES)) return rc;
-        if (int rc = ensure(h, h->gradQ, (size_t)R * GU::QCOLS * ES)) return rc;
-        if (int rc = ensure(h, h->gradW, (DW_FLOATS + HEAD) * ES)) return rc;     // + a scratch head row for layer 0's pass
-        const size_t dx_bytes = (size_t)N * nsb * L0::KT * 64 * ES;
-        for (int i = 0; i < (NL > 2 ? 2 : 1); ++i) if (int rc = ensure(h, h->gradDX[i], dx_bytes)) return rc;
-        RNNWF_HIP(h, hipMemsetAsync(h->gradW.p, 0, (DW_FLOATS + HEAD) * ES, h->stream));
-        if (parity) {
-            // log P_sym = log(0.5 (P_F + P_R)): both directions, teacher-forced, each sample weighted by the direction's share of
-            // P_sym (the single-layer case in rnnwf_vmc_gradient below explains the sequence)
-            if constexpr (NOUT == 1 && sizeof(T) == 4) {
+        if (int rc = ensure(h, h->gradP, (size_t)R * (NL > 1 ? GU::PCOLS : G0::G::PCOLS) * ES)) return rc;
+        if (int rc = ensure(h, h->gradQ, (size_t)R * (NL > 1 ? GU::QCOLS : G0::G::QCOLS) * ES)) return rc;
+        const size_t dx_bytes = (size_t)N * nsb * L0::KT * 64 * ES;         // dL/dx of one layer's pass, the dh_in of the next
+        for (int i = 0; i < std::min(NL - 1, 2); ++i) if (int rc = ensure(h, h->gradDX[i], dx_bytes)) return rc;
+        if constexpr (NOUT == 1 && sizeof(T) == 4)
+            if (h->model == RNNWF_MODEL_GRU1D_PARITY) {
+                // log P_sym = log(0.5 (P_F + P_R)) (1DTFIM/RNNwavefunction_paritysym.py:145): the gradient is the sum of the two
+                // directions' gradients, each sample weighted by the direction's share of P_sym.  The step left the checkpoints of ONE
+                // direction: both are redone here, teacher-forced, with the shares from the same two passes.
                 if (int rc = ensure(h, h->out_lp, (size_t)ns * 8)) return rc;
                 if (int rc = ensure(h, h->out_lp2, (size_t)ns * 8)) return rc;
                 double* lpF = (double*)h->out_lp.p;
                 double* lpR = (double*)h->out_lp2.p;
                 if (int rc = prnn_teacher_base(h, ns, false, lpF)) return rc;
-                if (int rc = prnn_teacher_base(h, ns, true, lpR)) return rc;
+                if (int rc = prnn_teacher_base(h, ns, true, lpR)) return rc;       // the reversed chains' states are resident now
                 if (int rc = run_parity_share(h, lpF, lpR, ns)) return rc;
-                if (int rc = passes(h, mean_energy, mean_energy_im, inv_norm, (const uint32_t*)h->bits2.p, lpR, mom_dev)) return rc;
+                if (int rc = passes(h, c, (const uint32_t*)h->bits2.p, lpR)) return rc;
                 if (int rc = prnn_teacher_base(h, ns, false, nullptr)) return rc;
-                if (int rc = passes(h, mean_energy, mean_energy_im, inv_norm, (const uint32_t*)h->bits.p, lpF, mom_dev)) return rc;
+                return passes(h, c, (const uint32_t*)h->bits.p, lpF);
             }
-        } else {
-            if (int rc = passes(h, mean_energy, mean_energy_im, inv_norm, (const uint32_t*)h->bits.p, nullptr, mom_dev)) return rc;
-        }
-        return RNNWF_OK;
+        return passes(h, c, (const uint32_t*)h->bits.p, nullptr);
     }
 
     // one backward pass per layer, top first, over the resident checkpoints of the chains in `bits`; everything is ADDED to gradW
-    static int passes(rnnwf_handle* h, double mean_energy, double mean_energy_im, double inv_norm, const uint32_t* bits, const double* wfac,
-                      const double* mom_dev) {
+    static int passes(rnnwf_handle* h, const GradCost& c, const uint32_t* bits, const double* wfac) {
         const int N = h->N;
         const int64_t ns = h->last_ns, R = ns * N, nsb = (ns + kChains - 1) / kChains;
         T* dW = (T*)h->gradW.p;
-        const char* bwd = (const char*)h->wbwd.p;
         const void* dh_in = nullptr;
-        for (int l = NL - 1; l >= 1; --l) {
-            UpperGradArgs a{};
-            a.wup = (const char*)h->wimg.p + L0::BYTES + (size_t)(l - 1) * U::BYTES;
-            a.wbwd = bwd + G0::G::BWD_BYTES + (size_t)(l - 1) * GU::BWD_BYTES;
-            a.whead = (const char*)h->wimg.p + L0::OFF_WD;
-            a.N = N; a.layer = l; a.hck_nl = NL;
-            a.ns = ns; a.nsb = nsb;
-            a.bits = bits;
-            a.wfac = wfac;
-            a.hck = h->hck.p;
-            a.eloc = (const double*)h->eloc.p;
-            a.eloc_c = (const float2*)h->eloc.p;
-            a.mean_e = mean_energy;
-            a.mean_im = mean_energy_im;
-            a.inv_norm = inv_norm;
-            a.mom = mom_dev;
-            a.dh_in = dh_in;
-            a.dx_out = h->gradDX[(NL - 1 - l) & 1].p;
-            a.P = h->gradP.p;
-            a.Q = h->gradQ.p;
-            a.head_grad = dW + DW0;
-            if (l == NL - 1) { if (int rc = upper_pass<true>(h, a)) return rc; }
-            else { if (int rc = upper_pass<false>(h, a)) return rc; }
-            if (int rc = gemm(h, (const T*)a.P, (const T*)a.Q, R, dW + DW0 + HEAD + (size_t)(l - 1) * DWU, true)) return rc;
-            dh_in = a.dx_out;
+        if constexpr (NL > 1) {
+            const char* bwd = (const char*)h->wbwd.p;
+            for (int l = NL - 1; l >= 1; --l) {
+                UpperGradArgs a{};
+                a.wup = (const char*)h->wimg.p + L0::BYTES + (size_t)(l - 1) * U::BYTES;
+                a.wbwd = bwd + G0::G::BWD_BYTES + (size_t)(l - 1) * GU::BWD_BYTES;
+                a.whead = (const char*)h->wimg.p + L0::OFF_WD;
+                a.N = N; a.layer = l; a.hck_nl = NL;
+                a.ns = ns; a.nsb = nsb;
+                a.bits = bits;
+                a.wfac = wfac;
+                a.hck = h->hck.p;
+                a.eloc = (const double*)h->eloc.p;
+                a.eloc_c = (const float2*)h->eloc.p;
+                a.mean_e = c.mean_e;
+                a.mean_im = c.mean_im;
+                a.inv_norm = c.inv_norm;
+                a.mom = c.mom;
+                a.dh_in = dh_in;
+                a.dx_out = h->gradDX[(NL - 1 - l) & 1].p;
+                a.P = h->gradP.p;
+                a.Q = h->gradQ.p;
+                a.head_grad = dW + DW0;
+                if (l == NL - 1) { if (int rc = upper_pass<true>(h, a)) return rc; }
+                else { if (int rc = upper_pass<false>(h, a)) return rc; }
+                if (int rc = tn_gemm_launch<T, GU::PCOLS / 16, GU::QCOLS / 16>(h, (const T*)a.P, (const T*)a.Q, R, dW + DW0 + HEAD + (size_t)(l - 1) * DWU))
+                    return rc;
+                dh_in = a.dx_out;
+            }
         }
         GradArgs a{};
         a.wimg = h->wimg.p;
         a.wbwd = h->wbwd.p;
         a.N = N; a.ns = ns; a.nsb = nsb;
         a.bits = bits;
+        a.wfac = NL > 1 ? nullptr : wfac;                  // a stack: w_s only weights the head terms, on the top layer
         a.hck = h->hck.p;
         a.eloc = (const double*)h->eloc.p;
         a.eloc_c = (const float2*)h->eloc.p;
-        a.mean_e = mean_energy;
-        a.mean_im = mean_energy_im;
-        a.inv_norm = inv_norm;
-        a.mom = mom_dev;
+        a.mean_e = c.mean_e;
+        a.mean_im = c.mean_im;
+        a.inv_norm = c.inv_norm;
+        a.mom = c.mom;
         a.P = h->gradP.p;
         a.Q = h->gradQ.p;
-        a.head_grad = dW + DW_FLOATS;          // scratch rows: layer 0 has no head term here (its adds are zeros)
+        a.head_grad = dW + (NL > 1 ? DW_FLOATS : DW0);     // a stack: the scratch row (layer 0 has no head term there; its adds are zeros)
         a.dh_in = dh_in;
         a.hck_nl = NL;
         return G0::run(h, a, R, dW);
@@ -482,211 +428,140 @@ struct MLGrad {
     }
 };
 
-#define MLGRAD_DISPATCH_(h, NOUT, EXPR)                                 \
-    do {                                                                \
-        if ((h)->NL == 2) {                                             \
-            switch ((h)->NFULL) {                                       \
-                case 1: { using K = MLGrad<1, 2, 4, NOUT>; EXPR; }      \
-                case 2: { using K = MLGrad<2, 2, 4, NOUT>; EXPR; }      \
-                case 3: { using K = MLGrad<3, 2, 4, NOUT>; EXPR; }      \
-                case 4: { using K = MLGrad<4, 2, 4, NOUT>; EXPR; }      \
-                case 6: { using K = MLGrad<6, 2, 4, NOUT>; EXPR; }      \
-            }                                                           \
-        } else if ((h)->NL == 4) {                                      \
-            switch ((h)->NFULL) {                                       \
-                case 1: { using K = MLGrad<1, 4, 4, NOUT>; EXPR; }      \
-                case 2: { using K = MLGrad<2, 4, 4, NOUT>; EXPR; }      \
-                case 3: { using K = MLGrad<3, 4, 4, NOUT>; EXPR; }      \
-                case 4: { using K = MLGrad<4, 4, 4, NOUT>; EXPR; }      \
-                case 6: { using K = MLGrad<6, 4, 4, NOUT>; EXPR; }      \
-            }                                                           \
-        } else if ((h)->NL == 3) {                                      \
-            switch ((h)->NFULL) {                                       \
-                case 1: { using K = MLGrad<1, 3, 4, NOUT>; EXPR; }      \
-                case 2: { using K = MLGrad<2, 3, 4, NOUT>; EXPR; }      \
-                case 3: { using K = MLGrad<3, 3, 4, NOUT>; EXPR; }      \
-                case 4: { using K = MLGrad<4, 3, 4, NOUT>; EXPR; }      \
-                case 6: { using K = MLGrad<6, 3, 4, NOUT>; EXPR; }      \
-            }                                                           \
-        }                                                               \
-    } while (0)
-#define MLGRAD_DISPATCH(h, EXPR)                                        \
-    do {                                                                \
-        if ((h)->model == RNNWF_MODEL_CRNN_U1) MLGRAD_DISPATCH_(h, 3, EXPR); \
-        else if ((h)->model == RNNWF_MODEL_GRU1D_F64) {                 \
-            if ((h)->NL == 2 && (h)->NFULL == 1) { using K = MLGrad<1, 2, 4, 1, double>; EXPR; } \
-            if ((h)->NL == 2 && (h)->NFULL == 2) { using K = MLGrad<2, 2, 4, 1, double>; EXPR; } \
-            if ((h)->NL == 3 && (h)->NFULL == 1) { using K = MLGrad<1, 3, 4, 1, double>; EXPR; } \
-            if ((h)->NL == 3 && (h)->NFULL == 2) { using K = MLGrad<2, 3, 4, 1, double>; EXPR; } \
-            if ((h)->NL == 2 && (h)->NFULL == 3) { using K = MLGrad<3, 2, 4, 1, double>; EXPR; } \
-            if ((h)->NL == 2 && (h)->NFULL == 4) { using K = MLGrad<4, 2, 4, 1, double>; EXPR; } \
-            if ((h)->NL == 3 && (h)->NFULL == 3) { using K = MLGrad<3, 3, 4, 1, double>; EXPR; } \
-            if ((h)->NL == 3 && (h)->NFULL == 4) { using K = MLGrad<4, 3, 4, 1, double>; EXPR; } \
-            if ((h)->NL == 4 && (h)->NFULL == 1) { using K = MLGrad<1, 4, 4, 1, double>; EXPR; } \
-            if ((h)->NL == 4 && (h)->NFULL == 2) { using K = MLGrad<2, 4, 4, 1, double>; EXPR; } \
-            if ((h)->NL == 4 && (h)->NFULL == 3) { using K = MLGrad<3, 4, 4, 1, double>; EXPR; } \
-            if ((h)->NL == 4 && (h)->NFULL == 4) { using K = MLGrad<4, 4, 4, 1, double>; EXPR; } \
-        } else MLGRAD_DISPATCH_(h, 1, EXPR);                            \
-    } while (0)
+// fn(K()) for this handle's gradient class K: the widths of each model, one layer (f32 8..16 and the float64 GRU's 6: kernels in
+// grad_wide.hip, GLaunch::WIDE) or a stack
+template <int NL, int NOUT, typename T, class Fn>
+int gru_widths(rnnwf_handle* h, Fn&& fn) {
+    constexpr bool f32 = std::is_same<T, float>::value;
+    switch (h->NFULL) {
+        case 1: return fn(MLGrad<1, NL, 4, NOUT, T>());
+        case 2: return fn(MLGrad<2, NL, 4, NOUT, T>());
+        case 3: return fn(MLGrad<3, NL, 4, NOUT, T>());
+        case 4: return fn(MLGrad<4, NL, 4, NOUT, T>());
+        case 6: if constexpr (f32 || NL == 1) return fn(MLGrad<6, NL, 4, NOUT, T>()); break;
+        case 8: if constexpr (f32 && NL == 1) return fn(MLGrad<8, NL, 4, NOUT, T>()); break;
+        case 12: if constexpr (f32 && NL == 1) return fn(MLGrad<12, NL, 4, NOUT, T>()); break;
+        case 16: if constexpr (f32 && NL == 1) return fn(MLGrad<16, NL, 4, NOUT, T>()); break;
+    }
+    return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: no gradient kernel for NFULL=%d with %d layers", h->NFULL, NL);
+}
+template <int NL, class Fn>
+int gru_models(rnnwf_handle* h, Fn&& fn) {
+    if (h->model == RNNWF_MODEL_CRNN_U1) return gru_widths<NL, 3, float>(h, fn);
+    if (h->model == RNNWF_MODEL_GRU1D_F64) return gru_widths<NL, 1, double>(h, fn);
+    return gru_widths<NL, 1, float>(h, fn);
+}
+template <class Fn>
+int with_gru_grad(rnnwf_handle* h, Fn&& fn) {
+    switch (h->NL) {
+        case 1: return gru_models<1>(h, fn);
+        case 2: return gru_models<2>(h, fn);
+        case 3: return gru_models<3>(h, fn);
+        case 4: return gru_models<4>(h, fn);
+    }
+    return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: no gradient kernel for %d layers", h->NL);
+}
+
+int grad_layout(rnnwf_handle* h, GradImage* out) {
+    return with_gru_grad(h, [&](auto k) { *out = decltype(k)::layout(); return 0; });
+}
+int grad_pack(rnnwf_handle* h, std::vector<char>* img) {
+    return with_gru_grad(h, [&](auto k) { decltype(k)::pack(h, img); return 0; });
+}
+int grad_launch(rnnwf_handle* h, const GradCost& c) {
+    return with_gru_grad(h, [&](auto k) { return decltype(k)::launch(h, c); });
+}
+void grad_unpack(rnnwf_handle* h, const void* img) {
+    with_gru_grad(h, [&](auto k) { decltype(k)::unpack(h, img); return 0; });
+}
+
+// fn(parameter, its gradient) in the order of rnnwf_set_params_flat; fails at a parameter without a gradient of its size
+template <class Fn>
+int each_grad(rnnwf_handle* h, const char* what, Fn&& fn) {
+    for (auto& kv : h->params) {
+        auto it = h->grads.find(kv.first);
+        if (it == h->grads.end() || it->second.size() != kv.second.value.size())
+            return h->fail(RNNWF_ERR_STATE, "%s: no gradient for '%s'", what, kv.first.c_str());
+        fn(kv.second, it->second);
+    }
+    return 0;
+}
+
+// the family's unpacker on an image whose element k holds k + 1
+template <typename T>
+void unpack_indices(rnnwf_handle* h, size_t n) {
+    std::vector<T> img(n);
+    for (size_t k = 0; k < n; ++k) img[k] = (T)(k + 1);
+    h->family->gradient->unpack(h, img.data());
+}
 
 }  // namespace
+
+const Gradient* rnnwf::gru_gradient() {
+    static const Gradient g = {grad_layout, grad_pack, grad_launch, grad_unpack};
+    return &g;
+}
+
+// The gradient's kernels on the batch of the last rnnwf_vmc_step: back-propagation through time + weight-gradient GEMMs, the
+// result (the family's dW images and head rows) left in h->gradW.
+int rnnwf::grad_device(rnnwf_handle* h, double mean_energy, double mean_energy_im, double norm, const double* mom_dev, GradImage* out) {
+    if (h->last_ns <= 0)
+        return h->fail(RNNWF_ERR_STATE, "rnnwf_vmc_gradient: call rnnwf_vmc_step first (its samples, states and E_loc are reused)");
+    if (!mom_dev && !(norm > 0)) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: norm must be positive");
+    RNNWF_HIP(h, hipSetDevice(h->cfg.device));
+    const Gradient& g = *h->family->gradient;
+    GradImage im;
+    if (int rc = g.layout(h, &im)) return rc;
+    if (!h->wbwd_valid) {
+        std::vector<char> img;
+        if (int rc = g.pack(h, &img)) return rc;
+        if (int rc = ensure(h, h->wbwd, img.size())) return rc;
+        if (int rc = upload(h, h->wbwd.p, img.data(), img.size())) return rc;
+        h->wbwd_valid = true;
+    }
+    const size_t bytes = im.alloc * (im.f64 ? 8 : 4);
+    if (int rc = ensure(h, h->gradW, bytes)) return rc;
+    RNNWF_HIP(h, hipMemsetAsync(h->gradW.p, 0, bytes, h->stream));
+    if (out) *out = im;
+    const double scale = h->family->complex_eloc ? 2.0 : 1.0;      // the complex cost carries a factor 2 (TrainingRNN_J1J2.py:197)
+    return g.launch(h, GradCost{mean_energy, mean_energy_im, mom_dev ? scale : scale / norm, mom_dev});
+}
 
 extern "C" int rnnwf_vmc_gradient(rnnwf_handle* h, double mean_energy, double mean_energy_im, double norm) {
     if (!h) return RNNWF_ERR_INVALID;
     if (int rc = require_gradient(h, "rnnwf_vmc_gradient")) return rc;
     if (!h->committed) return h->fail(RNNWF_ERR_STATE, "parameters not committed");
-    if (h->model == RNNWF_MODEL_MDRNN2D) return mdrnn_vmc_gradient(h, mean_energy, norm);
-    if (h->NL != 1) {
-        if (h->last_ns <= 0 || !h->last_has_ckpt)
-            return h->fail(RNNWF_ERR_STATE, "rnnwf_vmc_gradient: call rnnwf_vmc_step first (its samples, states and E_loc are reused)");
-        if (!(norm > 0)) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: norm must be positive");
-        RNNWF_HIP(h, hipSetDevice(h->cfg.device));
-        MLGRAD_DISPATCH(h, return K::run(h, mean_energy, mean_energy_im, norm));
-        return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: no stacked-layer kernel for this width");
-    }
-    size_t dw_floats = 0;
-    if (int rc = grad_single_layer_device(h, mean_energy, mean_energy_im, norm, nullptr, &dw_floats)) return rc;
-    const size_t es = h->model == RNNWF_MODEL_GRU1D_F64 ? 8 : 4;
-    int pcols = 0, qcols = 0;
-    GRAD_DISPATCH(h, { pcols = K::G::PCOLS; qcols = K::G::QCOLS; break; });
-    if (int rc = ensure_staging(h, dw_floats * es)) return rc;        // pinned: the copy is a plain DMA, the one wait is ours
-    RNNWF_HIP(h, hipMemcpyAsync(h->staging, h->gradW.p, dw_floats * es, hipMemcpyDeviceToHost, h->stream));
+    GradImage im;
+    if (int rc = grad_device(h, mean_energy, mean_energy_im, norm, nullptr, &im)) return rc;
+    const size_t bytes = im.count * (im.f64 ? 8 : 4);
+    if (int rc = ensure_staging(h, bytes)) return rc;        // pinned: the copy is a plain DMA, the one wait is ours
+    RNNWF_HIP(h, hipMemcpyAsync(h->staging, h->gradW.p, bytes, hipMemcpyDeviceToHost, h->stream));
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    GRAD_DISPATCH(h, { K::unpack(h, h->staging, (size_t)pcols * qcols); break; });
+    h->family->gradient->unpack(h, h->staging);
     return RNNWF_OK;
 }
 
-// The single-layer gradient's kernels on the batch of the last rnnwf_vmc_step: back-propagation through time + weight-gradient GEMM,
-// result (the dW image and the head rows) left in h->gradW.  mom_dev != nullptr (device-resident training, train.hip): mean energy
-// and norm come from the step's moments on the device (mean_energy / norm arguments unused) and nothing visits the host.
-int rnnwf::grad_single_layer_device(rnnwf_handle* h, double mean_energy, double mean_energy_im, double norm, const double* mom_dev,
-                                    size_t* dw_count) {
-    if (h->NL != 1) {                       // stacked layers: one backward pass per layer, top first (MLGrad)
-        if (h->last_ns <= 0 || !h->last_has_ckpt)
-            return h->fail(RNNWF_ERR_STATE, "rnnwf_vmc_gradient: call rnnwf_vmc_step first (its samples, states and E_loc are reused)");
-        RNNWF_HIP(h, hipSetDevice(h->cfg.device));
-        MLGRAD_DISPATCH(h, { if (dw_count) *dw_count = K::DW_FLOATS; return K::run_device(h, mean_energy, mean_energy_im, norm, mom_dev); });
-        return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: no stacked-layer kernel for this width");
-    }
-    const bool parity = h->model == RNNWF_MODEL_GRU1D_PARITY;
-    const bool cplx = h->model == RNNWF_MODEL_CRNN_U1;
-    const bool f64 = h->model == RNNWF_MODEL_GRU1D_F64;
-    const size_t es = f64 ? 8 : 4;
-    if (h->last_ns <= 0 || !h->last_has_ckpt)
-        return h->fail(RNNWF_ERR_STATE, "rnnwf_vmc_gradient: call rnnwf_vmc_step first (its samples, states and E_loc are reused)");
-    if (!mom_dev && !(norm > 0)) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: norm must be positive");
-    RNNWF_HIP(h, hipSetDevice(h->cfg.device));
-    const int N = h->N;
-    const int64_t ns = h->last_ns, R = ns * N;
-    int pcols = 0, qcols = 0, hgn = 0;
-    GRAD_DISPATCH(h, { pcols = K::G::PCOLS; qcols = K::G::QCOLS; hgn = K::G::HEAD_ROW * (cplx ? 3 : 1); break; });
-    if (!h->wbwd_valid) {
-        std::vector<char> img;
-        GRAD_DISPATCH(h, { img = K::template pack_bwd<double>(h); break; });
-        if (int rc = ensure(h, h->wbwd, img.size())) return rc;
-        if (int rc = upload(h, h->wbwd.p, img.data(), img.size())) return rc;
-        h->wbwd_valid = true;
-    }
-    if (int rc = ensure(h, h->gradP, (size_t)R * pcols * es)) return rc;
-    if (int rc = ensure(h, h->gradQ, (size_t)R * qcols * es)) return rc;
-    const size_t dw_floats = (size_t)pcols * qcols + hgn;
-    if (dw_count) *dw_count = dw_floats;
-    if (int rc = ensure(h, h->gradW, dw_floats * es)) return rc;
-    RNNWF_HIP(h, hipMemsetAsync(h->gradW.p, 0, dw_floats * es, h->stream));
-    GradArgs a{};
-    a.wimg = h->wimg.p;
-    a.wbwd = h->wbwd.p;
-    a.N = N;
-    a.ns = ns;
-    a.nsb = (ns + kChains - 1) / kChains;
-    a.bits = (const uint32_t*)h->bits.p;
-    a.hck = h->hck.p;
-    a.eloc = (const double*)h->eloc.p;
-    a.eloc_c = (const float2*)h->eloc.p;
-    a.mean_e = mean_energy;
-    a.mean_im = mean_energy_im;
-    a.mom = mom_dev;
-    a.inv_norm = mom_dev ? (cplx ? 2.0 : 1.0) : (cplx ? 2.0 : 1.0) / norm;      // the complex cost carries a factor 2 (TrainingRNN_J1J2.py:197)
-    a.P = h->gradP.p;
-    a.Q = h->gradQ.p;
-    a.head_grad = (char*)h->gradW.p + (size_t)pcols * qcols * es;
-    if (parity) {
-        // log P_sym = log(0.5 (P_F + P_R)) (1DTFIM/RNNwavefunction_paritysym.py:145): the gradient is the sum of the two directions'
-        // gradients, each sample weighted by the direction's share of P_sym.  The step left the checkpoints of ONE direction: both
-        // are redone here, teacher-forced, with the shares from the same two passes.
-        if (int rc = ensure(h, h->out_lp, (size_t)ns * 8)) return rc;
-        if (int rc = ensure(h, h->out_lp2, (size_t)ns * 8)) return rc;
-        double* lpF = (double*)h->out_lp.p;
-        double* lpR = (double*)h->out_lp2.p;
-        if (int rc = prnn_teacher_base(h, ns, false, lpF)) return rc;
-        if (int rc = prnn_teacher_base(h, ns, true, lpR)) return rc;              // the reversed chains' states are resident now
-        if (int rc = run_parity_share(h, lpF, lpR, ns)) return rc;
-        a.bits = (const uint32_t*)h->bits2.p;
-        a.wfac = lpR;
-        GRAD_DISPATCH(h, { if (int rc = K::run(h, a, R, h->gradW.p)) return rc; break; });
-        if (int rc = prnn_teacher_base(h, ns, false, nullptr)) return rc;
-        a.bits = (const uint32_t*)h->bits.p;
-        a.wfac = lpF;
-    }
-    GRAD_DISPATCH(h, { if (int rc = K::run(h, a, R, h->gradW.p)) return rc; break; });
-    return RNNWF_OK;
-}
-
-// ---- what train.hip needs from this translation unit (the layouts live in its anonymous namespace) -------------------------
-// table of a stack's forward buffer [layer 0 | upper layers] into the active PackTrace
+// table of a stack's forward buffer [layer 0 | upper layers] into the active PackTrace (train.hip; the layouts live here)
 int rnnwf::grad_stack_forward_table(rnnwf_handle* h) {
-    MLGRAD_DISPATCH(h, { K::pack_forward_table(h); return 0; });
-    return h->fail(RNNWF_ERR_INVALID, "no stacked-layer layout for NFULL=%d", h->NFULL);
+    return with_gru_grad(h, [&](auto k) { decltype(k)::pack_forward_table(h); return 0; });
 }
-// table of the backward image (pack_value.h) into the active PackTrace
-int rnnwf::grad_bwd_pack_table(rnnwf_handle* h) {
-    if (h->NL != 1) {
-        MLGRAD_DISPATCH(h, { K::pack_all_table(h); return 0; });
-        return h->fail(RNNWF_ERR_INVALID, "no stacked-layer gradient for NFULL=%d", h->NFULL);
-    }
-    GRAD_DISPATCH(h, { K::template pack_bwd<Lin>(h); return 0; });
-    return h->fail(RNNWF_ERR_INVALID, "no gradient kernel for NFULL=%d", h->NFULL);
-}
-// Where every entry of the flat gradient (order and shapes of rnnwf_get_grads_flat) sits in the dW image: the host unpacker run on an
-// image whose element k holds k + 1 - sidx[j] = +-(k + 1), 0: no source (stays 0).  is_f64: element type of the image.
-int rnnwf::grad_flat_probe(rnnwf_handle* h, std::vector<int32_t>& sidx, size_t* dw_count, bool* is_f64) {
-    const bool cplx = h->model == RNNWF_MODEL_CRNN_U1;
-    const bool f64 = h->model == RNNWF_MODEL_GRU1D_F64;
-    int pcols = 0, qcols = 0, hgn = 0;
-    size_t n = 0;
+
+// Where every entry of the flat gradient (order and shapes of rnnwf_get_grads_flat) sits in the h->gradW image: the family's
+// unpacker run on an image whose element k holds k + 1 - sidx[j] = +-(k + 1), 0: no source (stays 0).  The indices must be exact
+// in the image's element type and fit int32_t.
+int rnnwf::grad_flat_probe(rnnwf_handle* h, std::vector<int32_t>& sidx, GradImage* im) {
+    if (int rc = h->family->gradient->layout(h, im)) return rc;
+    const size_t n = im->count;
+    if (n == 0 || n >= ((size_t)1 << (im->f64 ? 31 : 24))) return h->fail(RNNWF_ERR_INVALID, "gradient image of %zu elements cannot be probed", n);
     const auto saved = h->grads;
-    if (h->NL != 1) {
-        bool done = false;
-        MLGRAD_DISPATCH(h, { if (K::DW_FLOATS < ((size_t)1 << 24)) { K::probe_unpack(h, &n); done = true; } break; });
-        if (!done) return h->fail(RNNWF_ERR_INVALID, "stacked gradient image cannot be probed");
-    } else {
-    GRAD_DISPATCH(h, { pcols = K::G::PCOLS; qcols = K::G::QCOLS; hgn = K::G::HEAD_ROW * (cplx ? 3 : 1); break; });
-    n = (size_t)pcols * qcols + hgn;
-    if (n == 0 || n >= ((size_t)1 << 24)) return h->fail(RNNWF_ERR_INVALID, "gradient image of %zu elements cannot be probed", n);
-    }
-    if (h->NL != 1) {
-    } else if (f64) {
-        std::vector<double> img(n);
-        for (size_t k = 0; k < n; ++k) img[k] = (double)(k + 1);
-        GRAD_DISPATCH(h, { K::unpack(h, img.data(), (size_t)pcols * qcols); break; });
-    } else {
-        std::vector<float> img(n);
-        for (size_t k = 0; k < n; ++k) img[k] = (float)(k + 1);
-        GRAD_DISPATCH(h, { K::unpack(h, img.data(), (size_t)pcols * qcols); break; });
-    }
+    if (im->f64) unpack_indices<double>(h, n);
+    else unpack_indices<float>(h, n);
     sidx.clear();
-    for (auto& kv : h->params) {
-        auto it = h->grads.find(kv.first);
-        if (it == h->grads.end() || it->second.size() != kv.second.value.size()) {
-            h->grads = saved;
-            return h->fail(RNNWF_ERR_STATE, "grad_flat_probe: no gradient for '%s'", kv.first.c_str());
-        }
-        for (size_t i = 0; i < kv.second.slot.size(); ++i) sidx.push_back((int32_t)std::llround(it->second[(size_t)kv.second.slot[i]]));
-    }
+    const int rc = each_grad(h, "grad_flat_probe", [&](const ParamSpec& p, const std::vector<double>& g) {
+        for (int64_t s : p.slot) sidx.push_back((int32_t)std::llround(g[(size_t)s]));
+    });
     h->grads = saved;
-    if (dw_count) *dw_count = n;
-    if (is_f64) *is_f64 = f64;
-    return 0;
+    return rc;
 }
 
 extern "C" int rnnwf_get_grad(rnnwf_handle* h, const char* name, void* data, int64_t count, int32_t dtype) {
@@ -714,16 +589,9 @@ extern "C" int rnnwf_get_grads_flat(rnnwf_handle* h, double* flat, int64_t count
     for (auto& kv : h->params) total += (int64_t)kv.second.slot.size();
     if (count != total)
         return h->fail(RNNWF_ERR_INVALID, "rnnwf_get_grads_flat: the model has %lld parameters, caller passed %lld", (long long)total, (long long)count);
-    int64_t off = 0;
-    for (auto& kv : h->params) {
-        auto it = h->grads.find(kv.first);
-        if (it == h->grads.end() || it->second.size() != kv.second.value.size())
-            return h->fail(RNNWF_ERR_STATE, "rnnwf_get_grads_flat: no gradient for '%s'", kv.first.c_str());
-        const std::vector<int64_t>& slot = kv.second.slot;
-        for (size_t i = 0; i < slot.size(); ++i) flat[off + (int64_t)i] = it->second[slot[i]];
-        off += (int64_t)slot.size();
-    }
-    return RNNWF_OK;
+    return each_grad(h, "rnnwf_get_grads_flat", [&](const ParamSpec& p, const std::vector<double>& g) {
+        for (int64_t s : p.slot) *flat++ = g[(size_t)s];
+    });
 }
 
 // the weight image changed: the backward image must be rebuilt on the next gradient call

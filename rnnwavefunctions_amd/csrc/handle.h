@@ -121,7 +121,6 @@ struct rnnwf_handle {
     int last_flip_engine = -1;    // engine of the last flip / swap launch (1 bf16x3, 0 f32-input MFMA), -1 none yet
     std::map<std::string, std::vector<double>> grads;
     int64_t last_ns = 0;          // batch of the last rnnwf_vmc_step still resident (bits, hck, eloc)
-    bool last_has_ckpt = false;
     void* pinned = nullptr;  // small pinned staging (moments)
     void* pinned_dev = nullptr;   // the same memory as the device addresses it: kernels write the step's 32 + 24 result bytes there directly
     double* moments_direct = nullptr;   // device address of the pinned row the moments kernel also writes to (set per iteration by rnnwf_train_steps)

@@ -188,7 +188,7 @@ const Family* rnnwf::lstm_family() {
     static const Family f = {
         "LSTM cell", pack_image, log_prob_pass, nullptr, eloc_on_device, max_chains_per_pass, nullptr, nullptr,
         1, 1,                 // Jz per site; Bx
-        false, false, false,  // float64 E_loc; the base pass alone keeps no states; no gradient (nothing stays resident)
+        false, false, nullptr,  // float64 E_loc; the base pass alone keeps no states; no gradient (nothing stays resident)
     };
     return &f;
 }

@@ -1,5 +1,5 @@
 // mdrnn.hip - host side of the 2D MDRNN wave function (model MDRNN2D, float64): weight image, base pass, fused 2D-TFIM local
-// energies (driven through mdrnn_family by rnnwf_api.hip) and the gradient.
+// energies (driven through mdrnn_family by rnnwf_api.hip) and the gradient's hooks (driven by grad.hip: grad_device).
 #include <algorithm>
 
 #include "grad_kernels.h"
@@ -299,21 +299,16 @@ int pack_image(rnnwf_handle* h, std::vector<char>& img) {
 
 }  // namespace
 
-const Family* rnnwf::mdrnn_family() {
-    static const Family f = {
-        "2D RNN", pack_image, log_prob_pass, nullptr, eloc_on_device, max_chains_per_pass, site_maps, nullptr,
-        1, 1,               // Jz per site; Bx
-        false, true, true,  // float64 E_loc; the base pass alone keeps every site's state; has a gradient
-    };
-    return &f;
-}
-
 // ---- gradient of the VMC cost (2DTFIM_2DRNN/Training2DRNN_2DTFIM.py:163-170) ----
 namespace {
 
 template <int NFULL, int WAVES>
 struct MGrad {
     using G = MdGradLayout<NFULL>;
+    static GradImage layout() {
+        const size_t n = (size_t)G::PCOLS * G::QCOLS + 2 * G::HEAD_ROW;
+        return {true, n, n};
+    }
 
     template <class S = double>
     static std::vector<char> pack(const rnnwf_handle* h) {
@@ -356,7 +351,30 @@ struct MGrad {
         return img;
     }
 
-    static int run(rnnwf_handle* h, MdGradArgs a, int64_t R, double* dW) {
+    static int launch(rnnwf_handle* h, const GradCost& c) {
+        Maps m;
+        if (int rc = get_maps(h, &m)) return rc;
+        const int N = h->N;
+        const int64_t ns = h->last_ns, R = ns * N;
+        if (int rc = ensure(h, h->gradP, (size_t)R * G::PCOLS * 8)) return rc;
+        if (int rc = ensure(h, h->gradQ, (size_t)R * G::QCOLS * 8)) return rc;
+        MdGradArgs a{};
+        a.wbwd = h->wbwd.p;
+        a.N = N;
+        a.Nx = h->Nx;
+        a.ns = ns;
+        a.nsb = (ns + kChains - 1) / kChains;
+        a.bits = (const uint32_t*)h->bits.p;
+        a.hs = (const double*)h->hck.p;
+        a.eloc = (const double*)h->eloc.p;
+        a.mean_e = c.mean_e;
+        a.inv_norm = c.inv_norm;
+        a.mom = c.mom;
+        a.P = (double*)h->gradP.p;
+        a.Q = (double*)h->gradQ.p;
+        a.head_grad = (double*)h->gradW.p + (size_t)G::PCOLS * G::QCOLS;
+        a.vert_pos = m.vert_pos;
+        a.row_first = m.row_first;
         const void* fn = (const void*)mdrnn_bwd_kernel<NFULL, WAVES>;
         int bpc = 0;
         if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, G::BYTES, &bpc)) return rc;
@@ -371,10 +389,13 @@ struct MGrad {
             head_reduce_launch<double>(h, (size_t)grid * WAVES, 2 * G::HEAD_ROW, a.head_grad);
         }
         RNNWF_HIP(h, hipGetLastError());
-        return tn_gemm_launch<double, G::PCOLS / 16, G::QCOLS / 16>(h, a.P, a.Q, R, dW);
+        return tn_gemm_launch<double, G::PCOLS / 16, G::QCOLS / 16>(h, a.P, a.Q, R, (double*)h->gradW.p);
     }
 
-    static void unpack(rnnwf_handle* h, const double* dW, const double* hg) {
+    // dW image [PCOLS][QCOLS], then the two head rows -> TF-named gradient arrays
+    static void unpack(rnnwf_handle* h, const void* img) {
+        const double* dW = (const double*)img;
+        const double* hg = dW + (size_t)G::PCOLS * G::QCOLS;
         const int H = h->H;
         auto col_of_unit = [&](int k) { return k < 16 * NFULL ? 16 * (k / 16) + 4 * (k % 4) + (k % 16) / 4 : 16 * NFULL + 4 * (k - 16 * NFULL); };
         const int xcol = 16 * NFULL + 1, onecol = 16 * NFULL + 3, voff = 16 * G::NT;
@@ -419,98 +440,39 @@ struct MGrad {
         }                                                       \
     } while (0)
 
+int no_grad_kernel(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: num_units > 84 not implemented"); }
+
+// the gradient hooks (models.h: Gradient)
+int grad_layout(rnnwf_handle* h, GradImage* out) {
+    MG_DISPATCH(h, { *out = K::layout(); return 0; });
+    return no_grad_kernel(h);
+}
+int grad_pack(rnnwf_handle* h, std::vector<char>* img) {
+    MG_DISPATCH(h, { if (img) *img = K::template pack<double>(h); else K::template pack<Lin>(h); return 0; });
+    return no_grad_kernel(h);
+}
+int grad_launch(rnnwf_handle* h, const GradCost& c) {
+    MG_DISPATCH(h, return K::launch(h, c));
+    return no_grad_kernel(h);
+}
+void grad_unpack(rnnwf_handle* h, const void* img) {
+    MG_DISPATCH(h, { K::unpack(h, img); return; });
+}
+
 }  // namespace
 
-// The gradient's kernels on the batch of the last rnnwf_vmc_step; result (dW image, then the head rows) left in h->gradW.
-// mom_dev != nullptr (device-resident training, train.hip): mean energy and norm come from the step's moments on the device.
-int rnnwf::mdrnn_grad_device(rnnwf_handle* h, double mean_energy, double norm, const double* mom_dev, size_t* dw_count) {
-    if (h->NFULL > 5) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: num_units > 84 not implemented");
-    if (h->last_ns <= 0 || !h->last_has_ckpt)
-        return h->fail(RNNWF_ERR_STATE, "rnnwf_vmc_gradient: call rnnwf_vmc_step first (its samples, states and E_loc are reused)");
-    if (!mom_dev && !(norm > 0)) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: norm must be positive");
-    RNNWF_HIP(h, hipSetDevice(h->cfg.device));
-    Maps m;
-    if (int rc = get_maps(h, &m)) return rc;
-    const int N = h->N;
-    const int64_t ns = h->last_ns, R = ns * N;
-    int pcols = 0, qcols = 0, hgn = 0;
-    MG_DISPATCH(h, { pcols = K::G::PCOLS; qcols = K::G::QCOLS; hgn = 2 * K::G::HEAD_ROW; break; });
-    if (!h->wbwd_valid) {
-        std::vector<char> img;
-        MG_DISPATCH(h, { img = K::template pack<double>(h); break; });
-        if (int rc = ensure(h, h->wbwd, img.size())) return rc;
-        if (int rc = upload(h, h->wbwd.p, img.data(), img.size())) return rc;
-        h->wbwd_valid = true;
-    }
-    if (int rc = ensure(h, h->gradP, (size_t)R * pcols * 8)) return rc;
-    if (int rc = ensure(h, h->gradQ, (size_t)R * qcols * 8)) return rc;
-    const size_t dwn = (size_t)pcols * qcols + hgn;
-    if (dw_count) *dw_count = dwn;
-    if (int rc = ensure(h, h->gradW, dwn * 8)) return rc;
-    RNNWF_HIP(h, hipMemsetAsync(h->gradW.p, 0, dwn * 8, h->stream));
-    MdGradArgs a{};
-    a.wbwd = h->wbwd.p;
-    a.N = N;
-    a.Nx = h->Nx;
-    a.ns = ns;
-    a.nsb = (ns + kChains - 1) / kChains;
-    a.bits = (const uint32_t*)h->bits.p;
-    a.hs = (const double*)h->hck.p;
-    a.eloc = (const double*)h->eloc.p;
-    a.mean_e = mean_energy;
-    a.inv_norm = mom_dev ? 1.0 : 1.0 / norm;
-    a.mom = mom_dev;
-    a.P = (double*)h->gradP.p;
-    a.Q = (double*)h->gradQ.p;
-    a.head_grad = (double*)h->gradW.p + (size_t)pcols * qcols;
-    a.vert_pos = m.vert_pos;
-    a.row_first = m.row_first;
-    MG_DISPATCH(h, { if (int rc = K::run(h, a, R, (double*)h->gradW.p)) return rc; break; });
-    return RNNWF_OK;
+const Family* rnnwf::mdrnn_family() {
+    static const Gradient g = {grad_layout, grad_pack, grad_launch, grad_unpack};
+    static const Family f = {
+        "2D RNN", pack_image, log_prob_pass, nullptr, eloc_on_device, max_chains_per_pass, site_maps, nullptr,
+        1, 1,               // Jz per site; Bx
+        false, true, &g,    // float64 E_loc; the base pass alone keeps every site's state
+    };
+    return &f;
 }
 
-int rnnwf::mdrnn_vmc_gradient(rnnwf_handle* h, double mean_energy, double norm) {
-    size_t dwn = 0;
-    if (int rc = mdrnn_grad_device(h, mean_energy, norm, nullptr, &dwn)) return rc;
-    int pcols = 0, qcols = 0;
-    MG_DISPATCH(h, { pcols = K::G::PCOLS; qcols = K::G::QCOLS; break; });
-    if (int rc = ensure_staging(h, dwn * 8)) return rc;
-    const double* host = (const double*)h->staging;
-    RNNWF_HIP(h, hipMemcpyAsync(h->staging, h->gradW.p, dwn * 8, hipMemcpyDeviceToHost, h->stream));
-    RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    MG_DISPATCH(h, { K::unpack(h, host, host + (size_t)pcols * qcols); break; });
-    return RNNWF_OK;
-}
-
-// ---- device-resident training (train.hip): the packers' tables and the gradient image's map ---------------------------------
-int rnnwf::mdrnn_pack_table(rnnwf_handle* h, bool backward) {
-    if (backward) { MG_DISPATCH(h, { K::template pack<Lin>(h); return 0; }); }
-    else { MD_DISPATCH(h, { K::template pack<Lin>(h); return 0; }); }
+// device-resident training (train.hip): the forward image's table
+int rnnwf::mdrnn_pack_table(rnnwf_handle* h) {
+    MD_DISPATCH(h, { K::template pack<Lin>(h); return 0; });
     return 1;
-}
-
-// sidx[i] = 1 + the gradient image element parameter i (order of rnnwf_set_params_flat) is read from, found by running the host
-// unpacker on an image holding its own indices
-int rnnwf::mdrnn_grad_probe(rnnwf_handle* h, std::vector<int32_t>& sidx, size_t* dw_count) {
-    int pcols = 0, qcols = 0, hgn = 0;
-    MG_DISPATCH(h, { pcols = K::G::PCOLS; qcols = K::G::QCOLS; hgn = 2 * K::G::HEAD_ROW; break; });
-    const size_t n = (size_t)pcols * qcols + hgn;
-    if (n == 0 || n >= ((size_t)1 << 31)) return h->fail(RNNWF_ERR_INVALID, "gradient image of %zu elements cannot be probed", n);
-    const auto saved = h->grads;
-    std::vector<double> img(n);
-    for (size_t k = 0; k < n; ++k) img[k] = (double)(k + 1);
-    MG_DISPATCH(h, { K::unpack(h, img.data(), img.data() + (size_t)pcols * qcols); break; });
-    sidx.clear();
-    int rc = 0;
-    for (auto& kv : h->params) {
-        auto it = h->grads.find(kv.first);
-        if (it == h->grads.end() || it->second.size() != kv.second.value.size()) {
-            rc = h->fail(RNNWF_ERR_STATE, "mdrnn_grad_probe: no gradient for '%s'", kv.first.c_str());
-            break;
-        }
-        for (size_t i = 0; i < kv.second.slot.size(); ++i) sidx.push_back((int32_t)std::llround(it->second[(size_t)kv.second.slot[i]]));
-    }
-    h->grads = saved;
-    if (dw_count) *dw_count = n;
-    return rc;
 }

@@ -25,6 +25,7 @@ int run_parity_share(rnnwf_handle* h, double* lpF, double* lpR, int64_t n);     
 // against it: chunk loop, copies back to the host, budget refusals and the resident-batch rule live there.
 struct Draw { uint64_t seed, step; int64_t offset; };     // where an entry point takes a Draw, nullptr = teacher-forced
                                                           // on the spins the driver packed into h->bits
+struct Gradient;
 struct Family {
     const char* name;
     int (*pack_image)(rnnwf_handle* h, std::vector<char>& img);
@@ -43,19 +44,47 @@ struct Family {
     int coupl_tail;            // ... followed by this many scalars read on the host (TFIM: Bx; J1-J2: periodic, marshall)
     bool complex_eloc;         // complex64 E_loc (else float64)
     bool base_keeps_states;    // the base pass alone needs the state budget: log_prob runs in passes, sample refuses past it
-    bool has_gradient;         // rnnwf_vmc_step leaves its batch resident for rnnwf_vmc_gradient
+    // the VMC-cost gradient; nullptr: none, and rnnwf_vmc_step leaves no batch resident for it
+    const Gradient* gradient;
+};
+
+// ---- the VMC-cost gradient: one hook table per family that has one (grad.hip: the GRUs, mdrnn.hip: the 2D RNN) ---------------
+// The driver (grad_device, grad.hip) checks the resident batch, scales the cost, packs and uploads the backward image when it is
+// stale, allocates and clears h->gradW and calls `launch`.  rnnwf_vmc_gradient downloads the result and calls `unpack`; device
+// training (train.hip) reads it on the device through a table probed from `unpack` (grad_flat_probe).
+struct GradImage {
+    bool f64;          // element type of h->gradW (else float)
+    size_t count;      // elements of the result: the dW images and the head rows
+    size_t alloc;      // elements allocated and cleared: count, plus the stacked GRU's scratch head row for its layer-0 pass
+};
+// w_s = (E_s - mean) * inv_norm; mom != nullptr: mean and norm are read from the step's moments on the device (GradArgs::mom)
+struct GradCost { double mean_e, mean_im, inv_norm; const double* mom; };
+struct Gradient {
+    int (*layout)(rnnwf_handle* h, GradImage* out);
+    // the backward image: img != nullptr: packed as doubles for upload; nullptr: its table over Lin into the active PackTrace
+    int (*pack)(rnnwf_handle* h, std::vector<char>* img);
+    // the backward kernels on the resident batch (h->bits, h->hck, h->eloc), adding into the cleared h->gradW
+    int (*launch)(rnnwf_handle* h, const GradCost& cost);
+    // a host copy of the h->gradW image -> h->grads
+    void (*unpack)(rnnwf_handle* h, const void* img);
 };
 // the tables are static locals of host functions: hipcc would emit a namespace-scope const table for the device as well
 const Family* gru_family();     // prnn.hip: GRU1D, GRU1D_PARITY, GRU1D_F64
 const Family* crnn_family();    // crnn.hip: CRNN_U1
 const Family* mdrnn_family();   // mdrnn.hip: MDRNN2D
 const Family* lstm_family();    // lstm.hip: LSTM1D_F64
+const Gradient* gru_gradient();   // grad.hip: the GRU hooks of gru_family and crnn_family (mdrnn.hip keeps the 2D RNN's)
 
 // the fused VMC step behind rnnwf_vmc_step and rnnwf_train_steps (rnnwf_api.hip); out_samples, out_eloc, moments may be nullptr
 int vmc_step(rnnwf_handle* h, int64_t ns, const Draw& draw, const double* couplings, int32_t* out_samples, void* out_eloc,
              double* moments);
 // RNNWF_ERR_INVALID ("<what>: no gradient for the ...") for a family without one
 int require_gradient(rnnwf_handle* h, const char* what);
+// the gradient driver (grad.hip): result left in h->gradW, its layout in *im (may be nullptr).  mom_dev != nullptr (device
+// training): mean energy and norm come from the step's moments on the device and the three doubles are unused
+int grad_device(rnnwf_handle* h, double mean_energy, double mean_energy_im, double norm, const double* mom_dev, GradImage* im);
+// sidx[i] = +-(1 + the h->gradW element flat parameter i is read from), 0: none (order of rnnwf_set_params_flat)
+int grad_flat_probe(rnnwf_handle* h, std::vector<int32_t>& sidx, GradImage* im);
 
 // complex RNN only (crnn.hip): amplitudes and J1-J2 local energies on caller-supplied samples
 int crnn_log_amp(rnnwf_handle* h, const int32_t* samples, int64_t B, float* out_re_im, double* out_logp);
@@ -104,18 +133,13 @@ int prnn_base_coop_bf(rnnwf_handle* h, const PrnnArgs& a);
 int crnn_base_coop_bf(rnnwf_handle* h, const CrnnArgs& a);
 
 // ---- gradient (grad.hip) ---------------------------------------------------------------------------
-int mdrnn_vmc_gradient(rnnwf_handle* h, double mean_energy, double norm);
 // grad_wide.hip: backward kernels compiled in their own translation unit (index: grad.hip, GLaunch::WIDE)
 struct GradArgs;
 const void* grad_wide_kernel(int which);
 void grad_wide_launch(int which, unsigned grid, size_t lds, hipStream_t stream, const GradArgs& a);
-int mdrnn_grad_device(rnnwf_handle* h, double mean_energy, double norm, const double* mom_dev, size_t* dw_count);
-int mdrnn_pack_table(rnnwf_handle* h, bool backward);
-int mdrnn_grad_probe(rnnwf_handle* h, std::vector<int32_t>& sidx, size_t* dw_count);
-int grad_single_layer_device(rnnwf_handle* h, double mean_energy, double mean_energy_im, double norm, const double* mom_dev, size_t* dw_count);
-int grad_bwd_pack_table(rnnwf_handle* h);
+// forward weight-image tables into the active PackTrace, for device training: the 2D RNN's (mdrnn.hip), a stack's [layer 0 | upper layers]
+int mdrnn_pack_table(rnnwf_handle* h);
 int grad_stack_forward_table(rnnwf_handle* h);
-int grad_flat_probe(rnnwf_handle* h, std::vector<int32_t>& sidx, size_t* dw_count, bool* is_f64);
 // ---- device-resident training (train.hip) ------------------------------------------------------------
 void train_params_changed_on_host(rnnwf_handle* h);           // rnnwf_set_param / rnnwf_commit_params: the device copy is stale
 int train_sync_params_to_host(rnnwf_handle* h);               // before the host reads its copy (rnnwf_get_param, checkpoints)

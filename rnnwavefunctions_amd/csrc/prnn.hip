@@ -396,7 +396,7 @@ const Family* rnnwf::gru_family() {
     static const Family f = {
         "GRU cell", pack_image, log_prob_pass, symmetrise, eloc_on_device, max_chains_per_pass, nullptr, nullptr,
         1, 1,                // Jz per site; Bx
-        false, false, true,  // float64 E_loc; the base pass alone keeps no states; has a gradient
+        false, false, gru_gradient(),   // float64 E_loc; the base pass alone keeps no states
     };
     return &f;
 }

@@ -530,7 +530,7 @@ int rnnwf::run_parity_share(rnnwf_handle* h, double* lpF, double* lpR, int64_t n
 constexpr int64_t kLogProbChunk = (int64_t)1 << 20;   // chains per base pass where the pass keeps no states
 
 int rnnwf::require_gradient(rnnwf_handle* h, const char* what) {
-    if (h->family->has_gradient) return 0;
+    if (h->family->gradient) return 0;
     return h->fail(RNNWF_ERR_INVALID, "%s: no gradient for the %s", what, h->family->name);
 }
 
@@ -543,9 +543,7 @@ static int64_t n_couplings(const rnnwf_handle* h) { return (int64_t)h->family->c
 
 // the batch just computed stays on the device (h->bits, h->hck, h->eloc) for rnnwf_vmc_gradient
 static void keep_resident(rnnwf_handle* h, int64_t ns) {
-    if (!h->family->has_gradient) return;
-    h->last_ns = ns;
-    h->last_has_ckpt = true;
+    if (h->family->gradient) h->last_ns = ns;
 }
 
 static int refuse_past_budget(rnnwf_handle* h, int64_t ns, const char* what) {

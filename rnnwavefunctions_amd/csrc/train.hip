@@ -4,8 +4,10 @@
 // The reference runs an iteration's update as one `sess.run(optstep)` on the device (1DTFIM/TrainingRNN_1DTFIM.py:113,162,221;
 // tf.train.AdamOptimizer, beta1 0.9, beta2 0.999, epsilon 1e-8).  Here, per iteration and without a host visit:
 //     rnnwf_vmc_step's kernels (samples, local energies, the four moments - left on the device)
-//     the gradient's kernels (grad.hip), mean energy and norm read from those moments on the device
-//     grad_flat_kernel    dW image -> flat f64 gradient in the order of rnnwf_set_params_flat (table probed from the host unpacker)
+//     the gradient's kernels (grad.hip: grad_device, the driver rnnwf_vmc_gradient runs), mean energy and norm read from those
+//                         moments on the device
+//     grad_flat_kernel    dW image -> flat f64 gradient in the order of rnnwf_set_params_flat (table probed from the family's
+//                         host unpacker: grad_flat_probe)
 //     [RCCL all-reduce of the flat gradient on the stream, multi-rank]
 //     adam_kernel         m, v, theta in f64; theta rounded to the model's type as the host optimizer does
 //     repack_all_kernel   every weight image rebuilt from theta by replaying the host packers' recorded tables (pack_value.h), one launch
@@ -187,10 +189,10 @@ int build(rnnwf_handle* h) {
     RNNWF_HIP(h, hipHostGetDevicePointer(&t.mom_host_dev, t.mom_host, 0));
     // gradient: dW image -> flat
     std::vector<int32_t> sidx;
-    if (md) {
-        t.dw_f64 = true;
-        if (int rc = mdrnn_grad_probe(h, sidx, &t.dw_count)) return rc;
-    } else if (int rc = grad_flat_probe(h, sidx, &t.dw_count, &t.dw_f64)) return rc;
+    GradImage im;
+    if (int rc = grad_flat_probe(h, sidx, &im)) return rc;
+    t.dw_count = im.count;
+    t.dw_f64 = im.f64;
     if ((int64_t)sidx.size() != t.nparams) return h->fail(RNNWF_ERR_STATE, "device training: gradient probe size mismatch");
     for (int32_t k : sidx)
         if ((size_t)(k < 0 ? -k : k) > t.dw_count) return h->fail(RNNWF_ERR_STATE, "device training: gradient probe index out of range");
@@ -199,7 +201,7 @@ int build(rnnwf_handle* h) {
     // images (the backward image's table is added on first use: its buffer exists once the gradient has packed it on the host)
     t.nimg = 0;
     if (md) {
-        if (int rc = add_image(h, &h->wimg, [&] { return mdrnn_pack_table(h, false); })) return rc;
+        if (int rc = add_image(h, &h->wimg, [&] { return mdrnn_pack_table(h); })) return rc;
     } else if (h->NL > 1) {
         // a stack: the forward buffer holds [layer 0 | upper layers] (grad.hip knows the layouts); on the bf16x3 engine (37..50 units)
         // the layer pipeline's images beside it (split.hip: prnn_stack_pack / crnn_stack_pack)
@@ -233,7 +235,7 @@ int ensure_bwd_image(rnnwf_handle* h) {
     for (int i = 0; i < t.nimg; ++i)
         if (t.img[i].target == &h->wbwd) return 0;
     if (!h->wbwd.p) return h->fail(RNNWF_ERR_STATE, "device training: the backward image has not been packed yet");
-    return add_image(h, &h->wbwd, [&] { return h->model == RNNWF_MODEL_MDRNN2D ? mdrnn_pack_table(h, true) : grad_bwd_pack_table(h); });
+    return add_image(h, &h->wbwd, [&] { return h->family->gradient->pack(h, nullptr); });
 }
 
 int params_to_device(rnnwf_handle* h) {
@@ -428,7 +430,6 @@ extern "C" int rnnwf_train_steps(rnnwf_handle* h, int32_t K, int64_t numsamples,
     RNNWF_HIP(h, hipSetDevice(h->cfg.device));
     if (int rc = build(h)) return rc;
     TrainState& t = h->train;
-    const bool md = h->model == RNNWF_MODEL_MDRNN2D;
     if (n_couplings != (int64_t)h->family->coupl_per_site * h->N + h->family->coupl_tail)
         return h->fail(RNNWF_ERR_INVALID, "rnnwf_train_steps: wrong number of couplings");
     if (int rc = params_to_device(h)) return rc;
@@ -440,8 +441,7 @@ extern "C" int rnnwf_train_steps(rnnwf_handle* h, int32_t K, int64_t numsamples,
         if (rc) return rc;
         if (h->reduce_in_step)
             RNNWF_HIP(h, hipMemcpyAsync((double*)t.mom_host + 4 * k, h->moments.p, 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        if (int r2 = md ? mdrnn_grad_device(h, 0.0, 0.0, (const double*)h->moments.p, nullptr)
-                        : grad_single_layer_device(h, 0.0, 0.0, 0.0, (const double*)h->moments.p, nullptr)) return r2;
+        if (int r2 = grad_device(h, 0.0, 0.0, 0.0, (const double*)h->moments.p, nullptr)) return r2;
         if (int r2 = ensure_bwd_image(h)) return r2;
         if (int r2 = launch_update(h, adam_lr_t(learning_rates[k], beta1, beta2, t.adam_t + k + 1), beta1, beta2, epsilon)) return r2;
     }
