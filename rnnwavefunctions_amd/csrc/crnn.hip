@@ -13,23 +13,15 @@ using namespace rnnwf;
 
 namespace {
 
-constexpr size_t kHckBudget = (size_t)48 << 30;
 constexpr int64_t kChunk = (int64_t)1 << 20;
 
 template <int NFULL, int WAVES>
 struct CLaunch {
     using L = GruLayout<float, NFULL, 3>;
-    static int blocks_per_cu(rnnwf_handle* h, const void* fn, int* out) { return rnnwf::blocks_per_cu(h, fn, WAVES * 64, L::LDS_BYTES, out); }
     static int base_coop(rnnwf_handle* h, const CrnnArgs& a) {
         if constexpr (NFULL <= 4) {
-            const void* fn = (const void*)crnn_base_coop_kernel<NFULL>;
             const size_t lds = L::BYTES + (size_t)2 * L::KT * 64 * 4 + 2 * 64 * 4;
-            int bpc = 0;
-            if (int rc = rnnwf::blocks_per_cu(h, fn, (NFULL + 1) * 64, lds, &bpc)) return rc;
-            const unsigned grid = (unsigned)std::min<int64_t>(a.nsb, (int64_t)bpc * h->cu_count);
-            TimedLaunch tl(h, 0);
-            crnn_base_coop_kernel<NFULL><<<grid, (NFULL + 1) * 64, lds, h->stream>>>(a);
-            RNNWF_HIP(h, hipGetLastError());
+            return launch_persistent(h, kTimerBase, crnn_base_coop_kernel<NFULL>, (NFULL + 1) * 64, lds, a.nsb, 1, a);
         }
         return 0;
     }
@@ -37,27 +29,11 @@ struct CLaunch {
         if (NFULL <= 3 && base_bf_available(h)) return crnn_base_coop_bf(h, a);      // bf16 cooperative kernel, every batch size (prnn.hip)
         // fewer 16-chain blocks than SIMDs: the cooperative kernel (NFULL + 1 waves per block, bit-identical)
         if (NFULL <= 4 && a.nsb <= (int64_t)4 * h->cu_count && !h->knobs.no_coop) return base_coop(h, a);
-        const void* fn = (const void*)crnn_base_kernel<NFULL, WAVES>;
-        int bpc = 0;
-        if (int rc = blocks_per_cu(h, fn, &bpc)) return rc;
-        const int64_t need = (a.nsb + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::min<int64_t>(need, (int64_t)bpc * h->cu_count);
-        TimedLaunch tl(h, 0);
-        crnn_base_kernel<NFULL, WAVES><<<grid, WAVES * 64, L::LDS_BYTES, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerBase, crnn_base_kernel<NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, a.nsb, WAVES, a);
     }
+    // the tile count lives on the device: the persistent grid is bounded by the worst case
     static int swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles) {
-        const void* fn = (const void*)crnn_swap_kernel<NFULL, WAVES>;
-        int bpc = 0;
-        if (int rc = blocks_per_cu(h, fn, &bpc)) return rc;
-        // the tile count lives on the device: launch the persistent grid, bounded by the worst case
-        const int64_t need = (max_tiles + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)bpc * h->cu_count));
-        TimedLaunch tl(h, 1);
-        crnn_swap_kernel<NFULL, WAVES><<<grid, WAVES * 64, L::LDS_BYTES, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerFlip, crnn_swap_kernel<NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, max_tiles, WAVES, a);
     }
     static std::vector<char> pack(const rnnwf_handle* h) { return pack_gru_image<float, NFULL, 3>(h); }
     static size_t hck_bytes_per_block() { return (size_t)L::KT * 64 * sizeof(float); }
@@ -73,40 +49,13 @@ struct CMLaunch {
         if constexpr (MlCoopLayout<NFULL, NL, 3>::FITS && M::SPILL == 0) {
             if (!h->knobs.no_coop) {
                 using ML = MlCoopLayout<NFULL, NL, 3>;
-                const void* cfn = (const void*)crnn_base_coop_kernel<NFULL, false, NL>;
-                int cb = 0;
-                if (int rc = rnnwf::blocks_per_cu(h, cfn, ML::THREADS, ML::LDS, &cb)) return rc;
-                const int64_t need = (a.nsb + ML::NB - 1) / ML::NB;
-                const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)cb * h->cu_count));
-                TimedLaunch tl(h, 0);
-                crnn_base_coop_kernel<NFULL, false, NL><<<grid, ML::THREADS, ML::LDS, h->stream>>>(a);
-                RNNWF_HIP(h, hipGetLastError());
-                return 0;
+                return launch_persistent(h, kTimerBase, crnn_base_coop_kernel<NFULL, false, NL>, ML::THREADS, ML::LDS, a.nsb, ML::NB, a);
             }
         }
-        const void* fn = (const void*)crnn_ml_base_kernel<NFULL, NL, WAVES>;
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, M::BYTES, &bpc)) return rc;
-        // as few waves per workgroup as still cover the batch with every resident workgroup busy (prnn.hip: MLaunchL::base)
-        const int64_t slots = (int64_t)bpc * h->cu_count;
-        const int wpb = (int)std::max<int64_t>(1, std::min<int64_t>(WAVES, (a.nsb + slots - 1) / slots));
-        const int64_t need = (a.nsb + wpb - 1) / wpb;
-        const unsigned grid = (unsigned)std::min<int64_t>(need, slots);
-        TimedLaunch tl(h, 0);
-        crnn_ml_base_kernel<NFULL, NL, WAVES><<<grid, wpb * 64, M::BYTES, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_shrinking<WAVES>(h, kTimerBase, crnn_ml_base_kernel<NFULL, NL, WAVES>, M::BYTES, a.nsb, a);
     }
     static int swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles) {
-        const void* fn = (const void*)crnn_ml_swap_kernel<NFULL, NL, WAVES>;
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, M::BYTES, &bpc)) return rc;
-        const int64_t need = (max_tiles + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)bpc * h->cu_count));
-        TimedLaunch tl(h, 1);
-        crnn_ml_swap_kernel<NFULL, NL, WAVES><<<grid, WAVES * 64, M::BYTES, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerFlip, crnn_ml_swap_kernel<NFULL, NL, WAVES>, WAVES * 64, M::BYTES, max_tiles, WAVES, a);
     }
     static std::vector<char> pack(const rnnwf_handle* h) {
         std::vector<char> img = pack_gru_image<float, NFULL, 3>(h);
@@ -119,61 +68,59 @@ struct CMLaunch {
     static size_t hck_bytes_per_block() { return (size_t)NL * M::KT * 64 * sizeof(float); }
 };
 
-#define CRNN_DISPATCH(h, EXPR)                                  \
-    do {                                                        \
-        if ((h)->NL == 2) {                                     \
-            switch ((h)->NFULL) {                               \
-                case 1: { using K = CMLaunch<1, 2, 4>; EXPR; }  \
-                case 2: { using K = CMLaunch<2, 2, 4>; EXPR; }  \
-                case 3: { using K = CMLaunch<3, 2, 8>; EXPR; }  \
-                case 4: { using K = CMLaunch<4, 2, 4>; EXPR; }  \
-                case 6: { using K = CMLaunch<6, 2, 4>; EXPR; }  \
-            }                                                   \
-            break;                                              \
-        }                                                       \
-        if ((h)->NL == 4) {                                     \
-            switch ((h)->NFULL) {                               \
-                case 1: { using K = CMLaunch<1, 4, 4>; EXPR; }  \
-                case 2: { using K = CMLaunch<2, 4, 4>; EXPR; }  \
-                case 3: { using K = CMLaunch<3, 4, 4>; EXPR; }  \
-                case 4: { using K = CMLaunch<4, 4, 4>; EXPR; }  \
-                case 6: { using K = CMLaunch<6, 4, 4>; EXPR; }  \
-            }                                                   \
-            break;                                              \
-        }                                                       \
-        if ((h)->NL == 3) {                                     \
-            switch ((h)->NFULL) {                               \
-                case 1: { using K = CMLaunch<1, 3, 4>; EXPR; }  \
-                case 2: { using K = CMLaunch<2, 3, 8>; EXPR; }  \
-                case 3: { using K = CMLaunch<3, 3, 8>; EXPR; }  \
-                case 4: { using K = CMLaunch<4, 3, 4>; EXPR; }  \
-                case 6: { using K = CMLaunch<6, 3, 4>; EXPR; }  \
-            }                                                   \
-            break;                                              \
-        }                                                       \
-        switch ((h)->NFULL) {                                   \
-            case 1: { using K = CLaunch<1, 4>; EXPR; }          \
-            case 2: { using K = CLaunch<2, 4>; EXPR; }          \
-            case 3: { using K = CLaunch<3, 4>; EXPR; }          \
-            case 4: { using K = CLaunch<4, 4>; EXPR; }          \
-            case 6: { using K = CLaunch<6, 8>; EXPR; }         \
-            case 8: { using K = CLaunch<8, 4>; EXPR; }          \
-            case 12: { using K = CLaunch<12, 4>; EXPR; }        \
-            case 16: { using K = CLaunch<16, 4>; EXPR; }        \
-        }                                                       \
-    } while (0)
+// fn(K()) for this handle's launch class K, false (fn not called) for a shape without kernels: <NFULL, [layers,] waves per workgroup>
+template <class Fn>
+bool with_launch(const rnnwf_handle* h, Fn&& fn) {
+    const int nf = h->NFULL;
+    switch (h->NL) {
+        case 2: switch (nf) {
+            case 1: fn(CMLaunch<1, 2, 4>()); return true;
+            case 2: fn(CMLaunch<2, 2, 4>()); return true;
+            case 3: fn(CMLaunch<3, 2, 8>()); return true;
+            case 4: fn(CMLaunch<4, 2, 4>()); return true;
+            case 6: fn(CMLaunch<6, 2, 4>()); return true;
+        } return false;
+        case 3: switch (nf) {
+            case 1: fn(CMLaunch<1, 3, 4>()); return true;
+            case 2: fn(CMLaunch<2, 3, 8>()); return true;
+            case 3: fn(CMLaunch<3, 3, 8>()); return true;
+            case 4: fn(CMLaunch<4, 3, 4>()); return true;
+            case 6: fn(CMLaunch<6, 3, 4>()); return true;
+        } return false;
+        case 4: switch (nf) {
+            case 1: fn(CMLaunch<1, 4, 4>()); return true;
+            case 2: fn(CMLaunch<2, 4, 4>()); return true;
+            case 3: fn(CMLaunch<3, 4, 4>()); return true;
+            case 4: fn(CMLaunch<4, 4, 4>()); return true;
+            case 6: fn(CMLaunch<6, 4, 4>()); return true;
+        } return false;
+    }
+    switch (nf) {
+        case 1: fn(CLaunch<1, 4>()); return true;
+        case 2: fn(CLaunch<2, 4>()); return true;
+        case 3: fn(CLaunch<3, 4>()); return true;
+        case 4: fn(CLaunch<4, 4>()); return true;
+        case 6: fn(CLaunch<6, 8>()); return true;
+        case 8: fn(CLaunch<8, 4>()); return true;
+        case 12: fn(CLaunch<12, 4>()); return true;
+        case 16: fn(CLaunch<16, 4>()); return true;
+    }
+    return false;
+}
 
+int no_kernel(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "no cRNN kernel for NFULL=%d", h->NFULL); }
 int launch_base(rnnwf_handle* h, const CrnnArgs& a) {
-    CRNN_DISPATCH(h, return K::base(h, a));
-    return h->fail(RNNWF_ERR_INVALID, "no cRNN kernel for NFULL=%d", h->NFULL);
+    int rc = 0;
+    return with_launch(h, [&](auto k) { rc = decltype(k)::base(h, a); }) ? rc : no_kernel(h);
 }
 int launch_swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles) {
-    CRNN_DISPATCH(h, return K::swap(h, a, max_tiles));
-    return h->fail(RNNWF_ERR_INVALID, "no cRNN kernel for NFULL=%d", h->NFULL);
+    int rc = 0;
+    return with_launch(h, [&](auto k) { rc = decltype(k)::swap(h, a, max_tiles); }) ? rc : no_kernel(h);
 }
 size_t hck_bytes_per_block(rnnwf_handle* h) {
-    CRNN_DISPATCH(h, return K::hck_bytes_per_block());
-    return 0;
+    size_t b = 0;
+    with_launch(h, [&](auto k) { b = decltype(k)::hck_bytes_per_block(); });
+    return b;
 }
 
 // sites with a stored state: a stack keeps all N (the layer-wise gradient reads the lower layers' last site too)
@@ -192,7 +139,7 @@ int64_t max_chains_per_pass(rnnwf_handle* h) {
     size_t per_block = (size_t)hck_sites(h) * hck_bytes_per_block(h);
     if (h->NL > 1 && h->engine_split)                         // the layer pipeline's records: ~2 items per sample and site, per 16 chains
         per_block += stack_record_bytes_per_32_chains(h, (int64_t)h->N * (h->N - 1) / 2) + stack_record_bytes_per_32_chains(h, 4 * (int64_t)h->N);
-    return std::max<int64_t>(1, (int64_t)(state_budget_bytes(h, kHckBudget) / per_block)) * kChains;
+    return std::max<int64_t>(1, (int64_t)(state_budget_bytes(h, kDefaultStateBudget) / per_block)) * kChains;
 }
 
 // Upper bound of the wave-steps (32-item tiles x chain length) of one swap pass: first-changed site lo owns the bonds (lo, lo + 1) and
@@ -248,7 +195,7 @@ int j1j2_on_device(rnnwf_handle* h, int64_t ns, bool sampling, uint64_t seed, ui
     e.cnt = cnt; e.items = (SwapItem*)h->tiles.p; e.cap = cap;
     e.contrib = (double2*)h->lpq.p; e.diag = diag;
     {
-        TimedLaunch tl(h, 2);
+        TimedLaunch tl(h, kTimerAssembly);
         dim3 grid((unsigned)((ns + 255) / 256), (unsigned)(2 * N));
         j1j2_enumerate_kernel<<<grid, 256, 0, h->stream>>>(e);
         RNNWF_HIP(h, hipGetLastError());
@@ -273,13 +220,9 @@ int j1j2_on_device(rnnwf_handle* h, int64_t ns, bool sampling, uint64_t seed, ui
     } else {
         if (int rc = launch_swap(h, a, max_tiles)) return rc;
     }
-    {
-        TimedLaunch tl(h, 2);
-        j1j2_eloc_kernel<<<(unsigned)((ns + 255) / 256), 256, 0, h->stream>>>((const double2*)h->lpq.p, diag, ns, N,
-                                                                            (float2*)h->eloc.p, N <= 256 ? cnt : nullptr);
-        RNNWF_HIP(h, hipGetLastError());
-        h->j1j2_cnt_clean = N <= 256;
-    }
+    if (int rc = timed_launch(h, kTimerAssembly, j1j2_eloc_kernel, (unsigned)((ns + 255) / 256), 256, 0, (const double2*)h->lpq.p, diag,
+                              ns, N, (float2*)h->eloc.p, N <= 256 ? cnt : nullptr)) return rc;
+    h->j1j2_cnt_clean = N <= 256;
     return 0;
 }
 
@@ -326,8 +269,7 @@ int pack_image(rnnwf_handle* h, std::vector<char>& img) {
         if (int rc = upload(h, h->wsplit.p, simg.data(), simg.size())) return rc;
     }
     if (int rc = base_bf_pack(h)) return rc;
-    CRNN_DISPATCH(h, { img = K::pack(h); return 0; });
-    return h->fail(RNNWF_ERR_INVALID, "no cRNN kernel for NFULL=%d", h->NFULL);
+    return with_launch(h, [&](auto k) { img = decltype(k)::pack(h); }) ? 0 : no_kernel(h);
 }
 
 }  // namespace

@@ -71,18 +71,16 @@ struct GLaunch {
     static int run_pair(rnnwf_handle* h, GradArgs a, int64_t R, void* dW) {
         if constexpr (PAIR_OK) {
             using GP = GradPair<T, NFULL, NOUT>;
-            const void* fn = (const void*)gru_bwd_kernel<T, NFULL, 2 * GP::NB, NOUT, true>;
-            int bpc = 0;
-            if (int rc = rnnwf::blocks_per_cu(h, fn, 2 * GP::NB * 64, GP::LDS, &bpc)) return rc;
-            const int64_t need = (a.nsb + GP::NB - 1) / GP::NB;
-            const unsigned grid = (unsigned)std::min<int64_t>(need, (int64_t)bpc * h->cu_count);
+            const auto kern = gru_bwd_kernel<T, NFULL, 2 * GP::NB, NOUT, true>;
+            unsigned grid = 0;
+            if (int rc = persistent_grid(h, kern, 2 * GP::NB * 64, GP::LDS, a.nsb, GP::NB, &grid)) return rc;
             constexpr int HN = NOUT * G::HEAD_ROW;
             T* part = nullptr;
             if (int rc = head_part_alloc<T>(h, (size_t)grid * GP::NB, HN, &part)) return rc;
             a.head_part = part;
             {
-                TimedLaunch tl(h, 3);
-                gru_bwd_kernel<T, NFULL, 2 * GP::NB, NOUT, true><<<grid, 2 * GP::NB * 64, GP::LDS, h->stream>>>(a);
+                TimedLaunch tl(h, kTimerBackprop);
+                kern<<<grid, 2 * GP::NB * 64, GP::LDS, h->stream>>>(a);
                 head_reduce_launch<T>(h, (size_t)grid * GP::NB, HN, (T*)a.head_grad);
             }
             RNNWF_HIP(h, hipGetLastError());
@@ -94,20 +92,17 @@ struct GLaunch {
     static int run(rnnwf_handle* h, GradArgs a, int64_t R, void* dW) {
         if constexpr (PAIR_OK)
             if (a.nsb <= (int64_t)GradPair<T, NFULL, NOUT>::NB * h->cu_count && !h->knobs.no_coop) return run_pair(h, a, R, dW);
-        const void* fn = kernel();
         const size_t lds = LDS;
         if (lds > 160 * 1024)
             return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: forward + backward weight images (%zu B) exceed the 160 KB LDS", lds);
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, lds, &bpc)) return rc;
-        const int64_t need = (a.nsb + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::min<int64_t>(need, (int64_t)bpc * h->cu_count);
+        unsigned grid = 0;
+        if (int rc = persistent_grid(h, kernel(), WAVES * 64, lds, a.nsb, WAVES, &grid)) return rc;
         constexpr int HN = NOUT * G::HEAD_ROW;
         T* part = nullptr;
         if (int rc = head_part_alloc<T>(h, (size_t)grid * WAVES, HN, &part)) return rc;
         a.head_part = part;
         {
-            TimedLaunch tl(h, 3);
+            TimedLaunch tl(h, kTimerBackprop);
             launch(grid, lds, h->stream, a);
             head_reduce_launch<T>(h, (size_t)grid * WAVES, HN, (T*)a.head_grad);
         }
@@ -282,13 +277,11 @@ struct MLGrad {
 
     template <bool TOP>
     static int upper_pass(rnnwf_handle* h, UpperGradArgs a) {
-        const void* fn = (const void*)gru_upper_bwd_kernel<T, NFULL, WAVES, TOP, NOUT>;
+        const auto kern = gru_upper_bwd_kernel<T, NFULL, WAVES, TOP, NOUT>;
         const size_t lds = GU::WIDE ? GU::HEAD_BYTES : U::BYTES + GU::BWD_BYTES + (TOP ? GU::HEAD_BYTES : 0);
         if (lds > 160 * 1024) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: stacked-layer images (%zu B) exceed the 160 KB LDS", lds);
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, lds, &bpc)) return rc;
-        const int64_t need = (a.nsb + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::min<int64_t>(need, (int64_t)bpc * h->cu_count);
+        unsigned grid = 0;
+        if (int rc = persistent_grid(h, kern, WAVES * 64, lds, a.nsb, WAVES, &grid)) return rc;
         constexpr int HN = NOUT * GU::HEAD_ROW;
         if (TOP) {
             T* part = nullptr;
@@ -296,8 +289,8 @@ struct MLGrad {
             a.head_part = part;
         }
         {
-            TimedLaunch tl(h, 3);
-            gru_upper_bwd_kernel<T, NFULL, WAVES, TOP, NOUT><<<grid, WAVES * 64, lds, h->stream>>>(a);
+            TimedLaunch tl(h, kTimerBackprop);
+            kern<<<grid, WAVES * 64, lds, h->stream>>>(a);
             if (TOP) head_reduce_launch<T>(h, (size_t)grid * WAVES, HN, (T*)a.head_grad);
         }
         RNNWF_HIP(h, hipGetLastError());

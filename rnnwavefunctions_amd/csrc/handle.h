@@ -22,6 +22,13 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// The kernel groups of rnnwf_timing_get (include/rnnwf.h), the index of rnnwf_handle::timers
+enum TimerId : int { kTimerBase = 0, kTimerFlip = 1, kTimerAssembly = 2, kTimerBackprop = 3, kTimerGemm = 4, kTimerCount };
+
+// Default bytes of checkpointed states per pass of the GRU, complex RNN, LSTM and Renyi swap passes (RNNWF_STATE_BUDGET_MB
+// overrides it: models.h: state_budget_bytes)
+constexpr size_t kDefaultStateBudget = (size_t)48 << 30;
+
 struct KernelTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
@@ -134,7 +141,7 @@ struct rnnwf_handle {
 
     bool timing_on = false;
     int timing_mask = 31;    // which kernel ids get HIP events (rnnwf_timing_enable: 1 = all, 2 = the dominant pass only)
-    rnnwf::KernelTimer timers[5];   // 0 base pass, 1 flip / swap pass, 2 assembly, 3 gradient back-propagation, 4 weight-gradient GEMM
+    rnnwf::KernelTimer timers[rnnwf::kTimerCount];   // indexed by rnnwf::TimerId
     double work[2] = {0.0, 0.0};
 
     rnnwf::Knobs knobs;
@@ -240,13 +247,13 @@ inline int blocks_per_cu(rnnwf_handle* h, const void* fn, int threads, size_t ld
     return 0;
 }
 
-// HIP-event bracket around one launch on the handle's stream
+// HIP-event bracket around the launches of its scope on the handle's stream
 struct TimedLaunch {
     rnnwf_handle* h;
-    int id;
+    TimerId id;
     std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
     bool on() const { return h->timing_on && ((h->timing_mask >> id) & 1); }
-    TimedLaunch(rnnwf_handle* h_, int id_) : h(h_), id(id_) {
+    TimedLaunch(rnnwf_handle* h_, TimerId id_) : h(h_), id(id_) {
         if (!on()) return;
         KernelTimer& t = h->timers[id];
         if (!t.pool.empty()) {
@@ -264,5 +271,47 @@ struct TimedLaunch {
         h->timers[id].pending.push_back(ev);
     }
 };
+
+// Grid of a persistent kernel: one workgroup per `per_block` items, at most as many workgroups as are resident at once (at
+// `threads` per workgroup and `lds` dynamic bytes), at least one.
+template <typename Kern>
+inline int persistent_grid(rnnwf_handle* h, Kern kern, int threads, size_t lds, int64_t items, int64_t per_block, unsigned* grid) {
+    int bpc = 0;
+    if (int rc = blocks_per_cu(h, (const void*)kern, threads, lds, &bpc)) return rc;
+    *grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, (int64_t)bpc * h->cu_count));
+    return 0;
+}
+
+// kern<<<grid, threads, lds, h->stream>>>(args...) inside the bracket of timer `id`
+template <typename Kern, typename... Args>
+inline int timed_launch(rnnwf_handle* h, TimerId id, Kern kern, dim3 grid, int threads, size_t lds, const Args&... args) {
+    TimedLaunch tl(h, id);
+    kern<<<grid, threads, lds, h->stream>>>(args...);
+    RNNWF_HIP(h, hipGetLastError());
+    return 0;
+}
+
+// persistent_grid + timed_launch
+template <typename Kern, typename... Args>
+inline int launch_persistent(rnnwf_handle* h, TimerId id, Kern kern, int threads, size_t lds, int64_t items, int64_t per_block,
+                             const Args&... args) {
+    unsigned grid = 0;
+    if (int rc = persistent_grid(h, kern, threads, lds, items, per_block, &grid)) return rc;
+    return timed_launch(h, id, kern, grid, threads, lds, args...);
+}
+
+// Items (16-chain blocks or flip tiles) one per wave: WAVES waves per workgroup where there are enough items to fill every
+// resident workgroup slot, as few as still keep every slot busy otherwise.  For kernels whose LDS image allows few workgroups per
+// CU, where a small batch in full-size workgroups would sit on a few CUs (config 2 with two layers: 625 blocks of 16 chains -> 3
+// waves on each of 209 CUs instead of 8 on 79).  The occupancy is that of full workgroups.
+template <int WAVES, typename Kern, typename... Args>
+inline int launch_shrinking(rnnwf_handle* h, TimerId id, Kern kern, size_t lds, int64_t items, const Args&... args) {
+    int bpc = 0;
+    if (int rc = blocks_per_cu(h, (const void*)kern, WAVES * 64, lds, &bpc)) return rc;
+    const int64_t slots = (int64_t)bpc * h->cu_count;
+    const int wpb = (int)std::max<int64_t>(1, std::min<int64_t>(WAVES, (items + slots - 1) / slots));
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + wpb - 1) / wpb, slots));
+    return timed_launch(h, id, kern, grid, wpb * 64, lds, args...);
+}
 
 }  // namespace rnnwf

@@ -12,7 +12,6 @@ using namespace rnnwf;
 
 namespace {
 
-constexpr size_t kHckBudget = (size_t)48 << 30;  // bytes of (h, c) checkpoints per pass (prnn.hip's budget)
 const char* kLstmPre = "multi_rnn_cell/cell_0/lstm_cell/";
 
 // Packs LSTMCell + Dense(2) into LstmLayout<NFULL>.  TF's kernel is [2 + H, 4H]: rows 0..1 the one-hot input, rows 2.. the
@@ -79,52 +78,57 @@ std::vector<char> pack_lstm_image(const rnnwf_handle* h) {
     return img;
 }
 
-// WAVES: waves per workgroup of the flip pass; BWAVES: of the base pass
+// WAVES: waves per workgroup of the flip pass; BWAVES: of the base pass.  The image takes most of a CU's LDS (one workgroup per
+// CU from 37 units up): both passes shrink their workgroups for small batches (handle.h: launch_shrinking; the run script's 4x4 /
+// 500 samples would sit on 60 of 256 CUs in full-size workgroups)
 template <int NFULL, int WAVES, int BWAVES = WAVES>
 struct LLaunch {
     using L = LstmLayout<NFULL>;
-    // items (16-chain blocks or flip tiles) one per wave: NW waves per workgroup where there are enough of them to fill every
-    // resident workgroup slot, fewer otherwise - the image takes most of a CU's LDS (one workgroup per CU from 37 units up), so
-    // a small batch in full-size workgroups would sit on a few CUs, two waves per SIMD (the run script's 4x4 / 500 samples:
-    // 60 of 256 CUs)
-    template <int NW, class Kern>
-    static int run(rnnwf_handle* h, Kern kern, int64_t items, int id, const LstmArgs& a) {
-        int bpc = 0;
-        if (int rc = blocks_per_cu(h, (const void*)kern, NW * 64, L::BYTES, &bpc)) return rc;
-        const int64_t slots = (int64_t)bpc * h->cu_count;
-        const int wpb = (int)std::max<int64_t>(1, std::min<int64_t>(NW, (items + slots - 1) / slots));
-        const int64_t need = (items + wpb - 1) / wpb;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, slots));
-        TimedLaunch tl(h, id);
-        kern<<<grid, wpb * 64, L::BYTES, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+    static int base(rnnwf_handle* h, const LstmArgs& a) {
+        return launch_shrinking<BWAVES>(h, kTimerBase, lstm_base_kernel<NFULL, BWAVES>, L::BYTES, a.nsb, a);
     }
-    static int base(rnnwf_handle* h, const LstmArgs& a) { return run<BWAVES>(h, lstm_base_kernel<NFULL, BWAVES>, a.nsb, 0, a); }
-    static int flip(rnnwf_handle* h, const LstmArgs& a) { return run<WAVES>(h, lstm_flip_kernel<NFULL, WAVES>, a.ntiles, 1, a); }
+    static int flip(rnnwf_handle* h, const LstmArgs& a) {
+        return launch_shrinking<WAVES>(h, kTimerFlip, lstm_flip_kernel<NFULL, WAVES>, L::BYTES, a.ntiles, a);
+    }
     static std::vector<char> pack(const rnnwf_handle* h) { return pack_lstm_image<NFULL>(h); }
     static size_t hck_bytes_per_block() { return (size_t)2 * L::KT * 64 * sizeof(double); }
     static double mfma_flops_per_step() { return (double)L::NT * L::KT * 2048.0; }
 };
 
-// NFULL 1..4 (<= 20, 36, 52, 68 units); 8 waves where one workgroup fills a CU's LDS (two per SIMD).  The base pass at 68 units
-// runs one wave per SIMD: with its checkpoint stores and sampler beside h, c and h' it needs more than the 256 registers of two
-// waves per SIMD (scratch otherwise); it is the short pass (N steps per chain against the flip pass's N (N - 1) / 2).
-#define LSTM_DISPATCH(h, EXPR)                                                 \
-    do {                                                                       \
-        switch ((h)->NFULL) {                                                  \
-            case 1: { using K = LLaunch<1, 4>; EXPR; }                         \
-            case 2: { using K = LLaunch<2, 4>; EXPR; }                         \
-            case 3: { using K = LLaunch<3, 8>; EXPR; }                         \
-            case 4: { using K = LLaunch<4, 8, 4>; EXPR; }                      \
-        }                                                                      \
-    } while (0)
+// fn(K()) for this handle's launch class K, false (fn not called) for a width without kernels.  NFULL 1..4 (<= 20, 36, 52, 68
+// units); 8 waves where one workgroup fills a CU's LDS (two per SIMD).  The base pass at 68 units runs one wave per SIMD: with
+// its checkpoint stores and sampler beside h, c and h' it needs more than the 256 registers of two waves per SIMD (scratch
+// otherwise); it is the short pass (N steps per chain against the flip pass's N (N - 1) / 2).
+template <class Fn>
+bool with_launch(const rnnwf_handle* h, Fn&& fn) {
+    switch (h->NFULL) {
+        case 1: fn(LLaunch<1, 4>()); return true;
+        case 2: fn(LLaunch<2, 4>()); return true;
+        case 3: fn(LLaunch<3, 8>()); return true;
+        case 4: fn(LLaunch<4, 8, 4>()); return true;
+    }
+    return false;
+}
 
 int no_kernel(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "no LSTM kernel for NFULL=%d (one layer, <= 68 units)", h->NFULL); }
-int launch_base(rnnwf_handle* h, const LstmArgs& a) { LSTM_DISPATCH(h, return K::base(h, a)); return no_kernel(h); }
-int launch_flip(rnnwf_handle* h, const LstmArgs& a) { LSTM_DISPATCH(h, return K::flip(h, a)); return no_kernel(h); }
-size_t hck_bytes_per_block(rnnwf_handle* h) { LSTM_DISPATCH(h, return K::hck_bytes_per_block()); return 0; }
-double mfma_flops_per_step(rnnwf_handle* h) { LSTM_DISPATCH(h, return K::mfma_flops_per_step()); return 0; }
+int launch_base(rnnwf_handle* h, const LstmArgs& a) {
+    int rc = 0;
+    return with_launch(h, [&](auto k) { rc = decltype(k)::base(h, a); }) ? rc : no_kernel(h);
+}
+int launch_flip(rnnwf_handle* h, const LstmArgs& a) {
+    int rc = 0;
+    return with_launch(h, [&](auto k) { rc = decltype(k)::flip(h, a); }) ? rc : no_kernel(h);
+}
+size_t hck_bytes_per_block(rnnwf_handle* h) {
+    size_t b = 0;
+    with_launch(h, [&](auto k) { b = decltype(k)::hck_bytes_per_block(); });
+    return b;
+}
+double mfma_flops_per_step(rnnwf_handle* h) {
+    double f = 0;
+    with_launch(h, [&](auto k) { f = decltype(k)::mfma_flops_per_step(); });
+    return f;
+}
 
 LstmArgs base_args(rnnwf_handle* h, int64_t ns) {
     LstmArgs a{};
@@ -137,7 +141,7 @@ LstmArgs base_args(rnnwf_handle* h, int64_t ns) {
 
 int64_t max_chains_per_pass(rnnwf_handle* h) {
     const size_t per_block = (size_t)std::max(h->N - 1, 1) * hck_bytes_per_block(h);
-    const int64_t blocks = std::max<int64_t>(1, (int64_t)(state_budget_bytes(h, kHckBudget) / per_block));
+    const int64_t blocks = std::max<int64_t>(1, (int64_t)(state_budget_bytes(h, kDefaultStateBudget) / per_block));
     return blocks * kChains;
 }
 
@@ -178,8 +182,7 @@ int log_prob_pass(rnnwf_handle* h, int64_t ns, const Draw* d) {
 }
 
 int pack_image(rnnwf_handle* h, std::vector<char>& img) {
-    LSTM_DISPATCH(h, { img = K::pack(h); return 0; });
-    return no_kernel(h);
+    return with_launch(h, [&](auto k) { img = decltype(k)::pack(h); }) ? 0 : no_kernel(h);
 }
 
 }  // namespace

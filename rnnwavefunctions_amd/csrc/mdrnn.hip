@@ -18,27 +18,10 @@ constexpr size_t kHsBudget = (size_t)24 << 30;   // bytes of per-site hidden sta
 template <int NFULL, int WAVES>
 struct MLaunch {
     using L = MdLayout<NFULL>;
-    static int blocks_per_cu(rnnwf_handle* h, const void* fn, int* out) { return rnnwf::blocks_per_cu(h, fn, WAVES * 64, L::BYTES, out); }
     static int base(rnnwf_handle* h, const MdArgs& a) {
-        const void* fn = (const void*)mdrnn_base_kernel<NFULL, WAVES>;
-        int bpc = 0;
-        if (int rc = blocks_per_cu(h, fn, &bpc)) return rc;
-        const int64_t need = (a.nsb + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::min<int64_t>(need, (int64_t)bpc * h->cu_count);
-        TimedLaunch tl(h, 0);
-        mdrnn_base_kernel<NFULL, WAVES><<<grid, WAVES * 64, L::BYTES, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerBase, mdrnn_base_kernel<NFULL, WAVES>, WAVES * 64, L::BYTES, a.nsb, WAVES, a);
     }
     static constexpr size_t FLIP_LDS = L::BYTES + (size_t)WAVES * L::WORDS_BYTES;     // image + the waves' spin words
-    static int flip_grid(rnnwf_handle* h, int64_t ntiles, unsigned* grid) {
-        const void* fn = (const void*)mdrnn_flip_kernel<NFULL, WAVES>;
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, FLIP_LDS, &bpc)) return rc;
-        const int64_t need = (ntiles + WAVES - 1) / WAVES;
-        *grid = (unsigned)std::min<int64_t>(need, (int64_t)bpc * h->cu_count);
-        return 0;
-    }
 #ifdef RNNWF_DIAGNOSTICS      // measured negative (profiles/r03_d_cfg4_prefetch.md), kept for A/B runs of tools/ only: not in the release library
     // prefetching variant (mdrnn_flip_pf_kernel): one 8-wave workgroup per CU, a staging slot per wave behind the spin words
     static constexpr int PF_WAVES = 8;
@@ -46,18 +29,14 @@ struct MLaunch {
     static constexpr bool PF_FITS = PF_LDS <= 160 * 1024;
     static int flip_pf(rnnwf_handle* h, MdArgs a) {
         if constexpr (PF_FITS) {
-            const void* fn = (const void*)mdrnn_flip_pf_kernel<NFULL, PF_WAVES>;
-            int bpc = 0;
-            if (int rc = rnnwf::blocks_per_cu(h, fn, PF_WAVES * 64, PF_LDS, &bpc)) return rc;
-            const int64_t need = (a.ntiles + PF_WAVES - 1) / PF_WAVES;
-            const unsigned grid = (unsigned)std::min<int64_t>(need, (int64_t)bpc * h->cu_count);
+            const auto kern = mdrnn_flip_pf_kernel<NFULL, PF_WAVES>;
+            unsigned grid = 0;
+            if (int rc = persistent_grid(h, kern, PF_WAVES * 64, PF_LDS, a.ntiles, PF_WAVES, &grid)) return rc;
             const size_t ring_bytes = (size_t)grid * PF_WAVES * a.Nx * ((L::KT + 1) / 2) * 64 * 16;
             if (int rc = ensure(h, h->rowbuf, ring_bytes)) return rc;
             a.ring = (double*)h->rowbuf.p;
             a.ablate = h->knobs.ablate;
-            TimedLaunch tl(h, 1);
-            mdrnn_flip_pf_kernel<NFULL, PF_WAVES><<<grid, PF_WAVES * 64, PF_LDS, h->stream>>>(a);
-            RNNWF_HIP(h, hipGetLastError());
+            return timed_launch(h, kTimerFlip, kern, grid, PF_WAVES * 64, PF_LDS, a);
         }
         return 0;
     }
@@ -66,16 +45,14 @@ struct MLaunch {
 #ifdef RNNWF_DIAGNOSTICS
         if (PF_FITS && NFULL == 3 && h->knobs.md_prefetch) return flip_pf(h, a);      // A/B only: measured slower (profiles/r03_d_cfg4_prefetch.md)
 #endif
+        const auto kern = mdrnn_flip_kernel<NFULL, WAVES>;
         unsigned grid = 0;
-        if (int rc = flip_grid(h, a.ntiles, &grid)) return rc;
+        if (int rc = persistent_grid(h, kern, WAVES * 64, FLIP_LDS, a.ntiles, WAVES, &grid)) return rc;
         const size_t ring_bytes = (size_t)grid * WAVES * a.Nx * ((L::KT + 1) / 2) * 64 * 16;      // one slot per lattice column
         if (int rc = ensure(h, h->rowbuf, ring_bytes)) return rc;
         a.ring = (double*)h->rowbuf.p;
         a.ablate = h->knobs.ablate;   // 0 unless a -DRNNWF_DIAGNOSTICS build read RNNWF_ABLATE
-        TimedLaunch tl(h, 1);
-        mdrnn_flip_kernel<NFULL, WAVES><<<grid, WAVES * 64, FLIP_LDS, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return timed_launch(h, kTimerFlip, kern, grid, WAVES * 64, FLIP_LDS, a);
     }
     static size_t hs_bytes_per_block() { return (size_t)((L::KT + 1) / 2) * 64 * 16; }
     static double mfma_flops_per_step() { return (double)NFULL * 2 * L::KT * 2048.0; }
@@ -159,32 +136,38 @@ struct MLaunch {
     }
 };
 
-#define MD_DISPATCH(h, EXPR)                                    \
-    do {                                                        \
-        switch ((h)->NFULL) {                                   \
-            case 1: { using K = MLaunch<1, 4>; EXPR; }          \
-            case 2: { using K = MLaunch<2, 4>; EXPR; }          \
-            case 3: { using K = MLaunch<3, 4>; EXPR; }          \
-            case 4: { using K = MLaunch<4, 4>; EXPR; }          \
-            case 5: { using K = MLaunch<5, 4>; EXPR; }          \
-        }                                                       \
-    } while (0)
+// fn(K<NFULL, 4>()) for the handle's width, false (fn not called) for a width without kernels: K = MLaunch (the forward passes) or
+// MGrad (the gradient)
+template <template <int, int> class K, class Fn>
+bool with_width(const rnnwf_handle* h, Fn&& fn) {
+    switch (h->NFULL) {
+        case 1: fn(K<1, 4>()); return true;
+        case 2: fn(K<2, 4>()); return true;
+        case 3: fn(K<3, 4>()); return true;
+        case 4: fn(K<4, 4>()); return true;
+        case 5: fn(K<5, 4>()); return true;
+    }
+    return false;
+}
 
+int no_kernel(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "MDRNN: num_units > 84 is not implemented on gfx950 yet"); }
 int launch_base(rnnwf_handle* h, const MdArgs& a) {
-    MD_DISPATCH(h, return K::base(h, a));
-    return h->fail(RNNWF_ERR_INVALID, "MDRNN: num_units > 84 is not implemented on gfx950 yet");
+    int rc = 0;
+    return with_width<MLaunch>(h, [&](auto k) { rc = decltype(k)::base(h, a); }) ? rc : no_kernel(h);
 }
 int launch_flip(rnnwf_handle* h, const MdArgs& a) {
-    MD_DISPATCH(h, return K::flip(h, a));
-    return h->fail(RNNWF_ERR_INVALID, "MDRNN: num_units > 84 is not implemented on gfx950 yet");
+    int rc = 0;
+    return with_width<MLaunch>(h, [&](auto k) { rc = decltype(k)::flip(h, a); }) ? rc : no_kernel(h);
 }
 size_t hs_bytes_per_block(rnnwf_handle* h) {
-    MD_DISPATCH(h, return K::hs_bytes_per_block());
-    return 1;
+    size_t b = 1;
+    with_width<MLaunch>(h, [&](auto k) { b = decltype(k)::hs_bytes_per_block(); });
+    return b;
 }
 double mfma_flops_per_step(rnnwf_handle* h) {
-    MD_DISPATCH(h, return K::mfma_flops_per_step());
-    return 0;
+    double f = 0;
+    with_width<MLaunch>(h, [&](auto k) { f = decltype(k)::mfma_flops_per_step(); });
+    return f;
 }
 
 // device maps, 6 x N int32: col_of_pos | pos_of_site | row_of_pos | vert_pos | row_first | (spare)
@@ -293,8 +276,7 @@ int site_maps(rnnwf_handle* h, const int32_t** col_of_pos, const int32_t** pos_o
 
 int pack_image(rnnwf_handle* h, std::vector<char>& img) {
     if (h->N > 256) return h->fail(RNNWF_ERR_INVALID, "MDRNN: lattices above 256 sites are not implemented");
-    MD_DISPATCH(h, { img = K::template pack<double>(h); return 0; });
-    return h->fail(RNNWF_ERR_INVALID, "MDRNN: num_units > 84 is not implemented on gfx950 yet");
+    return with_width<MLaunch>(h, [&](auto k) { img = decltype(k)::template pack<double>(h); }) ? 0 : no_kernel(h);
 }
 
 }  // namespace
@@ -375,16 +357,13 @@ struct MGrad {
         a.head_grad = (double*)h->gradW.p + (size_t)G::PCOLS * G::QCOLS;
         a.vert_pos = m.vert_pos;
         a.row_first = m.row_first;
-        const void* fn = (const void*)mdrnn_bwd_kernel<NFULL, WAVES>;
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, G::BYTES, &bpc)) return rc;
-        const int64_t need = (a.nsb + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::min<int64_t>(need, (int64_t)bpc * h->cu_count);
+        unsigned grid = 0;
+        if (int rc = persistent_grid(h, mdrnn_bwd_kernel<NFULL, WAVES>, WAVES * 64, G::BYTES, a.nsb, WAVES, &grid)) return rc;
         if (int rc = ensure(h, h->rowbuf, (size_t)grid * WAVES * 2 * a.Nx * G::KT * 64 * 8)) return rc;
         a.ring = (double*)h->rowbuf.p;
         if (int rc = head_part_alloc<double>(h, (size_t)grid * WAVES, 2 * G::HEAD_ROW, &a.head_part)) return rc;
         {
-            TimedLaunch tl(h, 3);
+            TimedLaunch tl(h, kTimerBackprop);
             mdrnn_bwd_kernel<NFULL, WAVES><<<grid, WAVES * 64, G::BYTES, h->stream>>>(a);
             head_reduce_launch<double>(h, (size_t)grid * WAVES, 2 * G::HEAD_ROW, a.head_grad);
         }
@@ -429,34 +408,25 @@ struct MGrad {
     }
 };
 
-#define MG_DISPATCH(h, EXPR)                                    \
-    do {                                                        \
-        switch ((h)->NFULL) {                                   \
-            case 1: { using K = MGrad<1, 4>; EXPR; }            \
-            case 2: { using K = MGrad<2, 4>; EXPR; }            \
-            case 3: { using K = MGrad<3, 4>; EXPR; }            \
-            case 4: { using K = MGrad<4, 4>; EXPR; }            \
-            case 5: { using K = MGrad<5, 4>; EXPR; }            \
-        }                                                       \
-    } while (0)
-
 int no_grad_kernel(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: num_units > 84 not implemented"); }
 
 // the gradient hooks (models.h: Gradient)
 int grad_layout(rnnwf_handle* h, GradImage* out) {
-    MG_DISPATCH(h, { *out = K::layout(); return 0; });
-    return no_grad_kernel(h);
+    return with_width<MGrad>(h, [&](auto k) { *out = decltype(k)::layout(); }) ? 0 : no_grad_kernel(h);
 }
 int grad_pack(rnnwf_handle* h, std::vector<char>* img) {
-    MG_DISPATCH(h, { if (img) *img = K::template pack<double>(h); else K::template pack<Lin>(h); return 0; });
-    return no_grad_kernel(h);
+    return with_width<MGrad>(h, [&](auto k) {
+        using K = decltype(k);
+        if (img) *img = K::template pack<double>(h);
+        else K::template pack<Lin>(h);
+    }) ? 0 : no_grad_kernel(h);
 }
 int grad_launch(rnnwf_handle* h, const GradCost& c) {
-    MG_DISPATCH(h, return K::launch(h, c));
-    return no_grad_kernel(h);
+    int rc = 0;
+    return with_width<MGrad>(h, [&](auto k) { rc = decltype(k)::launch(h, c); }) ? rc : no_grad_kernel(h);
 }
 void grad_unpack(rnnwf_handle* h, const void* img) {
-    MG_DISPATCH(h, { K::unpack(h, img); return; });
+    with_width<MGrad>(h, [&](auto k) { decltype(k)::unpack(h, img); });
 }
 
 }  // namespace
@@ -473,6 +443,5 @@ const Family* rnnwf::mdrnn_family() {
 
 // device-resident training (train.hip): the forward image's table
 int rnnwf::mdrnn_pack_table(rnnwf_handle* h) {
-    MD_DISPATCH(h, { K::template pack<Lin>(h); return 0; });
-    return 1;
+    return with_width<MLaunch>(h, [&](auto k) { decltype(k)::template pack<Lin>(h); }) ? 0 : 1;
 }

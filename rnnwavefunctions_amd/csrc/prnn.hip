@@ -13,23 +13,14 @@ using namespace rnnwf;
 
 namespace {
 
-constexpr size_t kHckBudget = (size_t)48 << 30;  // bytes of hidden-state checkpoints per pass
-
 template <typename T, int NFULL, int WAVES>
 struct Launch {
     using L = GruLayout<T, NFULL, 1>;
-    static int blocks_per_cu(rnnwf_handle* h, const void* fn, int* out) { return rnnwf::blocks_per_cu(h, fn, WAVES * 64, L::LDS_BYTES, out); }
     // fewer 16-chain blocks than SIMDs: the cooperative kernel (NFULL + 1 waves per block) cuts the per-site latency
     static int base_coop(rnnwf_handle* h, const PrnnArgs& a) {
         if constexpr (std::is_same<T, float>::value && NFULL <= 4) {
-            const void* fn = (const void*)prnn_base_coop_kernel<NFULL>;
             const size_t lds = L::BYTES + (size_t)2 * L::KT * 64 * 4 + 2 * 64 * 4;
-            int bpc = 0;
-            if (int rc = rnnwf::blocks_per_cu(h, fn, (NFULL + 1) * 64, lds, &bpc)) return rc;
-            const unsigned grid = (unsigned)std::min<int64_t>(a.nsb, (int64_t)bpc * h->cu_count);
-            TimedLaunch tl(h, 0);
-            prnn_base_coop_kernel<NFULL><<<grid, (NFULL + 1) * 64, lds, h->stream>>>(a);
-            RNNWF_HIP(h, hipGetLastError());
+            return launch_persistent(h, kTimerBase, prnn_base_coop_kernel<NFULL>, (NFULL + 1) * 64, lds, a.nsb, 1, a);
         }
         return 0;
     }
@@ -43,26 +34,10 @@ struct Launch {
     }
     // the one-wave-per-block kernel whatever the batch size
     static int plain(rnnwf_handle* h, const PrnnArgs& a) {
-        const void* fn = (const void*)prnn_base_kernel<T, NFULL, WAVES>;
-        int bpc = 0;
-        if (int rc = blocks_per_cu(h, fn, &bpc)) return rc;
-        const int64_t need = (a.nsb + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::min<int64_t>(need, (int64_t)bpc * h->cu_count);
-        TimedLaunch tl(h, 0);
-        prnn_base_kernel<T, NFULL, WAVES><<<grid, WAVES * 64, L::LDS_BYTES, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerBase, prnn_base_kernel<T, NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, a.nsb, WAVES, a);
     }
     static int flip(rnnwf_handle* h, const PrnnArgs& a) {
-        const void* fn = (const void*)prnn_flip_kernel<T, NFULL, WAVES>;
-        int bpc = 0;
-        if (int rc = blocks_per_cu(h, fn, &bpc)) return rc;
-        const int64_t need = (a.ntiles + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::min<int64_t>(need, (int64_t)bpc * h->cu_count);
-        TimedLaunch tl(h, 1);
-        prnn_flip_kernel<T, NFULL, WAVES><<<grid, WAVES * 64, L::LDS_BYTES, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerFlip, prnn_flip_kernel<T, NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, a.ntiles, WAVES, a);
     }
     static std::vector<char> pack(const rnnwf_handle* h) { return pack_gru_image<T, NFULL, 1>(h); }
     static size_t hck_bytes_per_block() { return (size_t)L::KT * 64 * sizeof(T); }
@@ -73,48 +48,19 @@ struct Launch {
 template <typename T, int NFULL, int NL, int WAVES>
 struct MLaunchL {
     using M = MlCore<NFULL, NL, T>;
-    static int blocks_per_cu(rnnwf_handle* h, const void* fn, int* out) { return rnnwf::blocks_per_cu(h, fn, WAVES * 64, M::BYTES, out); }
     static int base(rnnwf_handle* h, const PrnnArgs& a) {
         // all layers' images resident in LDS (f32, up to 52 units): the gate tiles of every layer spread over NFULL + 1 waves per block
         // of 16 chains (ml_coop.h) - for every batch size, its accumulation order is not the one-wave kernel's; RNNWF_NO_COOP=1 keeps that one
         if constexpr (std::is_same<T, float>::value && MlCoopLayout<NFULL, NL, 1>::FITS && M::SPILL == 0) {
             if (!h->knobs.no_coop) {
                 using ML = MlCoopLayout<NFULL, NL, 1>;
-                const void* cfn = (const void*)prnn_base_coop_kernel<NFULL, false, NL>;
-                int cb = 0;
-                if (int rc = rnnwf::blocks_per_cu(h, cfn, ML::THREADS, ML::LDS, &cb)) return rc;
-                const int64_t need = (a.nsb + ML::NB - 1) / ML::NB;
-                const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)cb * h->cu_count));
-                TimedLaunch tl(h, 0);
-                prnn_base_coop_kernel<NFULL, false, NL><<<grid, ML::THREADS, ML::LDS, h->stream>>>(a);
-                RNNWF_HIP(h, hipGetLastError());
-                return 0;
+                return launch_persistent(h, kTimerBase, prnn_base_coop_kernel<NFULL, false, NL>, ML::THREADS, ML::LDS, a.nsb, ML::NB, a);
             }
         }
-        const void* fn = (const void*)prnn_ml_base_kernel<T, NFULL, NL, WAVES>;
-        int bpc = 0;
-        if (int rc = blocks_per_cu(h, fn, &bpc)) return rc;
-        // waves per workgroup: as few as still cover the batch with every resident workgroup busy (config 2 with two layers: 625
-        // blocks of 16 chains -> 3 waves on each of 209 CUs instead of 8 on 79; measured 1.26 -> see DESIGN.md)
-        const int64_t slots = (int64_t)bpc * h->cu_count;
-        const int wpb = (int)std::max<int64_t>(1, std::min<int64_t>(WAVES, (a.nsb + slots - 1) / slots));
-        const int64_t need = (a.nsb + wpb - 1) / wpb;
-        const unsigned grid = (unsigned)std::min<int64_t>(need, slots);
-        TimedLaunch tl(h, 0);
-        prnn_ml_base_kernel<T, NFULL, NL, WAVES><<<grid, wpb * 64, M::BYTES, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_shrinking<WAVES>(h, kTimerBase, prnn_ml_base_kernel<T, NFULL, NL, WAVES>, M::BYTES, a.nsb, a);
     }
     static int flip(rnnwf_handle* h, const PrnnArgs& a) {
-        const void* fn = (const void*)prnn_ml_flip_kernel<T, NFULL, NL, WAVES>;
-        int bpc = 0;
-        if (int rc = blocks_per_cu(h, fn, &bpc)) return rc;
-        const int64_t need = (a.ntiles + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::min<int64_t>(need, (int64_t)bpc * h->cu_count);
-        TimedLaunch tl(h, 1);
-        prnn_ml_flip_kernel<T, NFULL, NL, WAVES><<<grid, WAVES * 64, M::BYTES, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerFlip, prnn_ml_flip_kernel<T, NFULL, NL, WAVES>, WAVES * 64, M::BYTES, a.ntiles, WAVES, a);
     }
     static int plain(rnnwf_handle* h, const PrnnArgs&) { return h->fail(RNNWF_ERR_INVALID, "stacked layers: no one-wave base pass"); }
     static std::vector<char> pack(const rnnwf_handle* h) {
@@ -131,91 +77,95 @@ struct MLaunchL {
     }
 };
 
-// one place that maps (dtype, NFULL, layers) to an instantiation
-#define PRNN_DISPATCH(h, EXPR)                                                              \
-    do {                                                                                    \
-        if ((h)->NL == 2 && (h)->f64) {                                                     \
-            switch ((h)->NFULL) {                                                           \
-                case 1: { using K = MLaunchL<double, 1, 2, 4>; EXPR; }                      \
-                case 2: { using K = MLaunchL<double, 2, 2, 8>; EXPR; }                      \
-                case 3: { using K = MLaunchL<double, 3, 2, 4>; EXPR; }                      \
-                case 4: { using K = MLaunchL<double, 4, 2, 4>; EXPR; }                      \
-            }                                                                               \
-        } else if ((h)->NL == 3 && (h)->f64) {                                              \
-            switch ((h)->NFULL) {                                                           \
-                case 1: { using K = MLaunchL<double, 1, 3, 4>; EXPR; }                      \
-                case 2: { using K = MLaunchL<double, 2, 3, 4>; EXPR; }                      \
-                case 3: { using K = MLaunchL<double, 3, 3, 4>; EXPR; }                      \
-                case 4: { using K = MLaunchL<double, 4, 3, 4>; EXPR; }                      \
-            }                                                                               \
-        } else if ((h)->NL == 4 && (h)->f64) {                                              \
-            switch ((h)->NFULL) {                                                           \
-                case 1: { using K = MLaunchL<double, 1, 4, 4>; EXPR; }                      \
-                case 2: { using K = MLaunchL<double, 2, 4, 4>; EXPR; }                      \
-                case 3: { using K = MLaunchL<double, 3, 4, 4>; EXPR; }                      \
-                case 4: { using K = MLaunchL<double, 4, 4, 4>; EXPR; }                      \
-            }                                                                               \
-        } else if ((h)->NL == 4) {                                                          \
-            switch ((h)->NFULL) {                                                           \
-                case 1: { using K = MLaunchL<float, 1, 4, 4>; EXPR; }                       \
-                case 2: { using K = MLaunchL<float, 2, 4, 4>; EXPR; }                       \
-                case 3: { using K = MLaunchL<float, 3, 4, 4>; EXPR; }                       \
-                case 4: { using K = MLaunchL<float, 4, 4, 4>; EXPR; }                       \
-                case 6: { using K = MLaunchL<float, 6, 4, 4>; EXPR; }                       \
-            }                                                                               \
-        } else if ((h)->NL == 2) {                                                          \
-            switch ((h)->NFULL) {                                                           \
-                case 1: { using K = MLaunchL<float, 1, 2, 4>; EXPR; }                       \
-                case 2: { using K = MLaunchL<float, 2, 2, 4>; EXPR; }                       \
-                case 3: { using K = MLaunchL<float, 3, 2, 8>; EXPR; }                       \
-                case 4: { using K = MLaunchL<float, 4, 2, 4>; EXPR; }                       \
-                case 6: { using K = MLaunchL<float, 6, 2, 4>; EXPR; }                       \
-            }                                                                               \
-        } else if ((h)->NL == 3) {                                                          \
-            switch ((h)->NFULL) {                                                           \
-                case 1: { using K = MLaunchL<float, 1, 3, 4>; EXPR; }                       \
-                case 2: { using K = MLaunchL<float, 2, 3, 8>; EXPR; }                       \
-                case 3: { using K = MLaunchL<float, 3, 3, 8>; EXPR; }                       \
-                case 4: { using K = MLaunchL<float, 4, 3, 4>; EXPR; }                       \
-                case 6: { using K = MLaunchL<float, 6, 3, 4>; EXPR; }                       \
-            }                                                                               \
-        } else if (!(h)->f64) {                                                             \
-            switch ((h)->NFULL) {                                                           \
-                case 1: { using K = Launch<float, 1, 4>; EXPR; }                            \
-                case 2: { using K = Launch<float, 2, 4>; EXPR; }                            \
-                case 3: { using K = Launch<float, 3, 4>; EXPR; }                            \
-                case 4: { using K = Launch<float, 4, 4>; EXPR; }                            \
-                case 6: { using K = Launch<float, 6, 8>; EXPR; }                            \
-                case 8: { using K = Launch<float, 8, 4>; EXPR; }                            \
-                case 12: { using K = Launch<float, 12, 4>; EXPR; }                          \
-                case 16: { using K = Launch<float, 16, 4>; EXPR; }                          \
-            }                                                                               \
-        } else {                                                                            \
-            switch ((h)->NFULL) {                                                           \
-                case 1: { using K = Launch<double, 1, 4>; EXPR; }                           \
-                case 2: { using K = Launch<double, 2, 4>; EXPR; }                           \
-                case 3: { using K = Launch<double, 3, 4>; EXPR; }                           \
-                case 4: { using K = Launch<double, 4, 8>; EXPR; }                           \
-                case 6: { using K = Launch<double, 6, 4>; EXPR; }                           \
-            }                                                                               \
-        }                                                                                   \
-    } while (0)
+// fn(K()) for this handle's launch class K, false (fn not called) for a shape without kernels: the one place that maps
+// (dtype, layers, NFULL) to an instantiation <element type, NFULL, [layers,] waves per workgroup>
+template <class Fn>
+bool with_launch(const rnnwf_handle* h, Fn&& fn) {
+    const int nf = h->NFULL;
+    if (h->f64) {
+        switch (h->NL) {
+            case 2: switch (nf) {
+                case 1: fn(MLaunchL<double, 1, 2, 4>()); return true;
+                case 2: fn(MLaunchL<double, 2, 2, 8>()); return true;
+                case 3: fn(MLaunchL<double, 3, 2, 4>()); return true;
+                case 4: fn(MLaunchL<double, 4, 2, 4>()); return true;
+            } return false;
+            case 3: switch (nf) {
+                case 1: fn(MLaunchL<double, 1, 3, 4>()); return true;
+                case 2: fn(MLaunchL<double, 2, 3, 4>()); return true;
+                case 3: fn(MLaunchL<double, 3, 3, 4>()); return true;
+                case 4: fn(MLaunchL<double, 4, 3, 4>()); return true;
+            } return false;
+            case 4: switch (nf) {
+                case 1: fn(MLaunchL<double, 1, 4, 4>()); return true;
+                case 2: fn(MLaunchL<double, 2, 4, 4>()); return true;
+                case 3: fn(MLaunchL<double, 3, 4, 4>()); return true;
+                case 4: fn(MLaunchL<double, 4, 4, 4>()); return true;
+            } return false;
+        }
+        switch (nf) {
+            case 1: fn(Launch<double, 1, 4>()); return true;
+            case 2: fn(Launch<double, 2, 4>()); return true;
+            case 3: fn(Launch<double, 3, 4>()); return true;
+            case 4: fn(Launch<double, 4, 8>()); return true;
+            case 6: fn(Launch<double, 6, 4>()); return true;
+        }
+        return false;
+    }
+    switch (h->NL) {
+        case 2: switch (nf) {
+            case 1: fn(MLaunchL<float, 1, 2, 4>()); return true;
+            case 2: fn(MLaunchL<float, 2, 2, 4>()); return true;
+            case 3: fn(MLaunchL<float, 3, 2, 8>()); return true;
+            case 4: fn(MLaunchL<float, 4, 2, 4>()); return true;
+            case 6: fn(MLaunchL<float, 6, 2, 4>()); return true;
+        } return false;
+        case 3: switch (nf) {
+            case 1: fn(MLaunchL<float, 1, 3, 4>()); return true;
+            case 2: fn(MLaunchL<float, 2, 3, 8>()); return true;
+            case 3: fn(MLaunchL<float, 3, 3, 8>()); return true;
+            case 4: fn(MLaunchL<float, 4, 3, 4>()); return true;
+            case 6: fn(MLaunchL<float, 6, 3, 4>()); return true;
+        } return false;
+        case 4: switch (nf) {
+            case 1: fn(MLaunchL<float, 1, 4, 4>()); return true;
+            case 2: fn(MLaunchL<float, 2, 4, 4>()); return true;
+            case 3: fn(MLaunchL<float, 3, 4, 4>()); return true;
+            case 4: fn(MLaunchL<float, 4, 4, 4>()); return true;
+            case 6: fn(MLaunchL<float, 6, 4, 4>()); return true;
+        } return false;
+    }
+    switch (nf) {
+        case 1: fn(Launch<float, 1, 4>()); return true;
+        case 2: fn(Launch<float, 2, 4>()); return true;
+        case 3: fn(Launch<float, 3, 4>()); return true;
+        case 4: fn(Launch<float, 4, 4>()); return true;
+        case 6: fn(Launch<float, 6, 8>()); return true;
+        case 8: fn(Launch<float, 8, 4>()); return true;
+        case 12: fn(Launch<float, 12, 4>()); return true;
+        case 16: fn(Launch<float, 16, 4>()); return true;
+    }
+    return false;
+}
 
+int no_kernel(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "no pRNN kernel for NFULL=%d f64=%d", h->NFULL, (int)h->f64); }
 int launch_base(rnnwf_handle* h, const PrnnArgs& a) {
-    PRNN_DISPATCH(h, return K::base(h, a));
-    return h->fail(RNNWF_ERR_INVALID, "no pRNN kernel for NFULL=%d f64=%d", h->NFULL, (int)h->f64);
+    int rc = 0;
+    return with_launch(h, [&](auto k) { rc = decltype(k)::base(h, a); }) ? rc : no_kernel(h);
 }
 int launch_flip(rnnwf_handle* h, const PrnnArgs& a) {
-    PRNN_DISPATCH(h, return K::flip(h, a));
-    return h->fail(RNNWF_ERR_INVALID, "no pRNN kernel for NFULL=%d f64=%d", h->NFULL, (int)h->f64);
+    int rc = 0;
+    return with_launch(h, [&](auto k) { rc = decltype(k)::flip(h, a); }) ? rc : no_kernel(h);
 }
 size_t hck_bytes_per_block(rnnwf_handle* h) {
-    PRNN_DISPATCH(h, return K::hck_bytes_per_block());
-    return 0;
+    size_t b = 0;
+    with_launch(h, [&](auto k) { b = decltype(k)::hck_bytes_per_block(); });
+    return b;
 }
 double mfma_flops_per_step(rnnwf_handle* h) {
-    PRNN_DISPATCH(h, return K::mfma_flops_per_step());
-    return 0;
+    double f = 0;
+    with_launch(h, [&](auto k) { f = decltype(k)::mfma_flops_per_step(); });
+    return f;
 }
 
 PrnnArgs base_args(rnnwf_handle* h, int64_t ns) {
@@ -347,7 +297,7 @@ int64_t max_chains_per_pass(rnnwf_handle* h) {
     size_t per_block = (size_t)(h->NL > 1 ? h->N : std::max(h->N - 1, 1)) * hck_bytes_per_block(h);
     if (h->NL > 1 && h->engine_split)                         // per 16 chains: half a 32-chain tile column of the layer pipeline's records
         per_block += stack_record_bytes_per_32_chains(h, (int64_t)h->N * (h->N - 1) / 2) / 2;
-    const int64_t blocks = std::max<int64_t>(1, (int64_t)(state_budget_bytes(h, kHckBudget) / per_block));
+    const int64_t blocks = std::max<int64_t>(1, (int64_t)(state_budget_bytes(h, kDefaultStateBudget) / per_block));
     return blocks * kChains;
 }
 
@@ -367,8 +317,7 @@ int pack_image(rnnwf_handle* h, std::vector<char>& img) {
         if (int rc = upload(h, h->wsplit.p, simg.data(), simg.size())) return rc;
     }
     if (int rc = base_bf_pack(h)) return rc;
-    PRNN_DISPATCH(h, { img = K::pack(h); return 0; });
-    return h->fail(RNNWF_ERR_INVALID, "no pRNN kernel for NFULL=%d f64=%d", h->NFULL, (int)h->f64);
+    return with_launch(h, [&](auto k) { img = decltype(k)::pack(h); }) ? 0 : no_kernel(h);
 }
 
 }  // namespace
@@ -386,8 +335,8 @@ int rnnwf::prnn_teacher_base(rnnwf_handle* h, int64_t ns, bool reversed, double*
 // The base pass on the one-wave-per-block kernel for every batch size (never the cooperative or bf16x3 kernels): the swap pass of
 // renyi.hip restarts from its checkpoints and must repeat its arithmetic step for step.
 int rnnwf::prnn_plain_base(rnnwf_handle* h, const PrnnArgs& a) {
-    PRNN_DISPATCH(h, return K::plain(h, a));
-    return h->fail(RNNWF_ERR_INVALID, "no pRNN kernel for NFULL=%d f64=%d", h->NFULL, (int)h->f64);
+    int rc = 0;
+    return with_launch(h, [&](auto k) { rc = decltype(k)::plain(h, a); }) ? rc : no_kernel(h);
 }
 PrnnArgs rnnwf::prnn_base_args(rnnwf_handle* h, int64_t ns) { return base_args(h, ns); }
 size_t rnnwf::prnn_hck_bytes_per_block(rnnwf_handle* h) { return hck_bytes_per_block(h); }

@@ -16,51 +16,45 @@ using namespace rnnwf;
 
 namespace {
 
-constexpr size_t kStateBudget = (size_t)48 << 30;   // the GRU family's default budget per pass (prnn.hip)
-
 template <typename T, int NFULL, int WAVES>
 struct SwapLaunch {
     using L = GruLayout<T, NFULL, 1>;
-    template <typename Fn>
-    static int launch(rnnwf_handle* h, Fn fn, int64_t items, int id, const SwapArgs& a) {
-        int bpc = 0;
-        if (int rc = blocks_per_cu(h, (const void*)fn, WAVES * 64, L::LDS_BYTES, &bpc)) return rc;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + WAVES - 1) / WAVES, (int64_t)bpc * h->cu_count));
-        TimedLaunch tl(h, id);
-        fn<<<grid, WAVES * 64, L::LDS_BYTES, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+    static int terms(rnnwf_handle* h, const SwapArgs& a) {
+        return launch_persistent(h, kTimerBase, prnn_site_terms_kernel<T, NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, a.nsb, WAVES, a);
     }
-    static int terms(rnnwf_handle* h, const SwapArgs& a) { return launch(h, prnn_site_terms_kernel<T, NFULL, WAVES>, a.nsb, 0, a); }
-    static int swap(rnnwf_handle* h, const SwapArgs& a) { return launch(h, prnn_swap_kernel<T, NFULL, WAVES>, a.ntiles, 1, a); }
+    static int swap(rnnwf_handle* h, const SwapArgs& a) {
+        return launch_persistent(h, kTimerFlip, prnn_swap_kernel<T, NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, a.ntiles, WAVES, a);
+    }
     static double mfma_flops_per_step() { return (double)L::NT * L::KT * 2048.0; }
 };
 
-// the one-layer rows of prnn.hip's dispatch table, with its flip pass's waves per workgroup - except f64 at 53..68 units: 4, not 8
-// (at 8 the swap kernel spills 20 bytes per lane to scratch; profiles/renyi_kernel_resources.txt)
-#define SWAP_DISPATCH(h, EXPR)                                                              \
-    do {                                                                                    \
-        if (!(h)->f64) {                                                                    \
-            switch ((h)->NFULL) {                                                           \
-                case 1: { using K = SwapLaunch<float, 1, 4>; EXPR; }                        \
-                case 2: { using K = SwapLaunch<float, 2, 4>; EXPR; }                        \
-                case 3: { using K = SwapLaunch<float, 3, 4>; EXPR; }                        \
-                case 4: { using K = SwapLaunch<float, 4, 4>; EXPR; }                        \
-                case 6: { using K = SwapLaunch<float, 6, 8>; EXPR; }                        \
-                case 8: { using K = SwapLaunch<float, 8, 4>; EXPR; }                        \
-                case 12: { using K = SwapLaunch<float, 12, 4>; EXPR; }                      \
-                case 16: { using K = SwapLaunch<float, 16, 4>; EXPR; }                      \
-            }                                                                               \
-        } else {                                                                            \
-            switch ((h)->NFULL) {                                                           \
-                case 1: { using K = SwapLaunch<double, 1, 4>; EXPR; }                       \
-                case 2: { using K = SwapLaunch<double, 2, 4>; EXPR; }                       \
-                case 3: { using K = SwapLaunch<double, 3, 4>; EXPR; }                       \
-                case 4: { using K = SwapLaunch<double, 4, 4>; EXPR; }                       \
-                case 6: { using K = SwapLaunch<double, 6, 4>; EXPR; }                       \
-            }                                                                               \
-        }                                                                                   \
-    } while (0)
+// fn(K()) for this handle's launch class K, false (fn not called) for a width without kernels: the one-layer rows of prnn.hip's
+// table, with its flip pass's waves per workgroup - except f64 at 53..68 units: 4, not 8 (at 8 the swap kernel spills 20 bytes per
+// lane to scratch; profiles/renyi_kernel_resources.txt)
+template <class Fn>
+bool with_swap(const rnnwf_handle* h, Fn&& fn) {
+    if (!h->f64) {
+        switch (h->NFULL) {
+            case 1: fn(SwapLaunch<float, 1, 4>()); return true;
+            case 2: fn(SwapLaunch<float, 2, 4>()); return true;
+            case 3: fn(SwapLaunch<float, 3, 4>()); return true;
+            case 4: fn(SwapLaunch<float, 4, 4>()); return true;
+            case 6: fn(SwapLaunch<float, 6, 8>()); return true;
+            case 8: fn(SwapLaunch<float, 8, 4>()); return true;
+            case 12: fn(SwapLaunch<float, 12, 4>()); return true;
+            case 16: fn(SwapLaunch<float, 16, 4>()); return true;
+        }
+        return false;
+    }
+    switch (h->NFULL) {
+        case 1: fn(SwapLaunch<double, 1, 4>()); return true;
+        case 2: fn(SwapLaunch<double, 2, 4>()); return true;
+        case 3: fn(SwapLaunch<double, 3, 4>()); return true;
+        case 4: fn(SwapLaunch<double, 4, 4>()); return true;
+        case 6: fn(SwapLaunch<double, 6, 4>()); return true;
+    }
+    return false;
+}
 
 // Scratch of one pass of ns chains in h->renyi, 256-byte aligned pieces
 struct Scratch {
@@ -82,7 +76,7 @@ struct Scratch {
 int64_t pairs_per_pass(rnnwf_handle* h) {
     const int N = h->N;
     const size_t per_block = (size_t)std::max(N - 1, 1) * prnn_hck_bytes_per_block(h) + Scratch(N, kChains).bytes;
-    const int64_t blocks = std::max<int64_t>(1, (int64_t)(state_budget_bytes(h, kStateBudget) / per_block));
+    const int64_t blocks = std::max<int64_t>(1, (int64_t)(state_budget_bytes(h, kDefaultStateBudget) / per_block));
     return blocks * kChains / 2;
 }
 
@@ -120,19 +114,19 @@ int swap_pass(rnnwf_handle* h, int64_t ns, const Scratch& sc, double* sums_host)
     a.terms = (double*)(buf + sc.terms);
     a.ntiles = (int64_t)(N - 1) * nsb;
     if (N > 1) {
-        bool found = false;
-        SWAP_DISPATCH(h, {
-            found = true;
-            if (int rc = K::terms(h, a)) return rc;
-            if (int rc = K::swap(h, a)) return rc;
-            h->work[1] += (double)nsb * N * (N - 1) / 2.0 * K::mfma_flops_per_step();
-            break;
+        int rc = 0;
+        const bool found = with_swap(h, [&](auto k) {
+            using K = decltype(k);
+            rc = K::terms(h, a);
+            if (!rc) rc = K::swap(h, a);
+            if (!rc) h->work[1] += (double)nsb * N * (N - 1) / 2.0 * K::mfma_flops_per_step();
         });
         if (!found) return h->fail(RNNWF_ERR_INVALID, "rnnwf_renyi2_swap: no swap kernel for NFULL=%d f64=%d", h->NFULL, (int)h->f64);
+        if (rc) return rc;
         h->work[0] += (double)ns * N * (N - 1) / 2.0;          // N (N - 1) cell evaluations per pair
     }
     {
-        TimedLaunch tl(h, 2);
+        TimedLaunch tl(h, kTimerAssembly);
         renyi_assemble_kernel<<<dim3((unsigned)sc.nblk, (unsigned)(N + 1)), kRenyiThreads, 0, h->stream>>>(
             a.tail, a.terms, N, ns, (double*)(buf + sc.lr), (double*)(buf + sc.part));
         RNNWF_HIP(h, hipGetLastError());

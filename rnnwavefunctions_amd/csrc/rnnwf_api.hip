@@ -478,18 +478,15 @@ int rnnwf::unpack_and_download(rnnwf_handle* h, const DevBuf& bits, int64_t B, i
 
 int rnnwf::run_moments(rnnwf_handle* h, const void* eloc_dev, int64_t ns, bool complex_f32, double* moments_host) {
     if (int rc = ensure(h, h->moments, 4 * sizeof(double))) return rc;
-    {
-        TimedLaunch tl(h, 2);
-        // single device: the kernel writes the four moments into pinned host memory itself (read behind the step's one stream
-        // sync; saves the copy launch - 4 us of config 1's 70); with the in-step all-reduce they travel device -> RCCL -> copy
-        double* direct = (moments_host && !h->reduce_in_step) ? (double*)h->pinned_dev : nullptr;
-        if (!moments_host && !h->reduce_in_step && h->moments_direct) direct = h->moments_direct;      // rnnwf_train_steps: iteration k's row of its pinned table
-        if (complex_f32)
-            moments_kernel<float><<<1, 1024, 0, h->stream>>>((const float*)eloc_dev, ns, 2, 1, (double*)h->moments.p, direct);
-        else
-            moments_kernel<double><<<1, 1024, 0, h->stream>>>((const double*)eloc_dev, ns, 1, 0, (double*)h->moments.p, direct);
-    }
-    RNNWF_HIP(h, hipGetLastError());
+    // single device: the kernel writes the four moments into pinned host memory itself (read behind the step's one stream
+    // sync; saves the copy launch - 4 us of config 1's 70); with the in-step all-reduce they travel device -> RCCL -> copy
+    double* direct = (moments_host && !h->reduce_in_step) ? (double*)h->pinned_dev : nullptr;
+    if (!moments_host && !h->reduce_in_step && h->moments_direct) direct = h->moments_direct;      // rnnwf_train_steps: iteration k's row of its pinned table
+    if (int rc = complex_f32 ? timed_launch(h, kTimerAssembly, moments_kernel<float>, 1, 1024, 0, (const float*)eloc_dev, ns, 2, 1,
+                                            (double*)h->moments.p, direct)
+                             : timed_launch(h, kTimerAssembly, moments_kernel<double>, 1, 1024, 0, (const double*)eloc_dev, ns, 1, 0,
+                                            (double*)h->moments.p, direct))
+        return rc;
     if (h->reduce_in_step)
         if (int rc = comm_allreduce_device(h, h->moments.p, 4)) return rc;
     if (moments_host) {
@@ -503,11 +500,8 @@ int rnnwf::run_moments(rnnwf_handle* h, const void* eloc_dev, int64_t ns, bool c
 
 int rnnwf::run_tfim_eloc(rnnwf_handle* h, const uint32_t* bits, const double* lpq, int64_t ns, int Nx, int Ny,
                          const int32_t* pos_of_site_dev, const double* Jz_dev, double Bx, double* eloc_dev) {
-    TimedLaunch tl(h, 2);
-    tfim_eloc_kernel<<<(unsigned)((ns + kElocSamples - 1) / kElocSamples), kElocSamples * kElocGroups, 0, h->stream>>>(
-        bits, lpq, ns, Nx, Ny, pos_of_site_dev, Jz_dev, Bx, eloc_dev);
-    RNNWF_HIP(h, hipGetLastError());
-    return 0;
+    return timed_launch(h, kTimerAssembly, tfim_eloc_kernel, (unsigned)((ns + kElocSamples - 1) / kElocSamples), kElocSamples * kElocGroups, 0,
+                        bits, lpq, ns, Nx, Ny, pos_of_site_dev, Jz_dev, Bx, eloc_dev);
 }
 
 int rnnwf::run_parity_combine(rnnwf_handle* h, const double* a, const double* b, int64_t n, double* out) {

@@ -22,35 +22,26 @@ template <int NF32, int RJ, int WAVES, int MODE>
 struct SLaunch {
     using L = SplitLayout<NF32, RJ, 1, MODE>;
     static int flip(rnnwf_handle* h, const PrnnArgs& a, int kt16) {
-        const void* fn = (const void*)prnn_flip_split_kernel<NF32, RJ, WAVES, MODE>;
         if (L::HP > 4 * kt16) return h->fail(RNNWF_ERR_INVALID, "bf16x3 layout wider than the checkpoint rows (%d > %d)", L::HP, 4 * kt16);
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, L::LDS_BYTES, &bpc)) return rc;
         const int64_t ntiles = (int64_t)(a.N - 1) * ((a.ns + 31) / 32);
-        const int64_t need = (ntiles + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)bpc * h->cu_count));
-        TimedLaunch tl(h, 1);
-        prnn_flip_split_kernel<NF32, RJ, WAVES, MODE><<<grid, WAVES * 64, L::LDS_BYTES, h->stream>>>(a, h->wsplit.p, kt16);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerFlip, prnn_flip_split_kernel<NF32, RJ, WAVES, MODE>, WAVES * 64, L::LDS_BYTES, ntiles, WAVES, a,
+                                 h->wsplit.p, kt16);
     }
     // ping-pong form (8 waves per workgroup, two per SIMD, alternating MFMA / VALU segments): K-packed layouts only
     static int flip_pp(rnnwf_handle* h, const PrnnArgs& a, int kt16) {
         if constexpr (MODE == 2) {
-            const void* fn = (const void*)prnn_flip_pp_kernel<NF32, RJ>;
+            const auto kern = prnn_flip_pp_kernel<NF32, RJ>;
             if (L::HP > 4 * kt16) return h->fail(RNNWF_ERR_INVALID, "bf16x3 layout wider than the checkpoint rows (%d > %d)", L::HP, 4 * kt16);
-            int bpc = 0;
-            if (int rc = rnnwf::blocks_per_cu(h, fn, 512, L::BYTES, &bpc)) return rc;
             const int64_t ntiles = (int64_t)(a.N - 1) * ((a.ns + 31) / 32);
-            const int64_t need = (ntiles + 7) / 8;
-            const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)bpc * h->cu_count));
+            unsigned grid = 0;
+            if (int rc = persistent_grid(h, kern, 512, L::BYTES, ntiles, 8, &grid)) return rc;
 #ifdef RNNWF_DIAGNOSTICS
             if (getenv("RNNWF_STAMPS")) {     // in-kernel cycle stamps, median over waves -> stderr (tools/stamps.py)
                 PrnnArgs b = a;
                 const size_t nwv = (size_t)grid * 8;
                 RNNWF_HIP(h, hipMalloc((void**)&b.stamps, nwv * 128));
                 RNNWF_HIP(h, hipMemsetAsync(b.stamps, 0, nwv * 128, h->stream));
-                prnn_flip_pp_kernel<NF32, RJ><<<grid, 512, L::BYTES, h->stream>>>(b, h->wsplit.p, kt16, StackArgs{});
+                kern<<<grid, 512, L::BYTES, h->stream>>>(b, h->wsplit.p, kt16, StackArgs{});
                 RNNWF_HIP(h, hipStreamSynchronize(h->stream));
                 std::vector<unsigned long long> st(nwv * 16);
                 RNNWF_HIP(h, hipMemcpy(st.data(), b.stamps, nwv * 128, hipMemcpyDeviceToHost));
@@ -68,10 +59,7 @@ struct SLaunch {
                 return 0;
             }
 #endif
-            TimedLaunch tl(h, 1);
-            prnn_flip_pp_kernel<NF32, RJ><<<grid, 512, L::BYTES, h->stream>>>(a, h->wsplit.p, kt16, StackArgs{});
-            RNNWF_HIP(h, hipGetLastError());
-            return 0;
+            return timed_launch(h, kTimerFlip, kern, grid, 512, L::BYTES, a, h->wsplit.p, kt16, StackArgs{});
         } else {
             return flip(h, a, kt16);
         }
@@ -80,47 +68,20 @@ struct SLaunch {
     static double mfma_flops_per_step() { return (double)L::NT * L::KS * 32768.0; }   // per 32-chain wave-step
 };
 
-#define SPLIT_DISPATCH(h, EXPR)                                      \
-    do {                                                             \
-        switch ((h)->NFULL) {                                        \
-            case 1: { using K = SLaunch<0, 10, 4, 1>; EXPR; }        \
-            case 2: { using K = SLaunch<1, 2, 4, 1>; EXPR; }         \
-            case 3: if ((h)->H <= 50) { using K = SLaunch<1, 9, 4, 2>; EXPR; } \
-                    else { using K = SLaunch<1, 10, 4, 0>; EXPR; }   \
-            case 4: { using K = SLaunch<2, 2, 4, 0>; EXPR; }         \
-        }                                                            \
-    } while (0)
-
-
 // ---- bf16x3 engine for the swap pass (num_units <= 68) ---------------------------------------------------
 template <int NF32, int RJ, int WAVES, int MODE>
 struct CSLaunch {
     using L = SplitLayout<NF32, RJ, 3, MODE>;
     static int swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles, int kt16) {
-        const void* fn = (const void*)crnn_swap_split_kernel<NF32, RJ, WAVES, MODE>;
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, L::BYTES, &bpc)) return rc;
-        const int64_t need = (max_tiles + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)bpc * h->cu_count));
-        TimedLaunch tl(h, 1);
-        crnn_swap_split_kernel<NF32, RJ, WAVES, MODE><<<grid, WAVES * 64, L::BYTES, h->stream>>>(a, h->wsplit.p, kt16);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerFlip, crnn_swap_split_kernel<NF32, RJ, WAVES, MODE>, WAVES * 64, L::BYTES, max_tiles, WAVES, a,
+                                 h->wsplit.p, kt16);
     }
     // ping-pong form (8 waves per workgroup, alternating MFMA / VALU segments): K-packed layout MODE 2 only
     static int swap_pp(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles, int kt16) {
         if constexpr (MODE == 2) {
-            const void* fn = (const void*)crnn_swap_pp_kernel<NF32, RJ>;
             if (L::HP > 4 * kt16) return h->fail(RNNWF_ERR_INVALID, "bf16x3 layout wider than the checkpoint rows (%d > %d)", L::HP, 4 * kt16);
-            int bpc = 0;
-            constexpr size_t LDS = SplitPP<NF32, RJ, 3>::LDS_WITH_SLOTS;
-            if (int rc = rnnwf::blocks_per_cu(h, fn, 512, LDS, &bpc)) return rc;
-            const int64_t need = (max_tiles + 7) / 8;
-            const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)bpc * h->cu_count));
-            TimedLaunch tl(h, 1);
-            crnn_swap_pp_kernel<NF32, RJ><<<grid, 512, LDS, h->stream>>>(a, h->wsplit.p, kt16, StackArgs{});
-            RNNWF_HIP(h, hipGetLastError());
-            return 0;
+            return launch_persistent(h, kTimerFlip, crnn_swap_pp_kernel<NF32, RJ>, 512, SplitPP<NF32, RJ, 3>::LDS_WITH_SLOTS, max_tiles, 8, a,
+                                     h->wsplit.p, kt16, StackArgs{});
         } else {
             return swap(h, a, max_tiles, kt16);
         }
@@ -129,16 +90,21 @@ struct CSLaunch {
     static double mfma_flops_per_step() { return (double)L::NT * L::KS * 32768.0; }
 };
 
-#define CSPLIT_DISPATCH(h, EXPR)                                     \
-    do {                                                             \
-        switch ((h)->NFULL) {                                        \
-            case 1: { using K = CSLaunch<0, 10, 4, 1>; EXPR; }       \
-            case 2: { using K = CSLaunch<1, 2, 4, 1>; EXPR; }        \
-            case 3: if ((h)->H <= 50) { using K = CSLaunch<1, 9, 4, 2>; EXPR; } \
-                    else { using K = CSLaunch<1, 10, 4, 0>; EXPR; }  \
-            case 4: { using K = CSLaunch<2, 2, 4, 0>; EXPR; }        \
-        }                                                            \
-    } while (0)
+// fn(K<NF32, RJ, WAVES, MODE>()) for the handle's width, false (fn not called) for a width without kernels: K = SLaunch (positive
+// RNN) or CSLaunch (complex RNN), which share the bf16x3 layouts of each width
+template <template <int, int, int, int> class K, class Fn>
+bool with_layout(const rnnwf_handle* h, Fn&& fn) {
+    switch (h->NFULL) {
+        case 1: fn(K<0, 10, 4, 1>()); return true;
+        case 2: fn(K<1, 2, 4, 1>()); return true;
+        case 3:
+            if (h->H <= 50) fn(K<1, 9, 4, 2>());
+            else fn(K<1, 10, 4, 0>());
+            return true;
+        case 4: fn(K<2, 2, 4, 0>()); return true;
+    }
+    return false;
+}
 
 
 // widths served by the riders form (split_stream.hip): 53..100 units (53..68: RNNWF_ENGINE=bf16x3-serial selects the padded
@@ -166,12 +132,10 @@ struct BfBase {
     }
     template <typename Args, typename Kern>
     static int launch(rnnwf_handle* h, const Args& a, Kern kern, size_t lds) {
-        const void* fn = (const void*)kern;
         const int threads = B::NB * (B::NW + 1) * 64;              // per block: NW product / gate waves + the sampler
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, threads, lds, &bpc)) return rc;
         // every CU gets work before any workgroup gets a second block: grid = min(blocks, CUs x resident workgroups)
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(a.nsb, (int64_t)bpc * h->cu_count));
+        unsigned grid = 0;
+        if (int rc = persistent_grid(h, kern, threads, lds, a.nsb, 1, &grid)) return rc;
 #ifdef RNNWF_DIAGNOSTICS
         if constexpr (std::is_same<Args, PrnnArgs>::value) {
             if (getenv("RNNWF_STAMPS_BASE")) {    // in-kernel cycle stamps, median over the waves of each role -> stderr (tools/stamps_base.py)
@@ -203,10 +167,7 @@ struct BfBase {
             }
         }
 #endif
-        TimedLaunch tl(h, 0);
-        kern<<<grid, threads, lds, h->stream>>>(a);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return timed_launch(h, kTimerBase, kern, grid, threads, lds, a);
     }
 };
 }  // namespace
@@ -261,13 +222,6 @@ using StackL0 = SplitLayout<kStackNF32, kStackRJ, 1, 2>;
 using StackU1 = SplitUpperLayout<kStackNF32, kStackRJ, 1>;
 using StackU3 = SplitUpperLayout<kStackNF32, kStackRJ, 3>;
 
-template <typename Kern>
-int stack_grid(rnnwf_handle* h, Kern kern, size_t lds, int64_t tiles, unsigned* grid) {
-    int bpc = 0;
-    if (int rc = rnnwf::blocks_per_cu(h, (const void*)kern, 512, lds, &bpc)) return rc;
-    *grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((tiles + 7) / 8, (int64_t)bpc * h->cu_count));
-    return 0;
-}
 }  // namespace
 
 bool rnnwf::stack_split_available(const rnnwf_handle* h) {
@@ -305,10 +259,10 @@ int rnnwf::prnn_stack_flip(rnnwf_handle* h, const PrnnArgs& a) {
     if (int rc = ensure(h, h->xrec[0], bytes)) return rc;
     if (NL > 2) if (int rc = ensure(h, h->xrec[1], bytes)) return rc;
     unsigned g0 = 0, gu = 0, gl = 0;
-    if (int rc = stack_grid(h, prnn_flip_pp_kernel<kStackNF32, kStackRJ, true>, StackL0::BYTES, ntiles, &g0)) return rc;
-    if (int rc = stack_grid(h, prnn_flip_pp_upper_kernel<kStackNF32, kStackRJ, false>, StackU1::LDS_BYTES, ntiles, &gu)) return rc;
-    if (int rc = stack_grid(h, prnn_flip_pp_upper_kernel<kStackNF32, kStackRJ, true>, StackU1::LDS_BYTES, ntiles, &gl)) return rc;
-    TimedLaunch tl(h, 1);                                     // the whole pipeline is the "flip pass" of the timers
+    if (int rc = persistent_grid(h, prnn_flip_pp_kernel<kStackNF32, kStackRJ, true>, 512, StackL0::BYTES, ntiles, 8, &g0)) return rc;
+    if (int rc = persistent_grid(h, prnn_flip_pp_upper_kernel<kStackNF32, kStackRJ, false>, 512, StackU1::LDS_BYTES, ntiles, 8, &gu)) return rc;
+    if (int rc = persistent_grid(h, prnn_flip_pp_upper_kernel<kStackNF32, kStackRJ, true>, 512, StackU1::LDS_BYTES, ntiles, 8, &gl)) return rc;
+    TimedLaunch tl(h, kTimerFlip);                                    // the whole pipeline is the "flip pass" of the timers
     StackArgs st{nullptr, (float*)h->xrec[0].p, NL * kt16, 0};
     prnn_flip_pp_kernel<kStackNF32, kStackRJ, true><<<g0, 512, StackL0::BYTES, h->stream>>>(a, h->wsplit.p, kt16, st);
     RNNWF_HIP(h, hipGetLastError());
@@ -372,10 +326,10 @@ int rnnwf::crnn_stack_swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles
     if (NL > 2) if (int rc = ensure(h, h->xrec[1], bytes)) return rc;
     unsigned g0 = 0, gu = 0, gl = 0;
     constexpr size_t LDS0 = SplitPP<kStackNF32, kStackRJ, 3>::LDS_WITH_SLOTS;
-    if (int rc = stack_grid(h, crnn_swap_pp_kernel<kStackNF32, kStackRJ, true>, LDS0, max_tiles, &g0)) return rc;
-    if (int rc = stack_grid(h, crnn_swap_pp_upper_kernel<kStackNF32, kStackRJ, false>, StackU3::LDS_BYTES, max_tiles, &gu)) return rc;
-    if (int rc = stack_grid(h, crnn_swap_pp_upper_kernel<kStackNF32, kStackRJ, true>, StackU3::LDS_BYTES, max_tiles, &gl)) return rc;
-    TimedLaunch tl(h, 1);
+    if (int rc = persistent_grid(h, crnn_swap_pp_kernel<kStackNF32, kStackRJ, true>, 512, LDS0, max_tiles, 8, &g0)) return rc;
+    if (int rc = persistent_grid(h, crnn_swap_pp_upper_kernel<kStackNF32, kStackRJ, false>, 512, StackU3::LDS_BYTES, max_tiles, 8, &gu)) return rc;
+    if (int rc = persistent_grid(h, crnn_swap_pp_upper_kernel<kStackNF32, kStackRJ, true>, 512, StackU3::LDS_BYTES, max_tiles, 8, &gl)) return rc;
+    TimedLaunch tl(h, kTimerFlip);
     StackArgs st{nullptr, (float*)h->xrec[0].p, NL * kt16, 0};
     crnn_swap_pp_kernel<kStackNF32, kStackRJ, true><<<g0, 512, LDS0, h->stream>>>(a, h->wsplit.p, kt16, st);
     RNNWF_HIP(h, hipGetLastError());
@@ -393,11 +347,12 @@ int rnnwf::crnn_stack_swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles
 int rnnwf::prnn_split_flip(rnnwf_handle* h, const PrnnArgs& a) {
     const int kt16 = 4 * h->NFULL + 1;
     if (riders(h)) return prnn_split_flip_stream(h, a, kt16);
+    int rc = 0;
 #ifdef RNNWF_DIAGNOSTICS
     if (riders16n(h)) return prnn_split_flip_16n(h, a, kt16);
-    if (h->knobs.engine == 3) { SPLIT_DISPATCH(h, return K::flip(h, a, kt16)); }      // RNNWF_ENGINE=bf16x3-serial: A/B only
+    if (h->knobs.engine == 3 && with_layout<SLaunch>(h, [&](auto k) { rc = decltype(k)::flip(h, a, kt16); })) return rc;   // RNNWF_ENGINE=bf16x3-serial: A/B only
 #endif
-    SPLIT_DISPATCH(h, return K::flip_pp(h, a, kt16));
+    if (with_layout<SLaunch>(h, [&](auto k) { rc = decltype(k)::flip_pp(h, a, kt16); })) return rc;
     return h->fail(RNNWF_ERR_INVALID, "no bf16x3 kernel for NFULL=%d", h->NFULL);
 }
 double rnnwf::prnn_split_flops_per_step(rnnwf_handle* h) {
@@ -405,8 +360,9 @@ double rnnwf::prnn_split_flops_per_step(rnnwf_handle* h) {
 #ifdef RNNWF_DIAGNOSTICS
     if (riders16n(h)) return prnn_split_16n_flops_per_step();
 #endif
-    SPLIT_DISPATCH(h, return K::mfma_flops_per_step());
-    return 0;
+    double f = 0;
+    with_layout<SLaunch>(h, [&](auto k) { f = decltype(k)::mfma_flops_per_step(); });
+    return f;
 }
 
 
@@ -417,28 +373,30 @@ int rnnwf::prnn_split_pack(rnnwf_handle* h, std::vector<char>& simg) {
         if (int rc = prnn_split_16n_pack(h)) return rc;
     }
 #endif
-    SPLIT_DISPATCH(h, { simg = K::pack(h); return 0; });
+    if (with_layout<SLaunch>(h, [&](auto k) { simg = decltype(k)::pack(h); })) return 0;
     return h->fail(RNNWF_ERR_INVALID, "no bf16x3 layout for NFULL=%d", h->NFULL);
 }
 
 int rnnwf::crnn_split_swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles) {
     const int kt16 = 4 * h->NFULL + 1;
     if (riders(h)) return crnn_split_swap_stream(h, a, max_tiles, kt16);
+    int rc = 0;
 #ifdef RNNWF_DIAGNOSTICS
-    if (h->knobs.engine == 3) { CSPLIT_DISPATCH(h, return K::swap(h, a, max_tiles, kt16)); }      // RNNWF_ENGINE=bf16x3-serial: A/B only
+    if (h->knobs.engine == 3 && with_layout<CSLaunch>(h, [&](auto k) { rc = decltype(k)::swap(h, a, max_tiles, kt16); })) return rc;   // RNNWF_ENGINE=bf16x3-serial: A/B only
 #endif
-    CSPLIT_DISPATCH(h, return K::swap_pp(h, a, max_tiles, kt16));
+    if (with_layout<CSLaunch>(h, [&](auto k) { rc = decltype(k)::swap_pp(h, a, max_tiles, kt16); })) return rc;
     return h->fail(RNNWF_ERR_INVALID, "no bf16x3 cRNN kernel for NFULL=%d", h->NFULL);
 }
 double rnnwf::crnn_split_flops_per_step(rnnwf_handle* h) {
     if (riders(h)) return crnn_split_stream_flops_per_step(h);
-    CSPLIT_DISPATCH(h, return K::mfma_flops_per_step());
-    return 0;
+    double f = 0;
+    with_layout<CSLaunch>(h, [&](auto k) { f = decltype(k)::mfma_flops_per_step(); });
+    return f;
 }
 
 
 int rnnwf::crnn_split_pack(rnnwf_handle* h, std::vector<char>& simg) {
     if (riders(h)) return crnn_split_stream_pack(h, simg);
-    CSPLIT_DISPATCH(h, { simg = K::pack(h); return 0; });
+    if (with_layout<CSLaunch>(h, [&](auto k) { simg = decltype(k)::pack(h); })) return 0;
     return h->fail(RNNWF_ERR_INVALID, "no bf16x3 layout for NFULL=%d", h->NFULL);
 }

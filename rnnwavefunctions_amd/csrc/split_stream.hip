@@ -14,6 +14,8 @@ using namespace rnnwf;
 
 namespace {
 constexpr int WAVES = 4;
+// 32-chain flip tiles of one pass
+int64_t ntiles(const PrnnArgs& a) { return (int64_t)(a.N - 1) * ((a.ns + 31) / 32); }
 template <int NF32, int RJ>
 struct RLaunch {
     using L = SplitLayout<NF32, RJ, 1, 3>;
@@ -31,61 +33,30 @@ struct RLaunch {
         else
 #endif
         {
-        const void* fn = (const void*)prnn_flip_split_kernel<NF32, RJ, WAVES, 3>;
         if (L::HP > 4 * kt16) return h->fail(RNNWF_ERR_INVALID, "bf16x3 layout wider than the checkpoint rows (%d > %d)", L::HP, 4 * kt16);
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, L::LDS_BYTES, &bpc)) return rc;
-        const int64_t ntiles = (int64_t)(a.N - 1) * ((a.ns + 31) / 32);
-        const int64_t need = (ntiles + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)bpc * h->cu_count));
-        TimedLaunch tl(h, 1);
-        prnn_flip_split_kernel<NF32, RJ, WAVES, 3><<<grid, WAVES * 64, L::LDS_BYTES, h->stream>>>(a, h->wsplit.p, kt16);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerFlip, prnn_flip_split_kernel<NF32, RJ, WAVES, 3>, WAVES * 64, L::LDS_BYTES, ntiles(a), WAVES, a,
+                                 h->wsplit.p, kt16);
         }
     }
 #ifdef RNNWF_DIAGNOSTICS
     // the same pass with the wave-step as one hand-scheduled asm block (split_riders_asm.h)
     static int flip_asm(rnnwf_handle* h, const PrnnArgs& a, int kt16) {
-        const void* fn = (const void*)prnn_flip_riders_asm_kernel<NF32, RJ, WAVES>;
         if (L::HP > 4 * kt16) return h->fail(RNNWF_ERR_INVALID, "bf16x3 layout wider than the checkpoint rows (%d > %d)", L::HP, 4 * kt16);
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, L::LDS_BYTES, &bpc)) return rc;
-        const int64_t ntiles = (int64_t)(a.N - 1) * ((a.ns + 31) / 32);
-        const int64_t need = (ntiles + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)bpc * h->cu_count));
-        TimedLaunch tl(h, 1);
-        prnn_flip_riders_asm_kernel<NF32, RJ, WAVES><<<grid, WAVES * 64, L::LDS_BYTES, h->stream>>>(a, h->wsplit.p, kt16);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerFlip, prnn_flip_riders_asm_kernel<NF32, RJ, WAVES>, WAVES * 64, L::LDS_BYTES, ntiles(a), WAVES, a,
+                                 h->wsplit.p, kt16);
     }
 #endif
     // the 16x16x32 form (split16_core.h), 69..100 units
     static int flip_asm16(rnnwf_handle* h, const PrnnArgs& a, int kt16) {
         using L16 = S16Layout<1>;
-        const void* fn = (const void*)prnn_flip_riders16_asm_kernel<WAVES>;
         if (kt16 != L16::NJ) return h->fail(RNNWF_ERR_INVALID, "the 16x16x32 form expects %d checkpoint k-steps, got %d", L16::NJ, kt16);
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, L16::LDS_BYTES, &bpc)) return rc;
-        const int64_t ntiles = (int64_t)(a.N - 1) * ((a.ns + 31) / 32);
-        const int64_t need = (ntiles + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)bpc * h->cu_count));
-        TimedLaunch tl(h, 1);
-        prnn_flip_riders16_asm_kernel<WAVES><<<grid, WAVES * 64, L16::LDS_BYTES, h->stream>>>(a, h->wsplit16.p, kt16);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerFlip, prnn_flip_riders16_asm_kernel<WAVES>, WAVES * 64, L16::LDS_BYTES, ntiles(a), WAVES, a,
+                                 h->wsplit16.p, kt16);
     }
     static int swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles, int kt16) {
-        const void* fn = (const void*)crnn_swap_split_kernel<NF32, RJ, WAVES, 3>;
         if (LC::HP > 4 * kt16) return h->fail(RNNWF_ERR_INVALID, "bf16x3 layout wider than the checkpoint rows (%d > %d)", LC::HP, 4 * kt16);
-        int bpc = 0;
-        if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, LC::LDS_BYTES, &bpc)) return rc;
-        const int64_t need = (max_tiles + WAVES - 1) / WAVES;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)bpc * h->cu_count));
-        TimedLaunch tl(h, 1);
-        crnn_swap_split_kernel<NF32, RJ, WAVES, 3><<<grid, WAVES * 64, LC::LDS_BYTES, h->stream>>>(a, h->wsplit.p, kt16);
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return launch_persistent(h, kTimerFlip, crnn_swap_split_kernel<NF32, RJ, WAVES, 3>, WAVES * 64, LC::LDS_BYTES, max_tiles, WAVES, a,
+                                 h->wsplit.p, kt16);
     }
 };
 using R100 = RLaunch<3, 2>;                                  // 69..100 units (NFULL = 6 of the f32 layout)
@@ -98,17 +69,12 @@ static_assert(!R68::L::STREAM && R68::L::HP == 68 && !R68::LC::STREAM, "layout m
 // ---- the 16x16x32 form at 37..52 units (split16_core.h: S16nLayout): A/B only (RNNWF_ENGINE=bf16x3-n16): measured 10 % slower than the ping-pong kernel ----
 int rnnwf::prnn_split_flip_16n(rnnwf_handle* h, const PrnnArgs& a, int kt16) {
     using L16 = S16nLayout<1>;
-    const void* fn = (const void*)prnn_flip_riders16n_asm_kernel<WAVES>;
+    const auto kern = prnn_flip_riders16n_asm_kernel<WAVES>;
     if (kt16 != L16::NJ) return h->fail(RNNWF_ERR_INVALID, "the 16x16x32 form expects %d checkpoint k-steps, got %d", L16::NJ, kt16);
-    int bpc = 0;
-    if (int rc = rnnwf::blocks_per_cu(h, fn, WAVES * 64, L16::BYTES, &bpc)) return rc;
-    const int64_t ntiles = (int64_t)(a.N - 1) * ((a.ns + 31) / 32);
-    const int64_t need = (ntiles + WAVES - 1) / WAVES;
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)h->cu_count));       // one wave per SIMD
-    TimedLaunch tl(h, 1);
-    prnn_flip_riders16n_asm_kernel<WAVES><<<grid, WAVES * 64, L16::BYTES, h->stream>>>(a, h->wsplit16.p, kt16);
-    RNNWF_HIP(h, hipGetLastError());
-    return 0;
+    unsigned grid = 0;
+    if (int rc = persistent_grid(h, kern, WAVES * 64, L16::BYTES, ntiles(a), WAVES, &grid)) return rc;
+    grid = std::min<unsigned>(grid, h->cu_count);       // one wave per SIMD
+    return timed_launch(h, kTimerFlip, kern, grid, WAVES * 64, L16::BYTES, a, h->wsplit16.p, kt16);
 }
 double rnnwf::prnn_split_16n_flops_per_step() { return (double)S16nLayout<1>::NT * S16nLayout<1>::KS * 2 * 16384.0; }
 int rnnwf::prnn_split_16n_pack(rnnwf_handle* h) {

@@ -33,7 +33,7 @@ inline int tn_gemm_launch(rnnwf_handle* h, const T* P, const T* Q, int64_t R, T*
     using S = TnGemmShape<T, PT, QT>;
     using CQ = RowChunks<T, QT>;
     constexpr int ACC_REGS = tn_max_tiles(PT, S::CW, S::WAVES) * QT * 4 * ((int)sizeof(T) / 4);     // accumulators of the busiest wave
-    TimedLaunch tl(h, 4);
+    TimedLaunch tl(h, kTimerGemm);
     if constexpr (ACC_REGS <= 208 || CQ::NC == 1) {
         return tn_gemm_launch_cols<T, PT, QT>(h, P, Q, R, dW, CQ::COLS, CQ::COLS);
     } else {
