@@ -4,6 +4,7 @@ differences of the float64 oracle, and the end-to-end acceptance test the refere
 import numpy as np
 import pytest
 
+from autograd_reference import fd_check as _fd_check      # central differences of the oracle's cost, 8-12 random elements per tensor
 from oracle import models as M
 from rnnwavefunctions_amd import params as P
 
@@ -362,24 +363,6 @@ def test_run_j1j2_approaches_the_exact_ground_state_energy():
 
 
 # ---- 2D drivers (float64): MDRNN on the zig-zag path, GRU on the raster path ------------------------
-
-def _fd_check(grads, prm64, cost, n_per_tensor=10, eps=1e-6):
-    rng = np.random.RandomState(0)
-    worst = 0.0
-    scale = max(np.abs(g).max() for g in grads.values())
-    for name, g in grads.items():
-        assert g.shape == prm64[name].shape
-        flat = prm64[name].ravel()
-        for idx in rng.choice(flat.size, size=min(flat.size, n_per_tensor), replace=False):
-            old = flat[idx]
-            flat[idx] = old + eps
-            cp = cost()
-            flat[idx] = old - eps
-            cm = cost()
-            flat[idx] = old
-            worst = max(worst, abs((cp - cm) / (2 * eps) - g.ravel()[idx]) / scale)
-    return worst
-
 
 @pytest.mark.parametrize("Nx,Ny,H,ns", [(3, 3, 6, 64), (4, 3, 20, 48), (3, 4, 50, 32), (5, 2, 64, 20), (3, 3, 70, 20), (3, 2, 84, 16)])
 def test_mdrnn_gradient_matches_finite_differences_of_the_oracle(Nx, Ny, H, ns):
