@@ -242,6 +242,29 @@ int rnnwf_adam_set_state(rnnwf_handle* h, const double* m_flat, const double* v_
 int rnnwf_renyi2_swap(rnnwf_handle* h, const int32_t* samples, int64_t npairs, uint64_t seed, uint64_t step,
                       int64_t pair_offset, double* sums, double* out_log_ratio, int32_t* out_samples);
 
+/* ---- correlation functions -------------------------------------------------------------------------
+ * The reference README's "correlation functions" of the positive one-layer GRU models (GRU1D, GRU1D_F64; every other model
+ * and stacked layers: RNNWF_ERR_INVALID), psi = sqrt(P), samples sigma ~ P, s = 2 sigma - 1 (docs/correlations.md):
+ *   <sz_i> = E[s_i],  <sz_i sz_j> = E[s_i s_j],
+ *   <sx_i> = E[r_i],        log r_i  = 1/2 [log P(sigma with i flipped)       - log P(sigma)],
+ *   <sx_i sx_j> = E[r_ij],  log r_ij = 1/2 [log P(sigma with i and j flipped) - log P(sigma)],  i < j, every pair.
+ * Sites in the model's order (raster order ny * Nx + nx for GRU1D_F64).  Flipped chains restart from hidden-state checkpoints:
+ * N(N-1)/2 + N(N-1)(N-2)/6 cell evaluations per chain.  Runs in passes under the state budget (whole 16-chain blocks per
+ * pass; results do not depend on the pass size); sums are reduced in a fixed order: a repeated call returns the same bits.
+ * A chain with log r > 709 makes the sums it enters +inf.  Overwrites the batch an earlier rnnwf_vmc_step left for
+ * rnnwf_vmc_gradient (a refused call does not).
+ *   samples      (ns, N) int32; nullptr: draw them on the device exactly as rnnwf_sample(h, ns, seed, step, sample_offset, ...)
+ *                would (seed, step, sample_offset ignored otherwise)
+ *   z_sums       (N) sum s_i;  zz_sums (N, N) sum s_i s_j, symmetric, diagonal ns
+ *   x_sums       (N, 2) sum r_i, sum r_i^2
+ *   xx_sums      (N, N, 5), entries i < j: sum r_ij, sum r_ij^2, sum r_ij r_i, sum r_ij r_j, sum r_i r_j; other entries 0
+ *   all four are required and additive over shards
+ *   out_log_ratio(N + N(N-1)/2, ns) f64 or nullptr: rows log r_i, then log r_ij in lexicographic order of (i, j)
+ *   out_samples  (ns, N) int32 or nullptr (drawn chains)                                                        */
+int rnnwf_correlations(rnnwf_handle* h, const int32_t* samples, int64_t ns, uint64_t seed, uint64_t step,
+                       int64_t sample_offset, double* z_sums, double* zz_sums, double* x_sums, double* xx_sums,
+                       double* out_log_ratio, int32_t* out_samples);
+
 /* ---- multi-GPU: one RCCL all-reduce of the energy moments -------------------------------------
  * The reference is single-process; these add the one data-parallel collective of SURVEY.md 8e.
  * One process per GPU: rank 0 calls rnnwf_comm_unique_id and ships the 128 bytes to the other
@@ -268,7 +291,8 @@ int rnnwf_comm_destroy(rnnwf_handle* h);
  * HIP-event timing of the kernels on the handle's stream (bench.py's roofline leg).
  * kernel ids: 0 = base pass (sample / teacher-forced + checkpoints), 1 = flip pass (dominant),
  *             2 = local-energy assembly + moments (rnnwf_renyi2_swap: 0 = base pass + site-term replay,
- *             1 = swap pass, 2 = log-ratio assembly + sums), 3 = back-propagation through time of rnnwf_vmc_gradient,
+ *             1 = swap pass, 2 = log-ratio assembly + sums; rnnwf_correlations: 0 = base pass + both-outcome replay, 1 = trunk +
+ *             branch passes, 2 = log-ratio assembly + sums), 3 = back-propagation through time of rnnwf_vmc_gradient,
  *             4 = its weight-gradient GEMM.  total_ms / launches accumulate since the
  *             last rnnwf_timing_reset.  Stacked layers on the bf16x3 engine: id 1 brackets the whole
  *             pipeline of per-layer kernels as ONE launch.  work[] is the same for every id: work[0] =

@@ -67,6 +67,7 @@ PROTOTYPES = {
     "rnnwf_adam_get_state": (C.c_int, [_P, _F64P, _F64P, _I64, C.POINTER(_I64)]),
     "rnnwf_adam_set_state": (C.c_int, [_P, _F64P, _F64P, _I64, _I64]),
     "rnnwf_renyi2_swap": (C.c_int, [_P, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _I32P]),
+    "rnnwf_correlations": (C.c_int, [_P, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "rnnwf_timing_enable": (C.c_int, [_P, _I32]),
     "rnnwf_timing_reset": (C.c_int, [_P]),
     "rnnwf_timing_get": (C.c_int, [_P, _I32, _F64P, C.POINTER(_I64), _F64P]),
@@ -391,6 +392,33 @@ class NativeWavefunction:
                                                lr.ctypes.data_as(_F64P) if lr is not None else None,
                                                smp.ctypes.data_as(_I32P) if smp is not None else None))
         out = {"sums": sums}
+        if want_log_ratio:
+            out["log_ratio"] = lr
+        if want_samples:
+            out["samples"] = smp if smp is not None else s
+        return out
+
+    # -- correlation functions --------------------------------------------------------------------
+    def correlations(self, ns, samples=None, seed=0, step=0, sample_offset=0, want_log_ratio=False, want_samples=False):
+        """Sums of the diagonal and off-diagonal two-point functions over ns chains (rnnwf_correlations).  samples: (ns, N) int32;
+        None: drawn on the device as sample(ns, seed, step, sample_offset) draws them.  Returns dict(z_sums=(N,), zz_sums=(N, N),
+        x_sums=(N, 2), xx_sums=(N, N, 5), log_ratio=(N + N(N-1)/2, ns)?, samples=(ns, N)?); see include/rnnwf.h for the entries."""
+        ns = int(ns)
+        N = self.N
+        sp = None
+        if samples is not None:
+            s, sp = _i32(samples)
+            if s.ndim < 2 or s.shape[0] != ns or int(np.prod(s.shape[1:])) != N:
+                raise ValueError("samples must have shape (ns, %d) = (%d, %d), got %r" % (N, ns, N, s.shape))
+        z, zz = np.empty(N, dtype=np.float64), np.empty((N, N), dtype=np.float64)
+        x, xx = np.empty((N, 2), dtype=np.float64), np.empty((N, N, 5), dtype=np.float64)
+        lr = np.empty((N + N * (N - 1) // 2, max(ns, 0)), dtype=np.float64) if want_log_ratio else None
+        smp = np.empty((max(ns, 0), N), dtype=np.int32) if want_samples and samples is None else None
+        self._check(self.lib.rnnwf_correlations(self.h, sp, ns, int(seed), int(step), int(sample_offset), z.ctypes.data_as(_F64P),
+                                                zz.ctypes.data_as(_F64P), x.ctypes.data_as(_F64P), xx.ctypes.data_as(_F64P),
+                                                lr.ctypes.data_as(_F64P) if lr is not None else None,
+                                                smp.ctypes.data_as(_I32P) if smp is not None else None))
+        out = {"z_sums": z, "zz_sums": zz, "x_sums": x, "xx_sums": xx}
         if want_log_ratio:
             out["log_ratio"] = lr
         if want_samples:

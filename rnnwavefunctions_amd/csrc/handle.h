@@ -138,6 +138,7 @@ struct rnnwf_handle {
     size_t upbuf_cap = 0, upbuf_off = 0;
     rnnwf::DevBuf reduce_scratch;
     rnnwf::DevBuf renyi;          // rnnwf_renyi2_swap: per-site terms, swap tails, log-ratios and partial sums of one pass (renyi.hip)
+    rnnwf::DevBuf tck, corr;      // rnnwf_correlations: trunk states [N(N-1)/2][nsb][KT][64]; site / trunk / branch terms, log-ratios and sums of one pass (corr.hip)
 
     bool timing_on = false;
     int timing_mask = 31;    // which kernel ids get HIP events (rnnwf_timing_enable: 1 = all, 2 = the dominant pass only)

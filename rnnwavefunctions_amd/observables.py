@@ -5,6 +5,12 @@ For pairs (sigma, tau) drawn independently from |psi|^2,  exp(-S2(l)) = E[r_l],
     r_l = psi(tau_A sigma_B) psi(sigma_A tau_B) / (psi(sigma) psi(tau)).
 Several devices: each draws its own pairs (pair_offset) and the (N + 1, 2) sums add up - all-reduce them with
 NativeWavefunction.allreduce_f64, then call renyi2_from_sums with the global pair count.  docs/renyi.md has the details.
+
+Two-point correlation functions (rnnwf_correlations, docs/correlations.md): with psi = sqrt(P), s = 2 sigma - 1,
+    <sz_i> = E[s_i], <sz_i sz_j> = E[s_i s_j], <sx_i> = E[r_i], <sx_i sx_j> = E[r_ij],
+    r_i = psi(sigma with i flipped) / psi(sigma),  r_ij = psi(sigma with i and j flipped) / psi(sigma).
+Several devices: each draws its own chains (sample_offset), the four sums add up - all-reduce each with
+NativeWavefunction.allreduce_f64, then call correlations_from_sums with the global sample count.
 """
 import warnings
 
@@ -20,7 +26,7 @@ def _native(wf):
     nat = getattr(wf, "_native", None)
     if isinstance(nat, _lib.NativeWavefunction):
         return nat
-    raise TypeError("renyi2_entropy needs a wave-function facade or a NativeWavefunction, got %r" % (wf,))
+    raise TypeError("observables need a wave-function facade or a NativeWavefunction, got %r" % (wf,))
 
 
 def renyi2_from_sums(sums, npairs):
@@ -56,3 +62,72 @@ def renyi2_entropy(wf, numpairs, seed=111, step=0, samples=None):
         samples = np.asarray(samples).reshape(2 * int(numpairs), nat.N)
     out = nat.renyi2_swap(int(numpairs), samples=samples, seed=seed, step=step)
     return renyi2_from_sums(out["sums"], numpairs)
+
+
+def correlations_from_sums(z_sums, zz_sums, x_sums, xx_sums, numsamples):
+    """Means and standard errors from the sums of rnnwf_correlations over numsamples chains.  Returns a dict of
+        z (N,), zz (N, N), x (N,), xx (N, N) (symmetric; diagonals 1), zz_c = zz - z z^T, xx_c = xx - x x^T,
+    and "<name>_err" for each.  Errors of the means: sqrt(var / n) with the population variance (s^2 = 1, so var s = 1 - z^2;
+    var r = mean r^2 - (mean r)^2).  Errors of the connected functions, first order (delta method): zz_c ~ mean of
+    g = s_i s_j - z_j s_i - z_i s_j and xx_c ~ mean of g = r_ij - x_j r_i - x_i r_j, whose variances follow from the cross moments
+    xx_sums carries; on the diagonal 1 - z_i^2 and 1 - x_i^2 with errors 2 |z_i| err z_i, 2 |x_i| err x_i.  Entries whose sums
+    are not finite (a chain with log r > 709) give nan, with a warning."""
+    n = float(numsamples)
+    z_sums, zz_sums = np.asarray(z_sums, dtype=np.float64), np.asarray(zz_sums, dtype=np.float64)
+    x_sums, xx_sums = np.asarray(x_sums, dtype=np.float64), np.asarray(xx_sums, dtype=np.float64)
+    N = z_sums.shape[0] if z_sums.ndim == 1 else -1
+    if N < 1 or zz_sums.shape != (N, N) or x_sums.shape != (N, 2) or xx_sums.shape != (N, N, 5) or n < 1:
+        raise ValueError("sums must have shapes (N,), (N, N), (N, 2), (N, N, 5) and numsamples be >= 1")
+    bad_x = ~np.all(np.isfinite(x_sums), axis=1)
+    bad_xx = ~np.all(np.isfinite(xx_sums), axis=2)
+    if bad_x.any() or bad_xx.any():
+        warnings.warn("correlations: the sums of sites %s and of %d pairs are not finite (a chain with log r > 709); x, xx are nan there"
+                      % (np.flatnonzero(bad_x).tolist(), int(np.triu(bad_xx, 1).sum())), RuntimeWarning, stacklevel=2)
+    x_sums = np.where(bad_x[:, None], np.nan, x_sums)
+    xx_sums = np.where(bad_xx[:, :, None], np.nan, xx_sums)
+    iu = np.triu_indices(N, 1)
+    eye = np.eye(N, dtype=bool)
+
+    def sym(upper, diag):
+        out = np.zeros((N, N))
+        out[iu] = upper[iu]
+        out = out + out.T
+        out[eye] = diag
+        return out
+
+    def root(v):
+        return np.sqrt(np.maximum(v, 0.0) / n)
+
+    z = z_sums / n
+    zz = zz_sums / n
+    x, x2 = x_sums[:, 0] / n, x_sums[:, 1] / n
+    m = xx_sums / n                                        # [r_ij, r_ij^2, r_ij r_i, r_ij r_j, r_i r_j], upper triangle
+    xx = sym(m[:, :, 0], 1.0)
+    out = {"z": z, "z_err": root(1.0 - z * z), "zz": zz, "zz_err": root(1.0 - zz * zz), "x": x, "x_err": root(x2 - x * x),
+           "xx": xx, "xx_err": sym(root(m[:, :, 1] - m[:, :, 0] ** 2), 0.0)}
+    zi, zj = z[:, None], z[None, :]
+    out["zz_c"] = zz - zi * zj
+    # E[g] = zz - 2 z_i z_j,  E[g^2] = 1 - z_i^2 - z_j^2 + 2 z_i z_j zz   (s^2 = 1, s_i s_j s_i = s_j)
+    zz_c_err = root(1.0 - zi * zi - zj * zj + 2.0 * zi * zj * zz - (zz - 2.0 * zi * zj) ** 2)
+    zz_c_err[eye] = 2.0 * np.abs(z) * out["z_err"]
+    out["zz_c_err"] = zz_c_err
+    xi, xj = x[:, None], x[None, :]
+    out["xx_c"] = xx - xi * xj
+    g1 = m[:, :, 0] - 2.0 * xi * xj
+    g2 = (m[:, :, 1] + xj * xj * x2[:, None] + xi * xi * x2[None, :] - 2.0 * xj * m[:, :, 2] - 2.0 * xi * m[:, :, 3]
+          + 2.0 * xi * xj * m[:, :, 4])
+    out["xx_c_err"] = sym(root(g2 - g1 * g1), 2.0 * np.abs(x) * out["x_err"])
+    return out
+
+
+def correlations(wf, numsamples, seed=111, step=0, samples=None):
+    """<sz_i>, <sz_i sz_j>, <sx_i>, <sx_i sx_j> and the connected two-point functions of `wf` (a facade such as
+    TFIM1D.RNNwavefunction / TFIM2D_1DRNN.RNNwavefunction, or a NativeWavefunction) from `numsamples` samples, with standard errors:
+    the dict of correlations_from_sums.  Sites in the model's order (raster order ny * Nx + nx for the 2D raster model).  samples:
+    (numsamples, N) spins; None draws them on the device from (seed, step).  Refused models (parity, complex RNN, 2D RNN, LSTM,
+    stacked layers) raise ValueError with the library's reason."""
+    nat = _native(wf)
+    if samples is not None:
+        samples = np.asarray(samples).reshape(int(numsamples), nat.N)
+    out = nat.correlations(int(numsamples), samples=samples, seed=seed, step=step)
+    return correlations_from_sums(out["z_sums"], out["zz_sums"], out["x_sums"], out["xx_sums"], numsamples)
