@@ -242,6 +242,23 @@ int rnnwf_adam_set_state(rnnwf_handle* h, const double* m_flat, const double* v_
 int rnnwf_renyi2_swap(rnnwf_handle* h, const int32_t* samples, int64_t npairs, uint64_t seed, uint64_t step,
                       int64_t pair_offset, double* sums, double* out_log_ratio, int32_t* out_samples);
 
+/* Second Renyi entropy of arbitrary regions (intervals, blocks, column cuts, disjoint pieces), by the same estimator with
+ * A any site set (docs/renyi_regions.md):  r_A = psi(tau_A sigma_B) psi(sigma_A tau_B) / (psi(sigma) psi(tau)),
+ * exp(-S2(A)) = E[r_A].  r_A = r_complement exactly, so each mask is normalised to site 0 not in A (complemented when
+ * regions[r][0] == 1); a region that is then empty has log r = 0 exactly and costs nothing; otherwise, with f the first site
+ * of A, the mixed chain (the partner's spins on A, the chain's own elsewhere) restarts from the chain's own checkpoint at
+ * f - 1: N - f cell evaluations per chain and region.  Models, passes, fixed-order sums, +inf on log r > 709 and the
+ * resident-batch rule as rnnwf_renyi2_swap.  RNNWF_ERR_INVALID, before any work: a refused model; nregions < 1 (or above
+ * 65535); npairs < 1; null regions or sums; a mask entry other than 0 / 1; pair_offset < 0 with device-drawn samples.
+ *   regions      (nregions, N) int32 of 0 / 1, 1 = site in A; sites in the model's order (raster ny * Nx + nx for GRU1D_F64)
+ *   samples      (2*npairs, N) int32, pair p = rows (2p, 2p+1); nullptr: draw them on the device exactly as
+ *                rnnwf_sample(h, 2*npairs, seed, step, 2*pair_offset, ...) would (pair_offset ignored otherwise)
+ *   sums         (nregions, 2) f64: sum_p r_A, sum_p r_A^2  (additive over shards)
+ *   out_log_ratio(nregions, npairs) f64 or nullptr;  out_samples (2*npairs, N) int32 or nullptr (drawn chains)      */
+int rnnwf_renyi2_regions(rnnwf_handle* h, const int32_t* regions, int32_t nregions, const int32_t* samples, int64_t npairs,
+                         uint64_t seed, uint64_t step, int64_t pair_offset, double* sums, double* out_log_ratio,
+                         int32_t* out_samples);
+
 /* ---- correlation functions -------------------------------------------------------------------------
  * The reference README's "correlation functions" of the positive one-layer GRU models (GRU1D, GRU1D_F64; every other model
  * and stacked layers: RNNWF_ERR_INVALID), psi = sqrt(P), samples sigma ~ P, s = 2 sigma - 1 (docs/correlations.md):
@@ -291,7 +308,7 @@ int rnnwf_comm_destroy(rnnwf_handle* h);
  * HIP-event timing of the kernels on the handle's stream (bench.py's roofline leg).
  * kernel ids: 0 = base pass (sample / teacher-forced + checkpoints), 1 = flip pass (dominant),
  *             2 = local-energy assembly + moments (rnnwf_renyi2_swap: 0 = base pass + site-term replay,
- *             1 = swap pass, 2 = log-ratio assembly + sums; rnnwf_correlations: 0 = base pass + both-outcome replay, 1 = trunk +
+ *             1 = swap pass, 2 = log-ratio assembly + sums, and the same for rnnwf_renyi2_regions; rnnwf_correlations: 0 = base pass + both-outcome replay, 1 = trunk +
  *             branch passes, 2 = log-ratio assembly + sums), 3 = back-propagation through time of rnnwf_vmc_gradient,
  *             4 = its weight-gradient GEMM.  total_ms / launches accumulate since the
  *             last rnnwf_timing_reset.  Stacked layers on the bf16x3 engine: id 1 brackets the whole

@@ -67,6 +67,7 @@ PROTOTYPES = {
     "rnnwf_adam_get_state": (C.c_int, [_P, _F64P, _F64P, _I64, C.POINTER(_I64)]),
     "rnnwf_adam_set_state": (C.c_int, [_P, _F64P, _F64P, _I64, _I64]),
     "rnnwf_renyi2_swap": (C.c_int, [_P, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _I32P]),
+    "rnnwf_renyi2_regions": (C.c_int, [_P, _I32P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _I32P]),
     "rnnwf_correlations": (C.c_int, [_P, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "rnnwf_timing_enable": (C.c_int, [_P, _I32]),
     "rnnwf_timing_reset": (C.c_int, [_P]),
@@ -396,6 +397,39 @@ class NativeWavefunction:
             out["log_ratio"] = lr
         if want_samples:
             out["samples"] = smp if smp is not None else s
+        return out
+
+    def renyi2_regions(self, regions, numpairs, samples=None, seed=111, step=0, pair_offset=0, log_ratio=False):
+        """Swap-trick sums of the second Renyi entropy of arbitrary regions (rnnwf_renyi2_regions).  regions: (R, N) masks of
+        0 / 1 (or one mask of N entries), 1 = site in A, sites in the model's order.  samples: (2 numpairs, N) int32, pair p =
+        rows 2p, 2p + 1; None: drawn on the device as sample(2 numpairs, seed, step, 2 pair_offset) draws them.  Returns
+        dict(sums=(R, 2) [sum r_A, sum r_A^2], samples=(2 numpairs, N) when drawn, log_ratio=(R, numpairs) when asked)."""
+        npairs = int(numpairs)
+        reg = np.asarray(regions)
+        if reg.ndim == 1:
+            reg = reg[None, :]
+        if reg.ndim < 2 or reg.shape[0] < 1 or int(np.prod(reg.shape[1:])) != self.N:
+            raise ValueError("regions must have shape (nregions >= 1, %d), got %r" % (self.N, reg.shape))
+        if not np.all(reg == reg.astype(np.int32)):
+            raise ValueError("regions must hold the integers 0 and 1")
+        reg, rp = _i32(reg.reshape(reg.shape[0], self.N))
+        R = reg.shape[0]
+        sp = None
+        if samples is not None:
+            s, sp = _i32(samples)
+            if s.ndim < 2 or s.shape[0] != 2 * npairs or int(np.prod(s.shape[1:])) != self.N:
+                raise ValueError("samples must have shape (2*numpairs, %d) = (%d, %d), got %r" % (self.N, 2 * npairs, self.N, s.shape))
+        sums = np.empty((R, 2), dtype=np.float64)
+        lr = np.empty((R, max(npairs, 0)), dtype=np.float64) if log_ratio else None
+        smp = np.empty((2 * max(npairs, 0), self.N), dtype=np.int32) if samples is None else None
+        self._check(self.lib.rnnwf_renyi2_regions(self.h, rp, R, sp, npairs, int(seed), int(step), int(pair_offset),
+                                                  sums.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
+                                                  smp.ctypes.data_as(_I32P) if smp is not None else None))
+        out = {"sums": sums}
+        if smp is not None:
+            out["samples"] = smp
+        if log_ratio:
+            out["log_ratio"] = lr
         return out
 
     # -- correlation functions --------------------------------------------------------------------

@@ -113,8 +113,9 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_site_terms_kernel(SwapArgs a)
     }
 }
 
+// (inline, as is renyi_sums_kernel: renyi.hip and renyi_regions.hip both include this header)
 // grid (ceil(npairs / 256), N + 1): thread = pair, blockIdx.y = cut.  log_ratio [N+1][npairs]; part [N+1][gridDim.x][2]
-__global__ void __launch_bounds__(kRenyiThreads) renyi_assemble_kernel(const double* tail, const double* terms, int N, int64_t ns,
+inline __global__ void __launch_bounds__(kRenyiThreads) renyi_assemble_kernel(const double* tail, const double* terms, int N, int64_t ns,
                                                                       double* log_ratio, double* part) {
     __shared__ double r1[kRenyiThreads], r2[kRenyiThreads];
     const int l = blockIdx.y;
@@ -152,7 +153,7 @@ __global__ void __launch_bounds__(kRenyiThreads) renyi_assemble_kernel(const dou
 }
 
 // one block per cut: sums[l] = the partial sums of renyi_assemble_kernel over its blocks, each thread a fixed stride, then a tree
-__global__ void __launch_bounds__(kRenyiThreads) renyi_sums_kernel(const double* part, int64_t nblk, double* sums) {
+inline __global__ void __launch_bounds__(kRenyiThreads) renyi_sums_kernel(const double* part, int64_t nblk, double* sums) {
     __shared__ double r1[kRenyiThreads], r2[kRenyiThreads];
     const int l = blockIdx.x;
     double a = 0.0, b = 0.0;

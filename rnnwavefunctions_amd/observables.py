@@ -6,6 +6,10 @@ For pairs (sigma, tau) drawn independently from |psi|^2,  exp(-S2(l)) = E[r_l],
 Several devices: each draws its own pairs (pair_offset) and the (N + 1, 2) sums add up - all-reduce them with
 NativeWavefunction.allreduce_f64, then call renyi2_from_sums with the global pair count.  docs/renyi.md has the details.
 
+Arbitrary regions (rnnwf_renyi2_regions, docs/renyi_regions.md): renyi2_regions takes site masks - interval_region,
+rectangle_region and column_cut_regions build the usual ones - and renyi2_mutual_information gives
+I2(A : B) = S2(A) + S2(B) - S2(A u B) of two disjoint regions from one set of pairs.
+
 Two-point correlation functions (rnnwf_correlations, docs/correlations.md): with psi = sqrt(P), s = 2 sigma - 1,
     <sz_i> = E[s_i], <sz_i sz_j> = E[s_i s_j], <sx_i> = E[r_i], <sx_i sx_j> = E[r_ij],
     r_i = psi(sigma with i flipped) / psi(sigma),  r_ij = psi(sigma with i and j flipped) / psi(sigma).
@@ -62,6 +66,83 @@ def renyi2_entropy(wf, numpairs, seed=111, step=0, samples=None):
         samples = np.asarray(samples).reshape(2 * int(numpairs), nat.N)
     out = nat.renyi2_swap(int(numpairs), samples=samples, seed=seed, step=step)
     return renyi2_from_sums(out["sums"], numpairs)
+
+
+def interval_region(N, a, b):
+    """(N,) int32 mask of the sites a..b-1 of a chain of N sites (0 <= a <= b <= N)."""
+    N, a, b = int(N), int(a), int(b)
+    if N < 1 or not 0 <= a <= b <= N:
+        raise ValueError("interval_region needs N >= 1 and 0 <= a <= b <= N, got N=%d, a=%d, b=%d" % (N, a, b))
+    m = np.zeros(N, dtype=np.int32)
+    m[a:b] = 1
+    return m
+
+
+def rectangle_region(Nx, Ny, x0, x1, y0, y1):
+    """(Nx Ny,) int32 mask of the sites x0 <= nx < x1, y0 <= ny < y1 of the 2D raster model, site index ny * Nx + nx."""
+    Nx, Ny, x0, x1, y0, y1 = (int(v) for v in (Nx, Ny, x0, x1, y0, y1))
+    if Nx < 1 or Ny < 1 or not (0 <= x0 <= x1 <= Nx and 0 <= y0 <= y1 <= Ny):
+        raise ValueError("rectangle_region needs 0 <= x0 <= x1 <= Nx and 0 <= y0 <= y1 <= Ny, got Nx=%d, Ny=%d, x %d..%d, y %d..%d"
+                         % (Nx, Ny, x0, x1, y0, y1))
+    m = np.zeros((Ny, Nx), dtype=np.int32)
+    m[y0:y1, x0:x1] = 1
+    return m.reshape(Nx * Ny)
+
+
+def column_cut_regions(Nx, Ny):
+    """(Nx - 1, Nx Ny) int32 masks of the vertical cuts of the 2D raster model: row c - 1 = the columns nx < c, c = 1..Nx-1."""
+    Nx, Ny = int(Nx), int(Ny)
+    if Nx < 2 or Ny < 1:
+        raise ValueError("column_cut_regions needs Nx >= 2 and Ny >= 1, got Nx=%d, Ny=%d" % (Nx, Ny))
+    return np.stack([rectangle_region(Nx, Ny, 0, c, 0, Ny) for c in range(1, Nx)])
+
+
+def renyi2_regions(wf, regions, numpairs, seed=111, step=0, samples=None):
+    """Second Renyi entropy S2(A) (R,) and its standard error (R,) of the regions `regions` ((R, N) masks of 0 / 1, or one mask;
+    1 = site in A, sites in the model's order: raster ny * Nx + nx for the 2D raster model) from `numpairs` pairs of independent
+    samples of `wf` (a facade or a NativeWavefunction).  samples: (2 numpairs, N) spins, pair p = rows 2p and 2p + 1; None draws
+    them on the device from (seed, step).  Refused models (parity, complex RNN, 2D RNN, LSTM, stacked layers) raise ValueError
+    with the library's reason."""
+    nat = _native(wf)
+    if samples is not None:
+        samples = np.asarray(samples).reshape(2 * int(numpairs), nat.N)
+    out = nat.renyi2_regions(regions, int(numpairs), samples=samples, seed=seed, step=step)
+    return renyi2_from_sums(out["sums"], numpairs)
+
+
+def mutual_information2_from_log_ratios(lr_a, lr_b, lr_ab):
+    """I2 = S2(A) + S2(B) - S2(A u B) and its standard error from the per-pair log r of A, B and A u B on the SAME n pairs ((n,)
+    each).  With m the means of r: I2 = -log m_A - log m_B + log m_AB; the error by the delta method on the per-pair values
+    g = -r_A / m_A - r_B / m_B + r_AB / m_AB:  err = std(g) / sqrt(n)  (population std; the three estimates share their pairs, so
+    their errors do not add in quadrature)."""
+    ra, rb, rab = (np.exp(np.asarray(v, dtype=np.float64)) for v in (lr_a, lr_b, lr_ab))
+    if ra.ndim != 1 or ra.shape != rb.shape or ra.shape != rab.shape or ra.size < 1:
+        raise ValueError("the three log-ratio arrays must be one-dimensional, of the same length >= 1")
+    ma, mb, mab = ra.mean(), rb.mean(), rab.mean()
+    g = -ra / ma - rb / mb + rab / mab
+    return float(-np.log(ma) - np.log(mb) + np.log(mab)), float(g.std() / np.sqrt(g.size))
+
+
+def _disjoint_masks(region_a, region_b):
+    a, b = np.asarray(region_a), np.asarray(region_b)
+    if a.ndim != 1 or a.shape != b.shape or not np.all((a == 0) | (a == 1)) or not np.all((b == 0) | (b == 1)):
+        raise ValueError("region_a and region_b must be masks of 0 / 1 of the same length")
+    a, b = a.astype(np.int32), b.astype(np.int32)
+    if np.any(a & b):
+        raise ValueError("region_a and region_b must be disjoint; both contain the sites %s" % np.flatnonzero(a & b).tolist())
+    return a, b
+
+
+def renyi2_mutual_information(wf, region_a, region_b, numpairs, seed=111, step=0, samples=None):
+    """Renyi-2 mutual information I2(A : B) = S2(A) + S2(B) - S2(A u B) of two DISJOINT regions (masks of N entries) and its standard
+    error (mutual_information2_from_log_ratios), from `numpairs` pairs; A, B and A u B run in one call on the same pairs.
+    samples, seed, step and the refused models as renyi2_regions."""
+    a, b = _disjoint_masks(region_a, region_b)
+    nat = _native(wf)
+    if samples is not None:
+        samples = np.asarray(samples).reshape(2 * int(numpairs), nat.N)
+    out = nat.renyi2_regions(np.stack([a, b, a | b]), int(numpairs), samples=samples, seed=seed, step=step, log_ratio=True)
+    return mutual_information2_from_log_ratios(*out["log_ratio"])
 
 
 def correlations_from_sums(z_sums, zz_sums, x_sums, xx_sums, numsamples):
