@@ -282,6 +282,39 @@ int rnnwf_correlations(rnnwf_handle* h, const int32_t* samples, int64_t ns, uint
                        int64_t sample_offset, double* z_sums, double* zz_sums, double* x_sums, double* xx_sums,
                        double* out_log_ratio, int32_t* out_samples);
 
+/* ---- Pauli strings and arbitrary spin Hamiltonians ---------------------------------------------------
+ * Expectation values of products of Pauli matrices and the local energy of any real-symmetric spin-1/2 Hamiltonian, for the
+ * positive one-layer GRU models (GRU1D, GRU1D_F64; every other model and stacked layers: RNNWF_ERR_INVALID), psi = sqrt(P),
+ * samples sigma ~ P, s = 2 sigma - 1 (docs/pauli.md).  Term k is O_k = (prod_{i in S_k} sz_i)(prod_{i in F_k} sx_i), sz to the left:
+ *   v_k(sigma) = prod_{i in S_k} s_i(sigma) * exp(1/2 [log P(sigma ^ F_k) - log P(sigma)]),   E[v_k] = <psi|O_k|psi>,
+ *   E_loc(sigma) = sum_k coeff_k v_k(sigma).
+ * (sy = -i sz sx: a string with an even number of sy is +-1 times such a term; rnnwavefunctions_amd.observables.pauli_terms.)
+ * Terms are grouped by flip mask: a mask shared by several terms is evaluated once, a term with empty F_k costs nothing, and order
+ * and duplication of the terms change no per-term bit.  With f the first site of F, the flipped chain restarts from the chain's own
+ * checkpoint at f - 1 (f = 0: from the zero state, all N sites): N - f cell evaluations per chain and distinct mask.  Runs in
+ * passes of whole 16-chain blocks under the state budget (per-sample results do not depend on the pass size); sums are reduced in
+ * a fixed order: a repeated call returns the same bits.  A chain with log r > 709 makes the sums it enters +inf.
+ * A call that ran in ONE pass leaves its batch (spins, checkpoints, E_loc) resident as rnnwf_vmc_step does: rnnwf_vmc_gradient
+ * then differentiates the VMC cost of this Hamiltonian.  A call in several passes leaves no batch; a refused call leaves an
+ * earlier one usable.  RNNWF_ERR_INVALID, before any work: a refused model; nterms < 1; more than 65535 distinct non-empty flip
+ * masks; ns < 1; null flip, sign, coeff or term_sums; a mask entry other than 0 / 1; sample_offset < 0 with device-drawn samples.
+ *   flip, sign   (nterms, N) int32 of 0 / 1: F_k and S_k, indexed by the position p = 0..N-1 along the model's chain (the column of
+ *                `samples`).  The pass attaches no geometry to p.  For GRU1D_F64 created with (nx, ny) rnnwf_tfim2d_eloc places lattice
+ *                site (i, j), 0 <= i < nx, 0 <= j < ny, at p = i * ny + j (j runs fastest), and observables.tfim_hamiltonian does the
+ *                same; "raster ny * Nx + nx" at the other observables names p by the fast and the slow index of the same chain
+ *   coeff        (nterms) f64
+ *   samples      (ns, N) int32; nullptr: draw them on the device exactly as rnnwf_sample(h, ns, seed, step, sample_offset, ...)
+ *                would (seed, step, sample_offset ignored otherwise)
+ *   term_sums    (nterms, 2) f64: sum v_k, sum v_k^2  (required, additive over shards)
+ *   out_eloc     (ns) f64 or nullptr;  moments[4] or nullptr: {sum E_loc, sum E_loc^2, ns, 0} as rnnwf_vmc_step returns them
+ *   out_log_ratio(nmasks, ns) f64 or nullptr: rows = the distinct non-empty flip masks in order of first appearance
+ *   out_samples  (ns, N) int32 or nullptr (drawn chains)
+ * Timing ids: 0 = base pass + site-term replay, 1 = flip-mask pass, 2 = log-ratios, term sums, E_loc and moments.  work[0] +=
+ * sum over distinct masks of N - f per chain.                                                                             */
+int rnnwf_pauli_step(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff, int32_t nterms,
+                     const int32_t* samples, int64_t ns, uint64_t seed, uint64_t step, int64_t sample_offset,
+                     double* term_sums, double* out_eloc, double* moments, double* out_log_ratio, int32_t* out_samples);
+
 /* ---- multi-GPU: one RCCL all-reduce of the energy moments -------------------------------------
  * The reference is single-process; these add the one data-parallel collective of SURVEY.md 8e.
  * One process per GPU: rank 0 calls rnnwf_comm_unique_id and ships the 128 bytes to the other

@@ -212,3 +212,179 @@ def correlations(wf, numsamples, seed=111, step=0, samples=None):
         samples = np.asarray(samples).reshape(int(numsamples), nat.N)
     out = nat.correlations(int(numsamples), samples=samples, seed=seed, step=step)
     return correlations_from_sums(out["z_sums"], out["zz_sums"], out["x_sums"], out["xx_sums"], numsamples)
+
+
+# ---- Pauli strings and arbitrary spin Hamiltonians (rnnwf_pauli_step, docs/pauli.md) ---------------------------------------
+# A string is a product of Pauli matrices, one letter per site: dense "XZIY..." of length N, or sparse [("X", i), ("Z", j), ...].
+# On a site X flips the spin, Z reads its sign s = 2 sigma - 1 and Y = -i Z X does both, so a string is
+#     factor * (prod_{i in S} sz_i)(prod_{i in F} sx_i),   F = sites with X or Y,  S = sites with Z or Y,  factor = (-i)^n_Y
+# (sz to the left on every site; operators of different sites commute).  For even n_Y the factor is real, (-1)^(n_Y / 2); for odd
+# n_Y the string has imaginary matrix elements in the sz basis and expectation exactly 0 in a real state psi = sqrt(P).
+_LETTERS = "IXYZ"
+
+
+def _string_sites(string, N):
+    """{site: letter} of one string, letters I dropped."""
+    if isinstance(string, str):
+        if len(string) != N:
+            raise ValueError("a dense Pauli string needs one letter per site: %d letters for N = %d in %r" % (len(string), N, string))
+        items = list(zip(string, range(N)))
+    else:
+        items = [(p, i) for p, i in string]
+    out = {}
+    for letter, site in items:
+        if not isinstance(letter, str) or len(letter) != 1 or letter.upper() not in _LETTERS:
+            raise ValueError("Pauli letter %r is not one of I, X, Y, Z" % (letter,))
+        if int(site) != site or not 0 <= int(site) < N:
+            raise ValueError("site %r out of range for N = %d" % (site, N))
+        site = int(site)
+        if site in out:
+            raise ValueError("site %d appears twice in the Pauli string %r" % (site, string))
+        if letter.upper() != "I":
+            out[site] = letter.upper()
+    return out
+
+
+def pauli_terms(strings, N):
+    """flip (K, N) int32, sign (K, N) int32 and factor (K,) complex of K Pauli strings on N sites: string k =
+    factor[k] * (prod_{sign[k]} sz)(prod_{flip[k]} sx), factor = (-i)^n_Y (real for even n_Y)."""
+    N = int(N)
+    if N < 1:
+        raise ValueError("N must be >= 1")
+    strings = list(strings)
+    flip = np.zeros((len(strings), N), dtype=np.int32)
+    sign = np.zeros((len(strings), N), dtype=np.int32)
+    factor = np.ones(len(strings), dtype=np.complex128)
+    for k, st in enumerate(strings):
+        ny = 0
+        for site, letter in _string_sites(st, N).items():
+            flip[k, site] = letter in "XY"
+            sign[k, site] = letter in "ZY"
+            ny += letter == "Y"
+        factor[k] = (1.0, -1j, -1.0, 1j)[ny % 4]
+    return flip, sign, factor
+
+
+def group_by_mask(flip):
+    """The distinct non-empty rows of flip (K, N) in order of first appearance and, per term, its row (-1: diagonal term): how
+    rnnwf_pauli_step shares one evaluation of sigma ^ F between the terms with the same flip mask."""
+    flip = np.asarray(flip)
+    seen, masks, index = {}, [], []
+    for row in flip:
+        key = tuple(int(v) for v in row)
+        if not any(key):
+            index.append(-1)
+            continue
+        if key not in seen:
+            seen[key] = len(masks)
+            masks.append(key)
+        index.append(seen[key])
+    return np.array(masks, dtype=np.int32).reshape(len(masks), flip.shape[1]), np.array(index, dtype=np.int32)
+
+
+class Hamiltonian:
+    """H = sum_k c_k P_k, real coefficients c_k and Pauli strings P_k (dense or sparse, see pauli_terms) with an even number of Y:
+    a real-symmetric matrix in the sz basis.  .flip, .sign (K, N) and .coeff (K,) are rnnwf_pauli_step's arguments (coeff carries
+    the strings' factors (-1)^(n_Y / 2))."""
+
+    def __init__(self, N, terms):
+        self.N = int(N)
+        terms = list(terms)
+        if not terms:
+            raise ValueError("a Hamiltonian needs at least one term")
+        coeffs = []
+        for c, _ in terms:
+            if isinstance(c, complex) and c.imag != 0.0:
+                raise ValueError("coefficients must be real, got %r" % (c,))
+            coeffs.append(float(np.real(c)))
+        self.terms = [(c, st) for c, (_, st) in zip(coeffs, terms)]
+        self.flip, self.sign, factor = pauli_terms([st for _, st in terms], self.N)
+        odd = np.flatnonzero(factor.imag != 0.0)
+        if odd.size:
+            raise ValueError("term %d (%r) has an odd number of Y: imaginary matrix elements in the σᶻ basis"
+                             % (int(odd[0]), terms[int(odd[0])][1]))
+        self.coeff = np.asarray(coeffs, dtype=np.float64) * factor.real
+
+    def __len__(self):
+        return len(self.terms)
+
+
+def tfim_hamiltonian(Jz, Bx):
+    """The transverse-field Ising model with open boundaries in the reference's conventions, H = -sum_bonds Jz sz sz - Bx sum sx.
+    Jz of shape (N,): the chain, bond (i, i+1) weighted Jz[i] (Jz[N-1] unused).  Jz of shape (Nx, Ny): the lattice of the 2D raster
+    model, site (i, j) at i * Ny + j, bonds (i, j)-(i+1, j) and (i, j)-(i, j+1) both weighted Jz[i, j]: E_loc of rnnwf_tfim_eloc /
+    rnnwf_tfim2d_eloc."""
+    Jz = np.asarray(Jz, dtype=np.float64)
+    if Jz.ndim == 1:
+        Jz = Jz[None, :]
+    if Jz.ndim != 2 or Jz.size < 1:
+        raise ValueError("Jz must have shape (N,) or (Nx, Ny)")
+    Nx, Ny = Jz.shape
+    terms = []
+    for i in range(Nx):
+        for j in range(Ny):
+            k = i * Ny + j
+            if i + 1 < Nx:
+                terms.append((-Jz[i, j], [("Z", k), ("Z", k + Ny)]))
+            if j + 1 < Ny:
+                terms.append((-Jz[i, j], [("Z", k), ("Z", k + 1)]))
+    terms += [(-float(Bx), [("X", k)]) for k in range(Nx * Ny)]
+    return Hamiltonian(Nx * Ny, terms)
+
+
+def xxz_hamiltonian(N, Jxy, Jz, periodic=False):
+    """H = sum_i [Jxy (sx_i sx_{i+1} + sy_i sy_{i+1}) + Jz sz_i sz_{i+1}] in Pauli matrices on a chain of N sites, open or periodic
+    (N >= 3).  Jxy < 0 is the ferromagnetic XY coupling, whose ground state is positive in the sz basis."""
+    N = int(N)
+    if N < 2 or (periodic and N < 3):
+        raise ValueError("xxz_hamiltonian needs N >= 2 (N >= 3 with periodic boundaries)")
+    terms = []
+    for i in range(N if periodic else N - 1):
+        j = (i + 1) % N
+        terms += [(Jxy, [("X", i), ("X", j)]), (Jxy, [("Y", i), ("Y", j)]), (Jz, [("Z", i), ("Z", j)])]
+    return Hamiltonian(N, terms)
+
+
+def pauli_from_sums(term_sums, numsamples):
+    """Mean and standard error (std / sqrt(n), population variance) per term from rnnwf_pauli_step's (K, 2) sums of v and v^2."""
+    sums = np.asarray(term_sums, dtype=np.float64)
+    n = float(numsamples)
+    mean = sums[:, 0] / n
+    return mean, np.sqrt(np.maximum(sums[:, 1] / n - mean * mean, 0.0) / n)
+
+
+def pauli_expectations(wf, strings, numsamples, seed=111, step=0, samples=None):
+    """<psi|P|psi> of every Pauli string P of `strings` (dense "XZIY..." or sparse [("X", i), ...]) with its standard error, from
+    `numsamples` samples of `wf` (a facade or a NativeWavefunction): {"value": (K,), "err": (K,)}.  Sites in the model's order.  A
+    string with an odd number of Y has expectation exactly 0 in the real state psi = sqrt(P): 0 +- 0, without device work.  samples:
+    (numsamples, N) spins; None draws them on the device from (seed, step).  Refused models (parity, complex RNN, 2D RNN, LSTM,
+    stacked layers) raise ValueError with the library's reason."""
+    nat = _native(wf)
+    flip, sign, factor = pauli_terms(strings, nat.N)
+    value, err = np.zeros(len(factor)), np.zeros(len(factor))
+    real = np.flatnonzero(factor.imag == 0.0)
+    if real.size:
+        if samples is not None:
+            samples = np.asarray(samples).reshape(int(numsamples), nat.N)
+        out = nat.pauli_step(flip[real], sign[real], np.ones(real.size), int(numsamples), samples=samples, seed=seed, step=step)
+        mean, e = pauli_from_sums(out["term_sums"], numsamples)
+        value[real], err[real] = factor.real[real] * mean, e
+    return {"value": value, "err": err}
+
+
+def energy(wf, ham, numsamples, seed=111, step=0, samples=None, want_eloc=False):
+    """Energy of `wf` under the Hamiltonian `ham` from `numsamples` samples: {"mean", "var" (population variance of E_loc), "err"
+    (sqrt(var / n)), "eloc" (numsamples,) when want_eloc}.  samples, seed, step and the refused models as pauli_expectations."""
+    nat = _native(wf)
+    if ham.N != nat.N:
+        raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, nat.N))
+    if samples is not None:
+        samples = np.asarray(samples).reshape(int(numsamples), nat.N)
+    out = nat.pauli_step(ham.flip, ham.sign, ham.coeff, int(numsamples), samples=samples, seed=seed, step=step, want_eloc=want_eloc)
+    m = out["moments"]
+    mean = m[0] / m[2]
+    var = max(m[1] / m[2] - mean * mean, 0.0)
+    res = {"mean": mean, "var": var, "err": float(np.sqrt(var / m[2]))}
+    if want_eloc:
+        res["eloc"] = out["eloc"]
+    return res

@@ -381,3 +381,34 @@ def run_2DTFIM_1DRNN(numsteps=2 * 10 ** 4, systemsize_x=5, systemsize_y=5, Bx=+2
                                   restore)
     run_2DTFIM_1DRNN.last_params = params
     return meanE, varE
+
+
+def minimize_hamiltonian(wf, ham, params, numsteps=1000, numsamples=500, learningrate=5e-3, seed=111, scope="RNNwavefunction",
+                         opt=None, comm=None, verbose=False):
+    """Minimise the energy of `wf` (a NativeWavefunction of a positive one-layer GRU model holding `params`, scoped by `scope`)
+    under `ham` (observables.Hamiltonian: any real-symmetric spin-1/2 Hamiltonian given as Pauli strings) with _train's host
+    optimizer loop: pauli_step (samples, local energies of `ham`, moments; the batch stays resident) -> cost_gradient -> Adam ->
+    set_params.  Returns (meanEnergy, varEnergy), one entry per iteration 0..numsteps like the run_* drivers; the trained
+    parameters are left in minimize_hamiltonian.last_params.  The batch of numsamples must fit one pass of the state budget (the
+    gradient refuses otherwise).  Single process only: no device-resident variant, and a communicator is refused."""
+    if comm is not None:
+        raise ValueError("minimize_hamiltonian runs in one process on one GPU: no communicator (comm=%r)" % (comm,))
+    if ham.N != wf.N:
+        raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, wf.N))
+    opt = opt or Adam()
+    params = {k: np.array(v) for k, v in params.items()}
+    wf.set_params(params, scope=scope)
+    meanEnergy, varEnergy = [], []
+    for it in range(numsteps + 1):
+        s1, s2, n, _ = wf.pauli_step(ham.flip, ham.sign, ham.coeff, numsamples, seed=seed, step=it)["moments"]
+        meanE = s1 / n
+        varE = s2 / n - meanE ** 2
+        meanEnergy.append(meanE)
+        varEnergy.append(varE)
+        if verbose and it % 10 == 0:
+            print("mean(E): {0}, var(E): {1}, #samples {2}, #Step {3} \n\n".format(meanE, varE, numsamples, it))
+        grads = cost_gradient(wf, params, scope, meanE, n)
+        params = opt.step(params, grads, learningrate)
+        wf.set_params(params, scope=scope)
+    minimize_hamiltonian.last_params = params
+    return meanEnergy, varEnergy
