@@ -58,6 +58,32 @@ def lstm_log_probability(params, samples, Nx, Ny, scope="RNNwavefunction"):
     return lp
 
 
+def lstm_site_probs(params, samples, Nx, Ny, scope="RNNwavefunction", dtype=np.float64):
+    """Teacher-forced conditional of spin 0 at every site of (B, Nx * Ny) configurations, (B, N) in the arithmetic `dtype`
+    (float64: the restatement above; float32: the same formulas on parameters rounded to float32 - the yardstick of the
+    sampler check's near-tie band, tests/sampler_reference.py).  p0 = exp(log_softmax(h Wd + bd))[:, 0], as lstm_sample records it."""
+    dt = np.dtype(dtype).type
+    K, b, Wd, bd = (a.astype(dt) for a in _unpack(params, scope))
+    s = np.asarray(samples).reshape(len(samples), -1).astype(np.int64)
+    B, N = s.shape
+    assert N == Nx * Ny
+    H = b.size // 4
+    eye = np.eye(2, dtype=dt)
+    x = np.zeros((B, 2), dtype=dt)
+    c = np.zeros((B, H), dtype=dt)
+    h = np.zeros((B, H), dtype=dt)
+    p0 = np.empty((B, N), dtype=dt)
+    for n in range(N):
+        z = np.concatenate([x, h], axis=1) @ K + b
+        i, j, f, o = z[:, :H], z[:, H:2 * H], z[:, 2 * H:3 * H], z[:, 3 * H:]
+        one = dt(1)
+        c = (one / (one + np.exp(-(f + one)))) * c + (one / (one + np.exp(-i))) * np.tanh(j)
+        h = (one / (one + np.exp(-o))) * np.tanh(c)
+        p0[:, n] = np.exp(_log_softmax(h @ Wd + bd)[:, 0])
+        x = eye[s[:, n]]
+    return p0
+
+
 def lstm_sample(params, Nx, Ny, u, scope="RNNwavefunction"):
     """Ancestral sampling (:35-82) with explicit uniforms u (ns, Nx * Ny) - oracle.philox.uniforms, the stream of the
     native sampler - and tf.multinomial's decision rule (oracle.models.multinomial_2).  Returns (samples int64,
