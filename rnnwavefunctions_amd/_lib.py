@@ -377,17 +377,22 @@ class NativeWavefunction:
             out[k] = self.get_param(nm, v.shape, v.dtype)
         return out
 
+    def _chain_samples(self, samples, rows, rows_name):
+        """(int32 array, pointer) of the caller's samples for an observable pass over `rows` chains, (None, None) for a device draw"""
+        if samples is None:
+            return None, None
+        s, sp = _i32(samples)
+        if s.ndim < 2 or s.shape[0] != rows or int(np.prod(s.shape[1:])) != self.N:
+            raise ValueError("samples must have shape (%s, %d) = (%d, %d), got %r" % (rows_name, self.N, rows, self.N, s.shape))
+        return s, sp
+
     # -- entanglement -----------------------------------------------------------------------------
     def renyi2_swap(self, npairs, samples=None, seed=0, step=0, pair_offset=0, want_log_ratio=False, want_samples=False):
         """Swap-trick sums of the second Renyi entropy for every cut l = 0..N (rnnwf_renyi2_swap).  samples: (2 npairs, N)
         int32, pair p = rows 2p, 2p + 1; None: drawn on the device as sample(2 npairs, seed, step, 2 pair_offset) draws them.
         Returns dict(sums=(N+1, 2) [sum r_l, sum r_l^2], log_ratio=(N+1, npairs)?, samples=(2 npairs, N)?)."""
         npairs = int(npairs)
-        sp = None
-        if samples is not None:
-            s, sp = _i32(samples)
-            if s.ndim < 2 or s.shape[0] != 2 * npairs or int(np.prod(s.shape[1:])) != self.N:
-                raise ValueError("samples must have shape (2*npairs, %d) = (%d, %d), got %r" % (self.N, 2 * npairs, self.N, s.shape))
+        s, sp = self._chain_samples(samples, 2 * npairs, "2*npairs")
         sums = np.empty((self.N + 1, 2), dtype=np.float64)
         lr = np.empty((self.N + 1, max(npairs, 0)), dtype=np.float64) if want_log_ratio else None
         smp = np.empty((2 * max(npairs, 0), self.N), dtype=np.int32) if want_samples and samples is None else None
@@ -416,11 +421,7 @@ class NativeWavefunction:
             raise ValueError("regions must hold the integers 0 and 1")
         reg, rp = _i32(reg.reshape(reg.shape[0], self.N))
         R = reg.shape[0]
-        sp = None
-        if samples is not None:
-            s, sp = _i32(samples)
-            if s.ndim < 2 or s.shape[0] != 2 * npairs or int(np.prod(s.shape[1:])) != self.N:
-                raise ValueError("samples must have shape (2*numpairs, %d) = (%d, %d), got %r" % (self.N, 2 * npairs, self.N, s.shape))
+        s, sp = self._chain_samples(samples, 2 * npairs, "2*numpairs")
         sums = np.empty((R, 2), dtype=np.float64)
         lr = np.empty((R, max(npairs, 0)), dtype=np.float64) if log_ratio else None
         smp = np.empty((2 * max(npairs, 0), self.N), dtype=np.int32) if samples is None else None
@@ -441,11 +442,7 @@ class NativeWavefunction:
         x_sums=(N, 2), xx_sums=(N, N, 5), log_ratio=(N + N(N-1)/2, ns)?, samples=(ns, N)?); see include/rnnwf.h for the entries."""
         ns = int(ns)
         N = self.N
-        sp = None
-        if samples is not None:
-            s, sp = _i32(samples)
-            if s.ndim < 2 or s.shape[0] != ns or int(np.prod(s.shape[1:])) != N:
-                raise ValueError("samples must have shape (ns, %d) = (%d, %d), got %r" % (N, ns, N, s.shape))
+        s, sp = self._chain_samples(samples, ns, "ns")
         z, zz = np.empty(N, dtype=np.float64), np.empty((N, N), dtype=np.float64)
         x, xx = np.empty((N, 2), dtype=np.float64), np.empty((N, N, 5), dtype=np.float64)
         lr = np.empty((N + N * (N - 1) // 2, max(ns, 0)), dtype=np.float64) if want_log_ratio else None
@@ -484,11 +481,7 @@ class NativeWavefunction:
         co, cp = _f64(np.atleast_1d(coeff))
         if co.shape != (K,):
             raise ValueError("coeff must have shape (%d,), got %r" % (K, co.shape))
-        sp = None
-        if samples is not None:
-            s, sp = _i32(samples)
-            if s.ndim < 2 or s.shape[0] != ns or int(np.prod(s.shape[1:])) != N:
-                raise ValueError("samples must have shape (ns, %d) = (%d, %d), got %r" % (N, ns, N, s.shape))
+        s, sp = self._chain_samples(samples, ns, "ns")
         sums = np.empty((K, 2), dtype=np.float64)
         mom = np.zeros(4, dtype=np.float64)
         el = np.empty(max(ns, 0), dtype=np.float64) if want_eloc else None

@@ -46,12 +46,17 @@ def _newest_header():
     return max(os.path.getmtime(h) for h in hs)
 
 
+def compile_flags(src):
+    """The flags one source of SOURCES is compiled with (tools/kernel_resources.sh reads them from here)."""
+    return FLAGS + ([] if src in AGPR_FORM_SOURCES else MFMA_VGPR_FORM) + PER_SOURCE_FLAGS.get(src, [])
+
+
 def _compile(src, extra, objdir=None):
     obj = os.path.join(objdir or OBJDIR, os.path.splitext(src)[0] + ".o")
     path = os.path.join(CSRC, src)
     if os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(path), _newest_header()) and (not extra or objdir):
         return obj, ""
-    cmd = [HIPCC] + FLAGS + ([] if src in AGPR_FORM_SOURCES else MFMA_VGPR_FORM) + PER_SOURCE_FLAGS.get(src, []) + extra + ["-c", path, "-o", obj]
+    cmd = [HIPCC] + compile_flags(src) + extra + ["-c", path, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed for %s:\n%s\n%s" % (src, " ".join(cmd), r.stderr[-6000:]))

@@ -24,19 +24,13 @@
 // Trunk and branch run the base pass's step form (step<true>, bias last) and head on states the base pass or the trunk stored, so
 // what should cancel (zero weights; a branch whose flips do not reach the tail) cancels to rounding of the f64 sums only.
 #pragma once
-#include "gru_core.h"
+#include "chain_kernels.h"
 
 namespace rnnwf {
 
 constexpr int kCorrThreads = 256;
 
-struct CorrArgs {
-    const void* wimg;            // packed weight image (GruLayout)
-    int32_t N;
-    int64_t ns;                  // chains of this pass
-    int64_t nsb;                 // ceil(ns / 16)
-    const uint32_t* bits;        // [ceil(N/32)][ns] packed spins
-    const void* hck;             // [N-1][nsb][KT][64] T: the base pass's checkpoints
+struct CorrArgs : ChainArgs {
     void* tck;                   // [N(N-1)/2][nsb][KT][64] T: trunk states, row pair_index(i, n) = trunk i after site n (n = N-1: unused)
     double* bsel;                // [N][ns]
     double* both;                // [N][ns]
@@ -50,34 +44,28 @@ __host__ __device__ __forceinline__ int64_t pair_index(int i, int n, int N) {
     return (int64_t)i * (2 * N - i - 1) / 2 + (n - i - 1);
 }
 
-__device__ __forceinline__ int corr_spin(const uint32_t* bits, int64_t ns, int64_t s, int n) {
-    return (int)((bits[(int64_t)(n >> 5) * ns + s] >> (n & 31)) & 1);
-}
-
 template <typename T, int NFULL, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) prnn_site_both_kernel(CorrArgs a) {
     using C = GruCore<T, NFULL, 1>;
     constexpr int KT = C::KT;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const char* img = C::stage(lds, a.wimg);
-    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const int64_t gw = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
-    const int64_t nw = (int64_t)gridDim.x * WAVES;
+    const WaveTile<WAVES> w;
     const int N = a.N;
-    for (int64_t sb = gw; sb < a.nsb; sb += nw) {
-        const int64_t s = sb * kChains + c;
+    for (int64_t sb = w.gw; sb < a.nsb; sb += w.nw) {
+        const int64_t s = sb * kChains + w.c;
         const bool valid = s < a.ns;
         const int64_t sc = valid ? s : a.ns - 1;
-        const T* ck = reinterpret_cast<const T*>(a.hck) + (sb * KT) * 64 + lane;      // + n nsb KT 64: hck[n]
+        const T* ck = reinterpret_cast<const T*>(a.hck) + (sb * KT) * 64 + w.lane;      // + n nsb KT 64: hck[n]
         T h[KT];
         auto term = [&](int n) {
             T z[1];
-            C::head(img, h, lane, z);
+            C::head(img, h, w.lane, z);
             T lp0, lp1;
             log_softmax2(z[0], lp0, lp1);
-            const int sig = corr_spin(a.bits, a.ns, sc, n);
+            const int sig = spin_of(a.bits, a.ns, sc, n);
             const double sel = (double)(sig ? lp1 : lp0), oth = (double)(sig ? lp0 : lp1);
-            if (valid && q == 0) {
+            if (valid && w.q == 0) {
                 a.bsel[(int64_t)n * a.ns + s] = sel;
                 a.both[(int64_t)n * a.ns + s] = oth - sel;
             }
@@ -90,7 +78,7 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_site_both_kernel(CorrArgs a) 
         // the last site's state is not checkpointed: one step from hck[N-2] (N = 1: from the zero state)
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) h[kt] = N > 1 ? ck[((int64_t)(N - 2) * a.nsb * KT + kt) * 64] : T(0);
-        C::template step<true>(img, N > 1 ? corr_spin(a.bits, a.ns, sc, N - 2) : -1, h, lane);
+        C::template step<true>(img, N > 1 ? spin_of(a.bits, a.ns, sc, N - 2) : -1, h, w.lane);
         term(N - 1);
     }
 }
@@ -101,38 +89,32 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_trunk_kernel(CorrArgs a) {
     constexpr int KT = C::KT;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const char* img = C::stage(lds, a.wimg);
-    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const int64_t gw = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
-    const int64_t nw = (int64_t)gridDim.x * WAVES;
+    const WaveTile<WAVES> w;
     const int N = a.N;
     // tiles longest chain first (i ascending), every wave strides through them: each wave receives the same mix of lengths
-    for (int64_t tile = gw; tile < a.ntiles; tile += nw) {
+    for (int64_t tile = w.gw; tile < a.ntiles; tile += w.nw) {
         const int i = (int)(tile / a.nsb);
         const int64_t sb = tile - (int64_t)i * a.nsb;
-        const int64_t s = sb * kChains + c;
+        const int64_t s = sb * kChains + w.c;
         const bool valid = s < a.ns;
         const int64_t sc = valid ? s : a.ns - 1;
         T h[KT];
-        {
-            const T* src = reinterpret_cast<const T*>(a.hck) + (((int64_t)i * a.nsb + sb) * KT) * 64 + lane;
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt) h[kt] = src[kt * 64];
-        }
-        int sig_in = 1 - corr_spin(a.bits, a.ns, sc, i);      // the flipped spin feeds site i+1
+        w.load_state(h, a.hck, i, a.nsb, sb, w.lane);
+        int sig_in = 1 - spin_of(a.bits, a.ns, sc, i);      // the flipped spin feeds site i+1
         int64_t p = pair_index(i, i + 1, N);
         for (int n = i + 1; n < N; ++n, ++p) {
-            const int sig = corr_spin(a.bits, a.ns, sc, n);
-            C::template step<true>(img, sig_in, h, lane);
+            const int sig = spin_of(a.bits, a.ns, sc, n);
+            C::template step<true>(img, sig_in, h, w.lane);
             if (n < N - 1) {                                   // no branch starts at the last site
-                T* dst = reinterpret_cast<T*>(a.tck) + ((p * a.nsb + sb) * KT) * 64 + lane;
+                T* dst = reinterpret_cast<T*>(a.tck) + ((p * a.nsb + sb) * KT) * 64 + w.lane;
 #pragma unroll
                 for (int kt = 0; kt < KT; ++kt) dst[kt * 64] = h[kt];
             }
             T z[1];
-            C::head(img, h, lane, z);
+            C::head(img, h, w.lane, z);
             T lp0, lp1;
             log_softmax2(z[0], lp0, lp1);
-            if (valid && q == 0) {
+            if (valid && w.q == 0) {
                 a.tsel[p * a.ns + s] = (double)(sig ? lp1 : lp0);
                 a.toth[p * a.ns + s] = (double)(sig ? lp0 : lp1);
             }
@@ -147,41 +129,26 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_branch_kernel(CorrArgs a) {
     constexpr int KT = C::KT;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const char* img = C::stage(lds, a.wimg);
-    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const int64_t gw = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
-    const int64_t nw = (int64_t)gridDim.x * WAVES;
+    const WaveTile<WAVES> w;
     const int N = a.N;
     // tile = (j (j - 1) / 2 + i) nsb + block, 0 <= i < j <= N-2: longest tail first (j ascending), every wave strides through them
-    for (int64_t tile = gw; tile < a.ntiles; tile += nw) {
+    for (int64_t tile = w.gw; tile < a.ntiles; tile += w.nw) {
         const int64_t m = tile / a.nsb;
         const int64_t sb = tile - m * a.nsb;
         int j = (int)((1.0f + sqrtf(1.0f + 8.0f * (float)m)) * 0.5f);
         while ((int64_t)j * (j - 1) / 2 > m) --j;
         while ((int64_t)(j + 1) * j / 2 <= m) ++j;
         const int i = (int)(m - (int64_t)j * (j - 1) / 2);
-        const int64_t s = sb * kChains + c;
+        const int64_t s = sb * kChains + w.c;
         const bool valid = s < a.ns;
         const int64_t sc = valid ? s : a.ns - 1;
         const int64_t p = pair_index(i, j, N);
         T h[KT];
-        {
-            const T* src = reinterpret_cast<const T*>(a.tck) + ((p * a.nsb + sb) * KT) * 64 + lane;
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt) h[kt] = src[kt * 64];
-        }
-        int sig_in = 1 - corr_spin(a.bits, a.ns, sc, j);      // the second flipped spin feeds site j+1
-        double lp = 0.0;
-        for (int n = j + 1; n < N; ++n) {
-            const int sig = corr_spin(a.bits, a.ns, sc, n);
-            C::template step<true>(img, sig_in, h, lane);
-            T z[1];
-            C::head(img, h, lane, z);
-            T lp0, lp1;
-            log_softmax2(z[0], lp0, lp1);
-            lp += (double)(sig ? lp1 : lp0);
-            sig_in = sig;
-        }
-        if (valid && q == 0) a.tail[p * a.ns + s] = lp;
+        w.load_state(h, a.tck, p, a.nsb, sb, w.lane);
+        // the second flipped spin feeds site j+1
+        const double lp = teacher_forced_tail<C>(img, h, 1 - spin_of(a.bits, a.ns, sc, j), j + 1, N, w.lane,
+                                                 [&](int n) { return spin_of(a.bits, a.ns, sc, n); });
+        if (valid && w.q == 0) a.tail[p * a.ns + s] = lp;
     }
 }
 
@@ -274,8 +241,8 @@ __global__ void __launch_bounds__(kCorrThreads) corr_diag_kernel(const uint32_t*
     if (j < i) return;
     long long cnt = 0;
     for (int64_t s = threadIdx.x; s < ns; s += kCorrThreads) {
-        const int si = corr_spin(bits, ns, s, i);
-        cnt += (i == j) ? si : (si ^ corr_spin(bits, ns, s, j));
+        const int si = spin_of(bits, ns, s, i);
+        cnt += (i == j) ? si : (si ^ spin_of(bits, ns, s, j));
     }
     red[threadIdx.x] = cnt;
     __syncthreads();

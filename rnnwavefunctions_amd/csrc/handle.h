@@ -137,7 +137,7 @@ struct rnnwf_handle {
     void* upbuf = nullptr;   // pinned buffer the weight images travel through on their way to the device (upload(), below)
     size_t upbuf_cap = 0, upbuf_off = 0;
     rnnwf::DevBuf reduce_scratch;
-    rnnwf::DevBuf renyi;          // rnnwf_renyi2_swap: per-site terms, swap tails, log-ratios and partial sums of one pass (renyi.hip)
+    rnnwf::DevBuf renyi;          // rnnwf_renyi2_swap, rnnwf_renyi2_regions, rnnwf_pauli_step: tables, per-site terms, tails, log-ratios and partial sums of one pass
     rnnwf::DevBuf tck, corr;      // rnnwf_correlations: trunk states [N(N-1)/2][nsb][KT][64]; site / trunk / branch terms, log-ratios and sums of one pass (corr.hip)
 
     bool timing_on = false;

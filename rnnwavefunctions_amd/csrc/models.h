@@ -102,7 +102,7 @@ int prnn_split_flip_stream(rnnwf_handle* h, const PrnnArgs& a, int kt16);
 double prnn_split_stream_flops_per_step(rnnwf_handle* h);
 int prnn_split_stream_pack(rnnwf_handle* h, std::vector<char>& simg);
 int prnn_teacher_base(rnnwf_handle* h, int64_t ns, bool reversed, double* out_lp);   // prnn.hip
-// prnn.hip, for the swap pass (renyi.hip): the base pass on the one-wave kernel only; its arguments; checkpoint bytes per 16 chains
+// prnn.hip, for the observable passes (observable.h): the base pass on the one-wave kernel only; its arguments; checkpoint bytes per 16 chains
 int prnn_plain_base(rnnwf_handle* h, const PrnnArgs& a);
 PrnnArgs prnn_base_args(rnnwf_handle* h, int64_t ns);
 size_t prnn_hck_bytes_per_block(rnnwf_handle* h);

@@ -1,6 +1,7 @@
 // pauli.hip - host driver of rnnwf_pauli_step (include/rnnwf.h): expectation values of Pauli strings and the local energy of any
 // real-symmetric spin-1/2 Hamiltonian given as terms (flip mask, sign mask, coefficient), for the positive GRU models (GRU1D,
-// GRU1D_F64, one layer); kernels in pauli_kernels.h, the method in docs/pauli.md.
+// GRU1D_F64, one layer); kernels in pauli_kernels.h and chain_kernels.h (prnn_masked_tail_kernel, not PAIRED), the
+// method in docs/pauli.md; the launch table, refusals, base pass, pass size and pass loop are observable.h's.
 //
 // Per call: the masks are checked and packed into words, the terms grouped by flip mask (a mask shared by several terms is
 // evaluated once) and the distinct masks sorted longest chain first.  Per pass of whole 16-chain blocks (the state budget, as
@@ -13,8 +14,7 @@
 #include <map>
 #include <vector>
 
-#include "gru_kernels.h"
-#include "models.h"
+#include "observable.h"
 #include "pauli_kernels.h"
 
 using namespace rnnwf;
@@ -22,47 +22,6 @@ using namespace rnnwf;
 namespace {
 
 constexpr int kMaxMasks = 65535;         // blockIdx.y of the log-ratio kernel
-
-template <typename T, int NFULL, int WAVES>
-struct PauliLaunch {
-    using L = GruLayout<T, NFULL, 1>;
-    static int terms(rnnwf_handle* h, const SwapArgs& a) {
-        return launch_persistent(h, kTimerBase, prnn_site_terms_kernel<T, NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, a.nsb, WAVES, a);
-    }
-    static int flip(rnnwf_handle* h, const FlipMaskArgs& a) {
-        return launch_persistent(h, kTimerFlip, prnn_flip_mask_kernel<T, NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, a.ntiles, WAVES, a);
-    }
-    static double mfma_flops_per_step() { return (double)L::NT * L::KT * 2048.0; }
-};
-
-// fn(K()) for this handle's launch class K, false (fn not called) for a width without kernels: the rows and waves per workgroup of
-// the region pass (renyi_regions.hip: with_region); no instantiation uses scratch at these (profiles/pauli_kernel_resources.txt)
-template <class Fn>
-bool with_pauli(const rnnwf_handle* h, Fn&& fn) {
-    if (!h->f64) {
-        switch (h->NFULL) {
-            case 1: fn(PauliLaunch<float, 1, 4>()); return true;
-            case 2: fn(PauliLaunch<float, 2, 4>()); return true;
-            case 3: fn(PauliLaunch<float, 3, 4>()); return true;
-            case 4: fn(PauliLaunch<float, 4, 4>()); return true;
-            case 6: fn(PauliLaunch<float, 6, 8>()); return true;
-            case 8: fn(PauliLaunch<float, 8, 4>()); return true;
-            case 12: fn(PauliLaunch<float, 12, 4>()); return true;
-            case 16: fn(PauliLaunch<float, 16, 4>()); return true;
-        }
-        return false;
-    }
-    switch (h->NFULL) {
-        case 1: fn(PauliLaunch<double, 1, 4>()); return true;
-        case 2: fn(PauliLaunch<double, 2, 4>()); return true;
-        case 3: fn(PauliLaunch<double, 3, 4>()); return true;
-        case 4: fn(PauliLaunch<double, 4, 4>()); return true;
-        case 6: fn(PauliLaunch<double, 6, 4>()); return true;
-    }
-    return false;
-}
-
-bool has_kernel(const rnnwf_handle* h) { return with_pauli(h, [](auto) {}); }
 
 // The terms of one call as the kernels read them
 struct Terms {
@@ -74,50 +33,29 @@ struct Terms {
     double steps = 0.0;                  // sum over masks of N - f: cell evaluations per chain
 };
 
-// Scratch of one pass of ns chains in h->renyi, 256-byte aligned pieces; the call's tables lead, at offsets that do not depend on ns
+// Scratch of one pass of ns chains in h->renyi; the call's tables lead, at offsets that do not depend on ns
 struct Scratch {
     size_t mask, order, first, sgn, tmask, coeff, terms, logp, tail, lr, part, sums, bytes;
     int64_t nblk;      // assembly blocks per term
     Scratch(int N, const Terms& g, int64_t ns) {
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        Carve c;
         const size_t M = (size_t)std::max(g.M, 1), K = (size_t)g.K;
         nblk = (ns + kPauliThreads - 1) / kPauliThreads;
-        mask = 0;
-        order = mask + al(M * g.W * 4);
-        first = order + al(M * 4);
-        sgn = first + al(M * 4);
-        tmask = sgn + al(K * g.W * 4);
-        coeff = tmask + al(K * 4);
-        terms = coeff + al(K * 8);
-        logp = terms + al((size_t)N * ns * 8);
-        tail = logp + al((size_t)ns * 8);
-        lr = tail + al(M * ns * 8);
-        part = lr + al(M * ns * 8);
-        sums = part + al(K * nblk * 16);
-        bytes = sums + al(K * 16);
+        mask = c.take(M * g.W * 4);
+        order = c.take(M * 4);
+        first = c.take(M * 4);
+        sgn = c.take(K * g.W * 4);
+        tmask = c.take(K * 4);
+        coeff = c.take(K * 8);
+        terms = c.take((size_t)N * ns * 8);
+        logp = c.take((size_t)ns * 8);
+        tail = c.take(M * ns * 8);
+        lr = c.take(M * ns * 8);
+        part = c.take(K * nblk * 16);
+        sums = c.take(K * 16);
+        bytes = c.bytes;
     }
 };
-
-// chains per pass: whole 16-chain blocks of checkpoints and scratch within the state budget; per block the checkpoints, the terms
-// (N x 16 x 8 bytes), log P (16 x 8), the tails and log-ratios (2 x M x 16 x 8) and E_loc (16 x 8)
-int64_t chains_per_pass(rnnwf_handle* h, int M) {
-    const int N = h->N;
-    const size_t per_block = (size_t)std::max(N - 1, 1) * prnn_hck_bytes_per_block(h) + (size_t)(N + 2 + 2 * M) * kChains * 8;
-    const int64_t blocks = std::max<int64_t>(1, (int64_t)(state_budget_bytes(h, kDefaultStateBudget) / per_block));
-    return blocks * kChains;
-}
-
-int refuse(rnnwf_handle* h) {
-    const char* why = nullptr;
-    switch (h->model) {
-        case RNNWF_MODEL_GRU1D_PARITY: why = "the parity model's symmetrised P is not autoregressive"; break;
-        case RNNWF_MODEL_CRNN_U1: why = "not implemented for the complex RNN"; break;
-        case RNNWF_MODEL_MDRNN2D: why = "not implemented for the 2D RNN (MDRNN)"; break;
-        case RNNWF_MODEL_LSTM1D_F64: why = "not implemented for the LSTM cell"; break;
-        default: if (h->NL > 1) why = "not implemented for stacked layers (one GRU layer only)";
-    }
-    return why ? h->fail(RNNWF_ERR_INVALID, "rnnwf_pauli_step: %s", why) : 0;
-}
 
 // check and pack the (K, N) flip and sign masks, group the terms by flip mask, sort the distinct masks
 int prepare(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, int K, Terms& g) {
@@ -165,47 +103,27 @@ int prepare(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, int K, Te
 // keep: the pass is the whole call, its checkpoints are left for rnnwf_vmc_gradient (diagonal terms alone need no base pass otherwise)
 int pauli_pass(rnnwf_handle* h, int64_t ns, const Terms& g, const Scratch& sc, bool keep, double* sums_host) {
     const int N = h->N, K = g.K, M = g.M;
-    const int64_t nsb = (ns + kChains - 1) / kChains;
-    if (int rc = ensure(h, h->hck, (size_t)std::max(N - 1, 1) * nsb * prnn_hck_bytes_per_block(h))) return rc;
     if (int rc = ensure(h, h->eloc, (size_t)ns * 8)) return rc;
     char* buf = (char*)h->renyi.p;
-    const uint32_t* bits = (const uint32_t*)h->bits.p;
     double* lr = (double*)(buf + sc.lr);
-    if (M > 0 || keep) {
-        PrnnArgs b = prnn_base_args(h, ns);
-        b.bits = (uint32_t*)h->bits.p;
-        b.hck = h->hck.p;
-        b.out_lp = (double*)(buf + sc.logp);
-        if (int rc = prnn_plain_base(h, b)) return rc;
-    }
+    if (M > 0 || keep)
+        if (int rc = observable_base(h, ns, (double*)(buf + sc.logp))) return rc;
+    const ChainArgs c = chain_args(h, ns);
     if (M > 0) {
-        SwapArgs t{};
-        t.wimg = h->wimg.p;
-        t.N = N;
-        t.ns = ns;
-        t.nsb = nsb;
-        t.bits = bits;
-        t.hck = h->hck.p;
+        SwapArgs t{c};
         t.terms = (double*)(buf + sc.terms);
-        FlipMaskArgs a{};
-        a.wimg = h->wimg.p;
-        a.N = N;
-        a.W = g.W;
-        a.ns = ns;
-        a.nsb = nsb;
-        a.bits = bits;
-        a.hck = h->hck.p;
+        MaskArgs a{c};
         a.mask = (const uint32_t*)(buf + sc.mask);
         a.order = (const int32_t*)(buf + sc.order);
         a.first = (const int32_t*)(buf + sc.first);
         a.tail = (double*)(buf + sc.tail);
-        a.ntiles = (int64_t)M * nsb;
+        a.ntiles = (int64_t)M * a.nsb;
         int rc = 0;
-        with_pauli(h, [&](auto k) {
+        with_gru1(h, [&](auto k) {
             using L = decltype(k);
-            if (g.replay) rc = L::terms(h, t);     // N >= 2
-            if (!rc) rc = L::flip(h, a);
-            if (!rc) h->work[1] += (double)nsb * g.steps * L::mfma_flops_per_step();
+            if (g.replay) rc = launch_waves(h, k, kTimerBase, prnn_site_terms_kernel<typename L::T, L::NFULL, L::WAVES>, t.nsb, t);     // N >= 2
+            if (!rc) rc = launch_waves(h, k, kTimerFlip, prnn_masked_tail_kernel<typename L::T, L::NFULL, L::WAVES, false>, a.ntiles, a);
+            if (!rc) h->work[1] += (double)a.nsb * g.steps * L::mfma_flops_per_step();
         });
         if (rc) return rc;
         h->work[0] += (double)ns * g.steps;        // sum over masks of N - f cell evaluations per chain
@@ -217,12 +135,12 @@ int pauli_pass(rnnwf_handle* h, int64_t ns, const Terms& g, const Scratch& sc, b
         TimedLaunch tl(h, kTimerAssembly);
         const uint32_t* sgn = (const uint32_t*)(buf + sc.sgn);
         const int32_t* tmask = (const int32_t*)(buf + sc.tmask);
-        pauli_term_kernel<<<(unsigned)(K * sc.nblk), kPauliThreads, 0, h->stream>>>(bits, sgn, tmask, lr, g.W, ns, sc.nblk,
+        pauli_term_kernel<<<(unsigned)(K * sc.nblk), kPauliThreads, 0, h->stream>>>(c.bits, sgn, tmask, lr, g.W, ns, sc.nblk,
                                                                                    (double*)(buf + sc.part));
         RNNWF_HIP(h, hipGetLastError());
         renyi_sums_kernel<<<(unsigned)K, kPauliThreads, 0, h->stream>>>((const double*)(buf + sc.part), sc.nblk, (double*)(buf + sc.sums));
         RNNWF_HIP(h, hipGetLastError());
-        pauli_eloc_kernel<<<(unsigned)sc.nblk, kPauliThreads, 0, h->stream>>>(bits, sgn, tmask, (const double*)(buf + sc.coeff), lr, K, g.W,
+        pauli_eloc_kernel<<<(unsigned)sc.nblk, kPauliThreads, 0, h->stream>>>(c.bits, sgn, tmask, (const double*)(buf + sc.coeff), lr, K, g.W,
                                                                              ns, (double*)h->eloc.p);
         RNNWF_HIP(h, hipGetLastError());
     }
@@ -237,18 +155,19 @@ extern "C" int rnnwf_pauli_step(rnnwf_handle* h, const int32_t* flip, const int3
                                 double* term_sums, double* out_eloc, double* moments, double* out_log_ratio, int32_t* out_samples) {
     // everything is validated before the resident batch (h->bits, h->hck, h->eloc) is touched: a refused call leaves it usable
     if (!h) return RNNWF_ERR_INVALID;
-    if (int rc = refuse(h)) return rc;
+    if (int rc = observable_refuse(h, "rnnwf_pauli_step")) return rc;
     if (!h->committed) return h->fail(RNNWF_ERR_STATE, "parameters not committed (call rnnwf_commit_params)");
     if (nterms < 1) return h->fail(RNNWF_ERR_INVALID, "rnnwf_pauli_step: nterms must be >= 1");
     if (ns < 1) return h->fail(RNNWF_ERR_INVALID, "rnnwf_pauli_step: ns must be >= 1");
     if (!flip || !sign || !coeff || !term_sums)
         return h->fail(RNNWF_ERR_INVALID, "rnnwf_pauli_step: flip, sign, coeff and term_sums must be non-null");
     if (!samples && sample_offset < 0) return h->fail(RNNWF_ERR_INVALID, "rnnwf_pauli_step: sample_offset must be >= 0");
-    if (!has_kernel(h)) return h->fail(RNNWF_ERR_INVALID, "rnnwf_pauli_step: no flip-mask kernel for NFULL=%d f64=%d", h->NFULL, (int)h->f64);
     Terms g;
     if (int rc = prepare(h, flip, sign, nterms, g)) return rc;
     const int N = h->N, K = nterms, M = g.M;
-    const int64_t chunk = chains_per_pass(h, M);
+    // chains per pass: per block, beside the checkpoints, the terms (N x 16 x 8 bytes), log P (16 x 8), the tails and log-ratios
+    // (2 x M x 16 x 8) and E_loc (16 x 8)
+    const int64_t chunk = blocks_per_pass(h, (size_t)(N + 2 + 2 * M) * kChains * 8) * kChains;
     if ((int64_t)K * ((std::min(chunk, ns) + kPauliThreads - 1) / kPauliThreads) > 0x7fffffffLL)
         return h->fail(RNNWF_ERR_INVALID, "rnnwf_pauli_step: nterms x ceil(ns / %d) exceeds the grid of the term kernel; split the batch", kPauliThreads);
     RNNWF_HIP(h, hipSetDevice(h->cfg.device));
@@ -269,32 +188,24 @@ extern "C" int rnnwf_pauli_step(rnnwf_handle* h, const int32_t* flip, const int3
     }
     h->last_ns = 0;                                   // h->bits, h->hck and h->eloc are overwritten from here on
     h->call_ns = ns;
-    std::vector<double> total((size_t)K * 2, 0.0), pass((size_t)K * 2);
-    double mom[4] = {0.0, 0.0, 0.0, 0.0}, pm[4];
-    for (int64_t s0 = 0; s0 < ns; s0 += chunk) {
-        const int64_t n = std::min(chunk, ns - s0);
-        const Scratch sc(N, g, n);
-        if (int rc = ensure(h, h->bits, (size_t)(N + 31) / 32 * n * 4)) return rc;
-        if (samples) {
-            if (int rc = upload_and_pack(h, samples + s0 * N, n, h->bits, 0, nullptr)) return rc;
-        } else {
-            const Draw d{seed, step, sample_offset + s0};            // rnnwf_sample's draw (its own base-pass kernel)
-            if (int rc = h->family->base(h, n, &d)) return rc;
-            if (out_samples)
-                if (int rc = unpack_and_download(h, h->bits, n, out_samples + s0 * N, nullptr)) return rc;
-        }
-        if (int rc = pauli_pass(h, n, g, sc, ns <= chunk, pass.data())) return rc;
-        if (out_log_ratio && M)
-            RNNWF_HIP(h, hipMemcpy2DAsync(out_log_ratio + s0, (size_t)ns * 8, (char*)h->renyi.p + sc.lr, (size_t)n * 8, (size_t)n * 8,
-                                          (size_t)M, hipMemcpyDeviceToHost, h->stream));
-        if (out_eloc) RNNWF_HIP(h, hipMemcpyAsync(out_eloc + s0, h->eloc.p, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
-        if (moments) {                                               // synchronises the stream
-            if (int rc = run_moments(h, h->eloc.p, n, false, pm)) return rc;
-            for (int k = 0; k < 3; ++k) mom[k] += pm[k];
-        }
-        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-        for (size_t k = 0; k < total.size(); ++k) total[k] += pass[k];
-    }
+    std::vector<double> total((size_t)K * 2, 0.0);
+    double mom[4] = {0.0, 0.0, 0.0, 0.0};
+    const ChainSource src{samples, seed, step, sample_offset, out_samples};
+    if (int rc = for_each_pass(h, src, ns, chunk, 1, total, [&](int64_t s0, int64_t, int64_t n, double* pass_sums) {
+            const Scratch sc(N, g, n);
+            if (int rc = pauli_pass(h, n, g, sc, ns <= chunk, pass_sums)) return rc;
+            if (out_log_ratio && M)
+                RNNWF_HIP(h, hipMemcpy2DAsync(out_log_ratio + s0, (size_t)ns * 8, (char*)h->renyi.p + sc.lr, (size_t)n * 8, (size_t)n * 8,
+                                              (size_t)M, hipMemcpyDeviceToHost, h->stream));
+            if (out_eloc) RNNWF_HIP(h, hipMemcpyAsync(out_eloc + s0, h->eloc.p, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+            if (moments) {                                               // synchronises the stream
+                double pm[4];
+                if (int rc = run_moments(h, h->eloc.p, n, false, pm)) return rc;
+                for (int k = 0; k < 3; ++k) mom[k] += pm[k];
+            }
+            return 0;
+        }))
+        return rc;
     memcpy(term_sums, total.data(), total.size() * 8);
     if (moments) memcpy(moments, mom, sizeof mom);
     // one pass: bits, checkpoints and E_loc of the whole batch are on the device, as rnnwf_vmc_step leaves them

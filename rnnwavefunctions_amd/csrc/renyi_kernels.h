@@ -15,30 +15,20 @@
 //                             head reads hck[n]; the last site takes one step from hck[N-2]).
 //   renyi_assemble_kernel   : log r_l of every pair and cut; per (cut, 256 pairs) the sums of r and r^2.
 //   renyi_sums_kernel       : those partial sums reduced per cut, in a fixed order (no atomics: a repeated call is bit-identical).
-// The swap and replay kernels run the base pass's step form (step<true>, bias last) and head on the states the base pass stored,
+// The arguments, the wave prologue, the site loop and the block reduction are chain_kernels.h's.  The swap and replay kernels run the base pass's step form (step<true>, bias last) and head on the states the base pass stored,
 // and the assembly adds the replayed terms in the swap kernel's order: a chain paired with itself gives d = 0 exactly.
 #pragma once
-#include "gru_core.h"
+#include "chain_kernels.h"
 
 namespace rnnwf {
 
-constexpr int kRenyiThreads = 256;   // pairs per block of the assembly
+constexpr int kRenyiThreads = kSumThreads;   // pairs per block of the assembly
 
-struct SwapArgs {
-    const void* wimg;            // packed weight image (GruLayout)
-    int32_t N;
-    int64_t ns;                  // chains of this pass: 2 x pairs
-    int64_t nsb;                 // ceil(ns / 16)
-    const uint32_t* bits;        // [ceil(N/32)][ns] packed spins
-    const void* hck;             // [N-1][nsb][KT][64] T: the base pass's checkpoints
+struct SwapArgs : ChainArgs {   // ns = 2 x pairs
     double* tail;                // [N-1][ns]: row l-1 = tail_s(l)
     double* terms;               // [N][ns]: row n = log p(sigma_n | sigma_<n) (row 0 not written)
     int64_t ntiles;              // (N-1) * nsb
 };
-
-__device__ __forceinline__ int spin_of(const SwapArgs& a, int64_t s, int n) {
-    return (int)((a.bits[(int64_t)(n >> 5) * a.ns + s] >> (n & 31)) & 1);
-}
 
 template <typename T, int NFULL, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) prnn_swap_kernel(SwapArgs a) {
@@ -46,35 +36,20 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_swap_kernel(SwapArgs a) {
     constexpr int KT = C::KT;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const char* img = C::stage(lds, a.wimg);       // LDS, or the global image where it exceeds LDS (GruLayout::SPILL)
-    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const int64_t gw = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
-    const int64_t nw = (int64_t)gridDim.x * WAVES;
+    const WaveTile<WAVES> w;
     const int N = a.N;
     // tiles longest chain first (i ascending), every wave strides through them: each wave receives the same mix of lengths
-    for (int64_t tile = gw; tile < a.ntiles; tile += nw) {
+    for (int64_t tile = w.gw; tile < a.ntiles; tile += w.nw) {
         const int i = (int)(tile / a.nsb);
         const int64_t sb = tile - (int64_t)i * a.nsb;
-        const int64_t s = sb * kChains + c;
+        const int64_t s = sb * kChains + w.c;
         const int64_t sc = s < a.ns ? s : a.ns - 1;
         T h[KT];
-        {
-            const T* src = reinterpret_cast<const T*>(a.hck) + (((int64_t)i * a.nsb + sb) * KT) * 64 + (lane ^ 1);
-#pragma unroll
-            for (int kt = 0; kt < KT; ++kt) h[kt] = src[kt * 64];
-        }
-        int sig_in = spin_of(a, sc ^ 1, i);        // the partner's spin l-1 feeds site l (ns is even: a valid chain's partner is valid)
-        double lp = 0.0;
-        for (int n = i + 1; n < N; ++n) {
-            const int sig = spin_of(a, sc, n);
-            C::template step<true>(img, sig_in, h, lane);
-            T z[1];
-            C::head(img, h, lane, z);
-            T lp0, lp1;
-            log_softmax2(z[0], lp0, lp1);
-            lp += (double)(sig ? lp1 : lp0);
-            sig_in = sig;
-        }
-        if (s < a.ns && q == 0) a.tail[(int64_t)i * a.ns + s] = lp;
+        w.load_state(h, a.hck, i, a.nsb, sb, w.lane ^ 1);
+        // the partner's spin l-1 feeds site l (ns is even: a valid chain's partner is valid)
+        const double lp = teacher_forced_tail<C>(img, h, spin_of(a.bits, a.ns, sc ^ 1, i), i + 1, N, w.lane,
+                                                 [&](int n) { return spin_of(a.bits, a.ns, sc, n); });
+        if (s < a.ns && w.q == 0) a.tail[(int64_t)i * a.ns + s] = lp;
     }
 }
 
@@ -84,22 +59,20 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_site_terms_kernel(SwapArgs a)
     constexpr int KT = C::KT;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const char* img = C::stage(lds, a.wimg);
-    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-    const int64_t gw = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
-    const int64_t nw = (int64_t)gridDim.x * WAVES;
+    const WaveTile<WAVES> w;
     const int N = a.N;
-    for (int64_t sb = gw; sb < a.nsb; sb += nw) {
-        const int64_t s = sb * kChains + c;
+    for (int64_t sb = w.gw; sb < a.nsb; sb += w.nw) {
+        const int64_t s = sb * kChains + w.c;
         const bool valid = s < a.ns;
         const int64_t sc = valid ? s : a.ns - 1;
-        const T* ck = reinterpret_cast<const T*>(a.hck) + (sb * KT) * 64 + lane;      // + n nsb KT 64: hck[n]
+        const T* ck = reinterpret_cast<const T*>(a.hck) + (sb * KT) * 64 + w.lane;      // + n nsb KT 64: hck[n]
         T h[KT];
         auto term = [&](int n) {
             T z[1];
-            C::head(img, h, lane, z);
+            C::head(img, h, w.lane, z);
             T lp0, lp1;
             log_softmax2(z[0], lp0, lp1);
-            if (valid && q == 0) a.terms[(int64_t)n * a.ns + s] = (double)(spin_of(a, sc, n) ? lp1 : lp0);
+            if (valid && w.q == 0) a.terms[(int64_t)n * a.ns + s] = (double)(spin_of(a.bits, a.ns, sc, n) ? lp1 : lp0);
         };
         for (int n = 1; n < N - 1; ++n) {
 #pragma unroll
@@ -108,7 +81,7 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_site_terms_kernel(SwapArgs a)
         }
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) h[kt] = ck[((int64_t)(N - 2) * a.nsb * KT + kt) * 64];
-        C::template step<true>(img, spin_of(a, sc, N - 2), h, lane);
+        C::template step<true>(img, spin_of(a.bits, a.ns, sc, N - 2), h, w.lane);
         term(N - 1);
     }
 }
@@ -135,16 +108,7 @@ inline __global__ void __launch_bounds__(kRenyiThreads) renyi_assemble_kernel(co
         log_ratio[(int64_t)l * np + p] = lr;
         r = exp(lr);                               // log r > 709: +inf, and so is this cut's sum (docs/renyi.md)
     }
-    r1[threadIdx.x] = r;
-    r2[threadIdx.x] = r * r;
-    __syncthreads();
-    for (int w = kRenyiThreads / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            r1[threadIdx.x] += r1[threadIdx.x + w];
-            r2[threadIdx.x] += r2[threadIdx.x + w];
-        }
-        __syncthreads();
-    }
+    block_sum2(r, r * r, r1, r2);
     if (threadIdx.x == 0) {
         double* o = part + ((int64_t)l * gridDim.x + blockIdx.x) * 2;
         o[0] = r1[0];
@@ -161,16 +125,7 @@ inline __global__ void __launch_bounds__(kRenyiThreads) renyi_sums_kernel(const 
         a += part[((int64_t)l * nblk + k) * 2];
         b += part[((int64_t)l * nblk + k) * 2 + 1];
     }
-    r1[threadIdx.x] = a;
-    r2[threadIdx.x] = b;
-    __syncthreads();
-    for (int w = kRenyiThreads / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-            r1[threadIdx.x] += r1[threadIdx.x + w];
-            r2[threadIdx.x] += r2[threadIdx.x + w];
-        }
-        __syncthreads();
-    }
+    block_sum2(a, b, r1, r2);
     if (threadIdx.x == 0) {
         sums[2 * l] = r1[0];
         sums[2 * l + 1] = r2[0];

@@ -1,15 +1,18 @@
 #!/bin/bash
-# usage: tools/kernel_resources.sh prnn   -> compact VGPR/AGPR/scratch/occupancy table for one TU
+# usage: tools/kernel_resources.sh prnn   -> compact VGPR/AGPR/scratch/occupancy table for one TU, compiled with the flags build.py
+# gives that file (build.compile_flags: no second copy of them here)
 f=${1:-prnn}
-VF="-mllvm -amdgpu-mfma-vgpr-form"; [ "$f" = split_stream ] && VF=""
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -Wno-unused-value -ffp-contract=fast $([ "$f" = split -o "$f" = split_stream ] && echo -fno-slp-vectorize) $VF \
-  -Rpass-analysis=kernel-resource-usage -c rnnwavefunctions_amd/csrc/$f.hip -o /tmp/$f.o 2>&1 |
+cd "$(dirname "$0")/.." || exit 1
+flags=$(python3 -c 'import sys; from rnnwavefunctions_amd import build; print(" ".join(build.compile_flags(sys.argv[1] + ".hip")))' "$f") || exit 1
+out=$(mktemp -d)
+trap 'rm -rf "$out"' EXIT
+${HIPCC:-/opt/rocm/bin/hipcc} $flags --cuda-device-only -Rpass-analysis=kernel-resource-usage -c rnnwavefunctions_amd/csrc/$f.hip -o $out/$f.o 2>&1 |
 python3 -c '
 import sys,re,subprocess
 cur=None; rows=[]
 for line in sys.stdin:
     m=re.search(r"remark: [^:]*:\d+:\d+: +(.*?) \[-Rpass", line) or re.search(r"remark: +(.*?) \[-Rpass", line)
-    if not m: 
+    if not m:
         m2=re.search(r": +(Function Name|Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]|SGPRs|VGPR Spill|SGPR Spill): (.*?) \[", line)
         if not m2: continue
         k,v=m2.group(1),m2.group(2)
