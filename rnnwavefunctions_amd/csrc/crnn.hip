@@ -261,7 +261,7 @@ int pack_image(rnnwf_handle* h, std::vector<char>& img) {
     // > 100 units: f32-input MFMA
     h->engine_split = h->knobs.engine != 1 && (h->NL == 1 ? h->NFULL <= 6 : stack_split_available(h));
     if (h->engine_split && h->NL > 1) {
-        if (int rc = crnn_stack_pack(h)) return rc;
+        if (int rc = stack_pack<3>(h)) return rc;
     } else if (h->engine_split) {
         std::vector<char> simg;
         if (int rc = crnn_split_pack(h, simg)) return rc;

@@ -316,7 +316,7 @@ static __global__ void __launch_bounds__(256) j1j2_enumerate_kernel(J1J2Args a) 
 // One wave: lane l takes the sites l, l + 64, ... (one load each instead of N dependent ones), wave-level prefix sums.
 // totals_host: the same three numbers straight into pinned host memory (read after the caller's stream sync; no copy launch).
 // rec_start (optional; stacked layers on the bf16x3 engine): rec_start[lo] = sum_{l < lo} tiles[l] (N-1-l), the first wave-step record of
-// the tiles of site lo in the layer pipeline's record buffers (split_kernels.h).
+// the tiles of site lo in the layer pipeline's record buffers (pp_kernels.h).
 static __global__ void __launch_bounds__(64) j1j2_tile_scan_kernel(const int32_t* cnt, int N, int32_t* tile_start, int64_t* totals,
                                                                    int64_t* totals_host, int tile_items, int64_t* rec_start = nullptr) {
     const int lane = threadIdx.x;

@@ -103,10 +103,10 @@ __global__ void __launch_bounds__(WAVES * 64, (3 * NF32 + (3 * RJ + 15) / 16) <=
     }
 }
 
-// Ping-pong form (see prnn_flip_pp_kernel in split_kernels.h for the scheme): 8 waves per workgroup, two per SIMD, MFMA
-// segment of one wave beside the VALU segment of the other, K-packed layout MODE 2 (37..50 units).  Tiles come from
-// the device-side table (tile_start[lo] = first 32-item tile of first-changed site lo, longest chains first); the walk
-// is the same snake, so the waves of a workgroup carry the same number of steps within a few.
+// Ping-pong form (see prnn_flip_pp_kernel in split_kernels.h for the scheme, pp_kernels.h for its shared parts): 8 waves per
+// workgroup, two per SIMD, MFMA segment of one wave beside the VALU segment of the other, K-packed layout MODE 2 (37..50 units).
+// Tiles come from the device-side table (tile_start[lo] = first 32-item tile of first-changed site lo, longest chains first); the
+// walk is the same snake, so the waves of a workgroup carry the same number of steps within a few.
 // STACK: first layer of a stack (see prnn_flip_pp_kernel): interleaved checkpoint rows, a record of every step's new state for the
 // layer above (record index: a.rec_start[lo] + (tile - tile_start[lo]) (N - 1 - lo) + step), no heads and no output.
 template <int NF32, int RJ, bool STACK = false>
@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(512) crnn_swap_pp_kernel(CrnnArgs a, const voi
     using PP = SplitPP<NF32, RJ, 3>;
     using C = typename PP::C;
     using L = typename C::L;
-    constexpr int NU = C::NU, NT = C::NT, NB = PP::NB, WAVES = 8;
+    constexpr int NU = C::NU, NT = C::NT, NB = PP::NB;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     __shared__ int max_steps;
     if (threadIdx.x == 0) max_steps = 0;
@@ -122,33 +122,13 @@ __global__ void __launch_bounds__(512) crnn_swap_pp_kernel(CrnnArgs a, const voi
     const int lane = threadIdx.x & 63, c = lane & 31, hh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool late = wave >= 4;
-    const int64_t gw = (int64_t)blockIdx.x * WAVES + wave;
-    const int64_t nw = (int64_t)gridDim.x * WAVES;
     const int N = a.N;
-    const int64_t ntiles = a.tile_start[N];
+    const PPWalk walk(wave, a.tile_start[N]);
     const float* hck = reinterpret_cast<const float*>(a.hck);
-    auto tile_of = [&](int64_t r) -> int64_t { return r * nw + ((r & 1) ? nw - 1 - gw : gw); };
-    auto lo_of = [&](int64_t t) -> int {
-        int l = 0, r = N;
-        while (r - l > 1) {
-            const int mid = (l + r) >> 1;
-            if (a.tile_start[mid] <= t) l = mid; else r = mid;
-        }
-        return l;
-    };
-    {
-        int mine = 0;
-        for (int64_t r = 0; r * nw < ntiles; ++r) {
-            const int64_t t = tile_of(r);
-            if (t < ntiles) mine += N - 1 - lo_of(t);
-        }
-        if (lane == 0) atomicMax(&max_steps, mine);
-        __syncthreads();
-    }
-    const int iters = max_steps;
+    const int iters = walk.lockstep_iters(&max_steps, [&](int64_t t) { return N - 1 - lo_of(a.tile_start, N, t); });
 
-    int64_t round = 0, tile = tile_of(0);
-    bool active = tile < ntiles;
+    int64_t round = 0, tile = walk.tile_of(0);
+    bool active = tile < walk.ntiles;
     int lo = 0, n = 0, sig_in = 0, num_up = 0, s = 0;
     bool valid = false;
     SwapItem it{};
@@ -164,45 +144,29 @@ __global__ void __launch_bounds__(512) crnn_swap_pp_kernel(CrnnArgs a, const voi
     // workgroup): the NEXT tile's item is fetched a whole tile ahead (at the switch into the current one), its checkpoint travels
     // by LDS-DMA (no register destination) into a per-wave staging slot during the current tile's last VALU segment, where the
     // chain's swap base and total are requested too; the switch itself then only reads LDS.
-    constexpr size_t SLOT_BYTES = (size_t)NU * 256;
-    char* slot = lds + ((L::BYTES + 15) / 16) * 16 + (size_t)wave * SLOT_BYTES;
-    typedef __attribute__((address_space(3))) void* LdsVoid;
-    typedef const __attribute__((address_space(1))) void* GlobVoid;
+    const PPSlot<L, NU, L::BYTES> slot(lds, wave, lane);
     int64_t tile_nx = -1, round_nx = 0;
     int lo_nx = 0;
     bool valid_nx = false;
     SwapItem it_nx{};
     auto fetch_item = [&](int64_t t, int& lo_t, bool& valid_t, SwapItem& it_t) {
-        lo_t = lo_of(t);
+        lo_t = lo_of(a.tile_start, N, t);
         const int k = (int)(t - a.tile_start[lo_t]) * 32 + c;
         valid_t = k < a.cnt[lo_t];
         it_t = a.items[(int64_t)lo_t * a.cap + (valid_t ? k : 0)];
     };
     auto peek = [&]() {                                        // the tile after the current one, and its item
         tile_nx = -1;
-        for (int64_t r = round + 1; r * nw < ntiles; ++r) {
-            const int64_t t = tile_of(r);
-            if (t < ntiles) { tile_nx = t; round_nx = r; break; }
-        }
+        walk.next(round, round_nx, tile_nx);                   // leaves tile_nx alone when the walk is over
         if (tile_nx >= 0) fetch_item(tile_nx, lo_nx, valid_nx, it_nx);
     };
-    auto dma_checkpoint = [&](int lo_t, int s_t) {             // entry e of every lane -> slot + 256 e + 4 lane
-        const float* src = hck + (((int64_t)lo_t * a.nsb + (s_t >> 4)) * (STACK ? st.kstride : kt16) + (STACK ? st.koff : 0)) * 64 + (s_t & 15);
-        auto off = [](int u) { return (u >> 2) * 64 + ((u & 3) << 4); };
-#pragma unroll
-        for (int e = 0; e < NU; ++e) {
-            const int u0 = L::unit_of(e, 0), u1 = L::unit_of(e, 1);
-            const int d = off(u1) - off(u0);                   // HP <= 4 kt16: host-checked
-            __builtin_amdgcn_global_load_lds((GlobVoid)(src + (hh ? d : 0) + off(u0)), (LdsVoid)(slot + e * 256), 4, 0, 0);
-        }
+    auto dma_checkpoint = [&](int lo_t, int s_t) {
+        slot.dma_checkpoint(checkpoint_src(hck, lo_t, a.nsb, s_t, STACK ? st.kstride : kt16, STACK ? st.koff : 0));
     };
-    auto wait_vm = [&]() { __builtin_amdgcn_s_waitcnt(0x0F70); asm volatile("" ::: "memory"); };
     // tile, lo, valid, it are set and the tile's checkpoint has landed in the slot
     auto enter_tile = [&]() {
         s = it.s;
-        const float* p = reinterpret_cast<const float*>(slot) + lane;
-#pragma unroll
-        for (int e = 0; e < NU; ++e) h[e] = p[e * 64];
+        slot.read_checkpoint(h);
         if constexpr (STACK) rec = a.rec_start[lo] + (tile - a.tile_start[lo]) * (int64_t)(N - 1 - lo);
         num_up = 0;
         for (int w = 0; w < (lo >> 5); ++w) num_up += __popc(a.bits[(int64_t)w * a.ns + s]);
@@ -217,22 +181,21 @@ __global__ void __launch_bounds__(512) crnn_swap_pp_kernel(CrnnArgs a, const voi
     if (active) {
         fetch_item(tile, lo, valid, it);
         dma_checkpoint(lo, it.s);
-        wait_vm();
+        slot.wait_vm();
         enter_tile();
         peek();
         PP::preload(lds, sig_in, lane, acc);
         PP::split(h, B);
     }
-    if (late) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); }
+    PPNoStamps stamps;
+    pp_begin(late, stamps);
     for (int itn = 0; itn < iters; ++itn) {
         if (active) PP::mfma_seg(lds, B, acc, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        pp_barrier(stamps, kStampMfma, kStampB1);
         if (active) {
             const bool last = n + 1 == N;
             double2 b_pre = make_double2(0.0, 0.0), t_pre = make_double2(0.0, 0.0);
-            if (last) {                                        // requested now, used at the end of the segment
+            if (last) {                                            // requested now, used at the end of the segment
                 if (!STACK && valid && hh == 0) {
                     b_pre = a.cb[(int64_t)lo * a.ns + s];
                     t_pre = a.tot[s];
@@ -277,9 +240,9 @@ __global__ void __launch_bounds__(512) crnn_swap_pp_kernel(CrnnArgs a, const voi
                 active = tile_nx >= 0;
                 if (active) {
                     round = round_nx; tile = tile_nx; lo = lo_nx; valid = valid_nx; it = it_nx;
-                    wait_vm();                                 // the checkpoint has landed
+                    slot.wait_vm();                                // the checkpoint has landed
                     enter_tile();
-                    peek();                                    // the item of the tile after this one: used a whole tile later
+                    peek();                                        // the item of the tile after this one: used a whole tile later
                 }
             } else if ((n & 31) == 0) {
                 word = a.bits[(int64_t)(n >> 5) * a.ns + s];
@@ -289,11 +252,9 @@ __global__ void __launch_bounds__(512) crnn_swap_pp_kernel(CrnnArgs a, const voi
                 PP::split(h, B);
             }
         }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        pp_barrier(stamps, kStampValu, kStampB2);
     }
-    if (!late) __builtin_amdgcn_s_barrier();
+    pp_end(late);
 }
 
 // One GRU layer above the first of the complex RNN's stack (its default: two layers, J1J2/ComplexRNNwavefunction.py:16,40), ping-pong
@@ -304,7 +265,7 @@ __global__ void __launch_bounds__(512) crnn_swap_pp_upper_kernel(CrnnArgs a, con
     using PU = SplitPPUpper<NF32, RJ, 3>;
     using U = typename PU::U;
     using L = typename PU::L;
-    constexpr int NU = PU::NU, NTA = PU::NTA, NB = PU::NB, WAVES = 8, REC = U::RECORD_FLOATS, NG = U::NG;
+    constexpr int NU = PU::NU, NTA = PU::NTA, NB = PU::NB;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     __shared__ int max_steps;
     if (threadIdx.x == 0) max_steps = 0;
@@ -312,34 +273,14 @@ __global__ void __launch_bounds__(512) crnn_swap_pp_upper_kernel(CrnnArgs a, con
     const int lane = threadIdx.x & 63, c = lane & 31, hh = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool late = wave >= 4;
-    const int64_t gw = (int64_t)blockIdx.x * WAVES + wave;
-    const int64_t nw = (int64_t)gridDim.x * WAVES;
     const int N = a.N;
-    const int64_t ntiles = a.tile_start[N];
+    const PPWalk walk(wave, a.tile_start[N]);
     const float* hck = reinterpret_cast<const float*>(a.hck);
-    char* slot = lds + ((U::BYTES + 15) / 16) * 16 + (size_t)wave * U::SLOT_BYTES;
-    auto tile_of = [&](int64_t r) -> int64_t { return r * nw + ((r & 1) ? nw - 1 - gw : gw); };
-    auto lo_of = [&](int64_t t) -> int {
-        int l = 0, r = N;
-        while (r - l > 1) {
-            const int mid = (l + r) >> 1;
-            if (a.tile_start[mid] <= t) l = mid; else r = mid;
-        }
-        return l;
-    };
-    {
-        int mine = 0;
-        for (int64_t r = 0; r * nw < ntiles; ++r) {
-            const int64_t t = tile_of(r);
-            if (t < ntiles) mine += N - 1 - lo_of(t);
-        }
-        if (lane == 0) atomicMax(&max_steps, mine);
-        __syncthreads();
-    }
-    const int iters = max_steps;
+    const PPSlot<L, NU, U::BYTES> slot(lds, wave, lane);
+    const int iters = walk.lockstep_iters(&max_steps, [&](int64_t t) { return N - 1 - lo_of(a.tile_start, N, t); });
 
-    int64_t round = 0, tile = tile_of(0), rec = 0;
-    bool active = tile < ntiles;
+    int64_t round = 0, tile = walk.tile_of(0), rec = 0;
+    bool active = tile < walk.ntiles;
     int lo = 0, n = 0, sig_in = 0, num_up = 0, s = 0;
     bool valid = false;
     SwapItem it{};
@@ -348,28 +289,6 @@ __global__ void __launch_bounds__(512) crnn_swap_pp_upper_kernel(CrnnArgs a, con
     float h[NU];
     u32x4 BX[NB], BH[NB];
     f32x16 acc[NTA];
-    typedef __attribute__((address_space(3))) void* LdsVoid;
-    typedef const __attribute__((address_space(1))) void* GlobVoid;
-    auto dma_record = [&](int64_t r) {
-        const float* base = st.xin + r * (int64_t)REC;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) __builtin_amdgcn_global_load_lds((GlobVoid)(base + g * 256 + lane * 4), (LdsVoid)(slot + g * 1024), 16, 0, RNNWF_RECORD_AUX);
-#pragma unroll
-        for (int t = 0; t < U::NTAIL; ++t)
-            __builtin_amdgcn_global_load_lds((GlobVoid)(base + NG * 256 + t * 64 + lane), (LdsVoid)(slot + NG * 1024 + t * 256), 4, 0, 0);
-    };
-    auto read_record = [&](float (&x)[NU]) {
-        const float4* p = reinterpret_cast<const float4*>(slot) + lane;
-#pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            const float4 v = p[g * 64];
-            x[4 * g] = v.x; x[4 * g + 1] = v.y; x[4 * g + 2] = v.z; x[4 * g + 3] = v.w;
-        }
-#pragma unroll
-        for (int t = 0; t < U::NTAIL; ++t) x[4 * NG + t] = reinterpret_cast<const float*>(slot + NG * 1024)[t * 64 + lane];
-    };
-    auto wait_vm = [&]() { __builtin_amdgcn_s_waitcnt(0x0F70); asm volatile("" ::: "memory"); };
-    auto wait_lds = [&]() { __builtin_amdgcn_s_waitcnt(0xC07F); asm volatile("" ::: "memory"); };
     // Tile switch as in crnn_swap_pp_kernel: the next tile's item is fetched a tile ahead, its checkpoint travels by LDS-DMA into the
     // staging slot during the current tile's last VALU segment (the slot is free there: a chain's last step requests no record);
     // at the switch the checkpoint is read out of LDS and the new tile's first record is requested - the one latency that shows.
@@ -378,40 +297,24 @@ __global__ void __launch_bounds__(512) crnn_swap_pp_upper_kernel(CrnnArgs a, con
     bool valid_nx = false;
     SwapItem it_nx{};
     auto fetch_item = [&](int64_t t, int& lo_t, bool& valid_t, SwapItem& it_t) {
-        lo_t = lo_of(t);
+        lo_t = lo_of(a.tile_start, N, t);
         const int k = (int)(t - a.tile_start[lo_t]) * 32 + c;
         valid_t = k < a.cnt[lo_t];
         it_t = a.items[(int64_t)lo_t * a.cap + (valid_t ? k : 0)];
     };
     auto peek = [&]() {
         tile_nx = -1;
-        for (int64_t r = round + 1; r * nw < ntiles; ++r) {
-            const int64_t t = tile_of(r);
-            if (t < ntiles) { tile_nx = t; round_nx = r; break; }
-        }
+        walk.next(round, round_nx, tile_nx);
         if (tile_nx >= 0) fetch_item(tile_nx, lo_nx, valid_nx, it_nx);
     };
-    auto dma_checkpoint = [&](int lo_t, int s_t) {             // entry e of every lane -> slot + 256 e + 4 lane
-        const float* src = hck + (((int64_t)lo_t * a.nsb + (s_t >> 4)) * st.kstride + st.koff) * 64 + (s_t & 15);
-        auto off = [](int u) { return (u >> 2) * 64 + ((u & 3) << 4); };
-#pragma unroll
-        for (int e = 0; e < NU; ++e) {
-            const int u0 = L::unit_of(e, 0), u1 = L::unit_of(e, 1);
-            const int d = off(u1) - off(u0);
-            __builtin_amdgcn_global_load_lds((GlobVoid)(src + (hh ? d : 0) + off(u0)), (LdsVoid)(slot + e * 256), 4, 0, 0);
-        }
-    };
+    auto dma_checkpoint = [&](int lo_t, int s_t) { slot.dma_checkpoint(checkpoint_src(hck, lo_t, a.nsb, s_t, st.kstride, st.koff)); };
     // tile, lo, valid, it are set and the tile's checkpoint has landed in the slot
     auto begin_tile = [&]() {
         s = it.s;
-        {
-            const float* p = reinterpret_cast<const float*>(slot) + lane;
-#pragma unroll
-            for (int e = 0; e < NU; ++e) h[e] = p[e * 64];
-        }
-        wait_lds();
+        slot.read_checkpoint(h);
+        slot.wait_lds();
         rec = a.rec_start[lo] + (tile - a.tile_start[lo]) * (int64_t)(N - 1 - lo);
-        dma_record(rec);
+        slot.dma_record(st.xin, rec);
         n = lo + 1;
         if constexpr (LAST) {
             num_up = 0;
@@ -424,37 +327,26 @@ __global__ void __launch_bounds__(512) crnn_swap_pp_upper_kernel(CrnnArgs a, con
             re = 0.0; im = 0.0;
         }
     };
-    auto load_quads = [&](bool fresh) {                       // BH <- h, BX <- the record in flight
-        PU::split(h, BH);
-        // behind the record's transfer only this segment's NG record stores may still be on their way (a fresh tile: wait for all)
-        if (LAST || fresh) __builtin_amdgcn_s_waitcnt(0x0F70);
-        else __builtin_amdgcn_s_waitcnt(0x0F70 | (NG + U::NTAIL));
-        asm volatile("" ::: "memory");
-        read_record(h);
-        PU::split(h, BX);
-        wait_lds();
-    };
     if (active) {
         fetch_item(tile, lo, valid, it);
         dma_checkpoint(lo, it.s);
-        wait_vm();
+        slot.wait_vm();
         begin_tile();
         peek();
-        load_quads(true);
+        slot.template load_quads<PU, LAST>(true, h, BH, BX);
     }
-    if (late) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); }
+    PPNoStamps stamps;
+    pp_begin(late, stamps);
     for (int itn = 0; itn < iters; ++itn) {
         if (active) PU::mfma_seg(lds, BX, BH, acc, lane);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        pp_barrier(stamps, kStampMfma, kStampB1);
         if (active) {
             const bool last = n + 1 == N;
             double2 b_pre = make_double2(0.0, 0.0), t_pre = make_double2(0.0, 0.0);
             if (!last) {
-                dma_record(rec + 1);
+                slot.dma_record(st.xin, rec + 1);
             } else {
-                if (LAST && valid && hh == 0) {                // the chain's swap base and total: requested now, used at the segment's end
+                if (LAST && valid && hh == 0) {                    // the chain's swap base and total: requested now, used at the segment's end
                     b_pre = a.cb[(int64_t)lo * a.ns + s];
                     t_pre = a.tot[s];
                 }
@@ -499,20 +391,18 @@ __global__ void __launch_bounds__(512) crnn_swap_pp_upper_kernel(CrnnArgs a, con
                 active = tile_nx >= 0;
                 if (active) {
                     round = round_nx; tile = tile_nx; lo = lo_nx; valid = valid_nx; it = it_nx;
-                    wait_vm();                                 // the checkpoint has landed (and this chain's stores have gone)
+                    slot.wait_vm();                                // the checkpoint has landed (and this chain's stores have gone)
                     begin_tile();
                     peek();
                 }
             } else if constexpr (LAST) {
                 if ((n & 31) == 0) word = a.bits[(int64_t)(n >> 5) * a.ns + s];
             }
-            if (active) load_quads(last);
+            if (active) slot.template load_quads<PU, LAST>(last, h, BH, BX);
         }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        pp_barrier(stamps, kStampValu, kStampB2);
     }
-    if (!late) __builtin_amdgcn_s_barrier();
+    pp_end(late);
 }
 
 }  // namespace rnnwf

@@ -283,13 +283,19 @@ inline int persistent_grid(rnnwf_handle* h, Kern kern, int threads, size_t lds, 
     return 0;
 }
 
-// kern<<<grid, threads, lds, h->stream>>>(args...) inside the bracket of timer `id`
+// kern<<<grid, threads, lds, h->stream>>>(args...), for a caller that holds the timer bracket itself (a pipeline of kernels under one)
 template <typename Kern, typename... Args>
-inline int timed_launch(rnnwf_handle* h, TimerId id, Kern kern, dim3 grid, int threads, size_t lds, const Args&... args) {
-    TimedLaunch tl(h, id);
+inline int plain_launch(rnnwf_handle* h, Kern kern, dim3 grid, int threads, size_t lds, const Args&... args) {
     kern<<<grid, threads, lds, h->stream>>>(args...);
     RNNWF_HIP(h, hipGetLastError());
     return 0;
+}
+
+// the same inside the bracket of timer `id`
+template <typename Kern, typename... Args>
+inline int timed_launch(rnnwf_handle* h, TimerId id, Kern kern, dim3 grid, int threads, size_t lds, const Args&... args) {
+    TimedLaunch tl(h, id);
+    return plain_launch(h, kern, grid, threads, lds, args...);
 }
 
 // persistent_grid + timed_launch

@@ -309,7 +309,7 @@ int pack_image(rnnwf_handle* h, std::vector<char>& img) {
     h->engine_split = !h->f64 && h->knobs.engine != 1 && (h->NL == 1 ? h->NFULL <= 6 : stack_split_available(h));     // above 100 units: f32-input MFMA, image through L2
     h->engine_forced = h->knobs.engine >= 2;
     if (h->engine_split && h->NL > 1) {
-        if (int rc = prnn_stack_pack(h)) return rc;
+        if (int rc = stack_pack<1>(h)) return rc;
     } else if (h->engine_split) {
         std::vector<char> simg;
         if (int rc = prnn_split_pack(h, simg)) return rc;

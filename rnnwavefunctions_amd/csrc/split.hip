@@ -17,6 +17,41 @@ using namespace rnnwf;
 
 namespace {
 
+#ifdef RNNWF_DIAGNOSTICS
+// In-kernel cycle stamps (tools/stamps.py, tools/stamps_base.py): launch(buffer) runs the kernel with a zeroed buffer of `words` counters
+// for each of `waves` waves, outside the timers; st <- the buffer.
+template <class Launch>
+int read_stamps(rnnwf_handle* h, Launch&& launch, size_t waves, int words, std::vector<unsigned long long>& st) {
+    unsigned long long* dev = nullptr;
+    const size_t bytes = waves * words * sizeof(unsigned long long);
+    RNNWF_HIP(h, hipMalloc((void**)&dev, bytes));
+    RNNWF_HIP(h, hipMemsetAsync(dev, 0, bytes, h->stream));
+    launch(dev);
+    RNNWF_HIP(h, hipStreamSynchronize(h->stream));
+    st.resize(waves * words);
+    RNNWF_HIP(h, hipMemcpy(st.data(), dev, bytes, hipMemcpyDeviceToHost));
+    RNNWF_HIP(h, hipFree(dev));
+    return 0;
+}
+// the same, then one stderr line: counter k's median, minimum and maximum over the waves under names[k]
+template <class Launch>
+int read_stamps(rnnwf_handle* h, Launch&& launch, size_t waves, int words, const char* label, unsigned grid, std::initializer_list<const char*> names) {
+    std::vector<unsigned long long> st;
+    if (int rc = read_stamps(h, launch, waves, words, st)) return rc;
+    fprintf(stderr, "%s grid=%u waves=%zu:", label, grid, waves);
+    int k = 0;
+    for (const char* name : names) {
+        std::vector<unsigned long long> v(waves);
+        for (size_t w = 0; w < waves; ++w) v[w] = st[w * words + k];
+        std::sort(v.begin(), v.end());
+        fprintf(stderr, " %s med %llu min %llu max %llu;", name, v[waves / 2], v[0], v[waves - 1]);
+        ++k;
+    }
+    fprintf(stderr, "\n");
+    return 0;
+}
+#endif
+
 // ---- bf16x3 engine for the flip pass (f32 models; above 68 units: split_stream.hip) ----------------------
 template <int NF32, int RJ, int WAVES, int MODE>
 struct SLaunch {
@@ -36,27 +71,11 @@ struct SLaunch {
             unsigned grid = 0;
             if (int rc = persistent_grid(h, kern, 512, L::BYTES, ntiles, 8, &grid)) return rc;
 #ifdef RNNWF_DIAGNOSTICS
-            if (getenv("RNNWF_STAMPS")) {     // in-kernel cycle stamps, median over waves -> stderr (tools/stamps.py)
-                PrnnArgs b = a;
-                const size_t nwv = (size_t)grid * 8;
-                RNNWF_HIP(h, hipMalloc((void**)&b.stamps, nwv * 128));
-                RNNWF_HIP(h, hipMemsetAsync(b.stamps, 0, nwv * 128, h->stream));
-                kern<<<grid, 512, L::BYTES, h->stream>>>(b, h->wsplit.p, kt16, StackArgs{});
-                RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-                std::vector<unsigned long long> st(nwv * 16);
-                RNNWF_HIP(h, hipMemcpy(st.data(), b.stamps, nwv * 128, hipMemcpyDeviceToHost));
-                RNNWF_HIP(h, hipFree(b.stamps));
-                const char* names[10] = {"mfma_seg", "barrier_after_mfma", "valu_seg_split_part", "barrier_after_valu", "tile_switch", "total_cycles",
-                                         "realtime_ticks_100MHz", "iterations", "valu_seg_gates", "valu_seg_head_logsoftmax"};
-                fprintf(stderr, "RNNWF_STAMPS grid=%u waves=%zu:", grid, nwv);
-                for (int k = 0; k < 10; ++k) {
-                    std::vector<unsigned long long> v(nwv);
-                    for (size_t w = 0; w < nwv; ++w) v[w] = st[w * 16 + k];
-                    std::sort(v.begin(), v.end());
-                    fprintf(stderr, " %s med %llu min %llu max %llu;", names[k], v[nwv / 2], v[0], v[nwv - 1]);
-                }
-                fprintf(stderr, "\n");
-                return 0;
+            if (getenv("RNNWF_STAMPS")) {
+                return read_stamps(h, [&](unsigned long long* buf) { PrnnArgs b = a; b.stamps = buf; kern<<<grid, 512, L::BYTES, h->stream>>>(b, h->wsplit.p, kt16, StackArgs{}); },
+                                   (size_t)grid * 8, 16, "RNNWF_STAMPS", grid,
+                                   {"mfma_seg", "barrier_after_mfma", "valu_seg_split_part", "barrier_after_valu", "tile_switch", "total_cycles",
+                                    "realtime_ticks_100MHz", "iterations", "valu_seg_gates", "valu_seg_head_logsoftmax"});
             }
 #endif
             return timed_launch(h, kTimerFlip, kern, grid, 512, L::BYTES, a, h->wsplit.p, kt16, StackArgs{});
@@ -138,16 +157,10 @@ struct BfBase {
         if (int rc = persistent_grid(h, kern, threads, lds, a.nsb, 1, &grid)) return rc;
 #ifdef RNNWF_DIAGNOSTICS
         if constexpr (std::is_same<Args, PrnnArgs>::value) {
-            if (getenv("RNNWF_STAMPS_BASE")) {    // in-kernel cycle stamps, median over the waves of each role -> stderr (tools/stamps_base.py)
-                Args b = a;
+            if (getenv("RNNWF_STAMPS_BASE")) {    // median over the waves of each role -> stderr (tools/stamps_base.py)
                 const size_t nwv = (size_t)grid * B::NB * (B::NW + 1);
-                RNNWF_HIP(h, hipMalloc((void**)&b.stamps, nwv * 64));
-                RNNWF_HIP(h, hipMemsetAsync(b.stamps, 0, nwv * 64, h->stream));
-                kern<<<grid, threads, lds, h->stream>>>(b);
-                RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-                std::vector<unsigned long long> st(nwv * 8);
-                RNNWF_HIP(h, hipMemcpy(st.data(), b.stamps, nwv * 64, hipMemcpyDeviceToHost));
-                RNNWF_HIP(h, hipFree(b.stamps));
+                std::vector<unsigned long long> st;
+                if (int rc = read_stamps(h, [&](unsigned long long* buf) { Args b = a; b.stamps = buf; kern<<<grid, threads, lds, h->stream>>>(b); }, nwv, 8, st)) return rc;
                 const char* names[7] = {"products", "wait_barrier_B", "gates_writes", "wait_barrier_A", "site", "total_cycles", "realtime_100MHz"};
                 for (int role = 0; role < 3; ++role) {
                     fprintf(stderr, "RNNWF_STAMPS_BASE grid=%u %s waves:", grid, role == 2 ? "sampler" : role ? "remainder" : "gate");
@@ -235,113 +248,76 @@ double rnnwf::stack_split_flops_per_step(rnnwf_handle* h) {
     return ((double)StackL0::NT * StackL0::KS + (double)(h->NL - 1) * 2.0 * StackU1::NTB * StackL0::KS) * 32768.0;
 }
 
-int rnnwf::prnn_stack_pack(rnnwf_handle* h) {
+template <int NOUT>
+int rnnwf::stack_pack(rnnwf_handle* h) {
     {
-        const std::vector<char> img = pack_split_image<kStackNF32, kStackRJ, 1, 2>(h);
+        const std::vector<char> img = pack_split_image<kStackNF32, kStackRJ, NOUT, 2>(h);
         if (int rc = ensure(h, h->wsplit, img.size())) return rc;
         if (int rc = upload(h, h->wsplit.p, img.data(), img.size())) return rc;
     }
     for (int l = 1; l < h->NL; ++l) {
-        const std::vector<char> img = pack_split_upper_image<kStackNF32, kStackRJ, 1>(h, l, l == h->NL - 1);
+        const std::vector<char> img = pack_split_upper_image<kStackNF32, kStackRJ, NOUT>(h, l, l == h->NL - 1);
         if (int rc = ensure(h, h->wsplit_up[l - 1], img.size())) return rc;
         if (int rc = upload(h, h->wsplit_up[l - 1].p, img.data(), img.size())) return rc;
     }
     return 0;
 }
+template int rnnwf::stack_pack<1>(rnnwf_handle*);
+template int rnnwf::stack_pack<3>(rnnwf_handle*);
 
-int rnnwf::prnn_stack_flip(rnnwf_handle* h, const PrnnArgs& a) {
+namespace {
+// The layer pipeline over `tiles` 32-chain tiles: first (the first layer's kernel, STACK form), then one upper kernel per further layer -
+// middle below the top, last at the top - each reading the records (h->xrec, record_bytes each, two buffers alternating) the one below
+// wrote.  The whole pipeline is the "flip pass" of the timers.
+template <class Args, class K0, class KU>
+int stack_pipeline(rnnwf_handle* h, const Args& a, K0 first, KU middle, KU last, size_t lds_first, size_t lds_upper, int64_t tiles, size_t record_bytes) {
     const int kt16 = 4 * h->NFULL + 1, NL = h->NL;
     if (StackL0::HP > 4 * kt16) return h->fail(RNNWF_ERR_INVALID, "bf16x3 layout wider than the checkpoint rows (%d > %d)", StackL0::HP, 4 * kt16);
-    const int64_t nsb32 = (a.ns + 31) / 32;
-    const int64_t ntiles = (int64_t)(a.N - 1) * nsb32;
-    const int64_t nrec = nsb32 * (int64_t)a.N * (a.N - 1) / 2;
-    const size_t bytes = (size_t)nrec * StackU1::RECORD_FLOATS * 4;
-    if (int rc = ensure(h, h->xrec[0], bytes)) return rc;
-    if (NL > 2) if (int rc = ensure(h, h->xrec[1], bytes)) return rc;
+    if (int rc = ensure(h, h->xrec[0], record_bytes)) return rc;
+    if (NL > 2) if (int rc = ensure(h, h->xrec[1], record_bytes)) return rc;
     unsigned g0 = 0, gu = 0, gl = 0;
-    if (int rc = persistent_grid(h, prnn_flip_pp_kernel<kStackNF32, kStackRJ, true>, 512, StackL0::BYTES, ntiles, 8, &g0)) return rc;
-    if (int rc = persistent_grid(h, prnn_flip_pp_upper_kernel<kStackNF32, kStackRJ, false>, 512, StackU1::LDS_BYTES, ntiles, 8, &gu)) return rc;
-    if (int rc = persistent_grid(h, prnn_flip_pp_upper_kernel<kStackNF32, kStackRJ, true>, 512, StackU1::LDS_BYTES, ntiles, 8, &gl)) return rc;
-    TimedLaunch tl(h, kTimerFlip);                                    // the whole pipeline is the "flip pass" of the timers
+    if (int rc = persistent_grid(h, first, 512, lds_first, tiles, 8, &g0)) return rc;
+    if (int rc = persistent_grid(h, middle, 512, lds_upper, tiles, 8, &gu)) return rc;
+    if (int rc = persistent_grid(h, last, 512, lds_upper, tiles, 8, &gl)) return rc;
+    TimedLaunch tl(h, kTimerFlip);
     StackArgs st{nullptr, (float*)h->xrec[0].p, NL * kt16, 0};
-    prnn_flip_pp_kernel<kStackNF32, kStackRJ, true><<<g0, 512, StackL0::BYTES, h->stream>>>(a, h->wsplit.p, kt16, st);
-    RNNWF_HIP(h, hipGetLastError());
+    if (int rc = plain_launch(h, first, g0, 512, lds_first, a, h->wsplit.p, kt16, st)) return rc;
     for (int l = 1; l < NL; ++l) {
+        const bool top = l == NL - 1;
         st.xin = (const float*)h->xrec[(l - 1) & 1].p;
-        st.xout = l < NL - 1 ? (float*)h->xrec[l & 1].p : nullptr;
+        st.xout = top ? nullptr : (float*)h->xrec[l & 1].p;
         st.koff = l * kt16;
 #ifdef RNNWF_DIAGNOSTICS
-        if (l == NL - 1 && getenv("RNNWF_STAMPS")) {          // in-kernel cycle stamps of the top layer's kernel, median over waves -> stderr (tools/stamps.py)
-            PrnnArgs b = a;
-            const size_t nwv = (size_t)gl * 8;
-            RNNWF_HIP(h, hipMalloc((void**)&b.stamps, nwv * 128));
-            RNNWF_HIP(h, hipMemsetAsync(b.stamps, 0, nwv * 128, h->stream));
-            prnn_flip_pp_upper_kernel<kStackNF32, kStackRJ, true><<<gl, 512, StackU1::LDS_BYTES, h->stream>>>(b, h->wsplit_up[l - 1].p, kt16, st);
-            RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-            std::vector<unsigned long long> sv(nwv * 16);
-            RNNWF_HIP(h, hipMemcpy(sv.data(), b.stamps, nwv * 128, hipMemcpyDeviceToHost));
-            RNNWF_HIP(h, hipFree(b.stamps));
-            const char* names[10] = {"mfma_seg", "barrier_after_mfma", "valu_seg_split_part", "barrier_after_valu", "tile_switch", "total_cycles",
-                                     "realtime_ticks_100MHz", "iterations", "valu_seg_head_gates", "valu_seg_store_head"};
-            fprintf(stderr, "RNNWF_STAMPS upper kernel grid=%u waves=%zu:", gl, nwv);
-            for (int k = 0; k < 10; ++k) {
-                std::vector<unsigned long long> v(nwv);
-                for (size_t w = 0; w < nwv; ++w) v[w] = sv[w * 16 + k];
-                std::sort(v.begin(), v.end());
-                fprintf(stderr, " %s med %llu min %llu max %llu;", names[k], v[nwv / 2], v[0], v[nwv - 1]);
+        if constexpr (std::is_same<Args, PrnnArgs>::value) {
+            if (top && getenv("RNNWF_STAMPS")) {                  // the top layer's kernel
+                const void* wup = h->wsplit_up[l - 1].p;
+                if (int rc = read_stamps(h, [&](unsigned long long* buf) { Args b = a; b.stamps = buf; last<<<gl, 512, lds_upper, h->stream>>>(b, wup, kt16, st); },
+                                         (size_t)gl * 8, 16, "RNNWF_STAMPS upper kernel", gl,
+                                         {"mfma_seg", "barrier_after_mfma", "valu_seg_split_part", "barrier_after_valu", "tile_switch", "total_cycles",
+                                          "realtime_ticks_100MHz", "iterations", "valu_seg_head_gates", "valu_seg_store_head"})) return rc;
+                continue;
             }
-            fprintf(stderr, "\n");
-            continue;
         }
 #endif
-        if (l < NL - 1) prnn_flip_pp_upper_kernel<kStackNF32, kStackRJ, false><<<gu, 512, StackU1::LDS_BYTES, h->stream>>>(a, h->wsplit_up[l - 1].p, kt16, st);
-        else prnn_flip_pp_upper_kernel<kStackNF32, kStackRJ, true><<<gl, 512, StackU1::LDS_BYTES, h->stream>>>(a, h->wsplit_up[l - 1].p, kt16, st);
-        RNNWF_HIP(h, hipGetLastError());
+        if (int rc = plain_launch(h, top ? last : middle, top ? gl : gu, 512, lds_upper, a, h->wsplit_up[l - 1].p, kt16, st)) return rc;
     }
     return 0;
 }
+}  // namespace
 
-
-int rnnwf::crnn_stack_pack(rnnwf_handle* h) {
-    {
-        const std::vector<char> img = pack_split_image<kStackNF32, kStackRJ, 3, 2>(h);
-        if (int rc = ensure(h, h->wsplit, img.size())) return rc;
-        if (int rc = upload(h, h->wsplit.p, img.data(), img.size())) return rc;
-    }
-    for (int l = 1; l < h->NL; ++l) {
-        const std::vector<char> img = pack_split_upper_image<kStackNF32, kStackRJ, 3>(h, l, l == h->NL - 1);
-        if (int rc = ensure(h, h->wsplit_up[l - 1], img.size())) return rc;
-        if (int rc = upload(h, h->wsplit_up[l - 1].p, img.data(), img.size())) return rc;
-    }
-    return 0;
+int rnnwf::prnn_stack_flip(rnnwf_handle* h, const PrnnArgs& a) {
+    const int64_t nsb32 = (a.ns + 31) / 32;
+    const int64_t nrec = nsb32 * (int64_t)a.N * (a.N - 1) / 2;
+    return stack_pipeline(h, a, prnn_flip_pp_kernel<kStackNF32, kStackRJ, true>, prnn_flip_pp_upper_kernel<kStackNF32, kStackRJ, false>,
+                          prnn_flip_pp_upper_kernel<kStackNF32, kStackRJ, true>, StackL0::BYTES, StackU1::LDS_BYTES, (int64_t)(a.N - 1) * nsb32,
+                          (size_t)nrec * StackU1::RECORD_FLOATS * 4);
 }
 
 // max_records: upper bound of the wave-steps of all tiles (crnn.hip derives it from the bonds a first-changed site can have)
 int rnnwf::crnn_stack_swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles, int64_t max_records) {
-    using CL0 = SplitLayout<kStackNF32, kStackRJ, 3, 2>;
-    const int kt16 = 4 * h->NFULL + 1, NL = h->NL;
-    if (CL0::HP > 4 * kt16) return h->fail(RNNWF_ERR_INVALID, "bf16x3 layout wider than the checkpoint rows (%d > %d)", CL0::HP, 4 * kt16);
-    const size_t bytes = (size_t)max_records * StackU3::RECORD_FLOATS * 4;
-    if (int rc = ensure(h, h->xrec[0], bytes)) return rc;
-    if (NL > 2) if (int rc = ensure(h, h->xrec[1], bytes)) return rc;
-    unsigned g0 = 0, gu = 0, gl = 0;
-    constexpr size_t LDS0 = SplitPP<kStackNF32, kStackRJ, 3>::LDS_WITH_SLOTS;
-    if (int rc = persistent_grid(h, crnn_swap_pp_kernel<kStackNF32, kStackRJ, true>, 512, LDS0, max_tiles, 8, &g0)) return rc;
-    if (int rc = persistent_grid(h, crnn_swap_pp_upper_kernel<kStackNF32, kStackRJ, false>, 512, StackU3::LDS_BYTES, max_tiles, 8, &gu)) return rc;
-    if (int rc = persistent_grid(h, crnn_swap_pp_upper_kernel<kStackNF32, kStackRJ, true>, 512, StackU3::LDS_BYTES, max_tiles, 8, &gl)) return rc;
-    TimedLaunch tl(h, kTimerFlip);
-    StackArgs st{nullptr, (float*)h->xrec[0].p, NL * kt16, 0};
-    crnn_swap_pp_kernel<kStackNF32, kStackRJ, true><<<g0, 512, LDS0, h->stream>>>(a, h->wsplit.p, kt16, st);
-    RNNWF_HIP(h, hipGetLastError());
-    for (int l = 1; l < NL; ++l) {
-        st.xin = (const float*)h->xrec[(l - 1) & 1].p;
-        st.xout = l < NL - 1 ? (float*)h->xrec[l & 1].p : nullptr;
-        st.koff = l * kt16;
-        if (l < NL - 1) crnn_swap_pp_upper_kernel<kStackNF32, kStackRJ, false><<<gu, 512, StackU3::LDS_BYTES, h->stream>>>(a, h->wsplit_up[l - 1].p, kt16, st);
-        else crnn_swap_pp_upper_kernel<kStackNF32, kStackRJ, true><<<gl, 512, StackU3::LDS_BYTES, h->stream>>>(a, h->wsplit_up[l - 1].p, kt16, st);
-        RNNWF_HIP(h, hipGetLastError());
-    }
-    return 0;
+    return stack_pipeline(h, a, crnn_swap_pp_kernel<kStackNF32, kStackRJ, true>, crnn_swap_pp_upper_kernel<kStackNF32, kStackRJ, false>,
+                          crnn_swap_pp_upper_kernel<kStackNF32, kStackRJ, true>, SplitPP<kStackNF32, kStackRJ, 3>::LDS_WITH_SLOTS, StackU3::LDS_BYTES,
+                          max_tiles, (size_t)max_records * StackU3::RECORD_FLOATS * 4);
 }
 
 int rnnwf::prnn_split_flip(rnnwf_handle* h, const PrnnArgs& a) {

@@ -204,7 +204,7 @@ int build(rnnwf_handle* h) {
         if (int rc = add_image(h, &h->wimg, [&] { return mdrnn_pack_table(h); })) return rc;
     } else if (h->NL > 1) {
         // a stack: the forward buffer holds [layer 0 | upper layers] (grad.hip knows the layouts); on the bf16x3 engine (37..50 units)
-        // the layer pipeline's images beside it (split.hip: prnn_stack_pack / crnn_stack_pack)
+        // the layer pipeline's images beside it (split.hip: stack_pack)
         if (int rc = add_image(h, &h->wimg, [&] { return grad_stack_forward_table(h); })) return rc;
         if (h->engine_split) {
             if (int rc = add_image(h, &h->wsplit, [&] { if (cplx) pack_split_image<1, 9, 3, 2, Lin>(h); else pack_split_image<1, 9, 1, 2, Lin>(h); return 0; })) return rc;

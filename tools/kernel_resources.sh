@@ -25,5 +25,5 @@ for line in sys.stdin:
     elif cur is not None: cur[k]=v
 for r in rows:
     n=subprocess.run(["c++filt",r["name"]],capture_output=True,text=True).stdout.strip().split("(")[0]
-    print("%-62s V=%-4s A=%-4s S=%-4s scratch=%-4s occ=%s" % (n[-62:], r.get("VGPRs"), r.get("AGPRs"), r.get("SGPRs"), r.get("ScratchSize [bytes/lane]"), r.get("Occupancy [waves/SIMD]")))
+    print("%-62s V=%-4s A=%-4s S=%-4s scratch=%-4s occ=%s" % (n[-62:], r.get("VGPRs"), r.get("AGPRs"), r.get("SGPRs", r.get("TotalSGPRs")), r.get("ScratchSize [bytes/lane]"), r.get("Occupancy [waves/SIMD]")))
 '
