@@ -315,6 +315,23 @@ int rnnwf_pauli_step(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, 
                      const int32_t* samples, int64_t ns, uint64_t seed, uint64_t step, int64_t sample_offset,
                      double* term_sums, double* out_eloc, double* moments, double* out_log_ratio, int32_t* out_samples);
 
+/* rnnwf_pauli_step_2d: the same estimator for the 2D RNN (RNNWF_MODEL_MDRNN2D, float64; docs/pauli_2d.md).  Arguments, layouts and
+ * outputs are rnnwf_pauli_step's, with N = Nx * Ny and one difference: the masks are indexed by the LATTICE index k = nx * Ny + ny,
+ * the C-order flattening of samples (ns, Nx, Ny) - the convention of rnnwf_tfim2d_eloc's Jz - not by the position along the
+ * zig-zag path; the driver maps them to visit order.  With f the first flipped position ALONG THE PATH, the flipped chain restarts
+ * from the base pass's state after position f (which no spin at or behind f enters), takes position f's term from the head and
+ * recomputes the positions f+1..N-1: N - 1 - f cell evaluations per chain and distinct mask.  Passes, fixed-order sums, the resident
+ * batch (one pass: spins, states and E_loc stay as rnnwf_tfim2d_eloc's step leaves them, for rnnwf_vmc_gradient) and the
+ * out_log_ratio rows (distinct non-empty masks in order of first appearance) as above.  RNNWF_ERR_INVALID, before any work and
+ * without a launch: any model but MDRNN2D (rnnwf_pauli_step serves the GRU models); a width without a kernel; uncommitted
+ * parameters; nterms < 1; ns < 1; null flip, sign, coeff or term_sums; a mask entry other than 0 / 1; more than 65535 distinct
+ * non-empty flip masks; sample_offset < 0 with device-drawn samples.
+ * Timing ids: 0 = base pass + site-term replay, 1 = masked-tail pass, 2 = log-ratios, term sums, E_loc and moments.  work[0] +=
+ * sum over distinct masks of N - 1 - f per chain.                                                                          */
+int rnnwf_pauli_step_2d(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff, int32_t nterms,
+                        const int32_t* samples, int64_t ns, uint64_t seed, uint64_t step, int64_t sample_offset,
+                        double* term_sums, double* out_eloc, double* moments, double* out_log_ratio, int32_t* out_samples);
+
 /* ---- multi-GPU: one RCCL all-reduce of the energy moments -------------------------------------
  * The reference is single-process; these add the one data-parallel collective of SURVEY.md 8e.
  * One process per GPU: rank 0 calls rnnwf_comm_unique_id and ships the 128 bytes to the other

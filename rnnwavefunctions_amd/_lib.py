@@ -71,6 +71,8 @@ PROTOTYPES = {
     "rnnwf_correlations": (C.c_int, [_P, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "rnnwf_pauli_step": (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _F64P, _F64P,
                                    _I32P]),
+    "rnnwf_pauli_step_2d": (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _F64P, _F64P,
+                                      _I32P]),
     "rnnwf_timing_enable": (C.c_int, [_P, _I32]),
     "rnnwf_timing_reset": (C.c_int, [_P]),
     "rnnwf_timing_get": (C.c_int, [_P, _I32, _F64P, C.POINTER(_I64), _F64P]),
@@ -466,6 +468,23 @@ class NativeWavefunction:
         sample_offset) draws them.  Returns dict(term_sums=(K, 2) [sum v_k, sum v_k^2], moments=(4,), eloc=(ns,)?,
         log_ratio=(distinct non-empty flip masks in order of first appearance, ns)?, samples=(ns, N)?).  A call that fits one pass
         leaves its batch resident for vmc_gradient."""
+        return self._pauli_call("rnnwf_pauli_step", (max(int(ns), 0), self.N), flip, sign, coeff, ns, samples, seed, step,
+                                sample_offset, want_eloc, want_log_ratio, want_samples)
+
+    def pauli_step_2d(self, flip, sign, coeff, ns, samples=None, seed=0, step=0, sample_offset=0, want_eloc=False,
+                      want_log_ratio=False, want_samples=False):
+        """pauli_step for the 2D RNN (rnnwf_pauli_step_2d).  flip, sign: (K, Nx*Ny) masks indexed by the lattice index nx*Ny + ny, the
+        C-order flattening of samples (ns, Nx, Ny), or (K, Nx, Ny).  samples: (ns, Nx, Ny) or (ns, Nx*Ny) int32; None: drawn on the
+        device as sample(ns, seed, step, sample_offset) draws them, and returned as (ns, Nx, Ny).  Returns what pauli_step returns."""
+        fl, sg = np.asarray(flip), np.asarray(sign)
+        if fl.ndim == 3 and fl.shape[1:] == (self.nx, self.ny) and sg.shape == fl.shape:
+            fl, sg = fl.reshape(fl.shape[0], self.N), sg.reshape(sg.shape[0], self.N)
+        return self._pauli_call("rnnwf_pauli_step_2d", (max(int(ns), 0), self.nx, self.ny), fl, sg, coeff, ns, samples, seed, step,
+                                sample_offset, want_eloc, want_log_ratio, want_samples)
+
+    def _pauli_call(self, entry, drawn_shape, flip, sign, coeff, ns, samples, seed, step, sample_offset, want_eloc, want_log_ratio,
+                    want_samples):
+        """the argument checks, buffers and result dict pauli_step and pauli_step_2d share"""
         ns = int(ns)
         N = self.N
         fl, sg = np.asarray(flip), np.asarray(sign)
@@ -487,11 +506,11 @@ class NativeWavefunction:
         el = np.empty(max(ns, 0), dtype=np.float64) if want_eloc else None
         nmasks = len({r.tobytes() for r in fl if r.any()})
         lr = np.empty((nmasks, max(ns, 0)), dtype=np.float64) if want_log_ratio else None
-        smp = np.empty((max(ns, 0), N), dtype=np.int32) if want_samples and samples is None else None
-        self._check(self.lib.rnnwf_pauli_step(self.h, fp, gp, cp, K, sp, ns, int(seed), int(step), int(sample_offset),
-                                              sums.ctypes.data_as(_F64P), el.ctypes.data_as(_F64P) if el is not None else None,
-                                              mom.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
-                                              smp.ctypes.data_as(_I32P) if smp is not None else None))
+        smp = np.empty(drawn_shape, dtype=np.int32) if want_samples and samples is None else None
+        self._check(getattr(self.lib, entry)(self.h, fp, gp, cp, K, sp, ns, int(seed), int(step), int(sample_offset),
+                       sums.ctypes.data_as(_F64P), el.ctypes.data_as(_F64P) if el is not None else None,
+                       mom.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
+                       smp.ctypes.data_as(_I32P) if smp is not None else None))
         out = {"term_sums": sums, "moments": mom}
         if want_eloc:
             out["eloc"] = el

@@ -21,8 +21,9 @@ namespace rnnwf {
 
 constexpr int kPauliThreads = kRenyiThreads;   // chains per block of the assembly kernels (renyi_sums_kernel reduces their partial sums)
 
+// (inline, as is renyi_sums_kernel: pauli.hip and mdrnn_pauli.hip both include this header)
 // grid (ceil(ns / 256), M): thread = chain, blockIdx.y = mask.  log_ratio [M][ns]
-__global__ void __launch_bounds__(kPauliThreads) pauli_log_ratio_kernel(const double* tail, const double* terms, const double* logp,
+inline __global__ void __launch_bounds__(kPauliThreads) pauli_log_ratio_kernel(const double* tail, const double* terms, const double* logp,
                                                                        const int32_t* first, int N, int64_t ns, double* log_ratio) {
     const int m = blockIdx.y;
     const int f = first[m];
@@ -51,7 +52,7 @@ __device__ __forceinline__ double pauli_value(const uint32_t* bits, const uint32
 }
 
 // grid nterms * nblk (nblk = ceil(ns / 256)): block = (term k, 256 chains).  part [nterms][nblk][2]
-__global__ void __launch_bounds__(kPauliThreads) pauli_term_kernel(const uint32_t* bits, const uint32_t* sgn, const int32_t* tmask,
+inline __global__ void __launch_bounds__(kPauliThreads) pauli_term_kernel(const uint32_t* bits, const uint32_t* sgn, const int32_t* tmask,
                                                                   const double* log_ratio, int W, int64_t ns, int64_t nblk, double* part) {
     __shared__ double r1[kPauliThreads], r2[kPauliThreads];
     const int64_t k = blockIdx.x / nblk, b = blockIdx.x - k * nblk;
@@ -66,7 +67,7 @@ __global__ void __launch_bounds__(kPauliThreads) pauli_term_kernel(const uint32_
 }
 
 // grid ceil(ns / 256): thread = chain; the terms in the caller's order
-__global__ void __launch_bounds__(kPauliThreads) pauli_eloc_kernel(const uint32_t* bits, const uint32_t* sgn, const int32_t* tmask,
+inline __global__ void __launch_bounds__(kPauliThreads) pauli_eloc_kernel(const uint32_t* bits, const uint32_t* sgn, const int32_t* tmask,
                                                                   const double* coeff, const double* log_ratio, int nterms, int W,
                                                                   int64_t ns, double* eloc) {
     const int64_t s = (int64_t)blockIdx.x * kPauliThreads + threadIdx.x;

@@ -1,0 +1,132 @@
+"""Pauli-string expectation values, energies of arbitrary real spin Hamiltonians and two-point functions for the 2D RNN (model
+MDRNN2D on the zig-zag path; rnnwf_pauli_step_2d, docs/pauli_2d.md).
+
+Sites are named by the LATTICE index k = site(Nx, Ny, nx, ny) = nx * Ny + ny, the C-order flattening of samples (ns, Nx, Ny): the
+convention of tfim_hamiltonian for a (Nx, Ny) Jz and of rnnwf_tfim2d_eloc.  The library maps k to the position along the path.  The
+estimator is observables.py's:  v(sigma) = prod_{i in S} s_i * exp(1/2 [log P(sigma ^ F) - log P(sigma)]),  E[v] = <psi|O|psi>.
+
+observables.pauli_expectations / energy / correlations keep refusing the 2D RNN; these are its own entry points.  They accept the
+TFIM2D_2DRNN.RNNwavefunction facade or a NativeWavefunction of model MDRNN2D and raise ValueError for every other model.
+"""
+import numpy as np
+
+from . import _lib
+from .observables import Hamiltonian, _native, group_by_mask, pauli_from_sums, pauli_terms, tfim_hamiltonian  # noqa: F401
+
+__all__ = ["site", "xxz_hamiltonian_2d", "tfim_hamiltonian", "Hamiltonian", "pauli_expectations", "energy", "correlations"]
+
+
+def site(Nx, Ny, nx, ny):
+    """The lattice index of site (nx, ny) of a Nx x Ny lattice: nx * Ny + ny."""
+    Nx, Ny = int(Nx), int(Ny)
+    if int(nx) != nx or int(ny) != ny or not (0 <= nx < Nx and 0 <= ny < Ny):
+        raise ValueError("site (%r, %r) is not on the %d x %d lattice" % (nx, ny, Nx, Ny))
+    return int(nx) * Ny + int(ny)
+
+
+def xxz_hamiltonian_2d(Nx, Ny, Jxy, Jz):
+    """H = sum_bonds [Jxy (sx sx + sy sy) + Jz sz sz] in Pauli matrices on the Nx x Ny lattice with open boundaries, bonds
+    (i, j)-(i+1, j) and (i, j)-(i, j+1).  Jxy < 0 is the ferromagnetic XY coupling, whose ground state is positive in the sz basis."""
+    Nx, Ny = int(Nx), int(Ny)
+    if Nx < 1 or Ny < 1 or Nx * Ny < 2:
+        raise ValueError("xxz_hamiltonian_2d needs a lattice of at least two sites, got %d x %d" % (Nx, Ny))
+    terms = []
+    for i in range(Nx):
+        for j in range(Ny):
+            a = site(Nx, Ny, i, j)
+            for b in ([site(Nx, Ny, i + 1, j)] if i + 1 < Nx else []) + ([site(Nx, Ny, i, j + 1)] if j + 1 < Ny else []):
+                terms += [(Jxy, [("X", a), ("X", b)]), (Jxy, [("Y", a), ("Y", b)]), (Jz, [("Z", a), ("Z", b)])]
+    return Hamiltonian(Nx * Ny, terms)
+
+
+def _native_2d(wf):
+    nat = _native(wf)
+    if nat.model != _lib.MODEL_MDRNN2D:
+        raise ValueError("observables_2d serves the 2D RNN (MDRNN2D) only; observables.py serves the GRU models")
+    return nat
+
+
+def _samples_2d(nat, samples, numsamples):
+    return None if samples is None else np.asarray(samples).reshape(int(numsamples), nat.nx, nat.ny)
+
+
+def pauli_expectations(wf, strings, numsamples, seed=111, step=0, samples=None):
+    """<psi|P|psi> of every Pauli string P of `strings` (dense "XZIY..." over the lattice index, or sparse [("X", k), ...]) with its
+    standard error, from `numsamples` samples: {"value": (K,), "err": (K,)}.  A string with an odd number of Y has expectation exactly
+    0 in the real state psi = sqrt(P): 0 +- 0, without device work.  samples: (numsamples, Nx, Ny) or (numsamples, Nx * Ny) spins;
+    None draws them on the device from (seed, step)."""
+    nat = _native_2d(wf)
+    flip, sign, factor = pauli_terms(strings, nat.N)
+    value, err = np.zeros(len(factor)), np.zeros(len(factor))
+    real = np.flatnonzero(factor.imag == 0.0)
+    if real.size:
+        out = nat.pauli_step_2d(flip[real], sign[real], np.ones(real.size), int(numsamples), samples=_samples_2d(nat, samples, numsamples),
+                                seed=seed, step=step)
+        mean, e = pauli_from_sums(out["term_sums"], numsamples)
+        value[real], err[real] = factor.real[real] * mean, e
+    return {"value": value, "err": err}
+
+
+def energy(wf, ham, numsamples, seed=111, step=0, samples=None, want_eloc=False):
+    """Energy of `wf` under the Hamiltonian `ham` (sites = lattice indices) from `numsamples` samples: {"mean", "var" (population
+    variance of E_loc), "err" (sqrt(var / n)), "eloc" (numsamples,) when want_eloc}.  A batch that fits one pass stays resident:
+    vmc_gradient then differentiates the VMC cost of this Hamiltonian."""
+    nat = _native_2d(wf)
+    if ham.N != nat.N:
+        raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, nat.N))
+    out = nat.pauli_step_2d(ham.flip, ham.sign, ham.coeff, int(numsamples), samples=_samples_2d(nat, samples, numsamples), seed=seed,
+                            step=step, want_eloc=want_eloc)
+    m = out["moments"]
+    mean = m[0] / m[2]
+    var = max(m[1] / m[2] - mean * mean, 0.0)
+    res = {"mean": mean, "var": var, "err": float(np.sqrt(var / m[2]))}
+    if want_eloc:
+        res["eloc"] = out["eloc"]
+    return res
+
+
+def correlations(wf, numsamples, pairs=None, seed=111, step=0, samples=None):
+    """<sz_k>, <sx_k> of every lattice site and, for the listed pairs of distinct sites, <sz_a sz_b>, <sx_a sx_b> and their connected
+    parts, with standard errors, from one pauli_step_2d call (one X mask per site, one XX mask per pair):
+
+        z, x (N,);  pairs (P, 2) lattice indices;  zz, xx, zz_c = zz - z_a z_b, xx_c = xx - x_a x_b (P,);  "<name>_err" for each.
+
+    pairs: None = every pair (c, k), k != c, with the lattice's centre site c = site(Nx, Ny, Nx // 2, Ny // 2).  There are no diagonal
+    entries: sz^2 = sx^2 = 1, and a pair (k, k) raises ValueError.  Errors: the plain std / sqrt(n) (population variance) of the
+    per-sample values s_k, r_k = exp(log r_k), s_a s_b, r_ab, which the call returns as log-ratios and samples - not the cross-moment
+    formulas of observables.correlations_from_sums.  Connected parts to first order (delta method): the std / sqrt(n) of
+    g = s_a s_b - z_b s_a - z_a s_b and of g = r_ab - x_b r_a - x_a r_b."""
+    nat = _native_2d(wf)
+    N, n = nat.N, int(numsamples)
+    if pairs is None:
+        c = site(nat.nx, nat.ny, nat.nx // 2, nat.ny // 2)
+        pairs = [(c, k) for k in range(N) if k != c]
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if np.any(pairs < 0) or np.any(pairs >= N) or np.any(pairs[:, 0] == pairs[:, 1]):
+        raise ValueError("pairs must name two distinct lattice sites in 0..%d each" % (N - 1))
+    npair = len(pairs)
+    flip = np.zeros((N + npair, N), dtype=np.int32)
+    flip[np.arange(N), np.arange(N)] = 1
+    for k, (a, b) in enumerate(pairs):
+        flip[N + k, [a, b]] = 1
+    out = nat.pauli_step_2d(flip, np.zeros_like(flip), np.ones(len(flip)), n, samples=_samples_2d(nat, samples, n), seed=seed, step=step,
+                            want_log_ratio=True, want_samples=True)
+    _, index = group_by_mask(flip)                       # (a, b) and (b, a) share a row
+    r = np.exp(out["log_ratio"])[index]                  # (N + P, n)
+    s = 2.0 * out["samples"].reshape(n, N).T - 1.0       # (N, n)
+
+    def stats(v):
+        return v.mean(axis=-1), v.std(axis=-1) / np.sqrt(n)
+
+    a, b = pairs[:, 0], pairs[:, 1]
+    res = {"pairs": pairs}
+    res["z"], res["z_err"] = stats(s)
+    res["x"], res["x_err"] = stats(r[:N])
+    res["zz"], res["zz_err"] = stats(s[a] * s[b])
+    res["xx"], res["xx_err"] = stats(r[N:])
+    z, x = res["z"], res["x"]
+    res["zz_c"] = res["zz"] - z[a] * z[b]
+    res["xx_c"] = res["xx"] - x[a] * x[b]
+    res["zz_c_err"] = stats(s[a] * s[b] - z[b][:, None] * s[a] - z[a][:, None] * s[b])[1]
+    res["xx_c_err"] = stats(r[N:] - x[b][:, None] * r[a] - x[a][:, None] * r[b])[1]
+    return res
