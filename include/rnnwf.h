@@ -259,6 +259,29 @@ int rnnwf_renyi2_regions(rnnwf_handle* h, const int32_t* regions, int32_t nregio
                          uint64_t seed, uint64_t step, int64_t pair_offset, double* sums, double* out_log_ratio,
                          int32_t* out_samples);
 
+/* rnnwf_renyi2_regions_2d: the same estimator for the 2D RNN (RNNWF_MODEL_MDRNN2D, float64; docs/renyi_2d.md).  Arguments, layouts and
+ * outputs are rnnwf_renyi2_regions's, with N = Nx * Ny and one difference: the masks are indexed by the LATTICE index k = nx * Ny + ny,
+ * the C-order flattening of samples (2*npairs, Nx, Ny) - the convention of rnnwf_pauli_step_2d - not by the position along the
+ * zig-zag path; the driver maps them to visit order.  Each mask is normalised so that position 0 of the path (lattice site 0) is not
+ * in A; a region that is then empty has log r = 0 exactly and costs nothing; otherwise, with f >= 1 the first position of A ALONG THE
+ * PATH, the mixed chain (the partner's spins on A, the chain's own elsewhere) restarts from the chain's own state after position f,
+ * takes position f's term from the head and recomputes the positions f+1..N-1: N - 1 - f cell evaluations per chain and region.
+ * Passes, fixed-order sums, +inf on log r > 709 and the resident-batch rule as rnnwf_renyi2_swap.  RNNWF_ERR_INVALID, before any work
+ * and without a launch: any model but MDRNN2D (rnnwf_renyi2_regions serves the GRU models); a width without a kernel; uncommitted
+ * parameters; nregions < 1 (or above 65535); npairs < 1; null regions or sums; a mask entry other than 0 / 1; pair_offset < 0 with
+ * device-drawn samples.
+ *   regions      (nregions, Nx*Ny) int32 of 0 / 1, 1 = site in A, by lattice index
+ *   samples      (2*npairs, Nx, Ny) int32, pair p = rows (2p, 2p+1); nullptr: draw them on the device exactly as
+ *                rnnwf_sample(h, 2*npairs, seed, step, 2*pair_offset, ...) would (pair_offset ignored otherwise)
+ *   sums         (nregions, 2) f64: sum_p r_A, sum_p r_A^2  (additive over shards)
+ *   out_log_ratio(nregions, npairs) f64 or nullptr, rows under the caller's region index;  out_samples (2*npairs, Nx, Ny) int32 or
+ *                nullptr (drawn chains)
+ * Timing ids: 0 = base pass + site-term replay, 1 = paired masked-tail pass, 2 = log-ratio assembly + sums.  work[0] += sum over
+ * non-empty regions of N - 1 - f per chain.                                                                                 */
+int rnnwf_renyi2_regions_2d(rnnwf_handle* h, const int32_t* regions, int32_t nregions, const int32_t* samples, int64_t npairs,
+                            uint64_t seed, uint64_t step, int64_t pair_offset, double* sums, double* out_log_ratio,
+                            int32_t* out_samples);
+
 /* ---- correlation functions -------------------------------------------------------------------------
  * The reference README's "correlation functions" of the positive one-layer GRU models (GRU1D, GRU1D_F64; every other model
  * and stacked layers: RNNWF_ERR_INVALID), psi = sqrt(P), samples sigma ~ P, s = 2 sigma - 1 (docs/correlations.md):
@@ -358,7 +381,8 @@ int rnnwf_comm_destroy(rnnwf_handle* h);
  * HIP-event timing of the kernels on the handle's stream (bench.py's roofline leg).
  * kernel ids: 0 = base pass (sample / teacher-forced + checkpoints), 1 = flip pass (dominant),
  *             2 = local-energy assembly + moments (rnnwf_renyi2_swap: 0 = base pass + site-term replay,
- *             1 = swap pass, 2 = log-ratio assembly + sums, and the same for rnnwf_renyi2_regions; rnnwf_correlations: 0 = base pass + both-outcome replay, 1 = trunk +
+ *             1 = swap pass, 2 = log-ratio assembly + sums, and the same for rnnwf_renyi2_regions and
+ *             rnnwf_renyi2_regions_2d (id 1 = its paired masked-tail pass); rnnwf_correlations: 0 = base pass + both-outcome replay, 1 = trunk +
  *             branch passes, 2 = log-ratio assembly + sums), 3 = back-propagation through time of rnnwf_vmc_gradient,
  *             4 = its weight-gradient GEMM.  total_ms / launches accumulate since the
  *             last rnnwf_timing_reset.  Stacked layers on the bf16x3 engine: id 1 brackets the whole

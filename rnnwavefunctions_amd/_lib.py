@@ -68,6 +68,7 @@ PROTOTYPES = {
     "rnnwf_adam_set_state": (C.c_int, [_P, _F64P, _F64P, _I64, _I64]),
     "rnnwf_renyi2_swap": (C.c_int, [_P, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _I32P]),
     "rnnwf_renyi2_regions": (C.c_int, [_P, _I32P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _I32P]),
+    "rnnwf_renyi2_regions_2d": (C.c_int, [_P, _I32P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _I32P]),
     "rnnwf_correlations": (C.c_int, [_P, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "rnnwf_pauli_step": (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _F64P, _F64P,
                                    _I32P]),
@@ -430,6 +431,39 @@ class NativeWavefunction:
         self._check(self.lib.rnnwf_renyi2_regions(self.h, rp, R, sp, npairs, int(seed), int(step), int(pair_offset),
                                                   sums.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
                                                   smp.ctypes.data_as(_I32P) if smp is not None else None))
+        out = {"sums": sums}
+        if smp is not None:
+            out["samples"] = smp
+        if log_ratio:
+            out["log_ratio"] = lr
+        return out
+
+    def renyi2_regions_2d(self, regions, numpairs, samples=None, seed=111, step=0, pair_offset=0, log_ratio=False):
+        """renyi2_regions for the 2D RNN (rnnwf_renyi2_regions_2d).  regions: (R, Nx*Ny) masks of 0 / 1 indexed by the lattice index
+        nx*Ny + ny, the C-order flattening of samples (2 numpairs, Nx, Ny), or (R, Nx, Ny), or one mask of Nx*Ny entries.  samples:
+        (2 numpairs, Nx, Ny) or (2 numpairs, Nx*Ny) int32, pair p = rows 2p, 2p + 1; None: drawn on the device as sample(2 numpairs,
+        seed, step, 2 pair_offset) draws them.  Returns dict(sums=(R, 2) [sum r_A, sum r_A^2], samples=(2 numpairs, Nx, Ny) when
+        drawn, log_ratio=(R, numpairs) when asked)."""
+        npairs = int(numpairs)
+        reg = np.asarray(regions)
+        if reg.ndim == 1:
+            reg = reg[None, :]
+        if reg.ndim == 3 and reg.shape[1:] == (self.nx, self.ny):
+            reg = reg.reshape(reg.shape[0], self.N)
+        if reg.ndim != 2 or reg.shape[0] < 1 or reg.shape[1] != self.N:
+            raise ValueError("regions must have shape (nregions >= 1, %d) or (nregions >= 1, %d, %d), got %r"
+                             % (self.N, self.nx, self.ny, reg.shape))
+        if not np.all(reg == reg.astype(np.int32)):
+            raise ValueError("regions must hold the integers 0 and 1")
+        reg, rp = _i32(reg)
+        R = reg.shape[0]
+        s, sp = self._chain_samples(samples, 2 * npairs, "2*numpairs")
+        sums = np.empty((R, 2), dtype=np.float64)
+        lr = np.empty((R, max(npairs, 0)), dtype=np.float64) if log_ratio else None
+        smp = np.empty((2 * max(npairs, 0), self.nx, self.ny), dtype=np.int32) if samples is None else None
+        self._check(self.lib.rnnwf_renyi2_regions_2d(self.h, rp, R, sp, npairs, int(seed), int(step), int(pair_offset),
+                                                     sums.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
+                                                     smp.ctypes.data_as(_I32P) if smp is not None else None))
         out = {"sums": sums}
         if smp is not None:
             out["samples"] = smp

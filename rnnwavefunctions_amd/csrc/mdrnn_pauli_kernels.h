@@ -14,6 +14,7 @@
 //                             the flipped outcome.  States at positions <= f are the base pass's; EVERY position > f is
 //                             recomputed and stored to its column slot, also where no flipped spin reaches it: the state above
 //                             (nx, ny+1) is then always the last one written to column nx, whatever the mask.
+//                             <..., PAIRED = true>: the same tail for the mixed chain of a replica pair (Renyi-2 of regions).
 // The cell, the head and the state layout are MdCore's, unchanged.
 #pragma once
 #include "mdrnn_kernels.h"
@@ -30,7 +31,7 @@ struct MdPauliArgs {
     const double* hs;              // [N][nsb][KP][64] double2: the base pass's states
     double* ring;                  // masked tails: [total waves][Nx][KP][64] double2, one private slot per lattice column
     double* terms;                 // [N][ns]: row p = log p_p(sigma_p | sigma_<p)
-    const uint32_t* mask;          // [M][W] distinct non-empty flip masks, visit order
+    const uint32_t* mask;          // [M][W] distinct non-empty flip masks (PAIRED: the normalised region masks), visit order
     const int32_t* order;          // [M] the masks f ascending (longest tail first), ties by index
     const int32_t* first;          // [M] first flipped position f, 0 <= f <= N-1
     double* tail;                  // [M][ns]
@@ -61,7 +62,10 @@ __global__ void __launch_bounds__(WAVES * 64, NFULL <= 3 ? 2 : 1) mdrnn_site_ter
     }
 }
 
-template <int NFULL, int WAVES>
+// PAIRED (mdrnn_renyi.hip, docs/renyi_2d.md): chains (2p, 2p + 1) are a replica pair and a masked position takes the PARTNER's spin
+// instead of the flipped one - the mixed chain of the swap estimator.  The host normalises the masks so that position 0 is never
+// masked (1 <= f <= N-1) and passes hold whole pairs (ns even).  Everything but the spin words is the same: hs[f] is the chain's own.
+template <int NFULL, int WAVES, bool PAIRED = false>
 __global__ void __launch_bounds__(WAVES * 64, NFULL <= 3 ? 2 : 1) mdrnn_masked_tail_kernel(MdPauliArgs a) {
     using C = MdCore<NFULL>;
     constexpr int KT = C::KT;
@@ -87,9 +91,20 @@ __global__ void __launch_bounds__(WAVES * 64, NFULL <= 3 ? 2 : 1) mdrnn_masked_t
         const int64_t s = sb * kChains + c;
         const bool valid = s < a.ns;
         const int64_t sc = valid ? s : a.ns - 1;
-        // the flipped configuration's spin words, [word][lane] in the wave's LDS slot (as mdrnn_flip_kernel)
+        // the changed configuration's spin words, [word][lane] in the wave's LDS slot (as mdrnn_flip_kernel).  PAIRED: ns is even,
+        // so sc ^ 1 < ns also for the clamped lanes of a ragged block
 #pragma unroll
-        for (int w = 0; w < 8; ++w) words[w * 64] = w < W ? a.bits[(int64_t)w * a.ns + sc] ^ mw[w] : 0u;
+        for (int w = 0; w < 8; ++w) {
+            uint32_t word = 0u;
+            if (w < W) {
+                const uint32_t own = a.bits[(int64_t)w * a.ns + sc];
+                if constexpr (PAIRED)
+                    word = (own & ~mw[w]) | (a.bits[(int64_t)w * a.ns + (sc ^ 1)] & mw[w]);
+                else
+                    word = own ^ mw[w];
+            }
+            words[w * 64] = word;
+        }
         double hv[KT], hn[KT];
         C::load_state(a.hs + (((int64_t)f * a.nsb + sb) * C::KP) * 128 + 2 * lane, hn);   // state after position f: spins < f only
         // position f's own term at the flipped outcome: no step, f = 0 and f = N-1 included

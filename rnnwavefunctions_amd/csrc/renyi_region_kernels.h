@@ -19,8 +19,9 @@
 
 namespace rnnwf {
 
+// (inline, as renyi_kernels.h's: renyi_regions.hip and mdrnn_renyi.hip both include this header)
 // grid (ceil(npairs / 256), R): thread = pair, blockIdx.y = region.  log_ratio [R][npairs]; part [R][gridDim.x][2]
-__global__ void __launch_bounds__(kRenyiThreads) renyi_region_assemble_kernel(const double* tail, const double* terms,
+inline __global__ void __launch_bounds__(kRenyiThreads) renyi_region_assemble_kernel(const double* tail, const double* terms,
                                                                              const int32_t* first, int N, int64_t ns,
                                                                              double* log_ratio, double* part) {
     __shared__ double r1[kRenyiThreads], r2[kRenyiThreads];

@@ -1,19 +1,25 @@
 """Pauli-string expectation values, energies of arbitrary real spin Hamiltonians and two-point functions for the 2D RNN (model
-MDRNN2D on the zig-zag path; rnnwf_pauli_step_2d, docs/pauli_2d.md).
+MDRNN2D on the zig-zag path; rnnwf_pauli_step_2d, docs/pauli_2d.md), and the second Renyi entropy of arbitrary lattice regions
+(rnnwf_renyi2_regions_2d, docs/renyi_2d.md).
 
 Sites are named by the LATTICE index k = site(Nx, Ny, nx, ny) = nx * Ny + ny, the C-order flattening of samples (ns, Nx, Ny): the
 convention of tfim_hamiltonian for a (Nx, Ny) Jz and of rnnwf_tfim2d_eloc.  The library maps k to the position along the path.  The
 estimator is observables.py's:  v(sigma) = prod_{i in S} s_i * exp(1/2 [log P(sigma ^ F) - log P(sigma)]),  E[v] = <psi|O|psi>.
 
-observables.pauli_expectations / energy / correlations keep refusing the 2D RNN; these are its own entry points.  They accept the
+Regions are masks over the same lattice index: r_A = psi(tau_A sigma_B) psi(sigma_A tau_B) / (psi(sigma) psi(tau)) on pairs of
+independent samples, exp(-S2(A)) = E[r_A] (observables.py's estimator).
+
+observables.pauli_expectations / energy / correlations / renyi2_regions keep refusing the 2D RNN; these are its own entry points.  They accept the
 TFIM2D_2DRNN.RNNwavefunction facade or a NativeWavefunction of model MDRNN2D and raise ValueError for every other model.
 """
 import numpy as np
 
 from . import _lib
-from .observables import Hamiltonian, _native, group_by_mask, pauli_from_sums, pauli_terms, tfim_hamiltonian  # noqa: F401
+from .observables import (Hamiltonian, _disjoint_masks, _native, group_by_mask, mutual_information2_from_log_ratios,  # noqa: F401
+                          pauli_from_sums, pauli_terms, renyi2_from_sums, tfim_hamiltonian)
 
-__all__ = ["site", "xxz_hamiltonian_2d", "tfim_hamiltonian", "Hamiltonian", "pauli_expectations", "energy", "correlations"]
+__all__ = ["site", "xxz_hamiltonian_2d", "tfim_hamiltonian", "Hamiltonian", "pauli_expectations", "energy", "correlations",
+           "rectangle_region", "row_cut_regions", "column_cut_regions", "renyi2_regions", "renyi2_mutual_information"]
 
 
 def site(Nx, Ny, nx, ny):
@@ -130,3 +136,57 @@ def correlations(wf, numsamples, pairs=None, seed=111, step=0, samples=None):
     res["zz_c_err"] = stats(s[a] * s[b] - z[b][:, None] * s[a] - z[a][:, None] * s[b])[1]
     res["xx_c_err"] = stats(r[N:] - x[b][:, None] * r[a] - x[a][:, None] * r[b])[1]
     return res
+
+
+def rectangle_region(Nx, Ny, x0, x1, y0, y1):
+    """(Nx Ny,) int32 mask over the lattice index of the sites x0 <= nx < x1, y0 <= ny < y1."""
+    Nx, Ny, x0, x1, y0, y1 = (int(v) for v in (Nx, Ny, x0, x1, y0, y1))
+    if Nx < 1 or Ny < 1 or not (0 <= x0 <= x1 <= Nx and 0 <= y0 <= y1 <= Ny):
+        raise ValueError("rectangle_region needs 0 <= x0 <= x1 <= Nx and 0 <= y0 <= y1 <= Ny, got Nx=%d, Ny=%d, x %d..%d, y %d..%d"
+                         % (Nx, Ny, x0, x1, y0, y1))
+    m = np.zeros((Nx, Ny), dtype=np.int32)
+    m[x0:x1, y0:y1] = 1
+    return m.reshape(Nx * Ny)
+
+
+def row_cut_regions(Nx, Ny):
+    """(Ny - 1, Nx Ny) int32 masks of the cuts between rows: row c - 1 = the sites ny < c, c = 1..Ny-1.  The model visits the lattice
+    row by row, so these are the prefixes of its path."""
+    Nx, Ny = int(Nx), int(Ny)
+    if Nx < 1 or Ny < 2:
+        raise ValueError("row_cut_regions needs Nx >= 1 and Ny >= 2, got Nx=%d, Ny=%d" % (Nx, Ny))
+    return np.stack([rectangle_region(Nx, Ny, 0, Nx, 0, c) for c in range(1, Ny)])
+
+
+def column_cut_regions(Nx, Ny):
+    """(Nx - 1, Nx Ny) int32 masks of the cuts between columns: row c - 1 = the sites nx < c, c = 1..Nx-1."""
+    Nx, Ny = int(Nx), int(Ny)
+    if Nx < 2 or Ny < 1:
+        raise ValueError("column_cut_regions needs Nx >= 2 and Ny >= 1, got Nx=%d, Ny=%d" % (Nx, Ny))
+    return np.stack([rectangle_region(Nx, Ny, 0, c, 0, Ny) for c in range(1, Nx)])
+
+
+def _pairs_2d(nat, samples, numpairs):
+    return None if samples is None else np.asarray(samples).reshape(2 * int(numpairs), nat.nx, nat.ny)
+
+
+def renyi2_regions(wf, regions, numpairs, seed=111, step=0, samples=None):
+    """Second Renyi entropy S2(A) (R,) and its standard error (R,) (observables.renyi2_from_sums) of the regions `regions`: (R, Nx Ny)
+    masks of 0 / 1 over the lattice index, (R, Nx, Ny), or one mask of Nx Ny entries; 1 = site in A.  From `numpairs` pairs of
+    independent samples; samples: (2 numpairs, Nx, Ny) or (2 numpairs, Nx Ny) spins, pair p = rows 2p and 2p + 1; None draws them on
+    the device from (seed, step)."""
+    nat = _native_2d(wf)
+    out = nat.renyi2_regions_2d(regions, int(numpairs), samples=_pairs_2d(nat, samples, numpairs), seed=seed, step=step)
+    return renyi2_from_sums(out["sums"], numpairs)
+
+
+def renyi2_mutual_information(wf, region_a, region_b, numpairs, seed=111, step=0, samples=None):
+    """Renyi-2 mutual information I2(A : B) = S2(A) + S2(B) - S2(A u B) of two DISJOINT regions (masks of Nx Ny entries over the
+    lattice index, or (Nx, Ny)) and its standard error by the delta method (observables.mutual_information2_from_log_ratios), from
+    `numpairs` pairs; A, B and A u B run in one call on the same pairs.  Overlapping regions raise ValueError before the wave function
+    is touched."""
+    a, b = _disjoint_masks(np.asarray(region_a).reshape(-1), np.asarray(region_b).reshape(-1))
+    nat = _native_2d(wf)
+    out = nat.renyi2_regions_2d(np.stack([a, b, a | b]), int(numpairs), samples=_pairs_2d(nat, samples, numpairs), seed=seed, step=step,
+                                log_ratio=True)
+    return mutual_information2_from_log_ratios(*out["log_ratio"])
