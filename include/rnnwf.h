@@ -355,6 +355,36 @@ int rnnwf_pauli_step_2d(rnnwf_handle* h, const int32_t* flip, const int32_t* sig
                         const int32_t* samples, int64_t ns, uint64_t seed, uint64_t step, int64_t sample_offset,
                         double* term_sums, double* out_eloc, double* moments, double* out_log_ratio, int32_t* out_samples);
 
+/* rnnwf_pauli_step_complex: the same estimator for the complex RNN with the U(1) mask (RNNWF_MODEL_CRNN_U1, one layer;
+ * docs/pauli_complex.md).  psi is complex, so is the estimator: with d = log psi(sigma ^ F_k) - log psi(sigma) (complex, float64,
+ * the unwrapped sum of the per-site log-amplitudes and phases; the imaginary part is never reduced modulo 2 pi)
+ *   v_k(sigma) = prod_{i in S_k} s_i(sigma) * exp(Re d) (cos Im d + i sin Im d),   E[v_k] = <psi|O_k|psi>,
+ *   E_loc(sigma) = sum_k coeff_k v_k(sigma)   with complex coeff_k: strings with an odd number of sy and terms with imaginary
+ * matrix elements are legal here.  A flipped configuration outside the zero-magnetisation sector has psi = 0 exactly: its v is
+ * exactly (0, 0), its out_log_ratio entry (-inf, 0), and no NaN appears.  Arguments as rnnwf_pauli_step, except:
+ *   coeff_re_im   (nterms, 2) f64: complex coefficients
+ *   term_sums     (nterms, 4) f64: sum Re v_k, sum Im v_k, sum (Re v_k)^2, sum (Im v_k)^2  (required, additive over shards)
+ *   out_eloc_re_im(ns, 2) f32 = complex64 or nullptr (the type of rnnwf_j1j2_eloc and of rnnwf_vmc_step for this model)
+ *   moments[4] or nullptr: {sum Re E, sum (Re E)^2, ns, sum Im E} of those complex64 values, as rnnwf_vmc_step returns them
+ *   out_log_ratio (nmasks, ns, 2) f64 or nullptr: (Re d, Im d), rows = the distinct non-empty flip masks in order of first appearance
+ * Grouping by flip mask, restart from the chain's own checkpoint at f - 1 (the U(1) count restarts from the ups of its own sites
+ * below f), N - f cell evaluations per chain and distinct mask, passes under the state budget, fixed-order sums and the signs read
+ * from the SAMPLED configuration as for rnnwf_pauli_step.  The checkpointed base pass always runs on the one-wave f32 kernel.
+ * A call that ran in ONE pass leaves spins, checkpoints and complex64 E_loc resident as rnnwf_vmc_step does for this model:
+ * rnnwf_vmc_gradient(mean_re, mean_im, ns) then differentiates the complex cost of this Hamiltonian.  A call in several passes
+ * leaves no batch; a refused call leaves an earlier one usable.  RNNWF_ERR_INVALID, before any work and without a launch: any
+ * model but CRNN_U1 (rnnwf_pauli_step serves the GRU models, rnnwf_pauli_step_2d the 2D RNN); stacked layers; nterms < 1; ns < 1;
+ * null flip, sign, coeff_re_im or term_sums; a mask entry other than 0 / 1; more than 65535 distinct non-empty flip masks;
+ * sample_offset < 0 with device-drawn samples; nterms x ceil(ns / 256) past the grid limit; a caller-supplied sample whose number
+ * of up spins is not N / 2 (samples must lie in the zero-magnetisation sector: outside it their own log psi is -inf and the
+ * ratio undefined; device-drawn chains always lie in it).  Uncommitted parameters:
+ * RNNWF_ERR_STATE.  rnnwf_pauli_step and rnnwf_pauli_step_2d keep refusing this model.
+ * Timing ids: 0 = base pass + site-term replay, 1 = flip-mask pass, 2 = log-ratios, term sums, E_loc and moments.  work[0] +=
+ * sum over distinct masks of N - f per chain.                                                                             */
+int rnnwf_pauli_step_complex(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff_re_im, int32_t nterms,
+                             const int32_t* samples, int64_t ns, uint64_t seed, uint64_t step, int64_t sample_offset,
+                             double* term_sums, float* out_eloc_re_im, double* moments, double* out_log_ratio, int32_t* out_samples);
+
 /* ---- multi-GPU: one RCCL all-reduce of the energy moments -------------------------------------
  * The reference is single-process; these add the one data-parallel collective of SURVEY.md 8e.
  * One process per GPU: rank 0 calls rnnwf_comm_unique_id and ships the 128 bytes to the other

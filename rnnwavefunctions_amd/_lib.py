@@ -74,6 +74,8 @@ PROTOTYPES = {
                                    _I32P]),
     "rnnwf_pauli_step_2d": (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _F64P, _F64P,
                                       _I32P]),
+    "rnnwf_pauli_step_complex": (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F32P, _F64P,
+                                           _F64P, _I32P]),
     "rnnwf_timing_enable": (C.c_int, [_P, _I32]),
     "rnnwf_timing_reset": (C.c_int, [_P]),
     "rnnwf_timing_get": (C.c_int, [_P, _I32, _F64P, C.POINTER(_I64), _F64P]),
@@ -545,6 +547,49 @@ class NativeWavefunction:
                        sums.ctypes.data_as(_F64P), el.ctypes.data_as(_F64P) if el is not None else None,
                        mom.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
                        smp.ctypes.data_as(_I32P) if smp is not None else None))
+        out = {"term_sums": sums, "moments": mom}
+        if want_eloc:
+            out["eloc"] = el
+        if want_log_ratio:
+            out["log_ratio"] = lr
+        if want_samples:
+            out["samples"] = smp if smp is not None else s
+        return out
+
+    def pauli_step_complex(self, flip, sign, coeff, numsamples, samples=None, seed=0, step=0, sample_offset=0, want_eloc=False,
+                           want_log_ratio=False, want_samples=False):
+        """pauli_step for the complex RNN (rnnwf_pauli_step_complex).  flip, sign: (K, N) masks of 0 / 1 (or one term of N entries),
+        coeff: (K,) complex.  samples: (ns, N) int32; None: drawn on the device as sample(ns, seed, step, sample_offset) draws them.
+        Returns dict(term_sums=(K, 4) [sum Re v, sum Im v, sum (Re v)^2, sum (Im v)^2], moments=(4,) [sum Re E, sum (Re E)^2, ns,
+        sum Im E], eloc=(ns,) complex64?, log_ratio=(distinct non-empty flip masks in order of first appearance, ns) complex128?
+        (-inf + 0j where the flipped configuration leaves the zero-magnetisation sector), samples=(ns, N)?).  A call that fits one
+        pass leaves its batch resident for vmc_gradient."""
+        ns = int(numsamples)
+        N = self.N
+        fl, sg = np.asarray(flip), np.asarray(sign)
+        if fl.ndim == 1:
+            fl, sg = fl[None, :], sg[None, :]
+        if fl.ndim != 2 or fl.shape[0] < 1 or fl.shape[1] != N or sg.shape != fl.shape:
+            raise ValueError("flip and sign must both have shape (nterms >= 1, %d), got %r and %r" % (N, fl.shape, sg.shape))
+        if not (np.all(fl == fl.astype(np.int32)) and np.all(sg == sg.astype(np.int32))):
+            raise ValueError("flip and sign must hold the integers 0 and 1")
+        fl, fp = _i32(fl)
+        sg, gp = _i32(sg)
+        K = fl.shape[0]
+        co = np.ascontiguousarray(np.atleast_1d(coeff), dtype=np.complex128)
+        if co.shape != (K,):
+            raise ValueError("coeff must have shape (%d,), got %r" % (K, co.shape))
+        s, sp = self._chain_samples(samples, ns, "ns")
+        sums = np.empty((K, 4), dtype=np.float64)
+        mom = np.zeros(4, dtype=np.float64)
+        el = np.empty(max(ns, 0), dtype=np.complex64) if want_eloc else None
+        nmasks = len({r.tobytes() for r in fl if r.any()})
+        lr = np.empty((nmasks, max(ns, 0)), dtype=np.complex128) if want_log_ratio else None
+        smp = np.empty((max(ns, 0), N), dtype=np.int32) if want_samples and samples is None else None
+        self._check(self.lib.rnnwf_pauli_step_complex(
+            self.h, fp, gp, co.ctypes.data_as(_F64P), K, sp, ns, int(seed), int(step), int(sample_offset), sums.ctypes.data_as(_F64P),
+            el.ctypes.data_as(_F32P) if el is not None else None, mom.ctypes.data_as(_F64P),
+            lr.ctypes.data_as(_F64P) if lr is not None else None, smp.ctypes.data_as(_I32P) if smp is not None else None))
         out = {"term_sums": sums, "moments": mom}
         if want_eloc:
             out["eloc"] = el

@@ -29,6 +29,10 @@ struct CLaunch {
         if (NFULL <= 3 && base_bf_available(h)) return crnn_base_coop_bf(h, a);      // bf16 cooperative kernel, every batch size (prnn.hip)
         // fewer 16-chain blocks than SIMDs: the cooperative kernel (NFULL + 1 waves per block, bit-identical)
         if (NFULL <= 4 && a.nsb <= (int64_t)4 * h->cu_count && !h->knobs.no_coop) return base_coop(h, a);
+        return plain(h, a);
+    }
+    // the one-wave kernel for every batch size (crnn_plain_base)
+    static int plain(rnnwf_handle* h, const CrnnArgs& a) {
         return launch_persistent(h, kTimerBase, crnn_base_kernel<NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, a.nsb, WAVES, a);
     }
     // the tile count lives on the device: the persistent grid is bounded by the worst case
@@ -54,6 +58,7 @@ struct CMLaunch {
         }
         return launch_shrinking<WAVES>(h, kTimerBase, crnn_ml_base_kernel<NFULL, NL, WAVES>, M::BYTES, a.nsb, a);
     }
+    static int plain(rnnwf_handle* h, const CrnnArgs&) { return h->fail(RNNWF_ERR_INVALID, "crnn_plain_base: one GRU layer only"); }
     static int swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles) {
         return launch_persistent(h, kTimerFlip, crnn_ml_swap_kernel<NFULL, NL, WAVES>, WAVES * 64, M::BYTES, max_tiles, WAVES, a);
     }
@@ -320,6 +325,15 @@ int rnnwf::crnn_j1j2_eloc(rnnwf_handle* h, const int32_t* samples, int64_t ns, c
     if (ncon) *ncon = total;
     return RNNWF_OK;
 }
+
+// The base pass on the one-wave-per-block kernel for every batch size (never the cooperative or bf16 kernels): the masked-tail pass
+// of crnn_pauli.hip restarts from its checkpoints and must repeat its arithmetic step for step.  One layer only.
+int rnnwf::crnn_plain_base(rnnwf_handle* h, const CrnnArgs& a) {
+    int rc = 0;
+    return with_launch(h, [&](auto k) { rc = decltype(k)::plain(h, a); }) ? rc : no_kernel(h);
+}
+CrnnArgs rnnwf::crnn_base_args(rnnwf_handle* h, int64_t ns) { return base_args(h, ns); }
+size_t rnnwf::crnn_hck_bytes_per_block(rnnwf_handle* h) { return hck_bytes_per_block(h); }
 
 const Family* rnnwf::crnn_family() {
     static const Family f = {

@@ -12,6 +12,7 @@
 //                         from the checkpoint of site lo, and writes  H_k exp(log psi(s') - log psi(s)).
 //   j1j2_eloc_kernel    : E_loc[s] = diag + sum_k contributions, in the reference's bond order (:277-279).
 #pragma once
+#include "chain_kernels.h"     // spin_of
 #include "gru_kernels.h"
 
 namespace rnnwf {
@@ -208,10 +209,6 @@ struct J1J2Args {
     double2* contrib;             // [2N][ns] (bond slot major), every entry zeroed here; the swap pass overwrites the active bonds
     double* diag;                 // [ns]
 };
-
-__device__ __forceinline__ int spin_of(const uint32_t* bits, int64_t ns, int64_t s, int p) {
-    return (int)((bits[(int64_t)(p >> 5) * ns + s] >> (p & 31)) & 1);
-}
 
 // first changed site of bond slot `slot` (J1 bond a -> slot a, J2 bond a -> slot N + a)
 __device__ __forceinline__ int lo_of_block(int N, int slot, int periodic) {

@@ -106,6 +106,10 @@ int prnn_teacher_base(rnnwf_handle* h, int64_t ns, bool reversed, double* out_lp
 int prnn_plain_base(rnnwf_handle* h, const PrnnArgs& a);
 PrnnArgs prnn_base_args(rnnwf_handle* h, int64_t ns);
 size_t prnn_hck_bytes_per_block(rnnwf_handle* h);
+// crnn.hip, for the complex RNN's Pauli pass (crnn_pauli.hip): the same three for the one-layer complex RNN
+int crnn_plain_base(rnnwf_handle* h, const CrnnArgs& a);
+CrnnArgs crnn_base_args(rnnwf_handle* h, int64_t ns);
+size_t crnn_hck_bytes_per_block(rnnwf_handle* h);
 // the 16x16x32 form at 37..52 units (split_stream.hip; image in h->wsplit16)
 int prnn_split_flip_16n(rnnwf_handle* h, const PrnnArgs& a, int kt16);
 double prnn_split_16n_flops_per_step();

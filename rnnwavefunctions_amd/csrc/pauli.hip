@@ -11,27 +11,17 @@
 // resident for rnnwf_vmc_gradient.
 #include <algorithm>
 #include <cstring>
-#include <map>
 #include <vector>
 
 #include "observable.h"
 #include "pauli_kernels.h"
+#include "pauli_terms.h"
 
 using namespace rnnwf;
 
 namespace {
 
-constexpr int kMaxMasks = 65535;         // blockIdx.y of the log-ratio kernel
-
-// The terms of one call as the kernels read them
-struct Terms {
-    int K = 0, M = 0, W = 0;
-    std::vector<uint32_t> mask, sgn;     // [M][W] distinct non-empty flip masks in order of first appearance; [K][W] sign masks
-    std::vector<int32_t> tmask;          // [K]: the term's row of `mask`, -1 for a diagonal term
-    std::vector<int32_t> first, order;   // [M]: first flipped site f; the masks f ascending, ties by index
-    bool replay = false;                 // some mask has f >= 1: the own suffixes need the replayed site terms
-    double steps = 0.0;                  // sum over masks of N - f: cell evaluations per chain
-};
+using Terms = PauliTerms;
 
 // Scratch of one pass of ns chains in h->renyi; the call's tables lead, at offsets that do not depend on ns
 struct Scratch {
@@ -56,48 +46,6 @@ struct Scratch {
         bytes = c.bytes;
     }
 };
-
-// check and pack the (K, N) flip and sign masks, group the terms by flip mask, sort the distinct masks
-int prepare(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, int K, Terms& g) {
-    const int N = h->N;
-    g.K = K;
-    g.W = (N + 31) / 32;
-    g.sgn.assign((size_t)K * g.W, 0u);
-    g.tmask.assign(K, -1);
-    std::map<std::vector<uint32_t>, int32_t> seen;
-    std::vector<uint32_t> words(g.W);
-    for (int k = 0; k < K; ++k) {
-        const int32_t *fk = flip + (size_t)k * N, *sk = sign + (size_t)k * N;
-        std::fill(words.begin(), words.end(), 0u);
-        int f = -1;
-        for (int n = 0; n < N; ++n) {
-            if (fk[n] != 0 && fk[n] != 1)
-                return h->fail(RNNWF_ERR_INVALID, "rnnwf_pauli_step: flip[%d][%d] = %d, a mask entry must be 0 or 1", k, n, (int)fk[n]);
-            if (sk[n] != 0 && sk[n] != 1)
-                return h->fail(RNNWF_ERR_INVALID, "rnnwf_pauli_step: sign[%d][%d] = %d, a mask entry must be 0 or 1", k, n, (int)sk[n]);
-            if (fk[n]) {
-                words[n >> 5] |= 1u << (n & 31);
-                if (f < 0) f = n;
-            }
-            if (sk[n]) g.sgn[(size_t)k * g.W + (n >> 5)] |= 1u << (n & 31);
-        }
-        if (f < 0) continue;                       // diagonal term: no cell evaluation
-        auto it = seen.find(words);
-        if (it == seen.end()) {
-            if (g.M == kMaxMasks)
-                return h->fail(RNNWF_ERR_INVALID, "rnnwf_pauli_step: more than %d distinct flip masks", kMaxMasks);
-            it = seen.emplace(words, g.M++).first;
-            g.mask.insert(g.mask.end(), words.begin(), words.end());
-            g.first.push_back(f);
-            g.order.push_back(it->second);
-            g.steps += (double)(N - f);
-            if (f > 0) g.replay = true;
-        }
-        g.tmask[k] = it->second;
-    }
-    std::stable_sort(g.order.begin(), g.order.end(), [&](int32_t x, int32_t y) { return g.first[x] < g.first[y]; });
-    return 0;
-}
 
 // one pass over the ns chains packed in h->bits: sums_host (K, 2) of this pass; the log-ratios stay in h->renyi, E_loc in h->eloc
 // keep: the pass is the whole call, its checkpoints are left for rnnwf_vmc_gradient (diagonal terms alone need no base pass otherwise)
@@ -163,7 +111,7 @@ extern "C" int rnnwf_pauli_step(rnnwf_handle* h, const int32_t* flip, const int3
         return h->fail(RNNWF_ERR_INVALID, "rnnwf_pauli_step: flip, sign, coeff and term_sums must be non-null");
     if (!samples && sample_offset < 0) return h->fail(RNNWF_ERR_INVALID, "rnnwf_pauli_step: sample_offset must be >= 0");
     Terms g;
-    if (int rc = prepare(h, flip, sign, nterms, g)) return rc;
+    if (int rc = prepare_pauli_terms(h, "rnnwf_pauli_step", flip, sign, nterms, g)) return rc;
     const int N = h->N, K = nterms, M = g.M;
     // chains per pass: per block, beside the checkpoints, the terms (N x 16 x 8 bytes), log P (16 x 8), the tails and log-ratios
     // (2 x M x 16 x 8) and E_loc (16 x 8)
