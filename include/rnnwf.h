@@ -282,6 +282,35 @@ int rnnwf_renyi2_regions_2d(rnnwf_handle* h, const int32_t* regions, int32_t nre
                             uint64_t seed, uint64_t step, int64_t pair_offset, double* sums, double* out_log_ratio,
                             int32_t* out_samples);
 
+/* rnnwf_renyi2_regions_complex: the same estimator for the complex RNN with the U(1) mask (RNNWF_MODEL_CRNN_U1, one layer;
+ * docs/renyi_complex.md).  psi is complex, so is the estimator: with log psi the float64 sum of the per-site log-amplitudes and
+ * phases (the imaginary part is never reduced modulo 2 pi)
+ *   log r_A = [log psi(tau_A sigma_B) - log psi(sigma)] + [log psi(sigma_A tau_B) - log psi(tau)]   (no factor 1/2: log psi has it),
+ *   r_A = exp(Re)(cos Im + i sin Im),   exp(-S2(A)) = E[Re r_A],   E[Im r_A] = 0 exactly.
+ * Masks, normalisation (site 0 not in A), pairs (2p, 2p+1), device draws and the restart from the chain's own checkpoint at f - 1
+ * (the U(1) count restarts from the ups of its own sites below f) as rnnwf_renyi2_regions.  Both chains of a pair lie in the
+ * zero-magnetisation sector, so the two mixed chains do iff sigma and tau have the same number of ups in A; otherwise r_A = 0
+ * exactly and the pair's out_log_ratio entry is (-inf, 0).  Only the surviving pairs are evaluated, compacted into full 16-chain
+ * tiles: N - f cell evaluations per SURVIVING chain and non-empty region.  Passes under the state budget (whole pairs per pass),
+ * fixed-order sums without float atomics (a repeated call returns the same bits) and the resident-batch rule as
+ * rnnwf_renyi2_regions.  RNNWF_ERR_INVALID, before any work and without a launch: any model but CRNN_U1 (rnnwf_renyi2_regions serves
+ * the GRU models, rnnwf_renyi2_regions_2d the 2D RNN); stacked layers; nregions < 1 (or above 65535); npairs < 1; null regions or
+ * sums; a mask entry other than 0 / 1; pair_offset < 0 with device-drawn samples; a caller-supplied sample whose number of up spins
+ * is not N / 2.  Uncommitted parameters: RNNWF_ERR_STATE.  rnnwf_renyi2_swap and rnnwf_renyi2_regions keep refusing this model.
+ *   regions      (nregions, N) int32 of 0 / 1, 1 = site in A
+ *   samples      (2*npairs, N) int32 in the sector, pair p = rows (2p, 2p+1); nullptr: draw them on the device exactly as
+ *                rnnwf_sample(h, 2*npairs, seed, step, 2*pair_offset, ...) would (pair_offset ignored otherwise)
+ *   sums         (nregions, 4) f64: sum Re r_A, sum Im r_A, sum (Re r_A)^2, sum (Im r_A)^2  (required, additive over shards)
+ *   out_log_ratio(nregions, npairs, 2) f64 or nullptr: (Re, Im) of log r_A; (-inf, 0) for a pair outside the sector
+ *   out_in_sector(nregions) int64 or nullptr: the surviving pairs of every region (additive over shards); npairs for a region that
+ *                is empty or full
+ *   out_samples  (2*npairs, N) int32 or nullptr (drawn chains)
+ * Timing ids: 0 = base passes + site-term replay, 1 = survivor lists + paired tail pass, 2 = log-ratios, values and sums.  work[0]
+ * += sum over non-empty regions of (N - f) x surviving chains; work[1] += the MFMA flops of the tiles run (padding included). */
+int rnnwf_renyi2_regions_complex(rnnwf_handle* h, const int32_t* regions, int32_t nregions, const int32_t* samples, int64_t npairs,
+                                 uint64_t seed, uint64_t step, int64_t pair_offset, double* sums, double* out_log_ratio,
+                                 int64_t* out_in_sector, int32_t* out_samples);
+
 /* ---- correlation functions -------------------------------------------------------------------------
  * The reference README's "correlation functions" of the positive one-layer GRU models (GRU1D, GRU1D_F64; every other model
  * and stacked layers: RNNWF_ERR_INVALID), psi = sqrt(P), samples sigma ~ P, s = 2 sigma - 1 (docs/correlations.md):

@@ -69,6 +69,8 @@ PROTOTYPES = {
     "rnnwf_renyi2_swap": (C.c_int, [_P, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _I32P]),
     "rnnwf_renyi2_regions": (C.c_int, [_P, _I32P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _I32P]),
     "rnnwf_renyi2_regions_2d": (C.c_int, [_P, _I32P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _I32P]),
+    "rnnwf_renyi2_regions_complex": (C.c_int, [_P, _I32P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, C.POINTER(C.c_int64),
+                                               _I32P]),
     "rnnwf_correlations": (C.c_int, [_P, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "rnnwf_pauli_step": (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64P, _F64P, _F64P,
                                    _I32P]),
@@ -467,6 +469,38 @@ class NativeWavefunction:
                                                      sums.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
                                                      smp.ctypes.data_as(_I32P) if smp is not None else None))
         out = {"sums": sums}
+        if smp is not None:
+            out["samples"] = smp
+        if log_ratio:
+            out["log_ratio"] = lr
+        return out
+
+    def renyi2_regions_complex(self, regions, numpairs, samples=None, seed=111, step=0, pair_offset=0, log_ratio=False):
+        """renyi2_regions for the complex RNN (rnnwf_renyi2_regions_complex).  regions: (R, N) masks of 0 / 1 (or one mask of N
+        entries), 1 = site in A.  samples: (2 numpairs, N) int32 of the zero-magnetisation sector, pair p = rows 2p, 2p + 1; None:
+        drawn on the device as sample(2 numpairs, seed, step, 2 pair_offset) draws them.  Returns dict(sums=(R, 4) [sum Re r, sum
+        Im r, sum (Re r)^2, sum (Im r)^2], in_sector=(R,) int64 surviving pairs, samples=(2 numpairs, N) when drawn,
+        log_ratio=(R, numpairs) complex128 when asked, -inf + 0j for a pair whose mixed chains leave the sector)."""
+        npairs = int(numpairs)
+        reg = np.asarray(regions)
+        if reg.ndim == 1:
+            reg = reg[None, :]
+        if reg.ndim != 2 or reg.shape[0] < 1 or reg.shape[1] != self.N:
+            raise ValueError("regions must have shape (nregions >= 1, %d), got %r" % (self.N, reg.shape))
+        if not np.all(reg == reg.astype(np.int32)):
+            raise ValueError("regions must hold the integers 0 and 1")
+        reg, rp = _i32(reg)
+        R = reg.shape[0]
+        s, sp = self._chain_samples(samples, 2 * npairs, "2*numpairs")
+        sums = np.empty((R, 4), dtype=np.float64)
+        ins = np.empty(R, dtype=np.int64)
+        lr = np.empty((R, max(npairs, 0)), dtype=np.complex128) if log_ratio else None
+        smp = np.empty((2 * max(npairs, 0), self.N), dtype=np.int32) if samples is None else None
+        self._check(self.lib.rnnwf_renyi2_regions_complex(
+            self.h, rp, R, sp, npairs, int(seed), int(step), int(pair_offset), sums.ctypes.data_as(_F64P),
+            lr.ctypes.data_as(_F64P) if lr is not None else None, ins.ctypes.data_as(C.POINTER(C.c_int64)),
+            smp.ctypes.data_as(_I32P) if smp is not None else None))
+        out = {"sums": sums, "in_sector": ins}
         if smp is not None:
             out["samples"] = smp
         if log_ratio:

@@ -13,20 +13,20 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "librnnwf_hip.so")
-SOURCES = ["rnnwf_api.hip", "prnn.hip", "crnn.hip", "split.hip", "split_stream.hip", "mdrnn.hip", "grad.hip", "comm.hip", "train.hip", "grad_wide.hip", "lstm.hip", "renyi.hip", "corr.hip", "renyi_regions.hip", "pauli.hip", "mdrnn_pauli.hip", "mdrnn_renyi.hip", "crnn_pauli.hip"]
+SOURCES = ["rnnwf_api.hip", "prnn.hip", "crnn.hip", "split.hip", "split_stream.hip", "mdrnn.hip", "grad.hip", "comm.hip", "train.hip", "grad_wide.hip", "lstm.hip", "renyi.hip", "corr.hip", "renyi_regions.hip", "pauli.hip", "mdrnn_pauli.hip", "mdrnn_renyi.hip", "crnn_pauli.hip", "crnn_renyi.hip"]
 # no SLP packing of adjacent f32 adds / fmas into v_pk_*_f32 in the bf16x3 engine's translation unit: packed-f32 (and v_dot2)
 # instructions stall behind bf16 MFMAs - their own wave's AND the SIMD partner's (measured: tools/microbench/issue_model,
 # a VALU segment with packed ops beside an MFMA partner 5 170 vs 3 337 cycles).  The f32-input-MFMA kernels keep it.
 # train.hip (device-side Adam and image re-pack) must round every operation on its own, as NumPy and the host packers do: no
 # contraction into fused multiply-adds (HIP's __dmul_rn / __dadd_rn are plain operators and were fused under -ffp-contract=fast;
 # found by tests/test_gpu_training.py: test_device_adam_step_and_checkpointed_state)
-# prnn.hip / crnn.hip / renyi.hip / corr.hip / renyi_regions.hip / pauli.hip / crnn_pauli.hip: the streamed-weight products of the 133..260-unit kernels (gru_core.h: mfma_streamed, 160 k-groups x 5 tiles) must
+# prnn.hip / crnn.hip / renyi.hip / corr.hip / renyi_regions.hip / pauli.hip / crnn_pauli.hip / crnn_renyi.hip: the streamed-weight products of the 133..260-unit kernels (gru_core.h: mfma_streamed, 160 k-groups x 5 tiles) must
 # unroll completely - their fragment ring is indexed by the loop counter.  Past clang's default size budget for `#pragma unroll` the loop
 # stayed rolled, the ring went to scratch memory and the 260-unit flip pass ran at 587 ms per config-2-sized step instead of 95
 # (profiles/r04_m_wide_widths.txt); the budget is raised for these two translation units.
 WIDE_UNROLL = ["-mllvm", "-pragma-unroll-threshold=400000"]
 PER_SOURCE_FLAGS = {"split.hip": ["-fno-slp-vectorize"], "split_stream.hip": ["-fno-slp-vectorize"], "train.hip": ["-ffp-contract=off"],
-                    "prnn.hip": WIDE_UNROLL, "crnn.hip": WIDE_UNROLL, "renyi.hip": WIDE_UNROLL, "corr.hip": WIDE_UNROLL, "renyi_regions.hip": WIDE_UNROLL, "pauli.hip": WIDE_UNROLL, "crnn_pauli.hip": WIDE_UNROLL,
+                    "prnn.hip": WIDE_UNROLL, "crnn.hip": WIDE_UNROLL, "renyi.hip": WIDE_UNROLL, "corr.hip": WIDE_UNROLL, "renyi_regions.hip": WIDE_UNROLL, "pauli.hip": WIDE_UNROLL, "crnn_pauli.hip": WIDE_UNROLL, "crnn_renyi.hip": WIDE_UNROLL,
                     "grad_wide.hip": WIDE_UNROLL}
 # the 100-unit bf16x3 kernel keeps its 160 accumulator registers in AGPRs (a wave addresses 256 VGPRs + 256 AGPRs; its
 # other live values need ~210 VGPRs): no -amdgpu-mfma-vgpr-form for its translation unit

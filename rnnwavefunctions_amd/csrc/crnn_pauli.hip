@@ -13,8 +13,8 @@
 #include <cstring>
 #include <vector>
 
+#include "crnn_observable.h"
 #include "crnn_pauli_kernels.h"
-#include "observable.h"
 #include "pauli_terms.h"
 
 using namespace rnnwf;
@@ -22,29 +22,6 @@ using namespace rnnwf;
 namespace {
 
 const char* const kEntry = "rnnwf_pauli_step_complex";
-
-template <int NFULL_, int WAVES_>
-struct CPauliLaunch {
-    using L = GruLayout<float, NFULL_, 3>;
-    static constexpr int NFULL = NFULL_, WAVES = WAVES_;
-    static double mfma_flops_per_step() { return (double)L::NT * L::KT * 2048.0; }
-};
-
-// the one-layer rows of crnn.hip's with_launch, with its waves per workgroup
-template <class Fn>
-bool with_crnn1(const rnnwf_handle* h, Fn&& fn) {
-    switch (h->NFULL) {
-        case 1: fn(CPauliLaunch<1, 4>()); return true;
-        case 2: fn(CPauliLaunch<2, 4>()); return true;
-        case 3: fn(CPauliLaunch<3, 4>()); return true;
-        case 4: fn(CPauliLaunch<4, 4>()); return true;
-        case 6: fn(CPauliLaunch<6, 8>()); return true;
-        case 8: fn(CPauliLaunch<8, 4>()); return true;
-        case 12: fn(CPauliLaunch<12, 4>()); return true;
-        case 16: fn(CPauliLaunch<16, 4>()); return true;
-    }
-    return false;
-}
 
 using Terms = PauliTerms;
 
@@ -71,12 +48,6 @@ struct Scratch {
         bytes = c.bytes;
     }
 };
-
-// whole 16-chain blocks per pass within the state budget: per block the checkpoints and the pass's `bytes_per_block` beside them
-int64_t crnn_blocks_per_pass(rnnwf_handle* h, size_t bytes_per_block) {
-    const size_t per_block = (size_t)std::max(h->N - 1, 1) * crnn_hck_bytes_per_block(h) + bytes_per_block;
-    return std::max<int64_t>(1, (int64_t)(state_budget_bytes(h, kDefaultStateBudget) / per_block));
-}
 
 // one pass over the ns chains packed in h->bits: sums_host (K, 4) of this pass; the log-ratios stay in h->renyi, E_loc in h->eloc
 // keep: the pass is the whole call, its checkpoints are left for rnnwf_vmc_gradient (diagonal terms alone need no base pass otherwise)
@@ -144,11 +115,6 @@ int pauli_pass(rnnwf_handle* h, int64_t ns, const Terms& g, const Scratch& sc, b
     return 0;
 }
 
-const char* model_name(int model) {
-    static const char* const names[] = {"GRU1D", "GRU1D_PARITY", "CRNN_U1", "GRU1D_F64", "MDRNN2D", "LSTM1D_F64"};
-    return model >= 0 && model < (int)(sizeof names / sizeof *names) ? names[model] : "unknown";
-}
-
 }  // namespace
 
 extern "C" int rnnwf_pauli_step_complex(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff_re_im, int32_t nterms,
@@ -170,13 +136,7 @@ extern "C" int rnnwf_pauli_step_complex(rnnwf_handle* h, const int32_t* flip, co
     if (!samples && sample_offset < 0) return h->fail(RNNWF_ERR_INVALID, "%s: sample_offset must be >= 0", kEntry);
     if (h->N < 2) return h->fail(RNNWF_ERR_INVALID, "%s: needs a chain of at least two sites", kEntry);
     if (samples)                                      // the caller's chains must lie in the sector: their own log psi is -inf otherwise
-        for (int64_t s = 0; s < ns; ++s) {
-            int up = 0;
-            for (int n = 0; n < h->N; ++n) up += samples[s * h->N + n] != 0;
-            if (up != h->N / 2)
-                return h->fail(RNNWF_ERR_INVALID, "%s: samples[%lld] has %d up spins, the zero-magnetisation sector has %d", kEntry, (long long)s,
-                               up, h->N / 2);
-        }
+        if (int rc = crnn_check_sector(h, kEntry, samples, ns)) return rc;
     Terms g;
     if (int rc = prepare_pauli_terms(h, kEntry, flip, sign, nterms, g)) return rc;
     const int N = h->N, K = nterms, M = g.M;

@@ -73,6 +73,28 @@ __global__ void __launch_bounds__(WAVES * 64) crnn_site_terms_kernel(CPauliArgs 
     }
 }
 
+// Sites n0..N-1 teacher-forced from state h, input spin sig_in and num_up ups below n0: the f64 sums of the sites' log-amplitudes
+// and phases (teacher_forced_tail for the complex cell; shared with crnn_paired_tail_kernel of crnn_renyi_kernels.h).  The base
+// pass's step form (step<true>, bias last) and head.
+template <class C, class NextSpin>
+__device__ __forceinline__ double2 crnn_teacher_forced_tail(const char* img, float (&h)[C::KT], int sig_in, int num_up, int n0, int N, int lane,
+                                                            NextSpin&& next_spin) {
+    double re = 0.0, im = 0.0;
+    for (int n = n0; n < N; ++n) {
+        const int sig = next_spin(n);
+        C::template step<true>(img, sig_in, h, lane);
+        float z[3];
+        C::head(img, h, lane, z);
+        float la0, la1, w0, ph0, ph1;
+        crnn_site(z, n, N, num_up, la0, la1, w0, ph0, ph1);
+        re += (double)(sig ? la1 : la0);                     // -inf from the site where the count overshoots, and stays -inf
+        im += (double)(sig ? ph1 : ph0);
+        num_up += sig;
+        sig_in = sig;
+    }
+    return make_double2(re, im);
+}
+
 template <int NFULL, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) crnn_masked_tail_kernel(CPauliArgs a) {
     using C = GruCore<float, NFULL, 3>;
@@ -106,21 +128,11 @@ __global__ void __launch_bounds__(WAVES * 64) crnn_masked_tail_kernel(CPauliArgs
         // 32 sites of the flipped chain at once, the mask word the same for the whole wave.  Bit 0 of `word` is the next site's spin.
         uint32_t word = (a.bits[(int64_t)(g >> 5) * a.ns + sc] ^ mrow[g >> 5]) >> (g & 31);
         int sig_in = f > 0 ? (int)(word & 1) : -1;
-        double re = 0.0, im = 0.0;
-        for (int n = f; n < N; ++n) {
+        const double2 lpsi = crnn_teacher_forced_tail<C>(img, h, sig_in, num_up, f, N, w.lane, [&](int n) {
             word = (n & 31) ? word >> 1 : a.bits[(int64_t)(n >> 5) * a.ns + sc] ^ mrow[n >> 5];
-            const int sig = (int)(word & 1);
-            C::template step<true>(img, sig_in, h, w.lane);      // the base pass's step form (bias last) and head
-            float z[3];
-            C::head(img, h, w.lane, z);
-            float la0, la1, w0, ph0, ph1;
-            crnn_site(z, n, N, num_up, la0, la1, w0, ph0, ph1);
-            re += (double)(sig ? la1 : la0);                     // -inf from the site where the count overshoots, and stays -inf
-            im += (double)(sig ? ph1 : ph0);
-            num_up += sig;
-            sig_in = sig;
-        }
-        if (s < a.ns && w.q == 0) a.tail[(int64_t)r * a.ns + s] = make_double2(re, im);
+            return (int)(word & 1);
+        });
+        if (s < a.ns && w.q == 0) a.tail[(int64_t)r * a.ns + s] = lpsi;
     }
 }
 

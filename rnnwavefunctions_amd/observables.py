@@ -115,7 +115,12 @@ def mutual_information2_from_log_ratios(lr_a, lr_b, lr_ab):
     each).  With m the means of r: I2 = -log m_A - log m_B + log m_AB; the error by the delta method on the per-pair values
     g = -r_A / m_A - r_B / m_B + r_AB / m_AB:  err = std(g) / sqrt(n)  (population std; the three estimates share their pairs, so
     their errors do not add in quadrature)."""
-    ra, rb, rab = (np.exp(np.asarray(v, dtype=np.float64)) for v in (lr_a, lr_b, lr_ab))
+    return mutual_information2_from_values(*(np.exp(np.asarray(v, dtype=np.float64)) for v in (lr_a, lr_b, lr_ab)))
+
+
+def mutual_information2_from_values(r_a, r_b, r_ab):
+    """The same from the per-pair values r themselves (observables_complex passes Re r of the complex estimator)."""
+    ra, rb, rab = (np.asarray(v, dtype=np.float64) for v in (r_a, r_b, r_ab))
     if ra.ndim != 1 or ra.shape != rb.shape or ra.shape != rab.shape or ra.size < 1:
         raise ValueError("the three log-ratio arrays must be one-dimensional, of the same length >= 1")
     ma, mb, mab = ra.mean(), rb.mean(), rab.mean()

@@ -1,5 +1,7 @@
 """Pauli-string expectation values, energies of arbitrary spin-1/2 Hamiltonians, spin-spin correlations and the structure factor
-for the complex RNN with the U(1) mask (model CRNN_U1, one layer; rnnwf_pauli_step_complex, docs/pauli_complex.md).
+for the complex RNN with the U(1) mask (model CRNN_U1, one layer; rnnwf_pauli_step_complex, docs/pauli_complex.md), and its second
+Renyi entropies of arbitrary regions, their mutual information and their resolution by the U(1) charge of the region
+(rnnwf_renyi2_regions_complex, docs/renyi_complex.md; the region builders are observables.interval_region and its kin).
 
 The term convention is observables.py's, O = (prod_{i in S} sz_i)(prod_{i in F} sx_i) with sz to the left; with sigma ~ |psi|^2 and
 s = 2 sigma - 1 the estimator is complex:
@@ -17,10 +19,11 @@ import warnings
 import numpy as np
 
 from . import _lib
-from .observables import _native, group_by_mask, pauli_terms
+from .observables import _disjoint_masks, _native, group_by_mask, mutual_information2_from_values, pauli_terms
 
 __all__ = ["ComplexHamiltonian", "pauli_expectations", "energy", "j1j2_hamiltonian", "spin_correlation_terms", "spin_correlations",
-           "structure_factor", "minimize_hamiltonian"]
+           "structure_factor", "minimize_hamiltonian", "renyi2_from_sums", "renyi2_regions", "renyi2_entropy",
+           "renyi2_mutual_information", "symmetry_resolved_renyi2"]
 
 
 def _native_complex(wf):
@@ -220,3 +223,109 @@ def minimize_hamiltonian(wf, ham, numsamples, steps, lr, params=None, seed=111, 
         facade.set_params(params)
     minimize_hamiltonian.last_params = params
     return meanEnergy, varEnergy
+
+
+# ---- second Renyi entropy (rnnwf_renyi2_regions_complex, docs/renyi_complex.md) ---------------------------------------------------
+# For pairs (sigma, tau) drawn independently from |psi|^2 the swap estimator is complex,
+#     r_A = psi(tau_A sigma_B) psi(sigma_A tau_B) / (psi(sigma) psi(tau)),   exp(-S2(A)) = E[Re r_A],   E[Im r_A] = 0,
+# and r_A = 0 exactly unless sigma and tau carry the same number of ups in A (the mixed chains leave the sector otherwise).
+
+def renyi2_from_sums(sums, numpairs):
+    """From the (R, 4) sums [sum Re r, sum Im r, sum (Re r)^2, sum (Im r)^2] of numpairs pairs: {"S2": -log(mean Re r) (R,), "err":
+    std(Re r) / (sqrt(n) mean Re r) (first-order error propagation), "imag": mean Im r, "err_imag": its standard error}.  The exact
+    mean of Im r is 0: "imag" within a few "err_imag" is a check of the sample, not a result.  A region whose mean is not positive
+    gives nan."""
+    t = np.asarray(sums, dtype=np.float64)
+    n = float(numpairs)
+    if t.ndim != 2 or t.shape[1] != 4 or n < 1:
+        raise ValueError("sums must have shape (R, 4) and numpairs be >= 1")
+    re, im = t[:, 0] / n, t[:, 1] / n
+    var_re, var_im = np.maximum(t[:, 2] / n - re * re, 0.0), np.maximum(t[:, 3] / n - im * im, 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        S2 = np.where(re > 0.0, -np.log(np.where(re > 0.0, re, 1.0)), np.nan)
+        err = np.where(re > 0.0, np.sqrt(var_re) / (np.sqrt(n) * np.where(re > 0.0, re, 1.0)), np.nan)
+    return {"S2": S2, "err": err, "imag": im, "err_imag": np.sqrt(var_im / n)}
+
+
+def _pairs(nat, samples, numpairs):
+    return None if samples is None else np.asarray(samples).reshape(2 * int(numpairs), nat.N)
+
+
+def renyi2_regions(wf, regions, numpairs, seed=111, step=0, samples=None, want_log_ratio=False):
+    """Second Renyi entropy S2(A) of the regions `regions` ((R, N) masks of 0 / 1, or one mask; observables.interval_region builds
+    them) from `numpairs` pairs of independent samples of the complex RNN `wf`: the dict of renyi2_from_sums plus "survivors" (R,),
+    the fraction of the pairs whose mixed chains stay in the zero-magnetisation sector (the only ones that cost anything), and, with
+    want_log_ratio, "log_ratio" (R, numpairs) complex128 (-inf + 0j outside the sector) and "samples" (2 numpairs, N).  samples:
+    (2 numpairs, N) spins of the sector, pair p = rows 2p and 2p + 1; None draws them on the device from (seed, step)."""
+    nat = _native_complex(wf)
+    s = _pairs(nat, samples, numpairs)
+    out = nat.renyi2_regions_complex(regions, int(numpairs), samples=s, seed=seed, step=step, log_ratio=want_log_ratio)
+    res = renyi2_from_sums(out["sums"], numpairs)
+    res["survivors"] = out["in_sector"] / float(numpairs)
+    if want_log_ratio:
+        res["log_ratio"] = out["log_ratio"]
+        res["samples"] = out["samples"] if s is None else s
+    return res
+
+
+def renyi2_entropy(wf, numpairs, seed=111, step=0, samples=None):
+    """renyi2_regions of the N - 1 cuts of the chain: row l - 1 is A = the first l sites, l = 1..N-1."""
+    nat = _native_complex(wf)
+    cuts = (np.arange(nat.N)[None, :] < np.arange(1, nat.N)[:, None]).astype(np.int32)
+    return renyi2_regions(nat, cuts, numpairs, seed=seed, step=step, samples=samples)
+
+
+def renyi2_mutual_information(wf, region_a, region_b, numpairs, seed=111, step=0, samples=None):
+    """Renyi-2 mutual information I2(A : B) = S2(A) + S2(B) - S2(A u B) of two DISJOINT regions (masks of N entries) and its standard
+    error by the delta method on the shared pairs (observables.mutual_information2_from_values on Re r); A, B and A u B run in one
+    call.  Overlapping regions raise ValueError."""
+    a, b = _disjoint_masks(region_a, region_b)
+    nat = _native_complex(wf)
+    out = nat.renyi2_regions_complex(np.stack([a, b, a | b]), int(numpairs), samples=_pairs(nat, samples, numpairs), seed=seed, step=step,
+                                     log_ratio=True)
+    return mutual_information2_from_values(*_ratio(out["log_ratio"]).real)
+
+
+def _ratio(log_ratio):
+    """exp of complex log-ratios, exactly 0 where the real part is -inf"""
+    lr = np.asarray(log_ratio, dtype=np.complex128)
+    zero = np.isneginf(lr.real)
+    return np.where(zero, 0.0, np.exp(np.where(zero, 0.0, lr)))
+
+
+def symmetry_resolved_renyi2(log_ratio_row, samples, region):
+    """The second Renyi entropy of region A resolved by the U(1) charge q = number of ups in A, from the per-pair log r_A of ONE
+    region ((n,) complex, the "log_ratio" row of renyi2_regions), the pairs' spins ((2 n, N), pair p = rows 2p, 2p + 1) and the mask
+    of A as it was asked for ((N,) of 0 / 1).  rho_A is block-diagonal in q; with q_p the charge of sigma_p (equal to tau_p's in every
+    pair that survives)
+
+        p_q = P(q) = E[(1(q_sigma = q) + 1(q_tau = q)) / 2],   Tr rho_A(q)^2 = E[Re r 1(q_sigma = q)],
+        S2(q) = -log(Tr rho_A(q)^2 / p_q^2)
+
+    for q = 0..|A|: {"q", "p", "p_err", "trace", "trace_err", "S2", "S2_err"}, each (|A| + 1,).  sum_q trace = mean Re r, the total.
+    S2_err by the delta method on g = -t / trace + 2 u / p of the per-pair values t, u.  A charge that no chain shows, or whose
+    estimated trace is not positive, has S2 = nan."""
+    lr = np.asarray(log_ratio_row, dtype=np.complex128)
+    m = np.asarray(region)
+    s = np.asarray(samples)
+    if lr.ndim != 1 or lr.size < 1 or m.ndim != 1 or not np.all((m == 0) | (m == 1)) or s.shape != (2 * lr.size, m.size):
+        raise ValueError("symmetry_resolved_renyi2 needs log r of n >= 1 pairs, samples (2 n, N) and a mask of N entries of 0 / 1")
+    n = lr.size
+    re = _ratio(lr).real
+    qs = s[0::2][:, m == 1].sum(axis=1)
+    qt = s[1::2][:, m == 1].sum(axis=1)
+    if np.any((re != 0.0) & (qs != qt)):
+        raise ValueError("a pair with r != 0 carries different charges in the region: log_ratio_row, samples and region do not belong together")
+    nq = int(m.sum()) + 1
+    out = {k: np.full(nq, np.nan) for k in ("p", "p_err", "trace", "trace_err", "S2", "S2_err")}
+    out["q"] = np.arange(nq)
+    for q in range(nq):
+        t = re * (qs == q)
+        u = 0.5 * ((qs == q).astype(np.float64) + (qt == q))
+        tr, p = t.mean(), u.mean()
+        out["p"][q], out["p_err"][q] = p, u.std() / np.sqrt(n)
+        out["trace"][q], out["trace_err"][q] = tr, t.std() / np.sqrt(n)
+        if p > 0.0 and tr > 0.0:
+            out["S2"][q] = -np.log(tr / (p * p))
+            out["S2_err"][q] = (-t / tr + 2.0 * u / p).std() / np.sqrt(n)
+    return out
