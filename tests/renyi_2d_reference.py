@@ -9,7 +9,8 @@ and scored from position 0, without normalisation, first position, state reuse, 
 what mdrnn_masked_tail_kernel<..., PAIRED = true> and the assembly compute - the mask mapped to visit order and normalised, restart at
 the first position f of the path, states <= f reused, every position > f recomputed - with switches for the defects whose rejection by
 the bound the CPU test shows.  Also the weights, regions and region pairs the exact and statistical GPU tests share
-(tests/test_gpu_renyi_2d.py).
+(tests/test_gpu_renyi_2d.py), and the regions and coverage rules of the full-size cases on lattices of three to eight spin words
+(tests/test_gpu_renyi_2d_full.py).
 """
 import numpy as np
 
@@ -72,6 +73,7 @@ def normalise(mask_visit):
 
 
 DEFECTS = ("lattice_order", "partner_is_self", "partner_after_f", "partner_state", "vertical_from_hs", "mask_word_0")
+WORD_DEFECTS = Q.WORD_DEFECTS + ("partner_words_from_2_own",)      # invisible on lattices of at most 64 sites (two words)
 
 
 def kernel_form(prm, pairs, masks, defect=None):
@@ -83,8 +85,13 @@ def kernel_form(prm, pairs, masks, defect=None):
       "partner_state"     the chain restarts from the PARTNER's state after position f
       "vertical_from_hs"  the vertical state of every position taken from the base pass, also where f < pv
       "mask_word_0"       the mask words of positions >= 32 read from word 0
+      "word_index_mod_2"  word (p >> 5) & 1 of the mixed configuration read for the own, horizontal and vertical spin of position p
+      "words_from_2_zero" the mask words >= 2 (positions >= 64) read as 0
+      "partner_words_from_2_own"  the partner's spin words >= 2 taken from the chain itself (another place of the kernel's line than
+                          "words_from_2_zero", the same mixed chain: own spins from position 64 on)
+    The last three (WORD_DEFECTS) are invisible on lattices of at most 64 sites.
     """
-    assert defect is None or defect in DEFECTS
+    assert defect is None or defect in DEFECTS + WORD_DEFECTS
     pairs = np.asarray(pairs)
     B, Nx, Ny = pairs.shape
     N = Nx * Ny
@@ -93,6 +100,8 @@ def kernel_form(prm, pairs, masks, defect=None):
     zeros_h, rows = np.zeros((B, H)), np.arange(B)
     spins = np.stack([pairs[:, nx, ny] for nx, ny, _ in order], axis=1)        # (B, N) in visit order
     partner = spins if defect == "partner_is_self" else spins[rows ^ 1]
+    if defect == "partner_words_from_2_own":
+        partner = np.where(np.arange(N)[None, :] < 64, partner, spins)
     row_first = [p % Nx == 0 for p in range(N)]
     vert = [-1 if ny == 0 else (ny - 1) * Nx + (nx if (ny - 1) % 2 == 0 else Nx - 1 - nx) for nx, ny, _ in order]
     one_hot = lambda s: np.eye(2)[s]
@@ -116,7 +125,11 @@ def kernel_form(prm, pairs, masks, defect=None):
             mv = (np.arange(N) >= f).astype(np.int64)
         elif defect == "mask_word_0":
             mv = mv[np.arange(N) & 31]
+        elif defect == "words_from_2_zero":
+            mv = np.where(np.arange(N) < 64, mv, 0)
         sp = np.where(mv[None, :].astype(bool), partner, spins)
+        if defect == "word_index_mod_2":
+            sp = sp[:, Q.word_index_mod_2(N)]
         start = hs[f][rows ^ 1] if defect == "partner_state" else hs[f]
         mine = {f: start}
         tail = Q._head(prm, start)[rows, sp[:, f]]
@@ -185,3 +198,91 @@ def i2_pairs(Nx, Ny):
     if (Nx, Ny) == (4, 3):
         out.append((mask_of(Nx, Ny, [(0, 0), (0, 1)]), mask_of(Nx, Ny, [(3, 2), (3, 1)])))
     return out
+
+
+# ---- full-size cases: lattices of three to eight spin words (tests/test_gpu_renyi_2d_full.py) ------------------------------------------
+
+def bulk_positions(Nx, Ny):
+    """The positions of the path whose site has four neighbours."""
+    return [p for p, (nx, ny, _) in enumerate(M.zigzag_order(Nx, Ny)) if 0 < nx < Nx - 1 and 0 < ny < Ny - 1]
+
+
+def bulk_block(Nx, Ny):
+    """(x0, y0, L) of the centred L x L block that touches no edge, L = max(2, min(Nx, Ny) // 3)."""
+    L = max(2, min(Nx, Ny) // 3)
+    return (Nx - L) // 2, (Ny - L) // 2, L
+
+
+def region_set_2d(Nx, Ny, fill=Q.MIN_MASKS, thin=False):
+    """[(name, lattice-indexed region)] of a full-size case, distinct: every row cut (the prefixes of the path) and column cut, the 2x2
+    corner block (lattice site 0 in it: complemented by the driver), a bulk L x L block, two separated pieces, lattice site 0 with
+    the far corner, a single bulk site in every word that holds one, the empty and the full region, and pauli_2d_reference's
+    word_masks_2d read as regions (single sites on bit 0 and the last bit of every word - position 0 alone is complemented -, first
+    position N-1, a run and a vertical pair across every word boundary, a horizontal pair, (1, N-2), the checkerboard, the second
+    half); then single sites spread evenly over the remaining positions until `fill` regions are non-empty after normalisation
+    (the tiles of the paired pass).  thin: without the filler (the CPU study's set)."""
+    N = Nx * Ny
+    out = [("row cut %d" % c, m) for c, m in enumerate(row_cuts(Nx, Ny), start=1)]
+    out += [("column cut %d" % c, m) for c, m in enumerate(column_cuts(Nx, Ny), start=1)]
+    x0, y0, L = bulk_block(Nx, Ny)
+    out += [("2x2 corner block", rectangle(Nx, Ny, 0, 2, 0, 2)), ("bulk %dx%d block at (%d,%d)" % (L, L, x0, y0), rectangle(Nx, Ny, x0, x0 + L, y0, y0 + L)),
+            ("two pieces", rectangle(Nx, Ny, 1, 2, 1, 3) | rectangle(Nx, Ny, Nx - 2, Nx - 1, Ny - 3, Ny - 1)),
+            ("site 0 and the far corner", mask_of(Nx, Ny, [(0, 0), (Nx - 1, Ny - 1)]))]
+    bulk = bulk_positions(Nx, Ny)
+    for w in range(Q.num_words(N)):
+        inside = [p for p in bulk if p >> 5 == w]
+        if inside:
+            out.append(("bulk site at position %d (word %d)" % (inside[0], w), Q.from_positions(Nx, Ny, inside[:1])))
+    out += [("empty", np.zeros(N, dtype=np.int32)), ("full", np.ones(N, dtype=np.int32))]
+    out = Q._distinct(out + Q.word_masks_2d(Nx, Ny))
+    if not thin:
+        have = {int(np.flatnonzero(Q.to_visit_order(m, Nx, Ny))[0]) for _, m in out if m.sum() == 1}
+        rest = [p for p in range(N) if p not in have]
+        out += [("position %d (filler)" % p, Q.from_positions(Nx, Ny, [p])) for p in Q._spread(rest, fill - (len(out) - 2))]      # but empty, full
+    return Q._distinct(out)
+
+
+def _pieces(mask, Nx, Ny):
+    """The sizes of the 4-connected components of a lattice-indexed mask."""
+    left = {(k // Ny, k % Ny) for k in np.flatnonzero(mask)}
+    sizes = []
+    while left:
+        todo, n = [left.pop()], 0
+        while todo:
+            nx, ny = todo.pop()
+            n += 1
+            for nb in ((nx + 1, ny), (nx - 1, ny), (nx, ny + 1), (nx, ny - 1)):
+                if nb in left:
+                    left.remove(nb)
+                    todo.append(nb)
+        sizes.append(n)
+    return sorted(sizes)
+
+
+def check_case_2d(Nx, Ny, masks):
+    """The coverage a full-size region set must have, asserted on the masks themselves: pauli_2d_reference.check_case_2d's word
+    coverage on the normalised masks, and a member of every kind region_set_2d names."""
+    N = Nx * Ny
+    masks = np.asarray(masks)
+    Q.check_case_2d(Nx, Ny, masks, regions=True)
+    have = {m.tobytes() for m in masks}
+    for m in row_cuts(Nx, Ny) + column_cuts(Nx, Ny) + [rectangle(Nx, Ny, 0, 2, 0, 2), np.zeros(N, dtype=np.int32), np.ones(N, dtype=np.int32)]:
+        assert m.astype(masks.dtype).tobytes() in have, "a row cut, a column cut, the 2x2 corner, the empty or the full region is missing"
+    prefixes = {m.tobytes() for m in Q.to_visit_order(masks, Nx, Ny)}
+    assert all((np.arange(N) < c * Nx).astype(masks.dtype).tobytes() in prefixes for c in range(1, Ny)), "the row cuts are not the prefixes"
+    blocks, two, bulk_words = False, False, set()
+    bulk = set(bulk_positions(Nx, Ny))
+    for m, mv in zip(masks, Q.to_visit_order(masks, Nx, Ny)):
+        grid = m.reshape(Nx, Ny)
+        xs, ys = np.flatnonzero(grid.any(axis=1)), np.flatnonzero(grid.any(axis=0))
+        if m.any() and len(xs) == len(ys) == xs[-1] - xs[0] + 1 == ys[-1] - ys[0] + 1 >= 2 and m.sum() == len(xs) * len(ys):
+            blocks = blocks or (xs[0] > 0 and ys[0] > 0 and xs[-1] < Nx - 1 and ys[-1] < Ny - 1)      # a filled square off every edge
+        sizes = _pieces(m, Nx, Ny)
+        two = two or (len(sizes) == 2 and sizes[0] >= 2 and not m[0])
+        if m.sum() == 1 and int(np.flatnonzero(mv)[0]) in bulk:
+            bulk_words.add(int(np.flatnonzero(mv)[0]) >> 5)
+    assert blocks, "no bulk L x L block"
+    assert two, "no region of two separated pieces"
+    assert bulk_words == {p >> 5 for p in bulk}, "a word with a bulk site has no single bulk site"
+    assert any(m[0] and not m.all() for m in masks), "no region contains lattice site 0"
+    assert any(normalise(mv)[1] == N - 1 for mv in Q.to_visit_order(masks, Nx, Ny)), "no region starts at position N-1"

@@ -1,5 +1,7 @@
 """CPU validation of tests/pauli_2d_reference.py (the float64 restatement of the 2D RNN's masked-tail form) and the defect study
 behind the GPU bound 1e-11 N: which errors of the pass the bound rejects."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -71,3 +73,68 @@ def test_exact_strings_are_not_vacuous():
     psi = np.exp(0.5 * M.mdrnn_log_probability(prm, c.reshape(-1, Nx, Ny)))
     for st in [[("X", 0)], [("Y", 1), ("Y", 4)], [("Z", 0), ("X", 5)], [("Y", 0), ("Z", 2), ("Y", 3), ("X", 4)]]:
         assert abs(Q.string_expectation(psi, c, st) - (psi @ PR.dense_string({i: p for p, i in st}, 6) @ psi).real) < 1e-14
+
+
+# ---- lattices of three to eight spin words: what tests/test_gpu_pauli_2d_full.py rests on -------------------------------------------------
+FULL_LATTICES = [(13, 5), (5, 13), (9, 11), (12, 12), (16, 16)]             # the lattices of the full-size GPU cases
+FULL_SCALE = 0.75
+
+
+def test_full_size_mask_sets_cover_what_the_cases_promise():
+    for Nx, Ny in FULL_LATTICES:
+        N = Nx * Ny
+        names, masks = zip(*Q.mask_set_2d(Nx, Ny))
+        Q.check_case_2d(Nx, Ny, masks)
+        assert len(set(names)) == len(names)
+        thin = np.stack([m for _, m in Q.mask_set_2d(Nx, Ny, thin=True)])
+        assert {m.tobytes() for m in thin} <= {m.tobytes() for m in masks}
+        # the strings: Z and Y letters on positions of every word, a Z in the last word with an X in word 0, a YY bond across a word
+        # boundary, one string of odd n_Y
+        strings = Q.sign_strings_2d(Nx, Ny)
+        flip, sign, factor = O.pauli_terms(strings, N)
+        fv, sv = Q.to_visit_order(flip, Nx, Ny), Q.to_visit_order(sign, Nx, Ny)
+        W = Q.num_words(N)
+        words_of = lambda row: {int(p) >> 5 for p in np.flatnonzero(row)}
+        assert set().union(*[words_of(r) for r in sv]) == set(range(W)) and set().union(*[words_of(r & f) for r, f in zip(sv, fv)]) == set(range(W))
+        assert any(W - 1 in words_of(r & ~f) and 0 in words_of(f & ~r) for r, f in zip(sv, fv))
+        assert any(r[b - 1] and r[b] and f[b - 1] and f[b] for r, f in zip(sv, fv) for b in range(32, N, 32))
+        assert np.sum(factor.imag != 0) == 1 and factor[-1].imag != 0
+        print("%dx%d: %d masks (%d thin), %d strings" % (Nx, Ny, len(masks), len(thin), len(strings)))
+    assert len(Q.mask_set_2d(12, 12)) >= Q.MIN_MASKS and Q.MIN_MASKS * ((2006 + 15) // 16) >= 16384
+    with pytest.raises(AssertionError):                              # the set of the existing cases has no single site per word edge
+        Q.check_case_2d(5, 7, Q.case_masks(5, 7))
+
+
+@functools.lru_cache(maxsize=None)
+def full_setup(Nx, Ny, ns=8):
+    """10 units, chains drawn by the oracle, the thinned mask set; the brute-force reference computed once per lattice.  Kernels
+    x 0.75: at x 1 ten elu units run away on flipped configurations and the float64 reference is -inf on 16x16"""
+    prm = Q.weights(10, 111, FULL_SCALE)
+    s, _ = M.mdrnn_sample(prm, Nx, Ny, np.random.RandomState(Nx + 10 * Ny).random_sample((ns, Nx * Ny)))
+    masks = np.stack([m for _, m in Q.mask_set_2d(Nx, Ny, thin=True)])
+    ref = Q.explicit_log_ratio(lambda x: M.mdrnn_log_probability(prm, x), s, masks)
+    ref.setflags(write=False)
+    return prm, s, masks, ref
+
+
+@pytest.mark.parametrize("Nx,Ny", FULL_LATTICES)
+def test_kernel_form_is_the_explicit_log_ratio_on_three_to_eight_words(Nx, Ny):
+    prm, s, masks, ref = full_setup(Nx, Ny)
+    err = np.abs(Q.kernel_form(prm, s, masks) - ref).max()
+    print("%dx%d: %d masks, max |kernel form - explicit| = %.2e, max |log r| = %.2f" % (Nx, Ny, len(masks), err, np.abs(ref).max()))
+    assert np.all(np.isfinite(ref)) and err <= Q.BOUND * Nx * Ny and np.abs(ref).max() > 0.1
+
+
+# the defects of the word index that only a third word shows: none moves a bit on 5x7 (two words), each is rejected by the bound of the
+# full-size cases by at least three orders of magnitude on three, five and eight words
+@pytest.mark.parametrize("defect", Q.WORD_DEFECTS)
+def test_word_defects_are_invisible_on_two_words_and_rejected_from_three(defect):
+    prm, s, masks, ref = full_setup(5, 7)
+    assert np.array_equal(Q.kernel_form(prm, s, masks, defect=defect), Q.kernel_form(prm, s, masks))
+    assert np.array_equal(Q.kernel_form(prm, s, Q.case_masks(5, 7), defect=defect), Q.kernel_form(prm, s, Q.case_masks(5, 7)))
+    for Nx, Ny in [(13, 5), (12, 12), (16, 16)]:
+        prm, s, masks, ref = full_setup(Nx, Ny)
+        err = np.abs(Q.kernel_form(prm, s, masks, defect=defect) - ref).max()
+        bound = Q.BOUND * Nx * Ny
+        print("%-18s %dx%d: max |d log r| = %.3g = %.2g x bound" % (defect, Nx, Ny, err, err / bound))
+        assert err >= 1e3 * bound

@@ -1,5 +1,6 @@
 """CPU validation of tests/renyi_2d_reference.py (the float64 brute force of the 2D RNN's region swap estimator and the restatement
 of the paired masked-tail form), the defect study behind the GPU bound 1e-11 N, and the inputs of the exact and statistical GPU tests."""
+import functools
 import itertools
 
 import numpy as np
@@ -190,3 +191,57 @@ def test_header_binding_and_build_list_name_the_entry_point():
     assert re.search(r"int rnnwf_renyi2_regions_2d\(rnnwf_handle\* h, const int32_t\* regions", header)
     assert _lib.PROTOTYPES["rnnwf_renyi2_regions_2d"] == _lib.PROTOTYPES["rnnwf_renyi2_regions"]
     assert "mdrnn_renyi.hip" in build.SOURCES and build.compile_flags("mdrnn_renyi.hip") == build.compile_flags("mdrnn.hip")
+
+
+# ---- lattices of three to eight spin words: what tests/test_gpu_renyi_2d_full.py rests on -------------------------------------------------
+FULL_LATTICES = [(13, 5), (5, 13), (9, 11), (12, 12), (16, 16)]             # the lattices of the full-size GPU cases
+FULL_SCALE = 0.75                                                           # tests/test_pauli_2d_reference.py: full_setup
+
+
+def test_full_size_region_sets_cover_what_the_cases_promise():
+    for Nx, Ny in FULL_LATTICES:
+        names, masks = zip(*R.region_set_2d(Nx, Ny))
+        R.check_case_2d(Nx, Ny, masks)
+        assert len(set(names)) == len(names)
+        thin = np.stack([m for _, m in R.region_set_2d(Nx, Ny, thin=True)])
+        assert {m.tobytes() for m in thin} <= {m.tobytes() for m in masks}
+        active = sum(R.normalise(m)[1] > 0 for m in Q.to_visit_order(np.stack(masks), Nx, Ny))
+        print("%dx%d: %d regions (%d thin), %d non-empty after normalisation" % (Nx, Ny, len(masks), len(thin), active))
+        if (Nx, Ny) == (12, 12):                                     # the tiles of the paired pass on 2006 chains
+            assert active >= Q.MIN_MASKS and active * ((2006 + 15) // 16) >= 16384
+    with pytest.raises(AssertionError):                              # the set of the existing cases has no single site per word edge
+        R.check_case_2d(5, 7, R.case_regions(5, 7))
+
+
+@functools.lru_cache(maxsize=None)
+def full_setup(Nx, Ny, npairs=4):
+    """10 units (kernels x 0.75), pairs drawn by the oracle, the thinned region set; the brute force computed once per lattice"""
+    prm = Q.weights(10, 111, FULL_SCALE)
+    pairs, _ = M.mdrnn_sample(prm, Nx, Ny, np.random.RandomState(Nx + 10 * Ny).random_sample((2 * npairs, Nx * Ny)))
+    masks = np.stack([m for _, m in R.region_set_2d(Nx, Ny, thin=True)])
+    ref = R.log_ratio_regions(scorer(prm), pairs, masks)
+    ref.setflags(write=False)
+    return prm, pairs, masks, ref
+
+
+@pytest.mark.parametrize("Nx,Ny", FULL_LATTICES)
+def test_kernel_form_is_the_brute_force_on_three_to_eight_words(Nx, Ny):
+    prm, pairs, masks, ref = full_setup(Nx, Ny)
+    err = np.abs(R.kernel_form(prm, pairs, masks) - ref).max()
+    print("%dx%d: %d regions, max |kernel form - brute force| = %.2e, max |log r| = %.2f" % (Nx, Ny, len(masks), err, np.abs(ref).max()))
+    assert np.all(np.isfinite(ref)) and err <= R.BOUND * Nx * Ny and np.abs(ref).max() > 0.1
+
+
+# the defects of the word index that only a third word shows: none moves a bit on 5x7 (two words), each is rejected by the bound of the
+# full-size cases by at least three orders of magnitude on three, five and eight words
+@pytest.mark.parametrize("defect", R.WORD_DEFECTS)
+def test_word_defects_are_invisible_on_two_words_and_rejected_from_three(defect):
+    prm, pairs, masks, ref = full_setup(5, 7)
+    assert np.array_equal(R.kernel_form(prm, pairs, masks, defect=defect), R.kernel_form(prm, pairs, masks))
+    assert np.array_equal(R.kernel_form(prm, pairs, R.case_regions(5, 7), defect=defect), R.kernel_form(prm, pairs, R.case_regions(5, 7)))
+    for Nx, Ny in [(13, 5), (12, 12), (16, 16)]:
+        prm, pairs, masks, ref = full_setup(Nx, Ny)
+        err = np.abs(R.kernel_form(prm, pairs, masks, defect=defect) - ref).max()
+        bound = R.BOUND * Nx * Ny
+        print("%-24s %dx%d: max |d log r| = %.3g = %.2g x bound" % (defect, Nx, Ny, err, err / bound))
+        assert err >= 1e3 * bound
