@@ -414,6 +414,30 @@ int rnnwf_pauli_step_complex(rnnwf_handle* h, const int32_t* flip, const int32_t
                              const int32_t* samples, int64_t ns, uint64_t seed, uint64_t step, int64_t sample_offset,
                              double* term_sums, float* out_eloc_re_im, double* moments, double* out_log_ratio, int32_t* out_samples);
 
+/* ---- stochastic reconfiguration (natural gradient, minSR; docs/sr.md) -------------------------------------------------------
+ * psi = sqrt(P) real and positive:  O[s][k] = d log psi(sigma_s) / d theta_k = 1/2 d log P(sigma_s) / d theta_k, theta in the flat
+ * order of rnnwf_set_params_flat;  dO = O - mean_s O;  eps_s = E_loc,s - mean E.  The minSR direction with diagonal shift lambda is
+ *   delta = dO^T (dO dO^T + ns lambda I)^-1 eps  =  (S + lambda I)^-1 F,   S = dO^T dO / ns,  F = dO^T eps / ns
+ * (2 F is the gradient rnnwf_vmc_gradient returns); the update is theta <- theta - lr delta.  The ns x ns solve is the caller's
+ * (rnnwavefunctions_amd/sr.py: Cholesky in float64); the device does the per-sample Jacobian, the centred Gram matrix and dO^T y.
+ * All three work on the RESIDENT batch of the last rnnwf_vmc_step / rnnwf_load_batch (RNNWF_ERR_STATE without one) and keep the
+ * Jacobian on the device, image order, element type of the model, until the batch or the parameters change.
+ * Models GRU1D and GRU1D_F64 with one layer of at most 68 units.  RNNWF_ERR_INVALID "<entry>: <why>", before any work: the parity
+ * model, the complex RNN, the 2D RNN, the LSTM, stacked layers, wider layers, a handle with a communicator.  RNNWF_ERR_NOMEM
+ * "... ns too large for the SR workspace": ns > 4096, or Jacobian + Gram matrix beyond the state budget (RNNWF_STATE_BUDGET_MB).
+ * A refused call leaves the resident batch usable.  Every sum has a fixed order: the same batch gives the same bits.
+ * rnnwf_log_derivatives: one backward pass with unit weights (per-sample head rows kept) and one N-row outer-product sum per
+ *   sample on the MFMA.  out (ns, nparams) f64 = O, or NULL: build the device Jacobian only.  ns and nparams must be the resident
+ *   batch's and rnnwf_num_params'.
+ * rnnwf_sr_gram: gram (ns, ns) f64 = dO dO^T (f64 MFMA on operands converted and centred on the fly; exactly symmetric),
+ *   eps (ns,) f64 from the resident local energies.  Builds the Jacobian when it is stale.
+ * rnnwf_sr_apply: y (ns,) f64 -> out_direction (nparams,) f64 = dO^T y, one pass over the Jacobian.  Builds it when it is stale.  */
+int rnnwf_log_derivatives(rnnwf_handle* h, double* out, int64_t ns, int64_t nparams);
+int rnnwf_sr_gram(rnnwf_handle* h, double* gram, double* eps);
+int rnnwf_sr_apply(rnnwf_handle* h, const double* y, double* out_direction);
+/* samples of the resident batch (what sizes the three calls above), 0 without one */
+int64_t rnnwf_resident_samples(const rnnwf_handle* h);
+
 /* ---- multi-GPU: one RCCL all-reduce of the energy moments -------------------------------------
  * The reference is single-process; these add the one data-parallel collective of SURVEY.md 8e.
  * One process per GPU: rank 0 calls rnnwf_comm_unique_id and ships the 128 bytes to the other

@@ -78,6 +78,10 @@ PROTOTYPES = {
                                       _I32P]),
     "rnnwf_pauli_step_complex": (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F32P, _F64P,
                                            _F64P, _I32P]),
+    "rnnwf_log_derivatives": (C.c_int, [_P, _F64P, _I64, _I64]),
+    "rnnwf_sr_gram": (C.c_int, [_P, _F64P, _F64P]),
+    "rnnwf_sr_apply": (C.c_int, [_P, _F64P, _F64P]),
+    "rnnwf_resident_samples": (_I64, [_P]),
     "rnnwf_timing_enable": (C.c_int, [_P, _I32]),
     "rnnwf_timing_reset": (C.c_int, [_P]),
     "rnnwf_timing_get": (C.c_int, [_P, _I32, _F64P, C.POINTER(_I64), _F64P]),
@@ -340,6 +344,42 @@ class NativeWavefunction:
             g = np.empty(shape, dtype=np.float64)
             self._check(self.lib.rnnwf_get_grad(self.h, name.encode(), g.ctypes.data_as(_P), g.size, F64))
             out[name] = g
+        return out
+
+    # -- stochastic reconfiguration (rnnwf_log_derivatives / rnnwf_sr_gram / rnnwf_sr_apply; docs/sr.md) -------------------------
+    def set_params_flat(self, flat):
+        """Every tensor in one float64 vector in the order of _layout() (rnnwf_set_params_flat); commits."""
+        f, fp = _f64(np.ravel(flat))
+        self._check(self.lib.rnnwf_set_params_flat(self.h, fp, f.size))
+
+    def resident_samples(self):
+        """samples of the batch the last vmc_step / load_batch left on the device, 0 without one (rnnwf_resident_samples)"""
+        return int(self.lib.rnnwf_resident_samples(self.h))
+
+    def log_derivatives(self):
+        """(ns, num_params) float64: O[s, k] = d log psi(sigma_s) / d theta_k = 1/2 d log P / d theta_k on the resident batch of the
+        last vmc_step / load_batch, theta in the flat order of _layout()."""
+        ns, n = self.resident_samples(), self.num_params()
+        out = np.empty((ns, n), dtype=np.float64)
+        self._check(self.lib.rnnwf_log_derivatives(self.h, out.ctypes.data_as(_F64P), ns, n))
+        return out
+
+    def sr_gram(self):
+        """(gram, eps): the centred Gram matrix dO dO^T (ns, ns) and eps = E_loc - mean E (ns,) of the resident batch, float64;
+        gram is exactly symmetric."""
+        ns = self.resident_samples()
+        gram, eps = np.empty((ns, ns), dtype=np.float64), np.empty(ns, dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_gram(self.h, gram.ctypes.data_as(_F64P), eps.ctypes.data_as(_F64P)))
+        return gram, eps
+
+    def sr_apply(self, y):
+        """(num_params,) float64: dO^T y for y of one entry per sample of the resident batch, in the flat order of _layout()."""
+        yv, yp = _f64(y)
+        ns = self.resident_samples()
+        if ns > 0 and yv.shape != (ns,):
+            raise ValueError("sr_apply: y must have shape (%d,), one entry per sample of the resident batch, got %r" % (ns, yv.shape))
+        out = np.empty(self.num_params(), dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_apply(self.h, yp if ns > 0 else None, out.ctypes.data_as(_F64P)))
         return out
 
     # -- device-resident training iteration (rnnwf_train_steps; single-layer float32 GRU models) ------------------

@@ -588,4 +588,7 @@ extern "C" int rnnwf_get_grads_flat(rnnwf_handle* h, double* flat, int64_t count
 }
 
 // the weight image changed: the backward image must be rebuilt on the next gradient call
-void rnnwf::grad_invalidate(rnnwf_handle* h) { h->wbwd_valid = false; }     // (the buffer stays: freeing and re-allocating it cost ~0.1 ms per training iteration)
+void rnnwf::grad_invalidate(rnnwf_handle* h) {     // (the buffer stays: freeing and re-allocating it cost ~0.1 ms per training iteration)
+    h->wbwd_valid = false;
+    h->sr_valid = false;          // the per-sample log-derivatives (sr.hip) belong to the old weights too
+}

@@ -116,8 +116,11 @@ struct GradPair {
     static constexpr bool FITS = !GruLayout<T, NFULL, NOUT>::SPILL && LDS <= 160 * 1024;
 };
 
-template <typename T, int NFULL, int WAVES, int NOUT, bool PAIR = false>
+// SR (sr.hip: the per-sample log-derivatives; NOUT = 1, no PAIR): unit weights w_s = 1 (no E_loc, no wfac) and the head row of every
+// chain kept on its own, head_part = [ns][HEAD_ROW] - slot 4 k + q a unit, 4 KT the bias - instead of one sum per wave.
+template <typename T, int NFULL, int WAVES, int NOUT, bool PAIR = false, bool SR = false>
 __global__ void __launch_bounds__(WAVES * 64) gru_bwd_kernel(GradArgs a) {
+    static_assert(!SR || (NOUT == 1 && !PAIR), "per-sample head rows: positive RNN, one wave per 16-chain block (no forward / backward wave pair)");
     using C = GruCore<T, NFULL, NOUT>;
     using G = GradLayout<NFULL, T>;
     using V4 = typename C::V4;
@@ -156,12 +159,14 @@ __global__ void __launch_bounds__(WAVES * 64) gru_bwd_kernel(GradArgs a) {
     const int N = a.N;
     const T* wd = reinterpret_cast<const T*>(img + C::L::OFF_WD) + q * C::L::WD_Q;
     const int hck_nl = a.hck_nl > 1 ? a.hck_nl : 1;
-    T hg[NOUT][KT], gb[NOUT];                             // head-row sums over all chains of this wave
+    // head-row sums over all chains of this wave; SR: of one chain, added up in f64 so that the stored row is rounded once
+    using HA = std::conditional_t<SR, double, T>;
+    HA hg[NOUT][KT], gb[NOUT];
 #pragma unroll
     for (int o = 0; o < NOUT; ++o) {
-        gb[o] = T(0);
+        gb[o] = HA(0);
 #pragma unroll
-        for (int k = 0; k < KT; ++k) hg[o][k] = T(0);
+        for (int k = 0; k < KT; ++k) hg[o][k] = HA(0);
     }
     for (int64_t base = 0; base < a.nsb; base += nw) {
         // PAIR: every wave of the workgroup runs the same number of barriers - a slot without a block of its own walks the last block
@@ -173,7 +178,12 @@ __global__ void __launch_bounds__(WAVES * 64) gru_bwd_kernel(GradArgs a) {
         const bool valid = active && s < a.ns;
         const int64_t sc = valid ? s : a.ns - 1;
         T w = T(0), w_im = T(0);
-        if (valid) {
+        if constexpr (SR) {
+            if (valid) w = T(1);
+            gb[0] = HA(0);
+#pragma unroll
+            for (int k = 0; k < KT; ++k) hg[0][k] = HA(0);
+        } else if (valid) {
             const double mean_e = a.mom ? a.mom[0] / a.mom[2] : a.mean_e, mean_im = a.mom ? a.mom[3] / a.mom[2] : a.mean_im;
             const double inv_norm = a.mom ? a.inv_norm / a.mom[2] : a.inv_norm;
             if constexpr (NOUT == 1) {
@@ -274,14 +284,14 @@ __global__ void __launch_bounds__(WAVES * 64) gru_bwd_kernel(GradArgs a) {
             T dp[VW * G::KBG];
             T dy[KT];
 #pragma unroll
-            for (int o = 0; o < NOUT; ++o) gb[o] += g[o];
+            for (int o = 0; o < NOUT; ++o) gb[o] += (HA)g[o];
 #pragma unroll
             for (int k = 0; k < KT; ++k) {
                 T d = dh[k];                                        // total dL/dh_n of this lane's unit
                 if (a.dh_in) d += reinterpret_cast<const T*>(a.dh_in)[(((int64_t)n * a.nsb + sb) * KT + k) * 64 + lane];
 #pragma unroll
                 for (int o = 0; o < NOUT; ++o) {
-                    hg[o][k] += g[o] * hn[k];
+                    hg[o][k] += (HA)g[o] * (HA)hn[k];
                     d += g[o] * wd[k * NOUT + o];
                 }
                 const T du = d * (h[k] - cc[k]);
@@ -350,8 +360,17 @@ __global__ void __launch_bounds__(WAVES * 64) gru_bwd_kernel(GradArgs a) {
                 for (int r = 0; r < 4; ++r) dh[4 * m + r] += accb[m][r];
             dh[KT - 1] += accb[NFULL][0];
         }
+        if constexpr (SR) {
+            if (valid) {
+                T* row = reinterpret_cast<T*>(a.head_part) + s * G::HEAD_ROW;
+#pragma unroll
+                for (int k = 0; k < KT; ++k) row[4 * k + q] = (T)hg[0][k];
+                row[4 * KT + q] = q == 0 ? (T)gb[0] : T(0);
+            }
+        }
     }
-    if (bwd_role) store_head_part<T, NOUT, KT>(reinterpret_cast<T*>(a.head_part) + (size_t)gw * NOUT * G::HEAD_ROW, G::HEAD_ROW, hg, gb, c, q);
+    if constexpr (!SR)
+        if (bwd_role) store_head_part<T, NOUT, KT>(reinterpret_cast<T*>(a.head_part) + (size_t)gw * NOUT * G::HEAD_ROW, G::HEAD_ROW, hg, gb, c, q);
 }
 
 // Partial sums of  P[row][:]^T Q[row][:]  over one contiguous chunk of rows per block (4 waves).

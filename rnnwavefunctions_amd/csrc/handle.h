@@ -138,6 +138,12 @@ struct rnnwf_handle {
     size_t upbuf_cap = 0, upbuf_off = 0;
     rnnwf::DevBuf reduce_scratch;
     rnnwf::DevBuf renyi;          // rnnwf_renyi2_swap, rnnwf_renyi2_regions, rnnwf_pauli_step: tables, per-site terms, tails, log-ratios and partial sums of one pass
+    // stochastic reconfiguration (sr.hip): the per-sample log-derivatives J[sr_ns][D] in image order, the chains' head rows, how many
+    // parameters read each image element, column sums [mean | J^T y], the centred Gram matrix, the weights y
+    rnnwf::DevBuf srJ, srHead, srMask, srCol, srGram, srY;
+    bool sr_valid = false;        // srJ belongs to the resident batch and the committed parameters (cleared where either changes)
+    int64_t sr_ns = 0;
+    std::vector<int32_t> sr_sidx; // grad_flat_probe's table, probed once
     rnnwf::DevBuf tck, corr;      // rnnwf_correlations: trunk states [N(N-1)/2][nsb][KT][64]; site / trunk / branch terms, log-ratios and sums of one pass (corr.hip)
 
     bool timing_on = false;

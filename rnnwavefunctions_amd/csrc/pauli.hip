@@ -158,5 +158,6 @@ extern "C" int rnnwf_pauli_step(rnnwf_handle* h, const int32_t* flip, const int3
     if (moments) memcpy(moments, mom, sizeof mom);
     // one pass: bits, checkpoints and E_loc of the whole batch are on the device, as rnnwf_vmc_step leaves them
     if (ns <= chunk && h->family->gradient) h->last_ns = ns;
+    h->sr_valid = false;                              // a new batch: its log-derivatives are not built yet (sr.hip)
     return RNNWF_OK;
 }

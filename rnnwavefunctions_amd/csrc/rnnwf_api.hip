@@ -257,7 +257,8 @@ extern "C" int rnnwf_destroy(rnnwf_handle* h) {
                       &h->xrec[0], &h->xrec[1], &h->wsplit_up[0], &h->wsplit_up[1], &h->wsplit_up[2],
                       &h->train.P, &h->train.M, &h->train.V, &h->train.G, &h->train.gidx, &h->train.img[0].table, &h->train.img[1].table,
                       &h->train.img[2].table, &h->train.img[3].table, &h->train.img[4].table, &h->train.img[5].table, &h->train.img[6].table,
-                      &h->train.img[7].table, &h->train.combo};
+                      &h->train.img[7].table, &h->train.combo,
+                      &h->srJ, &h->srHead, &h->srMask, &h->srCol, &h->srGram, &h->srY};
     static_assert(RNNWF_MAX_LAYERS == 4, "wsplit_up has RNNWF_MAX_LAYERS - 1 entries");
     for (DevBuf* b : bufs) free_buf(*b);
     for (auto& t : h->timers) {
@@ -538,6 +539,7 @@ static int64_t n_couplings(const rnnwf_handle* h) { return (int64_t)h->family->c
 // the batch just computed stays on the device (h->bits, h->hck, h->eloc) for rnnwf_vmc_gradient
 static void keep_resident(rnnwf_handle* h, int64_t ns) {
     if (h->family->gradient) h->last_ns = ns;
+    h->sr_valid = false;          // a new batch: its log-derivatives are not built yet (sr.hip)
 }
 
 static int refuse_past_budget(rnnwf_handle* h, int64_t ns, const char* what) {

@@ -1,0 +1,213 @@
+// sr_kernels.h - kernels of stochastic reconfiguration (docs/sr.md) on the per-sample log-derivative matrix
+//
+//   J[ns][D],  D = PCOLS QCOLS + HEAD_ROW:  row s = O_s = d log psi(sigma_s) / d theta = 1/2 d log P / d theta  in IMAGE order, the
+//   order of the gradient image h->gradW ([dW | head row], grad.hip), element type of the model.
+//
+//   sr_outer_kernel  : O_s = 1/2 sum_n p_{n ns + s} (x) q_{n ns + s} from the rows gru_bwd_kernel<SR> left in P and Q (unit weights),
+//                      plus 1/2 of the sample's head row; image elements that no parameter reads (padding) are written as zeros.
+//   sr_colsum_kernel : out[k] = scale sum_s w_s J[s][k] in f64 - the column mean (w = 1, scale = 1 / ns) and J^T y.
+//   sr_gram_kernel   : (J - mean) M (J - mean)^T (M: the parameters per image element) in f64 on the f64 MFMA, operands converted and centred on the fly; the lower triangle is
+//                      computed and mirrored.
+// Every sum has a fixed order (no atomics): the same batch gives the same bits.
+#pragma once
+#include "grad_kernels.h"
+
+namespace rnnwf {
+
+// One workgroup per sample; wave w owns the P tiles w, w + WAVES, ... (14 x 4 tiles at 50 units would be 224 accumulator registers in
+// one wave): 8 waves where 4 would own more than 112 registers of full rows of tiles, and the Q tiles are taken QCH at a time so that
+// a pass holds at most 64 accumulator registers - the N rows of P are read again per pass, from L2.
+template <typename T, int NFULL>
+struct SrShape {
+    using Elem = T;
+    using G = GradLayout<NFULL, T>;
+    static constexpr int NF = NFULL;
+    static constexpr int PT = G::PCOLS / 16, QT = G::QCOLS / 16;
+    static constexpr int FRAG_REGS = 4 * (int)sizeof(T) / 4;
+    static constexpr int WAVES = ((PT + 3) / 4) * QT * FRAG_REGS > 112 ? 8 : 4;
+    static constexpr int MP = (PT + WAVES - 1) / WAVES;
+    static constexpr int QCH = 64 / (MP * FRAG_REGS) < 1 ? 1 : 64 / (MP * FRAG_REGS) > QT ? QT : 64 / (MP * FRAG_REGS);
+    static constexpr int PASSES = (QT + QCH - 1) / QCH;
+    static constexpr int64_t DW0 = (int64_t)G::PCOLS * G::QCOLS;
+    static constexpr int64_t D = DW0 + G::HEAD_ROW;
+};
+
+// K = N is short: the last group of four sites is padded with zeros (its rows are read from site 0 and zeroed), no branch.
+template <typename T, int NFULL>
+__global__ void __launch_bounds__((SrShape<T, NFULL>::WAVES * 64)) sr_outer_kernel(const T* __restrict__ P, const T* __restrict__ Q,
+                                                                                 const T* __restrict__ head, const uint8_t* __restrict__ used,
+                                                                                 int N, int64_t ns, T* __restrict__ J) {
+    using S = SrShape<T, NFULL>;
+    using G = typename S::G;
+    using V4 = typename Frag<T>::V4;
+    constexpr int PT = S::PT, QT = S::QT, MP = S::MP, WAVES = S::WAVES, QCH = S::QCH;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int li = lane & 15, lk = lane >> 4;
+    const int kgroups = (N + 3) / 4;
+    for (int64_t s = blockIdx.x; s < ns; s += gridDim.x) {
+        T* out = J + s * S::D;
+#pragma unroll
+        for (int pass = 0; pass < S::PASSES; ++pass) {
+            const int t0 = pass * QCH;
+            V4 acc[MP][QCH];
+#pragma unroll
+            for (int i = 0; i < MP; ++i)
+#pragma unroll
+                for (int t = 0; t < QCH; ++t) acc[i][t] = V4{T(0), T(0), T(0), T(0)};
+            for (int kg = 0; kg < kgroups; ++kg) {
+                const int n = 4 * kg + lk;
+                const bool ok = n < N;
+                const int64_t row = (int64_t)(ok ? n : 0) * ns + s;
+                const T* prow = P + row * G::PCOLS + li;
+                const T* qrow = Q + row * G::QCOLS + li;
+                T qv[QCH], pv[MP];
+#pragma unroll
+                for (int t = 0; t < QCH; ++t) qv[t] = t0 + t < QT ? qrow[16 * (t0 + t)] : T(0);
+#pragma unroll
+                for (int i = 0; i < MP; ++i) {
+                    const int pt = wave + WAVES * i;              // a wave without an i-th tile multiplies the last tile again and drops it
+                    pv[i] = prow[16 * (pt < PT ? pt : PT - 1)];
+                }
+#pragma unroll
+                for (int t = 0; t < QCH; ++t) qv[t] = ok ? qv[t] : T(0);
+#pragma unroll
+                for (int i = 0; i < MP; ++i) {
+                    const T p = ok ? pv[i] : T(0);
+#pragma unroll
+                    for (int t = 0; t < QCH; ++t)
+                        if (t0 + t < QT) acc[i][t] = Frag<T>::mfma(p, qv[t], acc[i][t]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < MP; ++i) {
+                const int pt = wave + WAVES * i;
+                if (pt >= PT) continue;
+#pragma unroll
+                for (int t = 0; t < QCH; ++t) {
+                    if (t0 + t >= QT) continue;
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) {
+                        const int fr = sizeof(T) == 4 ? 4 * lk + rr : lk + 4 * rr;      // C/D fragment row of (lane quarter lk, register rr)
+                        const int idx = (16 * pt + fr) * G::QCOLS + 16 * (t0 + t) + li;
+                        out[idx] = used[idx] ? T(0.5) * acc[i][t][rr] : T(0);
+                    }
+                }
+            }
+        }
+        if ((int)threadIdx.x < G::HEAD_ROW) {
+            const int idx = (int)S::DW0 + threadIdx.x;
+            out[idx] = used[idx] ? T(0.5) * head[s * G::HEAD_ROW + threadIdx.x] : T(0);
+        }
+    }
+}
+
+// 64 columns per workgroup of 4 waves: wave g adds the g-th quarter of the rows in order, wave 0 the four sums.  w == nullptr: w_s = 1.
+template <typename T>
+__global__ void __launch_bounds__(256) sr_colsum_kernel(const T* __restrict__ J, int64_t ns, int64_t D, const double* __restrict__ w,
+                                                        double scale, double* __restrict__ out) {
+    __shared__ double part[4][64];
+    const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int64_t chunk = (ns + 3) / 4, s0 = g * chunk, s1 = s0 + chunk < ns ? s0 + chunk : ns;
+    const int64_t nblocks = (D + 63) / 64;
+    for (int64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+        const int64_t col = b * 64 + lane;
+        double v = 0.0;
+        if (col < D)
+            for (int64_t s = s0; s < s1; ++s) v += (w ? w[s] : 1.0) * (double)J[s * D + col];
+        part[g][lane] = v;
+        __syncthreads();
+        if (g == 0 && col < D) out[col] = scale * (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]);
+        __syncthreads();
+    }
+}
+
+// gram = (J - mean)(J - mean)^T, [ns][ns] f64.  One workgroup per 32 x 32 block (bi, bj <= bi) of the lower triangle: 2 x 2 MFMA
+// tiles per wave, the four waves take a quarter of the columns of J each (16 columns per step: a lane loads four consecutive
+// elements of its row, element j is k-step j - both operands use the same order) and wave 0 adds the four partial blocks in order.
+// Element (r, c), r >= c, is stored to (r, c) and (c, r): symmetric by construction.  D is a multiple of 4.
+// mult[k]: how many flat parameters read image element k (0 padding, 2 the head's logit-difference row, which the two columns of
+// wf_dense share with opposite signs) - the product is the flat-order one, sum over PARAMETERS.
+template <typename T>
+__global__ void __launch_bounds__(256) sr_gram_kernel(const T* __restrict__ J, const double* __restrict__ mean, const uint8_t* __restrict__ mult,
+                                                      int64_t ns, int64_t D, int64_t nblocks, double* __restrict__ gram) {
+    typedef double V4 __attribute__((ext_vector_type(4)));
+    typedef T T4 __attribute__((ext_vector_type(4)));
+    __shared__ V4 red[3][2][2][64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int li = lane & 15, lk = lane >> 4;
+    const int64_t ksteps = (D + 15) / 16, ks0 = wave * ksteps / 4, ks1 = (wave + 1) * ksteps / 4;
+    for (int64_t item = blockIdx.x; item < nblocks; item += gridDim.x) {
+        int64_t bi = 0;
+        while ((bi + 1) * (bi + 2) / 2 <= item) ++bi;
+        const int64_t bj = item - bi * (bi + 1) / 2;
+        const T* arow[2];
+        const T* brow[2];
+        bool aok[2], bok[2];
+#pragma unroll
+        for (int x = 0; x < 2; ++x) {
+            const int64_t ra = 32 * bi + 16 * x + li, rb = 32 * bj + 16 * x + li;
+            aok[x] = ra < ns;
+            bok[x] = rb < ns;
+            arow[x] = J + (aok[x] ? ra : 0) * D;                   // rows past ns are read from row 0 and zeroed
+            brow[x] = J + (bok[x] ? rb : 0) * D;
+        }
+        V4 acc[2][2];
+#pragma unroll
+        for (int x = 0; x < 2; ++x)
+#pragma unroll
+            for (int y = 0; y < 2; ++y) acc[x][y] = V4{0.0, 0.0, 0.0, 0.0};
+        for (int64_t ks = ks0; ks < ks1; ++ks) {
+            const int64_t k = 16 * ks + 4 * lk;
+            const bool kok = k < D;
+            const int64_t kc = kok ? k : 0;
+            const V4 m = *reinterpret_cast<const V4*>(mean + kc);
+            const uchar4 mu4 = *reinterpret_cast<const uchar4*>(mult + kc);
+            const double mu[4] = {(double)mu4.x, (double)mu4.y, (double)mu4.z, (double)mu4.w};
+            double av[2][4], bv[2][4];
+#pragma unroll
+            for (int x = 0; x < 2; ++x) {
+                const T4 a = *reinterpret_cast<const T4*>(arow[x] + kc);
+                const T4 b = *reinterpret_cast<const T4*>(brow[x] + kc);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    av[x][j] = aok[x] && kok ? ((double)a[j] - m[j]) * mu[j] : 0.0;
+                    bv[x][j] = bok[x] && kok ? (double)b[j] - m[j] : 0.0;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int x = 0; x < 2; ++x)
+#pragma unroll
+                    for (int y = 0; y < 2; ++y) acc[x][y] = Frag<double>::mfma(av[x][j], bv[y][j], acc[x][y]);
+        }
+        if (wave > 0) {
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int y = 0; y < 2; ++y) red[wave - 1][x][y][lane] = acc[x][y];
+        }
+        __syncthreads();
+        if (wave == 0) {
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int y = 0; y < 2; ++y) {
+                    V4 v = acc[x][y];
+#pragma unroll
+                    for (int w = 0; w < 3; ++w) v += red[w][x][y][lane];
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) {
+                        const int64_t r = 32 * bi + 16 * x + lk + 4 * rr, c = 32 * bj + 16 * y + li;     // f64 C/D fragment: row lk + 4 rr
+                        if (r < ns && c <= r) {
+                            gram[r * ns + c] = v[rr];
+                            gram[c * ns + r] = v[rr];
+                        }
+                    }
+                }
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace rnnwf

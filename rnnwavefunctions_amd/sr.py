@@ -1,0 +1,90 @@
+"""Stochastic reconfiguration (natural gradient) in its minSR form for the positive one-layer GRU (docs/sr.md).
+
+psi = sqrt(P) is real and positive.  With O[s, k] = d log psi(sigma_s) / d theta_k, dO = O - mean_s O and eps_s = E_loc,s - mean E
+the direction with diagonal shift lambda is
+
+    delta = dO^T (dO dO^T + ns lambda I)^-1 eps  =  (S + lambda I)^-1 F,     S = dO^T dO / ns,  F = dO^T eps / ns
+
+and the update is theta <- theta - lr delta (2 F is the gradient of the reference's cost).  The device builds the per-sample
+Jacobian, the ns x ns Gram matrix and dO^T y (NativeWavefunction.log_derivatives / sr_gram / sr_apply); the ns x ns solve is done
+here, on the host, by Cholesky in float64: O(ns^3) with ns <= 4096, not the hot path.
+"""
+import numpy as np
+
+
+def _check_shift(diag_shift):
+    lam = float(diag_shift)
+    if not (lam > 0.0 and np.isfinite(lam)):
+        raise ValueError("diag_shift must be positive and finite, got %r" % (diag_shift,))
+    return lam
+
+
+def solve_shifted(gram, eps, diag_shift):
+    """y of (gram + ns diag_shift I) y = eps by Cholesky in float64; gram (ns, ns) symmetric positive semi-definite, eps (ns,)."""
+    lam = _check_shift(diag_shift)
+    g = np.array(gram, dtype=np.float64)
+    e = np.asarray(eps, dtype=np.float64)
+    if g.ndim != 2 or g.shape[0] != g.shape[1] or e.shape != (g.shape[0],):
+        raise ValueError("gram must be (ns, ns) and eps (ns,), got %r and %r" % (g.shape, e.shape))
+    ns = g.shape[0]
+    g[np.diag_indices(ns)] += ns * lam
+    c = np.linalg.cholesky(g)
+    return np.linalg.solve(c.T, np.linalg.solve(c, e))
+
+
+def minsr_direction(wf, diag_shift):
+    """delta (num_params,) float64 on the resident batch of `wf` (the last vmc_step / load_batch), flat order of wf._layout()."""
+    _check_shift(diag_shift)
+    gram, eps = wf.sr_gram()
+    return wf.sr_apply(solve_shifted(gram, eps, diag_shift))
+
+
+def qgt(wf):
+    """S = dO^T dO / ns (num_params, num_params) float64 from the per-sample log-derivatives of the resident batch: the quantum
+    geometric tensor of a real positive wave function.  For diagnostics and small models (it holds num_params^2 doubles)."""
+    o = wf.log_derivatives()
+    d = o - o.mean(axis=0)
+    return d.T @ d / o.shape[0]
+
+
+def flatten_params(wf, params, scope="RNNwavefunction"):
+    """{scoped tf name: array} -> float64 vector in the order of wf._layout()"""
+    return np.concatenate([np.asarray(params[scope + "/" + nm], dtype=np.float64).ravel() for nm, _ in wf._layout()])
+
+
+def unflatten_params(wf, flat, like, scope="RNNwavefunction"):
+    """the inverse: {scoped tf name: array} with the shapes and dtypes of `like`"""
+    out, off = {}, 0
+    for nm, cnt in wf._layout():
+        k = scope + "/" + nm
+        out[k] = np.asarray(flat[off:off + cnt]).reshape(like[k].shape).astype(like[k].dtype)
+        off += cnt
+    return out
+
+
+def train_tfim(wf, Jz, Bx, params, numsteps=100, numsamples=500, learningrate=1e-2, diag_shift=1e-3, seed=111, scope="RNNwavefunction"):
+    """Minimise the 1D / raster TFIM energy of `wf` (a NativeWavefunction of GRU1D or GRU1D_F64 with one layer, holding `params`)
+    by minSR: vmc_step (samples, local energies, moments; the batch stays resident) -> minsr_direction -> theta -= lr delta ->
+    set_params_flat.  Returns (meanEnergy, varEnergy), one entry per iteration 0..numsteps like training.minimize_hamiltonian; the
+    trained parameters are left in train_tfim.last_params.  The parameters keep the dtype of `params` (float32 models round every
+    update to float32, as the Adam drivers do)."""
+    _check_shift(diag_shift)
+    if int(numsteps) < 0 or int(numsamples) < 2:
+        raise ValueError("numsteps must be >= 0 and numsamples >= 2, got %r and %r" % (numsteps, numsamples))
+    jz = np.asarray(Jz, dtype=np.float64).ravel()
+    if jz.size != wf.N:
+        raise ValueError("Jz must have %d entries, got %d" % (wf.N, jz.size))
+    couplings = np.concatenate([jz, [float(Bx)]])
+    dtype = next(iter(params.values())).dtype
+    theta = flatten_params(wf, params, scope).astype(dtype).astype(np.float64)
+    wf.set_params_flat(theta)
+    meanEnergy, varEnergy = [], []
+    for it in range(int(numsteps) + 1):
+        s1, s2, n, _ = wf.vmc_step(int(numsamples), seed, it, couplings)["moments"]
+        meanE = s1 / n
+        meanEnergy.append(meanE)
+        varEnergy.append(s2 / n - meanE ** 2)
+        theta = (theta - learningrate * minsr_direction(wf, diag_shift)).astype(dtype).astype(np.float64)
+        wf.set_params_flat(theta)
+    train_tfim.last_params = unflatten_params(wf, theta, params, scope)
+    return meanEnergy, varEnergy

@@ -1,0 +1,60 @@
+"""Times of the stochastic-reconfiguration entry points beside the plain gradient on the same resident batch (docs/sr.md):
+
+    python tools/sr_time.py [--N 20] [--units 50] [--ns 500] [--f64] [--reps 20]
+
+Per repetition the batch is loaded again (untimed), which drops the resident Jacobian; then, each ending in a device synchronise and
+timed with the host clock: the Jacobian build (rnnwf_log_derivatives with out = NULL), rnnwf_sr_gram, rnnwf_sr_apply, the host
+Cholesky solve, and rnnwf_vmc_gradient (untouched by the SR code: the gradient's time as before it).  Prints the median of each.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from rnnwavefunctions_amd import _lib, sr  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--N", type=int, default=20)
+    ap.add_argument("--units", type=int, default=50)
+    ap.add_argument("--ns", type=int, default=500)
+    ap.add_argument("--f64", action="store_true")
+    ap.add_argument("--reps", type=int, default=20)
+    a = ap.parse_args()
+    wf = _lib.NativeWavefunction(_lib.MODEL_GRU1D_F64 if a.f64 else _lib.MODEL_GRU1D, a.N, 1, (a.units,))
+    wf.init_params(111)
+    couplings = np.append(np.ones(a.N), 1.0)
+    out = wf.vmc_step(a.ns, 111, 0, couplings, want_samples=True, want_eloc=True)
+    s, e = out["samples"], out["eloc"]
+    times = {k: [] for k in ("jacobian", "gram", "solve", "apply", "gradient")}
+
+    def timed(key, fn):
+        t0 = time.perf_counter()
+        r = fn()
+        wf.synchronize()
+        times[key].append((time.perf_counter() - t0) * 1e3)
+        return r
+
+    def build_jacobian():
+        wf._check(wf.lib.rnnwf_log_derivatives(wf.h, None, 0, 0))
+
+    for rep in range(a.reps + 3):
+        wf.load_batch(s, e)
+        timed("jacobian", build_jacobian)
+        gram, eps = timed("gram", wf.sr_gram)
+        y = timed("solve", lambda: sr.solve_shifted(gram, eps, 1e-3))
+        timed("apply", lambda: wf.sr_apply(y))
+        timed("gradient", lambda: wf._check(wf.lib.rnnwf_vmc_gradient(wf.h, float(e.mean()), 0.0, float(a.ns))))
+    med = {k: float(np.median(v[3:])) for k, v in times.items()}          # the first three repetitions warm up
+    print("N %d units %d ns %d %s, %d params, median of %d repetitions [ms]: jacobian %.3f  gram %.3f  apply %.3f  host solve %.3f  |  vmc_gradient %.3f"
+          % (a.N, a.units, a.ns, "f64" if a.f64 else "f32", wf.num_params(), a.reps, med["jacobian"], med["gram"], med["apply"], med["solve"],
+             med["gradient"]))
+
+
+if __name__ == "__main__":
+    main()
