@@ -16,6 +16,30 @@ Bounds (none fitted to the kernels' output):
       float32 unit round-off, 16 N 2^-24 x the tensor's largest sum_s |2 w_s O_sk|.  The autograd difference alone cannot serve: on a
       tensor of two elements (wf_dense/bias) it can come out far below one float32 ulp of what either side adds up, by chance and
       depending on the reference's thread count, while a Jacobian stored in float32 cannot be closer than its own rounding.
+  sr_apply (dO^T y, y not centred), every case: float64 1e-10 N ns x the largest element of the reference (the bound of
+      test_resident_batch_rules); float32 FACTOR x the largest difference between the same product of the float32 and of the float64
+      reference Jacobian.
+
+Cases (CASES; each is one reference and one device run shared by the six parametrized tests) and the SrShape of sr_kernels.h they
+instantiate (P x Q tiles, waves, MP, QCH, passes; backward operand of gru_bwd_kernel<SR>):
+  units 10, 20   NFULL 1  f32 / f64  6 x 2,  4 waves, MP 2, QCH 2, 1 pass                    LDS
+  units 36       NFULL 2  f32        10 x 3, 4 waves, MP 3, QCH 3, 1 pass                    LDS
+                          f64        10 x 3, 4 waves, MP 3, QCH 2, 2 passes (2 + 1)          LDS
+  units 37, 50*, 52  NFULL 3  f32    14 x 4, 4 waves, MP 4, QCH 4, 1 pass                    LDS          (* f32 only, N = 8, ns = 48)
+                          f64        14 x 4, 8 waves, MP 2, QCH 4, 1 pass                    LDS
+  units 53, 68   NFULL 4  f32        18 x 5, 4 waves, MP 5, QCH 3, 2 passes (3 + 2)          LDS
+                          f64        18 x 5, 8 waves, MP 3, QCH 2, 3 passes (2 + 2 + 1)      global, through L2 (GradStream)
+  chain lengths (ns 37): units 20 f32 N = 4, 5, 8, 36 and N = 33; units 68 f64 N = 8
+  batch sizes (units 10, N = 6, both types): ns = 2, 16, 32, 33, 65, 100 beside 37 and 48; ns = 1 in test_one_sample; ns = 4096 in
+  test_strided_grids (second trip of the grid-stride loops of sr_outer_kernel and sr_gram_kernel).
+
+Measured on an MI355X over the added cases, float64 / float32 model (docs/sr.md has the table and the first cases' figures):
+  Jacobian            worst row error / row maximum 5.2e-15 (bound 1e-10 N)   /  deviation / yardstick at most 2.8 (bound 16)
+  tie, error / bound  0.034                                                    /  0.050
+  Gram matrix         error / largest diagonal 1.0e-15, ns 4096: 2.8e-15      /  error / bound at most 0.10
+  direction           error / bound at most 0.13                               /  0.089
+  sr_apply            error / largest element 6.7e-15, ns 4096: 7.0e-13       /  error / bound at most 0.12
+The module's 243 tests take 8 s (the two ns = 4096 tests 1.3 s each).
 """
 import functools
 
@@ -39,6 +63,16 @@ SR_LR, SR_SHIFT = 0.05, 1e-2          # train_tfim's learning rate and diagonal 
 # (N, units, float64 model, ns): units 10 = mixed tile only (plus a remainder), 20 = one full tile + the whole mixed tile, 36 = two full
 # tiles + the mixed tile; ns 37 = a partial last block of 16 chains; N = 33: the packed spins cross a word
 CASES = [(6, u, f64, ns) for u in (10, 20, 36) for f64 in (False, True) for ns in (37, 48)] + [(33, 20, False, 37)]
+# both ends of NFULL 3 (37..52 units) and NFULL 4 (53..68), the widths at which SrShape changes shape: eight waves per sample and
+# waves without an i-th tile (f64), two and three Q passes with a ragged last chunk (NFULL 4), gru_bwd_kernel<SR> with the
+# backward operand streamed through L2 (f64 above 52 units); and the width docs/sr.md times (50 units, f32)
+CASES += [(6, u, f64, 37) for u in (37, 52, 53, 68) for f64 in (False, True)] + [(8, 50, False, 48)]
+# chain lengths: N = 4, 8 multiples of four (no padded k-group in sr_outer_kernel), 5 = one valid site in the last group, 36 = a
+# multiple of four that crosses a spin word; N = 8 once more on the widest float64 shape
+CASES += [(N, 20, False, 37) for N in (4, 5, 8, 36)] + [(8, 68, True, 37)]
+# batch sizes at the edges of the 32 x 32 Gram blocks and the 16-chain blocks: 32 = exactly one Gram block, 33 = one valid row in the
+# second, 65 = the first off-diagonal block that is not next to the diagonal (2, 0), 100 = ten blocks
+CASES += [(6, 10, f64, ns) for f64 in (False, True) for ns in (2, 16, 32, 33, 65, 100)]
 IDS = ["N%d-u%d-%s-ns%d" % (N, u, "f64" if f else "f32", ns) for N, u, f, ns in CASES]
 
 
@@ -66,7 +100,7 @@ def case(N, units, f64, ns):
     prm = make_params(units, f64, seed=7 + units)
     s = rng.randint(0, 2, size=(ns, N)).astype(np.int32)
     e = rng.standard_normal(ns) * 2.0 - 3.0
-    c = dict(prm=prm, s=s, e=e)
+    c = dict(prm=prm, s=s, e=e, y=rng.standard_normal(ns) + 0.5)          # y for sr_apply: not centred
     c["o64"] = R.jacobian_dict(prm, s, torch.float64)
     c["o32"] = R.jacobian_dict(prm, s, torch.float32)
     c["g64"] = A.gradient("gru", prm, s, e, dtype=torch.float64)
@@ -82,24 +116,42 @@ def case(N, units, f64, ns):
     c["again"] = (wf.log_derivatives(), wf.sr_gram()[0], sr.minsr_direction(wf, LAMBDA))      # after the gradient reused P and Q
     wf.load_batch(s, e)
     c["reload"] = (wf.log_derivatives(), wf.sr_gram()[0], sr.minsr_direction(wf, LAMBDA))
+    c["apply"] = wf.sr_apply(c["y"])
     c["O_dict"] = wf_dict(wf, c["O"], prm)
     wf.close()
     return c
 
 
-@pytest.mark.parametrize("N,units,f64,ns", CASES, ids=IDS)
-def test_jacobian_every_element(N, units, f64, ns):
-    c = case(N, units, f64, ns)
-    O, ref = c["O"], R.flatten(c["o64"])
+def check_jacobian(O, O_dict, o64, o32, f64, N):
+    """every element of the device Jacobian O (O_dict: the same by tensor) against the float64 reference, with the bound of its type"""
+    ref = R.flatten(o64)
     assert O.shape == ref.shape and np.all(np.isfinite(O))
     if f64:
         rel = np.abs(O - ref).max(axis=1) / np.abs(ref).max(axis=1)
         print("jacobian f64: worst row error / row max %.3e (bound %.1e)" % (rel.max(), 1e-10 * N))
         assert rel.max() <= 1e-10 * N
     else:
-        worst, failures = A.verdict(c["O_dict"], c["o64"], c["o32"], label="jacobian")
+        worst, failures = A.verdict(O_dict, o64, o32, label="jacobian")
         print("jacobian f32: worst deviation / yardstick %.3f (bound %g)" % (worst, A.FACTOR))
         assert not failures, failures
+
+
+def check_apply(got, o64, o32, y, f64, N):
+    """dO^T y against the float64 reference: 1e-10 N ns relative for the float64 model (the bound of test_resident_batch_rules), FACTOR x
+    the spread of the same product over the float32 and float64 reference Jacobians for the float32 model"""
+    o = R.flatten(o64)
+    ns, ref = o.shape[0], R.centred(o).T @ y
+    bound = 1e-10 * N * ns * np.abs(ref).max() if f64 else A.FACTOR * np.abs(R.centred(R.flatten(o32)).T @ y - ref).max()
+    err = np.abs(got - ref).max()
+    print("apply: max error %.3e, bound %.3e, ratio %.3e (largest element %.3e)" % (err, bound, err / bound, np.abs(ref).max()))
+    assert got.shape == ref.shape and np.all(np.isfinite(got))
+    assert err <= bound
+
+
+@pytest.mark.parametrize("N,units,f64,ns", CASES, ids=IDS)
+def test_jacobian_every_element(N, units, f64, ns):
+    c = case(N, units, f64, ns)
+    check_jacobian(c["O"], c["O_dict"], c["o64"], c["o32"], f64, N)
 
 
 @pytest.mark.parametrize("N,units,f64,ns", CASES, ids=IDS)
@@ -159,6 +211,80 @@ def test_same_batch_same_bits(N, units, f64, ns):
         assert np.array_equal(first, other)
     for first, other in zip((c["O"], c["gram"], c["delta"]), c["reload"]):
         assert np.array_equal(first, other)
+
+
+@pytest.mark.parametrize("N,units,f64,ns", CASES, ids=IDS)
+def test_apply_matches_the_reference(N, units, f64, ns):
+    c = case(N, units, f64, ns)
+    check_apply(c["apply"], c["o64"], c["o32"], c["y"], f64, N)
+
+
+@pytest.mark.parametrize("f64", [False, True], ids=["f32", "f64"])
+def test_one_sample(f64):
+    """ns = 1: the centred Jacobian is exactly zero (the column mean of one row is that row), so the Gram matrix, eps and dO^T y are
+    exact zeros and there is no direction to compare (the direction test divides by the reference's norm); the Jacobian row itself
+    meets the reference like any other."""
+    N, units = 6, 10
+    prm = make_params(units, f64, seed=7 + units)
+    s = np.array([[1, 0, 1, 1, 0, 0]], dtype=np.int32)
+    e = np.array([-2.5])
+    o64, o32 = R.jacobian_dict(prm, s, torch.float64), R.jacobian_dict(prm, s, torch.float32)
+    wf = make_wf(N, units, f64)
+    wf.set_params(prm, scope=SCOPE)
+    wf.load_batch(s, e)
+    O = wf.log_derivatives()
+    gram, eps = wf.sr_gram()
+    applied = wf.sr_apply(np.array([3.0]))
+    O_dict = wf_dict(wf, O, prm)
+    wf.close()
+    assert np.abs(R.flatten(o64)).max() > 0
+    check_jacobian(O, O_dict, o64, o32, f64, N)
+    assert gram.shape == (1, 1) and np.array_equal(gram, [[0.0]])
+    assert np.array_equal(eps, [0.0])
+    assert applied.shape == (O.shape[1],) and np.array_equal(applied, np.zeros(O.shape[1]))
+
+
+@pytest.mark.parametrize("f64", [False, True], ids=["f32", "f64"])
+def test_strided_grids(f64):
+    """ns = 4096: more samples than sr_outer_kernel has resident workgroups (at most eight of 256 threads per CU), so its sample loop
+    makes a second trip, and 8256 Gram blocks, more than any resident grid, so sr_gram_kernel's item loop reuses its LDS array.
+    The batch is the 64 configurations of six spins tiled 64 times: row s holds configuration s mod 64, the reference needs the 64
+    distinct rows only, and equal inputs under a fixed summation order must give equal bits in whichever grid trip they land.
+    No solve here: the host solve is covered by the smaller cases."""
+    N, units, reps = 6, 10, 64
+    ns = 64 * reps
+    rng = np.random.RandomState(4096 + int(f64))
+    prm = make_params(units, f64, seed=7 + units)
+    conf = ((np.arange(64)[:, None] >> np.arange(N)) & 1).astype(np.int32)
+    s = np.tile(conf, (reps, 1))
+    e = rng.standard_normal(ns) * 2.0 - 3.0
+    y = rng.standard_normal(ns) + 0.5
+    o64 = {k: np.tile(v, (reps,) + (1,) * (v.ndim - 1)) for k, v in R.jacobian_dict(prm, conf, torch.float64).items()}
+    o32 = {k: np.tile(v, (reps,) + (1,) * (v.ndim - 1)) for k, v in R.jacobian_dict(prm, conf, torch.float32).items()}
+    wf = make_wf(N, units, f64)
+    assert 8 * wf.device_info()["cu_count"] < ns                   # the sample loop of sr_outer_kernel strides
+    wf.set_params(prm, scope=SCOPE)
+    wf.load_batch(s, e)
+    O = wf.log_derivatives()
+    gram, eps = wf.sr_gram()
+    applied = wf.sr_apply(y)
+    O_dict = wf_dict(wf, O, prm)
+    wf.close()
+    assert np.array_equal(s[64:], s[:-64])
+    check_jacobian(O, O_dict, o64, o32, f64, N)
+    assert np.array_equal(O.reshape(reps, 64, -1), np.broadcast_to(O[:64], (reps, 64, O.shape[1])))
+    ref, ref32 = R.gram(R.flatten(o64)), R.gram(R.flatten(o32))
+    scale = np.diag(ref).max()
+    bound = 1e-10 * N if f64 else A.FACTOR * np.abs(ref32 - ref).max() / scale
+    err = np.abs(gram - ref).max() / scale
+    print("gram: error / largest diagonal %.3e (bound %.3e)" % (err, bound))
+    assert gram.shape == (ns, ns) and np.array_equal(gram, gram.T)
+    assert err <= bound
+    assert np.array_equal(gram.reshape(reps, 64, reps, 64), np.broadcast_to(gram[:64, :64][None, :, None, :], (reps, 64, reps, 64)))
+    # eps: the library's mean is a serial float64 sum of ns terms, at most (ns - 1) 2^-53 sum |e| off, so the mean is within
+    # ns 2^-53 max |e|; the few roundings of the division, the subtraction and the reference's own mean are the + 8
+    assert np.abs(eps - R.epsilon(e)).max() <= (ns + 8) * EPS64 * np.abs(e).max()
+    check_apply(applied, o64, o32, y, f64, N)
 
 
 def test_qgt_matches_the_reference():
