@@ -38,7 +38,8 @@ typedef enum {
     RNNWF_ERR_HIP = -2,         /* a HIP runtime call failed                           */
     RNNWF_ERR_STATE = -3,       /* call order violated (e.g. parameters not committed) */
     RNNWF_ERR_COMM = -4,        /* RCCL failure                                        */
-    RNNWF_ERR_NOMEM = -5
+    RNNWF_ERR_NOMEM = -5,
+    RNNWF_ERR_NUMERIC = -6      /* a factorisation met a pivot that is not positive and finite */
 } rnnwf_status;
 
 /* Which reference wave function the handle implements. */
@@ -418,9 +419,10 @@ int rnnwf_pauli_step_complex(rnnwf_handle* h, const int32_t* flip, const int32_t
  * psi = sqrt(P) real and positive:  O[s][k] = d log psi(sigma_s) / d theta_k = 1/2 d log P(sigma_s) / d theta_k, theta in the flat
  * order of rnnwf_set_params_flat;  dO = O - mean_s O;  eps_s = E_loc,s - mean E.  The minSR direction with diagonal shift lambda is
  *   delta = dO^T (dO dO^T + ns lambda I)^-1 eps  =  (S + lambda I)^-1 F,   S = dO^T dO / ns,  F = dO^T eps / ns
- * (2 F is the gradient rnnwf_vmc_gradient returns); the update is theta <- theta - lr delta.  The ns x ns solve is the caller's
- * (rnnwavefunctions_amd/sr.py: Cholesky in float64); the device does the per-sample Jacobian, the centred Gram matrix and dO^T y.
- * All three work on the RESIDENT batch of the last rnnwf_vmc_step / rnnwf_load_batch (RNNWF_ERR_STATE without one) and keep the
+ * (2 F is the gradient rnnwf_vmc_gradient returns); the update is theta <- theta - lr delta.  The device does the per-sample
+ * Jacobian, the centred Gram matrix and dO^T y; the ns x ns solve is the caller's (rnnwf_sr_gram, a host Cholesky as in
+ * rnnwavefunctions_amd/sr.py, rnnwf_sr_apply) or the device's (rnnwf_sr_solve, rnnwf_sr_direction: blocked Cholesky in float64).
+ * All five work on the RESIDENT batch of the last rnnwf_vmc_step / rnnwf_load_batch (RNNWF_ERR_STATE without one) and keep the
  * Jacobian on the device, image order, element type of the model, until the batch or the parameters change.
  * Models GRU1D and GRU1D_F64 with one layer of at most 68 units.  RNNWF_ERR_INVALID "<entry>: <why>", before any work: the parity
  * model, the complex RNN, the 2D RNN, the LSTM, stacked layers, wider layers, a handle with a communicator.  RNNWF_ERR_NOMEM
@@ -431,11 +433,21 @@ int rnnwf_pauli_step_complex(rnnwf_handle* h, const int32_t* flip, const int32_t
  *   batch's and rnnwf_num_params'.
  * rnnwf_sr_gram: gram (ns, ns) f64 = dO dO^T (f64 MFMA on operands converted and centred on the fly; exactly symmetric),
  *   eps (ns,) f64 from the resident local energies.  Builds the Jacobian when it is stale.
- * rnnwf_sr_apply: y (ns,) f64 -> out_direction (nparams,) f64 = dO^T y, one pass over the Jacobian.  Builds it when it is stale.  */
+ * rnnwf_sr_apply: y (ns,) f64 -> out_direction (nparams,) f64 = dO^T y, one pass over the Jacobian.  Builds it when it is stale.
+ * rnnwf_sr_solve, rnnwf_sr_direction: the solve on the device.  Both build the Jacobian when it is stale, rebuild the Gram matrix
+ *   (no copy to the host), factorise gram + ns diag_shift I = L L^T by a blocked right-looking Cholesky in float64 (32 x 32 blocks,
+ *   trailing update on the f64 MFMA) with eps, formed on the device from the resident local energies, carried as one more row, and
+ *   finish with a blocked backward sweep.  rnnwf_sr_solve returns y (ns,) f64, the solution for the centred eps (not itself
+ *   centred); rnnwf_sr_direction goes on with dO^T y on the device and returns delta (nparams,) f64: nparams doubles cross the bus.
+ *   RNNWF_ERR_INVALID "<entry>: diag_shift must be positive and finite", before any work.  The workspace check counts the factor:
+ *   Jacobian + 2 ns^2 doubles within the state budget.  RNNWF_ERR_NUMERIC "<entry>: pivot <index> ... (diag_shift ...)": a pivot that
+ *   is not positive and finite (found at the call's one synchronisation; the resident batch stays usable).  */
 int rnnwf_log_derivatives(rnnwf_handle* h, double* out, int64_t ns, int64_t nparams);
 int rnnwf_sr_gram(rnnwf_handle* h, double* gram, double* eps);
 int rnnwf_sr_apply(rnnwf_handle* h, const double* y, double* out_direction);
-/* samples of the resident batch (what sizes the three calls above), 0 without one */
+int rnnwf_sr_solve(rnnwf_handle* h, double diag_shift, double* y);
+int rnnwf_sr_direction(rnnwf_handle* h, double diag_shift, double* out_direction);
+/* samples of the resident batch (what sizes the five calls above), 0 without one */
 int64_t rnnwf_resident_samples(const rnnwf_handle* h);
 
 /* ---- multi-GPU: one RCCL all-reduce of the energy moments -------------------------------------

@@ -16,6 +16,7 @@ F32, F64 = 0, 1
 ABI_VERSION = 1
 MAX_LAYERS = 4
 UNIQUE_ID_BYTES = 128
+SR_BLOCK = 32          # block width of the device Cholesky solve (kSrNB in csrc/sr_solve_kernels.h)
 
 
 class Config(C.Structure):
@@ -81,6 +82,8 @@ PROTOTYPES = {
     "rnnwf_log_derivatives": (C.c_int, [_P, _F64P, _I64, _I64]),
     "rnnwf_sr_gram": (C.c_int, [_P, _F64P, _F64P]),
     "rnnwf_sr_apply": (C.c_int, [_P, _F64P, _F64P]),
+    "rnnwf_sr_solve": (C.c_int, [_P, _F64, _F64P]),
+    "rnnwf_sr_direction": (C.c_int, [_P, _F64, _F64P]),
     "rnnwf_resident_samples": (_I64, [_P]),
     "rnnwf_timing_enable": (C.c_int, [_P, _I32]),
     "rnnwf_timing_reset": (C.c_int, [_P]),
@@ -346,7 +349,7 @@ class NativeWavefunction:
             out[name] = g
         return out
 
-    # -- stochastic reconfiguration (rnnwf_log_derivatives / rnnwf_sr_gram / rnnwf_sr_apply; docs/sr.md) -------------------------
+    # -- stochastic reconfiguration: rnnwf_log_derivatives, rnnwf_sr_* (docs/sr.md) ---------------
     def set_params_flat(self, flat):
         """Every tensor in one float64 vector in the order of _layout() (rnnwf_set_params_flat); commits."""
         f, fp = _f64(np.ravel(flat))
@@ -380,6 +383,20 @@ class NativeWavefunction:
             raise ValueError("sr_apply: y must have shape (%d,), one entry per sample of the resident batch, got %r" % (ns, yv.shape))
         out = np.empty(self.num_params(), dtype=np.float64)
         self._check(self.lib.rnnwf_sr_apply(self.h, yp if ns > 0 else None, out.ctypes.data_as(_F64P)))
+        return out
+
+    def sr_solve(self, diag_shift):
+        """(ns,) float64: y of (dO dO^T + ns diag_shift I) y = eps on the resident batch, factorised and solved on the device
+        (rnnwf_sr_solve); y is not centred."""
+        y = np.empty(self.resident_samples(), dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_solve(self.h, float(diag_shift), y.ctypes.data_as(_F64P)))
+        return y
+
+    def sr_direction(self, diag_shift):
+        """(num_params,) float64: the minSR direction dO^T (dO dO^T + ns diag_shift I)^-1 eps of the resident batch, everything on
+        the device (rnnwf_sr_direction), in the flat order of _layout()."""
+        out = np.empty(self.num_params(), dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_direction(self.h, float(diag_shift), out.ctypes.data_as(_F64P)))
         return out
 
     # -- device-resident training iteration (rnnwf_train_steps; single-layer float32 GRU models) ------------------

@@ -258,7 +258,7 @@ extern "C" int rnnwf_destroy(rnnwf_handle* h) {
                       &h->train.P, &h->train.M, &h->train.V, &h->train.G, &h->train.gidx, &h->train.img[0].table, &h->train.img[1].table,
                       &h->train.img[2].table, &h->train.img[3].table, &h->train.img[4].table, &h->train.img[5].table, &h->train.img[6].table,
                       &h->train.img[7].table, &h->train.combo,
-                      &h->srJ, &h->srHead, &h->srMask, &h->srCol, &h->srGram, &h->srY};
+                      &h->srJ, &h->srHead, &h->srMask, &h->srCol, &h->srGram, &h->srY, &h->srFac};
     static_assert(RNNWF_MAX_LAYERS == 4, "wsplit_up has RNNWF_MAX_LAYERS - 1 entries");
     for (DevBuf* b : bufs) free_buf(*b);
     for (auto& t : h->timers) {

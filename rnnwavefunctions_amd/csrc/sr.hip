@@ -1,9 +1,13 @@
-// sr.hip - stochastic reconfiguration (docs/sr.md): rnnwf_log_derivatives, rnnwf_sr_gram, rnnwf_sr_apply on the resident batch of the
-// one-layer positive GRU (GRU1D, GRU1D_F64; up to 68 units).  The per-sample log-derivatives J[ns][D] stay on the device in the order
-// of the gradient image (grad.hip) and are read through the table grad_flat_probe builds; the ns x ns solve is the caller's.
+// sr.hip - stochastic reconfiguration (docs/sr.md): rnnwf_log_derivatives, rnnwf_sr_gram, rnnwf_sr_apply, rnnwf_sr_solve,
+// rnnwf_sr_direction on the resident batch of the one-layer positive GRU (GRU1D, GRU1D_F64; up to 68 units).  The per-sample
+// log-derivatives J[ns][D] stay on the device in the order of the gradient image (grad.hip) and are read through the table
+// grad_flat_probe builds; the ns x ns solve is the caller's (rnnwf_sr_gram + rnnwf_sr_apply) or the device's (rnnwf_sr_solve,
+// rnnwf_sr_direction: blocked f64 Cholesky, sr_solve_kernels.h).
 #include <cmath>
+#include <cstring>
 
 #include "sr_kernels.h"
+#include "sr_solve_kernels.h"
 #include "models.h"
 
 using namespace rnnwf;
@@ -46,17 +50,20 @@ int64_t sr_image_size(rnnwf_handle* h) {
     return D;
 }
 
-// refusals, then the state checks every entry point shares
-int sr_ready(rnnwf_handle* h, const char* entry) {
+// refusals, then the state checks every entry point shares; `factor`: the entry also holds the ns x ns Cholesky factor
+int sr_ready(rnnwf_handle* h, const char* entry, bool factor = false) {
     if (int rc = sr_refuse(h, entry)) return rc;
     if (!h->committed) return h->fail(RNNWF_ERR_STATE, "%s: parameters not committed (call rnnwf_commit_params)", entry);
     if (h->last_ns <= 0) return h->fail(RNNWF_ERR_STATE, "%s: call rnnwf_vmc_step first (its samples, states and E_loc are reused)", entry);
     const int64_t ns = h->last_ns;
     const size_t es = h->f64 ? 8 : 4;
-    const size_t need = (size_t)ns * (size_t)sr_image_size(h) * es + (size_t)ns * ns * 8;
+    // the factor's workspace: ns^2 doubles, eps, y, the status word and the diagonal blocks (sr_solve_device), all counted
+    const size_t nb = (size_t)(ns + kSrNB - 1) / kSrNB;
+    const size_t fac = factor ? ((size_t)ns * ns + 2 * (size_t)ns + 1 + nb * kSrNB * kSrNB) * 8 : 0;
+    const size_t need = (size_t)ns * (size_t)sr_image_size(h) * es + (size_t)ns * ns * 8 + fac;
     if (ns > kSrMaxSamples || need > state_budget_bytes(h, kDefaultStateBudget))
-        return h->fail(RNNWF_ERR_NOMEM, "%s: ns too large for the SR workspace (%lld samples: Jacobian + Gram matrix take %zu bytes; at most %lld samples)",
-                       entry, (long long)ns, need, (long long)kSrMaxSamples);
+        return h->fail(RNNWF_ERR_NOMEM, "%s: ns too large for the SR workspace (%lld samples: Jacobian + Gram matrix%s take %zu bytes; at most %lld samples)",
+                       entry, (long long)ns, factor ? " + Cholesky factor" : "", need, (long long)kSrMaxSamples);
     RNNWF_HIP(h, hipSetDevice(h->cfg.device));
     return 0;
 }
@@ -129,6 +136,63 @@ int sr_colsum(rnnwf_handle* h, int64_t D, const double* w, double scale, double*
     return launch_persistent(h, kTimerGemm, sr_colsum_kernel<T>, 256, 0, (D + 63) / 64, 1, (const T*)h->srJ.p, h->sr_ns, D, w, scale, out);
 }
 
+// the column mean and the centred Gram matrix of the resident Jacobian, into h->srCol[0 .. D) and h->srGram
+int sr_gram_device(rnnwf_handle* h) {
+    const int64_t ns = h->sr_ns, D = sr_image_size(h);
+    if (int rc = ensure(h, h->srCol, (size_t)2 * D * 8)) return rc;
+    if (int rc = ensure(h, h->srGram, (size_t)ns * ns * 8)) return rc;
+    double* mean = (double*)h->srCol.p;
+    if (int rc = h->f64 ? sr_colsum<double>(h, D, nullptr, 1.0 / (double)ns, mean) : sr_colsum<float>(h, D, nullptr, 1.0 / (double)ns, mean)) return rc;
+    const int64_t nb = (ns + 31) / 32, nblocks = nb * (nb + 1) / 2;
+    if (int rc = h->f64 ? launch_persistent(h, kTimerGemm, sr_gram_kernel<double>, 256, 0, nblocks, 1, (const double*)h->srJ.p, (const double*)mean,
+                                            (const uint8_t*)h->srMask.p, ns, D, nblocks, (double*)h->srGram.p)
+                        : launch_persistent(h, kTimerGemm, sr_gram_kernel<float>, 256, 0, nblocks, 1, (const float*)h->srJ.p, (const double*)mean,
+                                            (const uint8_t*)h->srMask.p, ns, D, nblocks, (double*)h->srGram.p))
+        return rc;
+    return 0;
+}
+
+// (gram + ns diag_shift I) y = eps on the device: eps from the resident local energies into the eps row of the workspace, per
+// panel the diagonal factorisation + panel solve and the trailing update, then the backward sweep.  Leaves y and the pivot
+// status word behind the eps row (sr_y / sr_status), the factors of the diagonal blocks behind those; nothing is synchronised here.
+double* sr_y(rnnwf_handle* h) { return (double*)h->srFac.p + (size_t)h->sr_ns * h->sr_ns + (size_t)h->sr_ns; }
+long long* sr_status(rnnwf_handle* h) { return (long long*)(sr_y(h) + h->sr_ns); }
+
+int sr_solve_device(rnnwf_handle* h, double diag_shift) {
+    const int64_t ns = h->sr_ns;
+    const int nb = (int)((ns + kSrNB - 1) / kSrNB);
+    if (int rc = ensure(h, h->srFac, ((size_t)ns * ns + 2 * (size_t)ns + 1 + (size_t)nb * kSrNB * kSrNB) * 8)) return rc;
+    double* F = (double*)h->srFac.p;
+    double* Ld = (double*)(sr_status(h) + 1);                // the factorised diagonal blocks
+    const double* gram = (const double*)h->srGram.p;
+    const double shift = (double)ns * diag_shift;
+    if (int rc = timed_launch(h, kTimerGemm, sr_centre_kernel, 1, 256, 0, (const double*)h->eloc.p, ns, F + (size_t)ns * ns, sr_status(h))) return rc;
+    for (int k = 0; k < nb; ++k) {
+        const double* src = k == 0 ? gram : F;
+        if (int rc = launch_persistent(h, kTimerGemm, sr_chol_panel_kernel, 256, 0, nb - k, 1, src, F, ns, k, shift, Ld, sr_status(h))) return rc;
+        const int64_t m = nb - k - 1, nitems = m * (m + 1) / 2 + m;
+        if (nitems > 0)
+            if (int rc = launch_persistent(h, kTimerGemm, sr_chol_update_kernel, 256, 0, nitems, 1, src, F, ns, k, nitems)) return rc;
+    }
+    for (int k = nb - 1; k >= 0; --k)
+        if (int rc = launch_persistent(h, kTimerGemm, sr_chol_back_kernel, 64, 0, k + 1, 1, F, (const double*)Ld, ns, k, sr_y(h))) return rc;
+    return 0;
+}
+
+// the checks and the device work both solving entries share, up to y on the device
+int sr_solve_common(rnnwf_handle* h, const char* entry, double diag_shift) {
+    if (!(diag_shift > 0.0) || !std::isfinite(diag_shift)) return h->fail(RNNWF_ERR_INVALID, "%s: diag_shift must be positive and finite", entry);
+    if (int rc = sr_ready(h, entry, true)) return rc;
+    if (int rc = sr_build(h)) return rc;
+    if (int rc = sr_gram_device(h)) return rc;
+    return sr_solve_device(h, diag_shift);
+}
+
+int sr_pivot_error(rnnwf_handle* h, const char* entry, long long status, double diag_shift) {
+    return h->fail(RNNWF_ERR_NUMERIC, "%s: pivot %lld of the shifted Gram matrix is not positive and finite (diag_shift %g, %lld samples)", entry,
+                   status - 1, diag_shift, (long long)h->sr_ns);
+}
+
 // flat[i] = +-img[|sidx[i]| - 1] (0 where the parameter has no source): the gather of rnnwf_get_grads_flat
 template <typename T>
 void sr_gather(const std::vector<int32_t>& sidx, const T* img, double* flat) {
@@ -167,17 +231,8 @@ extern "C" int rnnwf_sr_gram(rnnwf_handle* h, double* gram, double* eps) {
     if (int rc = sr_ready(h, "rnnwf_sr_gram")) return rc;
     if (!gram || !eps) return h->fail(RNNWF_ERR_INVALID, "rnnwf_sr_gram: bad arguments");
     if (int rc = sr_build(h)) return rc;
-    const int64_t ns = h->sr_ns, D = sr_image_size(h);
-    if (int rc = ensure(h, h->srCol, (size_t)2 * D * 8)) return rc;
-    if (int rc = ensure(h, h->srGram, (size_t)ns * ns * 8)) return rc;
-    double* mean = (double*)h->srCol.p;
-    if (int rc = h->f64 ? sr_colsum<double>(h, D, nullptr, 1.0 / (double)ns, mean) : sr_colsum<float>(h, D, nullptr, 1.0 / (double)ns, mean)) return rc;
-    const int64_t nb = (ns + 31) / 32, nblocks = nb * (nb + 1) / 2;
-    if (int rc = h->f64 ? launch_persistent(h, kTimerGemm, sr_gram_kernel<double>, 256, 0, nblocks, 1, (const double*)h->srJ.p, (const double*)mean,
-                                            (const uint8_t*)h->srMask.p, ns, D, nblocks, (double*)h->srGram.p)
-                        : launch_persistent(h, kTimerGemm, sr_gram_kernel<float>, 256, 0, nblocks, 1, (const float*)h->srJ.p, (const double*)mean,
-                                            (const uint8_t*)h->srMask.p, ns, D, nblocks, (double*)h->srGram.p))
-        return rc;
+    if (int rc = sr_gram_device(h)) return rc;
+    const int64_t ns = h->sr_ns;
     RNNWF_HIP(h, hipMemcpyAsync(gram, h->srGram.p, (size_t)ns * ns * 8, hipMemcpyDeviceToHost, h->stream));
     RNNWF_HIP(h, hipMemcpyAsync(eps, h->eloc.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream));
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));
@@ -207,6 +262,40 @@ extern "C" int rnnwf_sr_apply(rnnwf_handle* h, const double* y, double* out_dire
     if (int rc = ensure_staging(h, (size_t)D * 8)) return rc;
     RNNWF_HIP(h, hipMemcpyAsync(h->staging, col, (size_t)D * 8, hipMemcpyDeviceToHost, h->stream));
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));
+    sr_gather(h->sr_sidx, (const double*)h->staging, out_direction);
+    return RNNWF_OK;
+}
+
+extern "C" int rnnwf_sr_solve(rnnwf_handle* h, double diag_shift, double* y) {
+    if (!h) return RNNWF_ERR_INVALID;
+    if (!y) return h->fail(RNNWF_ERR_INVALID, "rnnwf_sr_solve: bad arguments");
+    if (int rc = sr_solve_common(h, "rnnwf_sr_solve", diag_shift)) return rc;
+    const int64_t ns = h->sr_ns;
+    if (int rc = ensure_staging(h, (size_t)(ns + 1) * 8)) return rc;
+    RNNWF_HIP(h, hipMemcpyAsync(h->staging, sr_y(h), (size_t)(ns + 1) * 8, hipMemcpyDeviceToHost, h->stream));      // y | status
+    RNNWF_HIP(h, hipStreamSynchronize(h->stream));
+    const long long status = ((const long long*)h->staging)[ns];
+    if (status) return sr_pivot_error(h, "rnnwf_sr_solve", status, diag_shift);
+    memcpy(y, h->staging, (size_t)ns * 8);
+    return RNNWF_OK;
+}
+
+extern "C" int rnnwf_sr_direction(rnnwf_handle* h, double diag_shift, double* out_direction) {
+    if (!h) return RNNWF_ERR_INVALID;
+    if (!out_direction) return h->fail(RNNWF_ERR_INVALID, "rnnwf_sr_direction: bad arguments");
+    if (int rc = sr_solve_common(h, "rnnwf_sr_direction", diag_shift)) return rc;
+    const int64_t ns = h->sr_ns, D = sr_image_size(h);
+    // dO^T y = J^T (y - mean y), as rnnwf_sr_apply, with the centring on the device
+    if (int rc = ensure(h, h->srY, (size_t)ns * 8)) return rc;
+    if (int rc = timed_launch(h, kTimerGemm, sr_centre_kernel, 1, 256, 0, (const double*)sr_y(h), ns, (double*)h->srY.p, (long long*)nullptr)) return rc;
+    double* col = (double*)h->srCol.p + D;
+    if (int rc = h->f64 ? sr_colsum<double>(h, D, (const double*)h->srY.p, 1.0, col) : sr_colsum<float>(h, D, (const double*)h->srY.p, 1.0, col)) return rc;
+    if (int rc = ensure_staging(h, (size_t)(D + 1) * 8)) return rc;
+    RNNWF_HIP(h, hipMemcpyAsync(h->staging, col, (size_t)D * 8, hipMemcpyDeviceToHost, h->stream));
+    RNNWF_HIP(h, hipMemcpyAsync((double*)h->staging + D, sr_status(h), 8, hipMemcpyDeviceToHost, h->stream));
+    RNNWF_HIP(h, hipStreamSynchronize(h->stream));
+    const long long status = ((const long long*)h->staging)[D];
+    if (status) return sr_pivot_error(h, "rnnwf_sr_direction", status, diag_shift);
     sr_gather(h->sr_sidx, (const double*)h->staging, out_direction);
     return RNNWF_OK;
 }

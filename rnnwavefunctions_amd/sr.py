@@ -6,8 +6,10 @@ the direction with diagonal shift lambda is
     delta = dO^T (dO dO^T + ns lambda I)^-1 eps  =  (S + lambda I)^-1 F,     S = dO^T dO / ns,  F = dO^T eps / ns
 
 and the update is theta <- theta - lr delta (2 F is the gradient of the reference's cost).  The device builds the per-sample
-Jacobian, the ns x ns Gram matrix and dO^T y (NativeWavefunction.log_derivatives / sr_gram / sr_apply); the ns x ns solve is done
-here, on the host, by Cholesky in float64: O(ns^3) with ns <= 4096, not the hot path.
+Jacobian, the ns x ns Gram matrix and dO^T y (NativeWavefunction.log_derivatives / sr_gram / sr_apply).  The ns x ns solve is a
+Cholesky factorisation in float64, O(ns^3) with ns <= 4096: solver="host" (the default) does it here with LAPACK on the matrix
+sr_gram copies back, solver="device" leaves it to NativeWavefunction.sr_direction, which factorises and solves on the device and
+returns the direction alone.
 """
 import numpy as np
 
@@ -32,9 +34,18 @@ def solve_shifted(gram, eps, diag_shift):
     return np.linalg.solve(c.T, np.linalg.solve(c, e))
 
 
-def minsr_direction(wf, diag_shift):
-    """delta (num_params,) float64 on the resident batch of `wf` (the last vmc_step / load_batch), flat order of wf._layout()."""
-    _check_shift(diag_shift)
+def _check_solver(solver):
+    if solver not in ("host", "device"):
+        raise ValueError("solver must be 'host' or 'device', got %r" % (solver,))
+    return solver
+
+
+def minsr_direction(wf, diag_shift, solver="host"):
+    """delta (num_params,) float64 on the resident batch of `wf` (the last vmc_step / load_batch), flat order of wf._layout().
+    solver "host": Gram matrix to the host, LAPACK Cholesky, sr_apply; "device": wf.sr_direction, the whole direction on the device."""
+    lam = _check_shift(diag_shift)
+    if _check_solver(solver) == "device":
+        return wf.sr_direction(lam)
     gram, eps = wf.sr_gram()
     return wf.sr_apply(solve_shifted(gram, eps, diag_shift))
 
@@ -62,13 +73,15 @@ def unflatten_params(wf, flat, like, scope="RNNwavefunction"):
     return out
 
 
-def train_tfim(wf, Jz, Bx, params, numsteps=100, numsamples=500, learningrate=1e-2, diag_shift=1e-3, seed=111, scope="RNNwavefunction"):
+def train_tfim(wf, Jz, Bx, params, numsteps=100, numsamples=500, learningrate=1e-2, diag_shift=1e-3, seed=111, scope="RNNwavefunction",
+               solver="host"):
     """Minimise the 1D / raster TFIM energy of `wf` (a NativeWavefunction of GRU1D or GRU1D_F64 with one layer, holding `params`)
     by minSR: vmc_step (samples, local energies, moments; the batch stays resident) -> minsr_direction -> theta -= lr delta ->
     set_params_flat.  Returns (meanEnergy, varEnergy), one entry per iteration 0..numsteps like training.minimize_hamiltonian; the
     trained parameters are left in train_tfim.last_params.  The parameters keep the dtype of `params` (float32 models round every
-    update to float32, as the Adam drivers do)."""
+    update to float32, as the Adam drivers do).  `solver` as in minsr_direction."""
     _check_shift(diag_shift)
+    _check_solver(solver)
     if int(numsteps) < 0 or int(numsamples) < 2:
         raise ValueError("numsteps must be >= 0 and numsamples >= 2, got %r and %r" % (numsteps, numsamples))
     jz = np.asarray(Jz, dtype=np.float64).ravel()
@@ -84,7 +97,7 @@ def train_tfim(wf, Jz, Bx, params, numsteps=100, numsamples=500, learningrate=1e
         meanE = s1 / n
         meanEnergy.append(meanE)
         varEnergy.append(s2 / n - meanE ** 2)
-        theta = (theta - learningrate * minsr_direction(wf, diag_shift)).astype(dtype).astype(np.float64)
+        theta = (theta - learningrate * minsr_direction(wf, diag_shift, solver)).astype(dtype).astype(np.float64)
         wf.set_params_flat(theta)
     train_tfim.last_params = unflatten_params(wf, theta, params, scope)
     return meanEnergy, varEnergy

@@ -4,7 +4,9 @@
 
 Per repetition the batch is loaded again (untimed), which drops the resident Jacobian; then, each ending in a device synchronise and
 timed with the host clock: the Jacobian build (rnnwf_log_derivatives with out = NULL), rnnwf_sr_gram, rnnwf_sr_apply, the host
-Cholesky solve, and rnnwf_vmc_gradient (untouched by the SR code: the gradient's time as before it).  Prints the median of each.
+Cholesky solve, and rnnwf_vmc_gradient (untouched by the SR code: the gradient's time as before it); then, on a Jacobian that is
+already built, one rnnwf_sr_direction call (Gram matrix, Cholesky factorisation, both triangular solves and dO^T y on the device): the
+"device direction" column, to be set against gram + host solve + apply.  Prints the median of each.
 """
 import argparse
 import os
@@ -31,7 +33,7 @@ def main():
     couplings = np.append(np.ones(a.N), 1.0)
     out = wf.vmc_step(a.ns, 111, 0, couplings, want_samples=True, want_eloc=True)
     s, e = out["samples"], out["eloc"]
-    times = {k: [] for k in ("jacobian", "gram", "solve", "apply", "gradient")}
+    times = {k: [] for k in ("jacobian", "gram", "solve", "apply", "gradient", "direction")}
 
     def timed(key, fn):
         t0 = time.perf_counter()
@@ -50,10 +52,12 @@ def main():
         y = timed("solve", lambda: sr.solve_shifted(gram, eps, 1e-3))
         timed("apply", lambda: wf.sr_apply(y))
         timed("gradient", lambda: wf._check(wf.lib.rnnwf_vmc_gradient(wf.h, float(e.mean()), 0.0, float(a.ns))))
+        build_jacobian()                                                  # untimed: the gradient reused the Jacobian's inputs
+        timed("direction", lambda: wf.sr_direction(1e-3))
     med = {k: float(np.median(v[3:])) for k, v in times.items()}          # the first three repetitions warm up
-    print("N %d units %d ns %d %s, %d params, median of %d repetitions [ms]: jacobian %.3f  gram %.3f  apply %.3f  host solve %.3f  |  vmc_gradient %.3f"
+    print("N %d units %d ns %d %s, %d params, median of %d repetitions [ms]: jacobian %.3f  gram %.3f  apply %.3f  host solve %.3f  device direction %.3f  |  vmc_gradient %.3f"
           % (a.N, a.units, a.ns, "f64" if a.f64 else "f32", wf.num_params(), a.reps, med["jacobian"], med["gram"], med["apply"], med["solve"],
-             med["gradient"]))
+             med["direction"], med["gradient"]))
 
 
 if __name__ == "__main__":
