@@ -1,8 +1,8 @@
-// crnn_observable.h - what the host drivers of the complex RNN's observable passes share: rnnwf_pauli_step_complex (crnn_pauli.hip)
-// and rnnwf_renyi2_regions_complex (crnn_renyi.hip).  Both serve CRNN_U1 with one GRU layer and run, per pass of whole 16-chain
-// blocks within the state budget: spins -> teacher-forced base pass on the one-wave f32 kernel with checkpoints (crnn_plain_base) ->
-// their own kernels on chains restarted from the checkpoints.  Here are the launch table, the pass size, the sector check of the
-// caller's samples and the model names of the refusals; the scratch carving, the chain source and the pass loop are observable.h's.
+// crnn_observable.h - what the complex RNN's policies of the Pauli and region-Renyi drivers share: rnnwf_pauli_step_complex
+// (crnn_pauli.hip, pauli_driver.h) and rnnwf_renyi2_regions_complex (crnn_renyi.hip, region_driver.h).  Both serve CRNN_U1 with one
+// GRU layer and run, per pass of whole 16-chain blocks within the state budget: spins -> teacher-forced base pass on the one-wave f32
+// kernel with checkpoints -> their own kernels on chains restarted from the checkpoints.  Here are the launch table, the model
+// refusal, the base pass, the pass size and the sector check of the caller's samples.
 #pragma once
 #include <algorithm>
 
@@ -40,9 +40,27 @@ inline int64_t crnn_blocks_per_pass(rnnwf_handle* h, size_t bytes_per_block) {
     return std::max<int64_t>(1, (int64_t)(state_budget_bytes(h, kDefaultStateBudget) / per_block));
 }
 
-inline const char* model_name(int model) {
-    static const char* const names[] = {"GRU1D", "GRU1D_PARITY", "CRNN_U1", "GRU1D_F64", "MDRNN2D", "LSTM1D_F64"};
-    return model >= 0 && model < (int)(sizeof names / sizeof *names) ? names[model] : "unknown";
+// 0, or RNNWF_ERR_INVALID for another model, stacked layers or a width without kernels; gru_entry, md_entry: the entry points that
+// serve the GRU models and the 2D RNN
+inline int crnn_refuse(rnnwf_handle* h, const char* entry, const char* gru_entry, const char* md_entry) {
+    if (h->model != RNNWF_MODEL_CRNN_U1)
+        return h->fail(RNNWF_ERR_INVALID, "%s: serves the complex RNN (CRNN_U1) only, this handle's model is %s; %s serves the GRU models, %s "
+                       "the 2D RNN", entry, model_name(h->model), gru_entry, md_entry);
+    if (h->NL > 1) return h->fail(RNNWF_ERR_INVALID, "%s: not implemented for stacked layers (one GRU layer only)", entry);
+    if (!with_crnn1(h, [](auto) {})) return h->fail(RNNWF_ERR_INVALID, "%s: no kernel for NFULL=%d", entry, h->NFULL);
+    return 0;
+}
+
+// the teacher-forced base pass over the ns chains in h->bits on the one-wave kernel, checkpoints into h->hck; tot: [ns] log psi on the
+// device, or nullptr
+inline int crnn_observable_base(rnnwf_handle* h, int64_t ns, double2* tot) {
+    const int64_t nsb = (ns + kChains - 1) / kChains;
+    if (int rc = ensure(h, h->hck, (size_t)std::max(h->N - 1, 1) * nsb * crnn_hck_bytes_per_block(h))) return rc;
+    CrnnArgs b = crnn_base_args(h, ns);
+    b.bits = (uint32_t*)h->bits.p;
+    b.hck = h->hck.p;
+    b.tot = tot;
+    return crnn_plain_base(h, b);
 }
 
 // 0, or RNNWF_ERR_INVALID naming the first of the caller's ns chains outside the zero-magnetisation sector: its own log psi is -inf

@@ -78,6 +78,14 @@ const Gradient* gru_gradient();   // grad.hip: the GRU hooks of gru_family and c
 // the fused VMC step behind rnnwf_vmc_step and rnnwf_train_steps (rnnwf_api.hip); out_samples, out_eloc, moments may be nullptr
 int vmc_step(rnnwf_handle* h, int64_t ns, const Draw& draw, const double* couplings, int32_t* out_samples, void* out_eloc,
              double* moments);
+// the batch just computed stays on the device (h->bits, h->hck, h->eloc) for rnnwf_vmc_gradient (rnnwf_api.hip): h->last_ns and
+// h->sr_valid change together.  ns = 0: no batch is resident
+void keep_resident(rnnwf_handle* h, int64_t ns);
+// the name of an rnnwf_model value, for the refusals
+inline const char* model_name(int model) {
+    static const char* const names[] = {"GRU1D", "GRU1D_PARITY", "CRNN_U1", "GRU1D_F64", "MDRNN2D", "LSTM1D_F64"};
+    return model >= 0 && model < (int)(sizeof names / sizeof *names) ? names[model] : "unknown";
+}
 // RNNWF_ERR_INVALID ("<what>: no gradient for the ...") for a family without one
 int require_gradient(rnnwf_handle* h, const char* what);
 // the gradient driver (grad.hip): result left in h->gradW, its layout in *im (may be nullptr).  mom_dev != nullptr (device

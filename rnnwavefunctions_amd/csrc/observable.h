@@ -1,10 +1,11 @@
-// observable.h - what the host drivers of the four observable passes share: rnnwf_renyi2_swap (renyi.hip), rnnwf_correlations
-// (corr.hip), rnnwf_renyi2_regions (renyi_regions.hip) and rnnwf_pauli_step (pauli.hip).  All four serve the positive GRU models with
-// one layer (GRU1D, GRU1D_F64) and run, per pass of whole 16-chain blocks within the state budget: spins (the caller's, or drawn
-// exactly as rnnwf_sample draws them) -> teacher-forced base pass on the one-wave kernel with checkpoints -> their own kernels on
-// chains restarted from the checkpoints (chain_kernels.h) -> log-ratios and sums.  The sums of the passes are added on the host in
-// pass order.  Each .hip instantiates its own kernels, under its own flags; here are the launch table, the refusals, the common
-// kernel arguments, the base pass, the pass size, the scratch carving and the pass loop.
+// observable.h - what the host drivers of the observable passes share.  The launch table, the refusals, the common kernel arguments,
+// the base pass and the pass size serve the positive GRU models with one layer (GRU1D, GRU1D_F64): rnnwf_renyi2_swap (renyi.hip),
+// rnnwf_correlations (corr.hip), rnnwf_renyi2_regions (renyi_regions.hip) and rnnwf_pauli_step (pauli.hip).  The scratch carving, the
+// chain source and the pass loop serve every family: the complex RNN's pieces are in crnn_observable.h, the 2D RNN's in
+// mdrnn_observable.h, the drivers of the Pauli and region-Renyi entry points of all three in pauli_driver.h and region_driver.h.
+// Per pass of whole 16-chain blocks within the state budget: spins (the caller's, or drawn exactly as rnnwf_sample draws them) ->
+// base pass that keeps the states -> the entry's own kernels on chains restarted from them -> log-ratios and sums.  The sums of the
+// passes are added on the host in pass order.  Each .hip instantiates its own kernels, under its own flags.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -127,30 +128,44 @@ struct ChainSource {
     int32_t* out_samples;
 };
 
-// The pass loop: `count` units (chains_per_unit = 1: chains, 2: pairs) in passes of `chunk`.  Per pass: the spins into h->bits, then
-// pass(u0, n_units, ns, pass_sums) launches and queues its own copies to the host (this pass's sums into pass_sums, total.size()
-// doubles); after the synchronisation pass_sums is added to `total`, in pass order.
+// The pass loop of every family: `count` units (chains_per_unit = 1: chains, 2: pairs) in passes of `chunk`.  Per pass: the spins into
+// h->bits in the family's site order (Family::site_maps) - after the caller's samples the family's base pass, where that is what
+// keeps the states (Family::base_keeps_states) - then pass(u0, n_units, ns, pass_sums) launches and queues its own copies to the host
+// (this pass's sums into pass_sums, total.size() doubles); after the synchronisation pass_sums is added to `total`, in pass order.
 template <class Pass>
 int for_each_pass(rnnwf_handle* h, const ChainSource& src, int64_t count, int64_t chunk, int chains_per_unit, std::vector<double>& total,
                   Pass&& pass) {
     const int N = h->N;
+    const Family& f = *h->family;
+    const int32_t *col_of_pos = nullptr, *pos_of_site = nullptr;
+    if (f.site_maps)
+        if (int rc = f.site_maps(h, &col_of_pos, &pos_of_site)) return rc;
     std::vector<double> pass_sums(total.size());
     for (int64_t u0 = 0; u0 < count; u0 += chunk) {
         const int64_t nu = std::min(chunk, count - u0), ns = chains_per_unit * nu, s0 = chains_per_unit * u0;
         if (int rc = ensure(h, h->bits, (size_t)(N + 31) / 32 * ns * 4)) return rc;
         if (src.samples) {
-            if (int rc = upload_and_pack(h, src.samples + s0 * N, ns, h->bits, 0, nullptr)) return rc;
+            if (int rc = upload_and_pack(h, src.samples + s0 * N, ns, h->bits, 0, col_of_pos)) return rc;
+            if (f.base_keeps_states)
+                if (int rc = f.base(h, ns, nullptr)) return rc;
         } else {
             const Draw d{src.seed, src.step, chains_per_unit * src.offset + s0};      // rnnwf_sample's draw (its own base-pass kernel)
-            if (int rc = h->family->base(h, ns, &d)) return rc;
+            if (int rc = f.base(h, ns, &d)) return rc;
             if (src.out_samples)
-                if (int rc = unpack_and_download(h, h->bits, ns, src.out_samples + s0 * N, nullptr)) return rc;
+                if (int rc = unpack_and_download(h, h->bits, ns, src.out_samples + s0 * N, pos_of_site)) return rc;
         }
         if (int rc = pass(u0, nu, ns, pass_sums.data())) return rc;
         RNNWF_HIP(h, hipStreamSynchronize(h->stream));
         for (size_t k = 0; k < total.size(); ++k) total[k] += pass_sums[k];
     }
     return 0;
+}
+
+// the refusal of a handle whose parameters are not committed: RNNWF_ERR_STATE, or (the 2D entries) RNNWF_ERR_INVALID with the entry
+inline int refuse_uncommitted(rnnwf_handle* h, const char* entry, bool invalid_with_entry) {
+    if (h->committed) return 0;
+    if (invalid_with_entry) return h->fail(RNNWF_ERR_INVALID, "%s: parameters not committed (call rnnwf_commit_params)", entry);
+    return h->fail(RNNWF_ERR_STATE, "parameters not committed (call rnnwf_commit_params)");
 }
 
 }  // namespace rnnwf

@@ -1,0 +1,115 @@
+// pauli_driver.h - the host driver of the Pauli-step entry points of every family: rnnwf_pauli_step (pauli.hip), rnnwf_pauli_step_2d
+// (mdrnn_pauli.hip) and rnnwf_pauli_step_complex (crnn_pauli.hip).  Per call: validation, the terms (pauli_terms.h), the pass size,
+// one scratch allocation sized by the largest pass with the tables uploaded once, the pass loop (observable.h) with the per-pass
+// copies of log-ratios, E_loc and moments, and the resident-batch rule.  A family's .hip supplies a policy struct P:
+//   kEntry, kCoeff             names in the refusals
+//   kElem, kComplex, kOwnLogP  bytes of a value (8 real, 16 complex); complex64 E_loc and four moments; a [ns] piece for the log
+//                              psi of the pass's own base pass
+//   kThreads                   chains per assembly block
+//   kUncommittedInvalid        the code of the "not committed" refusal (observable.h: refuse_uncommitted)
+//   refuse(h), precheck(h, samples, ns), positions(h), cells(h), chunk(h, M)     the model refusal; further checks of the caller's
+//                              arguments; site -> position map (empty: the same) and cell evaluations of a chain flipped from
+//                              position 0 on (pauli_terms.h); chains per pass
+//   pass(h, ns, g, sc, keep, sums_host)   the kernels of one pass over the chains in h->bits: log-ratios at sc.lr, E_loc in h->eloc
+#pragma once
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "observable.h"
+#include "pauli_terms.h"
+
+namespace rnnwf {
+
+// Scratch of one pass of ns chains in h->renyi; the call's tables lead, at offsets that do not depend on ns
+struct PauliScratch {
+    size_t mask, order, first, sgn, tmask, coeff, terms, logp, tail, lr, part, sums, bytes;
+    int64_t nblk;      // assembly blocks per term
+    PauliScratch(int N, const PauliTerms& g, int64_t ns, size_t elem, bool own_logp, int threads) {
+        Carve c;
+        const size_t M = (size_t)std::max(g.M, 1), K = (size_t)g.K;
+        nblk = (ns + threads - 1) / threads;
+        mask = c.take(M * g.W * 4);
+        order = c.take(M * 4);
+        first = c.take(M * 4);
+        sgn = c.take(K * g.W * 4);
+        tmask = c.take(K * 4);
+        coeff = c.take(K * elem);
+        terms = c.take((size_t)N * ns * elem);
+        logp = c.take(own_logp ? (size_t)ns * elem : 0);
+        tail = c.take(M * ns * elem);
+        lr = c.take(M * ns * elem);
+        part = c.take(K * nblk * 2 * elem);
+        sums = c.take(K * 2 * elem);
+        bytes = c.bytes;
+    }
+};
+
+// coeff: [K] values of P::kElem bytes; out_eloc: [ns] float64 or complex64, 8 bytes either way; term_sums: [K] rows of P::kElem / 4 doubles
+template <class P>
+int pauli_step(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const void* coeff, int32_t nterms, const int32_t* samples,
+               int64_t ns, uint64_t seed, uint64_t step, int64_t sample_offset, double* term_sums, void* out_eloc, double* moments,
+               double* out_log_ratio, int32_t* out_samples) {
+    // everything is validated before the resident batch (h->bits, h->hck, h->eloc) is touched: a refused call leaves it usable
+    if (!h) return RNNWF_ERR_INVALID;
+    if (int rc = P::refuse(h)) return rc;
+    if (int rc = refuse_uncommitted(h, P::kEntry, P::kUncommittedInvalid)) return rc;
+    if (nterms < 1) return h->fail(RNNWF_ERR_INVALID, "%s: nterms must be >= 1", P::kEntry);
+    if (ns < 1) return h->fail(RNNWF_ERR_INVALID, "%s: ns must be >= 1", P::kEntry);
+    if (!flip || !sign || !coeff || !term_sums)
+        return h->fail(RNNWF_ERR_INVALID, "%s: flip, sign, %s and term_sums must be non-null", P::kEntry, P::kCoeff);
+    if (!samples && sample_offset < 0) return h->fail(RNNWF_ERR_INVALID, "%s: sample_offset must be >= 0", P::kEntry);
+    if (int rc = P::precheck(h, samples, ns)) return rc;
+    PauliTerms g;
+    const std::vector<int32_t> pos = P::positions(h);
+    if (int rc = prepare_pauli_terms(h, P::kEntry, flip, sign, nterms, pos.empty() ? nullptr : pos.data(), P::cells(h), g)) return rc;
+    const int N = h->N, K = nterms, M = g.M;
+    const size_t E = P::kElem;
+    const int64_t chunk = P::chunk(h, M);
+    if ((int64_t)K * ((std::min(chunk, ns) + P::kThreads - 1) / P::kThreads) > 0x7fffffffLL)
+        return h->fail(RNNWF_ERR_INVALID, "%s: nterms x ceil(ns / %d) exceeds the grid of the term kernel; split the batch", P::kEntry,
+                       P::kThreads);
+    RNNWF_HIP(h, hipSetDevice(h->cfg.device));
+    // the first pass is the largest: one allocation for the call, the tables uploaded once
+    const PauliScratch big(N, g, std::min(chunk, ns), E, P::kOwnLogP, P::kThreads);
+    if (int rc = ensure(h, h->renyi, big.bytes)) return rc;
+    {
+        char* buf = (char*)h->renyi.p;
+        if (M) {
+            RNNWF_HIP(h, hipMemcpyAsync(buf + big.mask, g.mask.data(), g.mask.size() * 4, hipMemcpyHostToDevice, h->stream));
+            RNNWF_HIP(h, hipMemcpyAsync(buf + big.order, g.order.data(), (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
+            RNNWF_HIP(h, hipMemcpyAsync(buf + big.first, g.first.data(), (size_t)M * 4, hipMemcpyHostToDevice, h->stream));
+        }
+        RNNWF_HIP(h, hipMemcpyAsync(buf + big.sgn, g.sgn.data(), g.sgn.size() * 4, hipMemcpyHostToDevice, h->stream));
+        RNNWF_HIP(h, hipMemcpyAsync(buf + big.tmask, g.tmask.data(), (size_t)K * 4, hipMemcpyHostToDevice, h->stream));
+        RNNWF_HIP(h, hipMemcpyAsync(buf + big.coeff, coeff, (size_t)K * E, hipMemcpyHostToDevice, h->stream));
+        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    h->last_ns = 0;                                   // h->bits, h->hck and h->eloc are overwritten from here on
+    h->call_ns = ns;
+    std::vector<double> total((size_t)K * E / 4, 0.0);
+    double mom[4] = {0.0, 0.0, 0.0, 0.0};
+    const ChainSource src{samples, seed, step, sample_offset, out_samples};
+    if (int rc = for_each_pass(h, src, ns, chunk, 1, total, [&](int64_t s0, int64_t, int64_t n, double* pass_sums) {
+            const PauliScratch sc(N, g, n, E, P::kOwnLogP, P::kThreads);
+            if (int rc = P::pass(h, n, g, sc, ns <= chunk, pass_sums)) return rc;
+            if (out_log_ratio && M)
+                RNNWF_HIP(h, hipMemcpy2DAsync((char*)out_log_ratio + s0 * E, (size_t)ns * E, (char*)h->renyi.p + sc.lr, (size_t)n * E,
+                                              (size_t)n * E, (size_t)M, hipMemcpyDeviceToHost, h->stream));
+            if (out_eloc) RNNWF_HIP(h, hipMemcpyAsync((char*)out_eloc + s0 * 8, h->eloc.p, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+            if (moments) {                                               // synchronises the stream
+                double pm[4];
+                if (int rc = run_moments(h, h->eloc.p, n, P::kComplex, pm)) return rc;
+                for (int k = 0; k < (P::kComplex ? 4 : 3); ++k) mom[k] += pm[k];
+            }
+            return 0;
+        }))
+        return rc;
+    memcpy(term_sums, total.data(), total.size() * 8);
+    if (moments) memcpy(moments, mom, sizeof mom);
+    // one pass: bits, states and E_loc of the whole batch are on the device, as rnnwf_vmc_step leaves them
+    keep_resident(h, ns <= chunk ? ns : 0);
+    return RNNWF_OK;
+}
+
+}  // namespace rnnwf

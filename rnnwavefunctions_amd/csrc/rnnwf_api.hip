@@ -537,7 +537,7 @@ static int site_maps(rnnwf_handle* h, const int32_t** col_of_pos, const int32_t*
 static int64_t n_couplings(const rnnwf_handle* h) { return (int64_t)h->family->coupl_per_site * h->N + h->family->coupl_tail; }
 
 // the batch just computed stays on the device (h->bits, h->hck, h->eloc) for rnnwf_vmc_gradient
-static void keep_resident(rnnwf_handle* h, int64_t ns) {
+void rnnwf::keep_resident(rnnwf_handle* h, int64_t ns) {
     if (h->family->gradient) h->last_ns = ns;
     h->sr_valid = false;          // a new batch: its log-derivatives are not built yet (sr.hip)
 }

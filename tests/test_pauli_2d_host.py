@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def driver_pos_of_site(Nx, Ny, k):
-    """pos_of_site of csrc/mdrnn_pauli.hip, restated (the GPU tests check the compiled one through the log-ratios)."""
+    """pos_of_site of csrc/mdrnn_observable.h, restated (the GPU tests check the compiled one through the log-ratios)."""
     nx, ny = divmod(k, Ny)
     return ny * Nx + (nx if ny % 2 == 0 else Nx - 1 - nx)
 
@@ -34,7 +34,7 @@ def test_lattice_masks_map_to_the_zigzag_order(Nx, Ny):
         one[k] = 1
         assert np.flatnonzero(Q.to_visit_order(one, Nx, Ny)).tolist() == [p]
     # the driver's formula is in the source as restated here
-    src = open(os.path.join(ROOT, "rnnwavefunctions_amd", "csrc", "mdrnn_pauli.hip")).read()
+    src = open(os.path.join(ROOT, "rnnwavefunctions_amd", "csrc", "mdrnn_observable.h")).read()
     assert "const int nx = k / h->Ny, ny = k % h->Ny;" in src and "ny * h->Nx + (ny % 2 == 0 ? nx : h->Nx - 1 - nx)" in src
     # a mask that is not symmetric under the map: the first flipped POSITION is not the first flipped lattice index
     m = np.zeros(N, dtype=np.int32)
