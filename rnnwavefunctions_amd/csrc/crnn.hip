@@ -5,7 +5,6 @@
 #include <cstdlib>
 
 #include "crnn_kernels.h"
-#include "crnn_ml_kernels.h"
 #include "models.h"
 #include "pack.h"
 
@@ -15,103 +14,65 @@ namespace {
 
 constexpr int64_t kChunk = (int64_t)1 << 20;
 
-template <int NFULL, int WAVES>
+// The kernels of one shape: NL == 1 one GRU layer, NL > 1 stacked layers (T: float, the one element type of this family).
+template <typename T, int NFULL, int NL, int WAVES>
 struct CLaunch {
-    using L = GruLayout<float, NFULL, 3>;
-    static int base_coop(rnnwf_handle* h, const CrnnArgs& a) {
-        if constexpr (NFULL <= 4) {
-            const size_t lds = L::BYTES + (size_t)2 * L::KT * 64 * 4 + 2 * 64 * 4;
-            return launch_persistent(h, kTimerBase, crnn_base_coop_kernel<NFULL>, (NFULL + 1) * 64, lds, a.nsb, 1, a);
-        }
-        return 0;
-    }
+    using S = GruStack<T, NFULL, NL, 3>;
+    using L = GruLayout<T, NFULL, 3>;
     static int base(rnnwf_handle* h, const CrnnArgs& a) {
-        if (NFULL <= 3 && base_bf_available(h)) return crnn_base_coop_bf(h, a);      // bf16 cooperative kernel, every batch size (prnn.hip)
-        // fewer 16-chain blocks than SIMDs: the cooperative kernel (NFULL + 1 waves per block, bit-identical)
-        if (NFULL <= 4 && a.nsb <= (int64_t)4 * h->cu_count && !h->knobs.no_coop) return base_coop(h, a);
-        return plain(h, a);
+        if constexpr (NL > 1) {
+            // all layers' images resident in LDS (up to 52 units): the gate tiles of every layer spread over NFULL + 1 waves per block of
+            // 16 chains (ml_coop.h) - for every batch size, its accumulation order is not the one-wave kernel's; RNNWF_NO_COOP=1 keeps that one
+            if constexpr (MlCoopLayout<NFULL, NL, 3>::FITS && S::SPILL == 0) {
+                if (!h->knobs.no_coop) {
+                    using ML = MlCoopLayout<NFULL, NL, 3>;
+                    return launch_persistent(h, kTimerBase, crnn_base_coop_kernel<NFULL, false, NL>, ML::THREADS, ML::LDS, a.nsb, ML::NB, a);
+                }
+            }
+            return launch_shrinking<WAVES>(h, kTimerBase, crnn_ml_base_kernel<NFULL, NL, WAVES>, S::LDS_BYTES, a.nsb, a);
+        } else {
+            if (NFULL <= 3 && base_bf_available(h)) return crnn_base_coop_bf(h, a);      // bf16 cooperative kernel, every batch size (prnn.hip)
+            // fewer 16-chain blocks than SIMDs: the cooperative kernel (NFULL + 1 waves per block, bit-identical)
+            if constexpr (NFULL <= 4) {
+                if (a.nsb <= (int64_t)4 * h->cu_count && !h->knobs.no_coop) {
+                    const size_t lds = L::BYTES + (size_t)2 * L::KT * 64 * 4 + 2 * 64 * 4;
+                    return launch_persistent(h, kTimerBase, crnn_base_coop_kernel<NFULL>, (NFULL + 1) * 64, lds, a.nsb, 1, a);
+                }
+            }
+            return plain(h, a);
+        }
     }
     // the one-wave kernel for every batch size (crnn_plain_base)
     static int plain(rnnwf_handle* h, const CrnnArgs& a) {
-        return launch_persistent(h, kTimerBase, crnn_base_kernel<NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, a.nsb, WAVES, a);
+        if constexpr (NL > 1) return h->fail(RNNWF_ERR_INVALID, "crnn_plain_base: one GRU layer only");
+        else return launch_persistent(h, kTimerBase, crnn_base_kernel<NFULL, WAVES>, WAVES * 64, S::LDS_BYTES, a.nsb, WAVES, a);
     }
     // the tile count lives on the device: the persistent grid is bounded by the worst case
     static int swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles) {
-        return launch_persistent(h, kTimerFlip, crnn_swap_kernel<NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, max_tiles, WAVES, a);
-    }
-    static std::vector<char> pack(const rnnwf_handle* h) { return pack_gru_image<float, NFULL, 3>(h); }
-    static size_t hck_bytes_per_block() { return (size_t)L::KT * 64 * sizeof(float); }
-};
-
-// stacked layers (forward passes on the f32-input MFMA; crnn_ml_kernels.h)
-template <int NFULL, int NL, int WAVES>
-struct CMLaunch {
-    using M = CrnnMlCore<NFULL, NL>;
-    static int base(rnnwf_handle* h, const CrnnArgs& a) {
-        // all layers' images resident in LDS (up to 52 units): the gate tiles of every layer spread over NFULL + 1 waves per block of
-        // 16 chains (ml_coop.h) - for every batch size, its accumulation order is not the one-wave kernel's; RNNWF_NO_COOP=1 keeps that one
-        if constexpr (MlCoopLayout<NFULL, NL, 3>::FITS && M::SPILL == 0) {
-            if (!h->knobs.no_coop) {
-                using ML = MlCoopLayout<NFULL, NL, 3>;
-                return launch_persistent(h, kTimerBase, crnn_base_coop_kernel<NFULL, false, NL>, ML::THREADS, ML::LDS, a.nsb, ML::NB, a);
-            }
-        }
-        return launch_shrinking<WAVES>(h, kTimerBase, crnn_ml_base_kernel<NFULL, NL, WAVES>, M::BYTES, a.nsb, a);
-    }
-    static int plain(rnnwf_handle* h, const CrnnArgs&) { return h->fail(RNNWF_ERR_INVALID, "crnn_plain_base: one GRU layer only"); }
-    static int swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles) {
-        return launch_persistent(h, kTimerFlip, crnn_ml_swap_kernel<NFULL, NL, WAVES>, WAVES * 64, M::BYTES, max_tiles, WAVES, a);
+        if constexpr (NL > 1) return launch_persistent(h, kTimerFlip, crnn_ml_swap_kernel<NFULL, NL, WAVES>, WAVES * 64, S::LDS_BYTES, max_tiles, WAVES, a);
+        else return launch_persistent(h, kTimerFlip, crnn_swap_kernel<NFULL, WAVES>, WAVES * 64, S::LDS_BYTES, max_tiles, WAVES, a);
     }
     static std::vector<char> pack(const rnnwf_handle* h) {
-        std::vector<char> img = pack_gru_image<float, NFULL, 3>(h);
-        for (int l = 1; l < NL; ++l) {
-            const std::vector<char> up = pack_upper_image<NFULL>(h, l);
-            img.insert(img.end(), up.begin(), up.end());
-        }
+        std::vector<char> img = pack_gru_image<T, NFULL, 3>(h);
+        if constexpr (NL > 1)
+            for (int l = 1; l < NL; ++l) {
+                const std::vector<char> up = pack_upper_image<NFULL>(h, l);
+                img.insert(img.end(), up.begin(), up.end());
+            }
         return img;
     }
-    static size_t hck_bytes_per_block() { return (size_t)NL * M::KT * 64 * sizeof(float); }
+    static size_t hck_bytes_per_block() { return (size_t)S::ROW * 64 * sizeof(T); }
 };
 
-// fn(K()) for this handle's launch class K, false (fn not called) for a shape without kernels: <NFULL, [layers,] waves per workgroup>
+// (layers, NFULL) -> waves per workgroup: every shape with kernels
+template <int NL, int NFULL, int WAVES> using R = KernelRow<float, NL, NFULL, WAVES>;
+using Kernels = KernelTable<
+    R<1, 1, 4>, R<1, 2, 4>, R<1, 3, 4>, R<1, 4, 4>, R<1, 6, 8>, R<1, 8, 4>, R<1, 12, 4>, R<1, 16, 4>,
+    R<2, 1, 4>, R<2, 2, 4>, R<2, 3, 8>, R<2, 4, 4>, R<2, 6, 4>,
+    R<3, 1, 4>, R<3, 2, 8>, R<3, 3, 8>, R<3, 4, 4>, R<3, 6, 4>,
+    R<4, 1, 4>, R<4, 2, 4>, R<4, 3, 4>, R<4, 4, 4>, R<4, 6, 4>>;
 template <class Fn>
-bool with_launch(const rnnwf_handle* h, Fn&& fn) {
-    const int nf = h->NFULL;
-    switch (h->NL) {
-        case 2: switch (nf) {
-            case 1: fn(CMLaunch<1, 2, 4>()); return true;
-            case 2: fn(CMLaunch<2, 2, 4>()); return true;
-            case 3: fn(CMLaunch<3, 2, 8>()); return true;
-            case 4: fn(CMLaunch<4, 2, 4>()); return true;
-            case 6: fn(CMLaunch<6, 2, 4>()); return true;
-        } return false;
-        case 3: switch (nf) {
-            case 1: fn(CMLaunch<1, 3, 4>()); return true;
-            case 2: fn(CMLaunch<2, 3, 8>()); return true;
-            case 3: fn(CMLaunch<3, 3, 8>()); return true;
-            case 4: fn(CMLaunch<4, 3, 4>()); return true;
-            case 6: fn(CMLaunch<6, 3, 4>()); return true;
-        } return false;
-        case 4: switch (nf) {
-            case 1: fn(CMLaunch<1, 4, 4>()); return true;
-            case 2: fn(CMLaunch<2, 4, 4>()); return true;
-            case 3: fn(CMLaunch<3, 4, 4>()); return true;
-            case 4: fn(CMLaunch<4, 4, 4>()); return true;
-            case 6: fn(CMLaunch<6, 4, 4>()); return true;
-        } return false;
-    }
-    switch (nf) {
-        case 1: fn(CLaunch<1, 4>()); return true;
-        case 2: fn(CLaunch<2, 4>()); return true;
-        case 3: fn(CLaunch<3, 4>()); return true;
-        case 4: fn(CLaunch<4, 4>()); return true;
-        case 6: fn(CLaunch<6, 8>()); return true;
-        case 8: fn(CLaunch<8, 4>()); return true;
-        case 12: fn(CLaunch<12, 4>()); return true;
-        case 16: fn(CLaunch<16, 4>()); return true;
-    }
-    return false;
-}
+bool with_launch(const rnnwf_handle* h, Fn&& fn) { return with_kernels<CLaunch>(Kernels(), h, fn); }
 
 int no_kernel(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "no cRNN kernel for NFULL=%d", h->NFULL); }
 int launch_base(rnnwf_handle* h, const CrnnArgs& a) {

@@ -1,6 +1,7 @@
 // crnn_kernels.h - complex RNN wave function with the U(1) zero-magnetisation mask and the J1-J2
 // local-energy path (J1J2/ComplexRNNwavefunction.py, J1J2/TrainingRNN_J1J2.py).
 //
+// (crnn_ml_base_kernel / crnn_ml_swap_kernel: the same two passes for NL > 1 stacked GRU layers.)
 //   crnn_base_kernel    : masked ancestral sampling (:45-103) or teacher-forced log-amplitude (:105-169),
 //                         16 chains per wave; optional checkpoints of the hidden state after every site and
 //                         "swap base" values  cb[n][s] = sum_{m<n} log psi_m(s_m) + log psi_n(1 - s_n).
@@ -30,7 +31,7 @@ struct CrnnArgs {
     int32_t N;
     int64_t ns, nsb;
     uint32_t* bits;
-    void* hck;                 // [N-1][nsb][KT][64] float, nullptr: no checkpoints
+    void* hck;                 // [N-1][nsb][KT][64] float (a stack: [N][nsb][NL][KT][64], gru_core.h: GruStack), nullptr: no checkpoints
     double2* cb;               // [N][ns] swap base, nullptr: none
     double2* tot;              // [ns] log psi(s) (re, im) in f64
     float2* out_amp;           // [ns] complex64 log-amplitude (may be nullptr)
@@ -75,12 +76,14 @@ __device__ __forceinline__ void crnn_site(const float (&z)[3], int n, int N, int
     ph1 = 3.14159265358979323846f * (z[2] / (1.0f + fabsf(z[2])));
 }
 
+// One GRU layer, and NL > 1 stacked layers (the reference's DEFAULT: units=[10,10], J1J2/ComplexRNNwavefunction.py:16; MultiRNNCell at
+// :40; units=[num_units]*num_layers at J1J2/TrainingRNN_J1J2.py:148): the same text over the layer stack S (gru_core.h: GruStack, three
+// head rows), as in gru_kernels.h.  One layer: the first step adds its bias last, bit-identical to crnn_base_coop_kernel.
 template <int NFULL, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) crnn_base_kernel(CrnnArgs a) {
-    using C = GruCore<float, NFULL, 3>;
-    constexpr int KT = C::KT;
+    using S = GruStack<float, NFULL, 1, 3>;
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    const char* img = C::stage(lds, a.wimg);       // LDS, or the global image where it exceeds LDS (GruLayout::SPILL)
+    const char* img = S::stage(lds, a.wimg);
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int64_t gw = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     const int64_t nw = (int64_t)gridDim.x * WAVES;
@@ -89,17 +92,19 @@ __global__ void __launch_bounds__(WAVES * 64) crnn_base_kernel(CrnnArgs a) {
         const int64_t s = sb * kChains + c;
         const bool valid = s < a.ns;
         const int64_t sc = valid ? s : a.ns - 1;
-        float h[KT];
+        float h[S::NL][S::KT];
 #pragma unroll
-        for (int kt = 0; kt < KT; ++kt) h[kt] = 0.0f;
+        for (int l = 0; l < S::NL; ++l)
+#pragma unroll
+            for (int kt = 0; kt < S::KT; ++kt) h[l][kt] = 0.0f;
         int sig_in = -1, num_up = 0;
         uint32_t word = 0;
         double re = 0.0, im = 0.0;
         for (int n = 0; n < N; ++n) {
             if (!a.sampling && (n & 31) == 0) word = a.bits[(int64_t)(n >> 5) * a.ns + sc];
-            C::template step<true>(img, sig_in, h, lane);    // bias last: bit-identical to crnn_base_coop_kernel
+            S::template step<S::BASE_BIAS_LAST>(img, a.wimg, sig_in, h, lane);
             float z[3];
-            C::head(img, h, lane, z);
+            S::head(img, h, lane, z);
             float la0, la1, w0, ph0, ph1;
             crnn_site(z, n, N, num_up, la0, la1, w0, ph0, ph1);
             int sig;
@@ -118,10 +123,75 @@ __global__ void __launch_bounds__(WAVES * 64) crnn_base_kernel(CrnnArgs a) {
                 a.cb[(int64_t)n * a.ns + s] = make_double2(re + (double)(sig ? la0 : la1), im + (double)(sig ? ph0 : ph1));
             re += (double)(sig ? la1 : la0);
             im += (double)(sig ? ph1 : ph0);
-            if (a.hck && n < N - 1) {
-                float* dst = reinterpret_cast<float*>(a.hck) + (((int64_t)n * a.nsb + sb) * KT) * 64 + lane;
+            if (a.hck && (S::CKPT_LAST_SITE || n < N - 1)) {
+                float* dst = reinterpret_cast<float*>(a.hck) + (((int64_t)n * a.nsb + sb) * S::ROW) * 64 + lane;
 #pragma unroll
-                for (int kt = 0; kt < KT; ++kt) dst[kt * 64] = h[kt];
+                for (int l = 0; l < S::NL; ++l)
+#pragma unroll
+                    for (int kt = 0; kt < S::KT; ++kt) dst[(l * S::KT + kt) * 64] = h[l][kt];
+            }
+            num_up += sig;
+            sig_in = sig;
+        }
+        if (valid && q == 0) {
+            if (a.tot) a.tot[s] = make_double2(re, im);
+            if (a.out_amp) a.out_amp[s] = make_float2((float)re, (float)im);
+            if (a.out_logp) a.out_logp[s] = 2.0 * re;
+        }
+    }
+}
+
+template <int NFULL, int NL, int WAVES>
+__global__ void __launch_bounds__(WAVES * 64) crnn_ml_base_kernel(CrnnArgs a) {
+    using S = GruStack<float, NFULL, NL, 3>;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const char* img = S::stage(lds, a.wimg);
+    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
+    const int64_t wpb = blockDim.x >> 6;        // launched with WAVES waves or fewer (launch_shrinking, as prnn_ml_base_kernel)
+    const int64_t gw = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6);
+    const int64_t nw = (int64_t)gridDim.x * wpb;
+    const int N = a.N;
+    for (int64_t sb = gw; sb < a.nsb; sb += nw) {
+        const int64_t s = sb * kChains + c;
+        const bool valid = s < a.ns;
+        const int64_t sc = valid ? s : a.ns - 1;
+        float h[S::NL][S::KT];
+#pragma unroll
+        for (int l = 0; l < S::NL; ++l)
+#pragma unroll
+            for (int kt = 0; kt < S::KT; ++kt) h[l][kt] = 0.0f;
+        int sig_in = -1, num_up = 0;
+        uint32_t word = 0;
+        double re = 0.0, im = 0.0;
+        for (int n = 0; n < N; ++n) {
+            if (!a.sampling && (n & 31) == 0) word = a.bits[(int64_t)(n >> 5) * a.ns + sc];
+            S::template step<S::BASE_BIAS_LAST>(img, a.wimg, sig_in, h, lane);
+            float z[3];
+            S::head(img, h, lane, z);
+            float la0, la1, w0, ph0, ph1;
+            crnn_site(z, n, N, num_up, la0, la1, w0, ph0, ph1);
+            int sig;
+            if (a.sampling) {
+                // tf.random.categorical(log(a^2)): class 0 iff u * total < a0^2; a masked class has logit -inf
+                // and is skipped by TF's kernel - same outcome here since its weight is exactly 0
+                const float u = philox_uniform(a.seed, a.step, (uint64_t)(a.sample_offset + sc), n);
+                sig = (u < w0) ? 0 : 1;
+                word |= (uint32_t)sig << (n & 31);
+                if (((n & 31) == 31 || n == N - 1) && valid && q == 0) a.bits[(int64_t)(n >> 5) * a.ns + s] = word;
+                if ((n & 31) == 31) word = 0;
+            } else {
+                sig = (word >> (n & 31)) & 1;
+            }
+            if (a.cb && valid && q == 0)
+                a.cb[(int64_t)n * a.ns + s] = make_double2(re + (double)(sig ? la0 : la1), im + (double)(sig ? ph0 : ph1));
+            re += (double)(sig ? la1 : la0);
+            im += (double)(sig ? ph1 : ph0);
+            if (a.hck && (S::CKPT_LAST_SITE || n < N - 1)) {
+                float* dst = reinterpret_cast<float*>(a.hck) + (((int64_t)n * a.nsb + sb) * S::ROW) * 64 + lane;
+#pragma unroll
+                for (int l = 0; l < S::NL; ++l)
+#pragma unroll
+                    for (int kt = 0; kt < S::KT; ++kt) dst[(l * S::KT + kt) * 64] = h[l][kt];
             }
             num_up += sig;
             sig_in = sig;
@@ -365,10 +435,9 @@ static __global__ void __launch_bounds__(64) j1j2_tile_scan_kernel(const int32_t
 
 template <int NFULL, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) crnn_swap_kernel(CrnnArgs a) {
-    using C = GruCore<float, NFULL, 3>;
-    constexpr int KT = C::KT;
+    using S = GruStack<float, NFULL, 1, 3>;
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    const char* img = C::stage(lds, a.wimg);       // LDS, or the global image where it exceeds LDS (GruLayout::SPILL)
+    const char* img = S::stage(lds, a.wimg);
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int64_t gw = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     const int64_t nw = (int64_t)gridDim.x * WAVES;
@@ -388,12 +457,14 @@ __global__ void __launch_bounds__(WAVES * 64) crnn_swap_kernel(CrnnArgs a) {
         const bool valid = k < a.cnt[lo];
         const SwapItem it = a.items[(int64_t)lo * a.cap + (valid ? k : 0)];
         const int64_t s = it.s;
-        float h[KT];
+        float h[S::NL][S::KT];
         {
             const float* src = reinterpret_cast<const float*>(a.hck) +
-                               (((int64_t)lo * a.nsb + (s >> 4)) * KT) * 64 + (q << 4) + (s & 15);
+                               (((int64_t)lo * a.nsb + (s >> 4)) * S::ROW) * 64 + (q << 4) + (s & 15);
 #pragma unroll
-            for (int kt = 0; kt < KT; ++kt) h[kt] = src[kt * 64];
+            for (int l = 0; l < S::NL; ++l)
+#pragma unroll
+                for (int kt = 0; kt < S::KT; ++kt) h[l][kt] = src[(l * S::KT + kt) * 64];
         }
         int num_up = 0;                               // ups among sites < lo, then the swapped spin at lo
         for (int w = 0; w < (lo >> 5); ++w) num_up += __popc(a.bits[(int64_t)w * a.ns + s]);
@@ -404,9 +475,72 @@ __global__ void __launch_bounds__(WAVES * 64) crnn_swap_kernel(CrnnArgs a) {
         double re = 0.0, im = 0.0;
         for (int n = lo + 1; n < N; ++n) {
             if ((n & 31) == 0) word = a.bits[(int64_t)(n >> 5) * a.ns + s];
-            C::step(img, sig_in, h, lane);
+            S::template step<false>(img, a.wimg, sig_in, h, lane);
             float z[3];
-            C::head(img, h, lane, z);
+            S::head(img, h, lane, z);
+            float la0, la1, w0, ph0, ph1;
+            crnn_site(z, n, N, num_up, la0, la1, w0, ph0, ph1);
+            const int sig = (int)((word >> (n & 31)) & 1) ^ (n == it.hi ? 1 : 0);
+            re += (double)(sig ? la1 : la0);
+            im += (double)(sig ? ph1 : ph0);
+            num_up += sig;
+            sig_in = sig;
+        }
+        if (valid && q == 0) {
+            const double2 b = a.cb[(int64_t)lo * a.ns + s];
+            const double2 t = a.tot[s];
+            const double dre = b.x + re - t.x, dim = b.y + im - t.y;
+            const double mag = exp(dre) * (double)it.coef;
+            a.contrib[(int64_t)it.slot * a.ns + s] = make_double2(mag * cos(dim), mag * sin(dim));
+        }
+    }
+}
+
+template <int NFULL, int NL, int WAVES>
+__global__ void __launch_bounds__(WAVES * 64) crnn_ml_swap_kernel(CrnnArgs a) {
+    using S = GruStack<float, NFULL, NL, 3>;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const char* img = S::stage(lds, a.wimg);
+    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
+    const int64_t gw = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const int64_t nw = (int64_t)gridDim.x * WAVES;
+    const int N = a.N;
+    const int64_t ntiles = a.tile_start[N];
+    for (int64_t tile = gw; tile < ntiles; tile += nw) {
+        int lo = 0;                                   // largest lo with tile_start[lo] <= tile (wave-uniform)
+        {
+            int l = 0, r = N;
+            while (r - l > 1) {
+                const int mid = (l + r) >> 1;
+                if (a.tile_start[mid] <= tile) l = mid; else r = mid;
+            }
+            lo = l;
+        }
+        const int k = (int)(tile - a.tile_start[lo]) * kChains + c;
+        const bool valid = k < a.cnt[lo];
+        const SwapItem it = a.items[(int64_t)lo * a.cap + (valid ? k : 0)];
+        const int64_t s = it.s;
+        float h[S::NL][S::KT];
+        {
+            const float* src = reinterpret_cast<const float*>(a.hck) +
+                               (((int64_t)lo * a.nsb + (s >> 4)) * S::ROW) * 64 + (q << 4) + (s & 15);
+#pragma unroll
+            for (int l = 0; l < S::NL; ++l)
+#pragma unroll
+                for (int kt = 0; kt < S::KT; ++kt) h[l][kt] = src[(l * S::KT + kt) * 64];
+        }
+        int num_up = 0;                               // ups among sites < lo, then the swapped spin at lo
+        for (int w = 0; w < (lo >> 5); ++w) num_up += __popc(a.bits[(int64_t)w * a.ns + s]);
+        uint32_t word = a.bits[(int64_t)(lo >> 5) * a.ns + s];
+        num_up += __popc(word & ((1u << (lo & 31)) - 1u));
+        int sig_in = 1 - (int)((word >> (lo & 31)) & 1);
+        num_up += sig_in;
+        double re = 0.0, im = 0.0;
+        for (int n = lo + 1; n < N; ++n) {
+            if ((n & 31) == 0) word = a.bits[(int64_t)(n >> 5) * a.ns + s];
+            S::template step<false>(img, a.wimg, sig_in, h, lane);
+            float z[3];
+            S::head(img, h, lane, z);
             float la0, la1, w0, ph0, ph1;
             crnn_site(z, n, N, num_up, la0, la1, w0, ph0, ph1);
             const int sig = (int)((word >> (n & 31)) & 1) ^ (n == it.hi ? 1 : 0);

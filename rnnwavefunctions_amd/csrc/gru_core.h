@@ -166,11 +166,6 @@ struct GruCore {
     static __device__ __forceinline__ void step(const char* lds, int sig, T (&h)[KT], int lane, int ablate = 0) {
         step_impl(lds, sig, h, lane, ablate, BIAS_LAST);
     }
-    // non-template entry for the stacked-layer cores (hipcc's host pass fails to resolve step<> from inside a second
-    // class template for T = double)
-    static __device__ __forceinline__ void step_plain(const char* lds, int sig, T (&h)[KT], int lane) {
-        step_impl(lds, sig, h, lane, 0, false);
-    }
     // BIAS_LAST is a compile-time constant at every call site (forced inlining folds the branches)
     static __device__ __forceinline__ void step_impl(const char* lds, int sig, T (&h)[KT], int lane, int ablate, const bool BIAS_LAST) {
         const int q = lane >> 4;
@@ -471,6 +466,60 @@ struct UpperCore {
             h[KT - 1] = cc + ug * (h[KT - 1] - cc);
         }
     }
+};
+
+// A stack of NL GRU layers with NOUT head rows on the top one - what the one-wave forward passes of every family run per site
+// (gru_kernels.h, crnn_kernels.h); NL == 1 is the single layer.  Every layer's state stays in registers in B-fragment order
+// and the new state of layer l is directly the X operand of layer l + 1 (UpperCore).
+// Image: [GruLayout<T, NFULL, NOUT> | UpperLayout<NFULL, T> x (NL - 1)]; the top SPILL layers of a stack stay in global memory
+// (layout.h: MlSpill), a single layer's image does where it exceeds LDS (GruLayout::SPILL).
+// Checkpoints hck[sites][nsb][NL][KT][64]: a single layer keeps the states after sites 0..N-2, a stack after all N sites (the
+// layer-wise gradient of ml_grad_kernels.h needs the last site's lower-layer states too).
+template <typename T_, int NFULL, int NL_, int NOUT>
+struct GruStack {
+    using T = T_;
+    using C0 = GruCore<T, NFULL, NOUT>;
+    using CU = UpperCore<NFULL, T>;
+    static constexpr int NL = NL_, KT = C0::KT;
+    static constexpr int ROW = NL * KT;                    // checkpoint row: values per lane, 64 lanes apart
+    static constexpr bool CKPT_LAST_SITE = NL > 1;
+    // The first layer's base-pass step adds the bias after the products where a cooperative kernel must agree with it bit for bit
+    // (GruCore::step<BIAS_LAST>; one layer) - the cooperative stack kernel (ml_coop.h) has its own accumulation order.
+    static constexpr bool BASE_BIAS_LAST = NL == 1;
+    static constexpr int spill() {
+        if constexpr (NL > 1) return MlSpill<NFULL, NL, T, NOUT>::value;
+        else return 0;
+    }
+    static constexpr int SPILL = spill();
+    // the timing-only hooks of diagnostics builds (layout.h: RNNWF_ABLATED) exist for one layer only
+    static __device__ __forceinline__ bool ablated(int mask, int bit) { return NL == 1 && RNNWF_ABLATED(mask, bit); }
+    static constexpr size_t LDS_BYTES = NL == 1 ? C0::L::LDS_BYTES : C0::L::BYTES + (size_t)(NL - 1 - SPILL) * CU::U::BYTES;
+
+    // returns where the first layer's image and the head are found
+    static __device__ __forceinline__ const char* stage(char* lds, const void* wimg) {
+        if constexpr (NL == 1) {
+            return C0::stage(lds, wimg);
+        } else {
+            const uint4* src = reinterpret_cast<const uint4*>(wimg);
+            uint4* dst = reinterpret_cast<uint4*>(lds);
+            for (int i = threadIdx.x; i < (int)(LDS_BYTES / 16); i += blockDim.x) dst[i] = src[i];
+            __syncthreads();
+            return lds;
+        }
+    }
+    // all layers for one site (`ablate`: GruCore::step, single-layer diagnostics only)
+    template <bool BIAS_LAST>
+    static __device__ __forceinline__ void step(const char* img, const void* wimg, int sig, T (&h)[NL][KT], int lane, int ablate = 0) {
+        C0::template step<BIAS_LAST>(img, sig, h[0], lane, NL == 1 ? ablate : 0);
+#pragma unroll
+        for (int l = 1; l < NL; ++l) {
+            const size_t off = C0::L::BYTES + (size_t)(l - 1) * CU::U::BYTES;
+            if (l < NL - SPILL) CU::step(img + off, h[l - 1], h[l], lane);
+            else CU::step(reinterpret_cast<const char*>(wimg) + off, h[l - 1], h[l], lane, NFULL * (int)sizeof(T) >= 16);      // wide layers (f32 >= 53, f64 >= 37 units): bounded look-ahead (UpperCore::block)
+        }
+    }
+    // head rows of the top layer
+    static __device__ __forceinline__ void head(const char* img, const T (&h)[NL][KT], int lane, T (&z)[NOUT]) { C0::head(img, h[NL - 1], lane, z); }
 };
 
 }  // namespace rnnwf

@@ -1,4 +1,4 @@
-// gru_kernels.h - the two recurrent kernels of the positive-RNN (pRNN) path.
+// gru_kernels.h - the two recurrent kernels of the positive-RNN (pRNN) path, for one GRU layer and (prnn_ml_*) for stacked layers.
 //
 //   prnn_base_kernel : one pass over all N sites for every chain (16 chains per wave): ancestral
 //                      sampling (1DTFIM/RNNwavefunction.py:35-74) or teacher-forced evaluation
@@ -11,7 +11,8 @@
 //
 // Device layouts (all coalesced per wave):
 //   bits [W = ceil(N/32)][ns] u32   spin n of chain s = bit (n & 31) of bits[n >> 5][s]
-//   hck  [N-1][nsb][KT][64]   T     hidden state after site n, in B-fragment order (lane-linear)
+//   hck  [N-1][nsb][KT][64]   T     hidden state after site n, in B-fragment order (lane-linear); a stack of NL layers:
+//        [N][nsb][NL][KT][64]          (gru_core.h: GruStack)
 //   lpq  [N+1][ns]            f64   row 0: log P(s); row k+1: log P(s with site k flipped)
 #pragma once
 #include "gru_core.h"
@@ -41,12 +42,16 @@ struct PrnnArgs {
 };
 
 
+// The kernels of one GRU layer and of NL > 1 stacked layers (units = [h] * num_layers, 1DTFIM/TrainingRNN_1DTFIM.py:98; MultiRNNCell at
+// 1DTFIM/RNNwavefunction.py:32; T = double: 2DTFIM_1DRNN, Training1DRNN_2DTFIM.py:94) are the same text over the layer stack S
+// (gru_core.h: GruStack), apart from the waves per workgroup of the stack's base pass.  The loops stay in each kernel's own scope:
+// moved into force-inlined pass templates they compiled to other register allocations, occupancies and loop versions
+// (profiles/forward_stack_isa.txt).
 template <typename T, int NFULL, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) prnn_base_kernel(PrnnArgs a) {
-    using C = GruCore<T, NFULL, 1>;
-    constexpr int KT = C::KT;
+    using S = GruStack<T, NFULL, 1, 1>;
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    const char* img = C::stage(lds, a.wimg);       // LDS, or the global image where it exceeds LDS (GruLayout::SPILL)
+    const char* img = S::stage(lds, a.wimg);
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int64_t gw = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     const int64_t nw = (int64_t)gridDim.x * WAVES;
@@ -55,23 +60,25 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_base_kernel(PrnnArgs a) {
         const int64_t s = sb * kChains + c;
         const bool valid = s < a.ns;
         const int64_t sc = valid ? s : a.ns - 1;
-        T h[KT];
+        T h[S::NL][S::KT];
 #pragma unroll
-        for (int kt = 0; kt < KT; ++kt) h[kt] = T(0);
+        for (int l = 0; l < S::NL; ++l)
+#pragma unroll
+            for (int kt = 0; kt < S::KT; ++kt) h[l][kt] = T(0);
         int sig_in = -1;
         uint32_t word = 0;
         double cum = 0.0;
         for (int n = 0; n < N; ++n) {
             if (!a.sampling && (n & 31) == 0) word = a.bits[(int64_t)(n >> 5) * a.ns + sc];
-            C::template step<true>(img, sig_in, h, lane);
+            S::template step<S::BASE_BIAS_LAST>(img, a.wimg, sig_in, h, lane);
             T z[1];
-            C::head(img, h, lane, z);
+            S::head(img, h, lane, z);
             T lp0, lp1;
             log_softmax2(z[0], lp0, lp1);
             int sig;
             if (a.sampling) {
                 // tf.multinomial(log p): class 0 iff u * total < p0
-                const float u = RNNWF_ABLATED(a.ablate, 32) ? 0.5f : philox_uniform(a.seed, a.step, (uint64_t)(a.sample_offset + sc), n);
+                const float u = S::ablated(a.ablate, 32) ? 0.5f : philox_uniform(a.seed, a.step, (uint64_t)(a.sample_offset + sc), n);
                 sig = ((T)u < prob0(z[0])) ? 0 : 1;
                 word |= (uint32_t)sig << (n & 31);
                 if (((n & 31) == 31 || n == N - 1) && valid && q == 0) a.bits[(int64_t)(n >> 5) * a.ns + s] = word;
@@ -80,16 +87,18 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_base_kernel(PrnnArgs a) {
                 sig = (word >> (n & 31)) & 1;
             }
             const double lsel = (double)(sig ? lp1 : lp0);
-            if (a.lpq && !RNNWF_ABLATED(a.ablate, 16)) {
+            if (a.lpq && !S::ablated(a.ablate, 16)) {
                 const double loth = (double)(sig ? lp0 : lp1);
                 const int64_t row = a.row_of_pos ? a.row_of_pos[n] : n + 1;
                 if (valid && q == 0) a.lpq[row * a.ns + s] = cum + loth;
             }
             cum += lsel;
-            if (a.hck && n < N - 1 && !RNNWF_ABLATED(a.ablate, 8)) {
-                T* dst = reinterpret_cast<T*>(a.hck) + (((int64_t)n * a.nsb + sb) * KT) * 64 + lane;
+            if (a.hck && (S::CKPT_LAST_SITE || n < N - 1) && !S::ablated(a.ablate, 8)) {
+                T* dst = reinterpret_cast<T*>(a.hck) + (((int64_t)n * a.nsb + sb) * S::ROW) * 64 + lane;
 #pragma unroll
-                for (int kt = 0; kt < KT; ++kt) dst[kt * 64] = h[kt];
+                for (int l = 0; l < S::NL; ++l)
+#pragma unroll
+                    for (int kt = 0; kt < S::KT; ++kt) dst[(l * S::KT + kt) * 64] = h[l][kt];
             }
             sig_in = sig;
         }
@@ -102,10 +111,9 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_base_kernel(PrnnArgs a) {
 
 template <typename T, int NFULL, int WAVES>
 __global__ void __launch_bounds__(WAVES * 64) prnn_flip_kernel(PrnnArgs a) {
-    using C = GruCore<T, NFULL, 1>;
-    constexpr int KT = C::KT;
+    using S = GruStack<T, NFULL, 1, 1>;
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    const char* img = C::stage(lds, a.wimg);       // LDS, or the global image where it exceeds LDS (GruLayout::SPILL)
+    const char* img = S::stage(lds, a.wimg);
     const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
     const int64_t gw = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     const int64_t nw = (int64_t)gridDim.x * WAVES;
@@ -118,11 +126,13 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_flip_kernel(PrnnArgs a) {
         const int64_t s = sb * kChains + c;
         const bool valid = s < a.ns;
         const int64_t sc = valid ? s : a.ns - 1;
-        T h[KT];
+        T h[S::NL][S::KT];
         {
-            const T* src = reinterpret_cast<const T*>(a.hck) + (((int64_t)i * a.nsb + sb) * KT) * 64 + lane;
+            const T* src = reinterpret_cast<const T*>(a.hck) + (((int64_t)i * a.nsb + sb) * S::ROW) * 64 + lane;
 #pragma unroll
-            for (int kt = 0; kt < KT; ++kt) h[kt] = src[kt * 64];
+            for (int l = 0; l < S::NL; ++l)
+#pragma unroll
+                for (int kt = 0; kt < S::KT; ++kt) h[l][kt] = src[(l * S::KT + kt) * 64];
         }
         // Site n consumes spin n-1 and its head needs spin n: one coalesced 4-byte load per site, fetched a site
         // ahead (branch-free loop body, so the scheduler can interleave MFMA and VALU work across the whole step).
@@ -131,10 +141,124 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_flip_kernel(PrnnArgs a) {
         double lp = 0.0;
         for (int n = i + 1; n < N; ++n) {
             const int sig = spin(n);
-            C::step(img, sig_in, h, lane, a.ablate);
-            if (!RNNWF_ABLATED(a.ablate, 4)) {
+            S::template step<false>(img, a.wimg, sig_in, h, lane, a.ablate);
+            if (!S::ablated(a.ablate, 4)) {
                 T z[1];
-                C::head(img, h, lane, z);
+                S::head(img, h, lane, z);
+                T lp0, lp1;
+                log_softmax2(z[0], lp0, lp1);
+                lp += (double)(sig ? lp1 : lp0);
+            }
+            sig_in = sig;
+        }
+        if (valid && q == 0) {
+            const int64_t row = a.row_of_pos ? a.row_of_pos[i] : i + 1;
+            a.lpq[row * a.ns + s] += lp;
+        }
+    }
+}
+
+template <typename T, int NFULL, int NL, int WAVES>
+__global__ void __launch_bounds__(WAVES * 64) prnn_ml_base_kernel(PrnnArgs a) {
+    using S = GruStack<T, NFULL, NL, 1>;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const char* img = S::stage(lds, a.wimg);
+    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
+    // (launched with WAVES waves or fewer - launch_shrinking: a batch of fewer 16-chain blocks than the chip has SIMDs spreads over all
+    //  CUs, one wave per SIMD, instead of filling a third of them with eight - the pass is N dependent steps of MFMA latency per wave)
+    const int64_t wpb = blockDim.x >> 6;
+    const int64_t gw = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6);
+    const int64_t nw = (int64_t)gridDim.x * wpb;
+    const int N = a.N;
+    for (int64_t sb = gw; sb < a.nsb; sb += nw) {
+        const int64_t s = sb * kChains + c;
+        const bool valid = s < a.ns;
+        const int64_t sc = valid ? s : a.ns - 1;
+        T h[S::NL][S::KT];
+#pragma unroll
+        for (int l = 0; l < S::NL; ++l)
+#pragma unroll
+            for (int kt = 0; kt < S::KT; ++kt) h[l][kt] = T(0);
+        int sig_in = -1;
+        uint32_t word = 0;
+        double cum = 0.0;
+        for (int n = 0; n < N; ++n) {
+            if (!a.sampling && (n & 31) == 0) word = a.bits[(int64_t)(n >> 5) * a.ns + sc];
+            S::template step<S::BASE_BIAS_LAST>(img, a.wimg, sig_in, h, lane);
+            T z[1];
+            S::head(img, h, lane, z);
+            T lp0, lp1;
+            log_softmax2(z[0], lp0, lp1);
+            int sig;
+            if (a.sampling) {
+                // tf.multinomial(log p): class 0 iff u * total < p0
+                const float u = S::ablated(a.ablate, 32) ? 0.5f : philox_uniform(a.seed, a.step, (uint64_t)(a.sample_offset + sc), n);
+                sig = ((T)u < prob0(z[0])) ? 0 : 1;
+                word |= (uint32_t)sig << (n & 31);
+                if (((n & 31) == 31 || n == N - 1) && valid && q == 0) a.bits[(int64_t)(n >> 5) * a.ns + s] = word;
+                if ((n & 31) == 31) word = 0;
+            } else {
+                sig = (word >> (n & 31)) & 1;
+            }
+            const double lsel = (double)(sig ? lp1 : lp0);
+            if (a.lpq && !S::ablated(a.ablate, 16)) {
+                const double loth = (double)(sig ? lp0 : lp1);
+                const int64_t row = a.row_of_pos ? a.row_of_pos[n] : n + 1;
+                if (valid && q == 0) a.lpq[row * a.ns + s] = cum + loth;
+            }
+            cum += lsel;
+            if (a.hck && (S::CKPT_LAST_SITE || n < N - 1) && !S::ablated(a.ablate, 8)) {
+                T* dst = reinterpret_cast<T*>(a.hck) + (((int64_t)n * a.nsb + sb) * S::ROW) * 64 + lane;
+#pragma unroll
+                for (int l = 0; l < S::NL; ++l)
+#pragma unroll
+                    for (int kt = 0; kt < S::KT; ++kt) dst[(l * S::KT + kt) * 64] = h[l][kt];
+            }
+            sig_in = sig;
+        }
+        if (valid && q == 0) {
+            if (a.lpq) a.lpq[s] = cum;
+            if (a.out_lp) a.out_lp[s] = cum;
+        }
+    }
+}
+
+template <typename T, int NFULL, int NL, int WAVES>
+__global__ void __launch_bounds__(WAVES * 64) prnn_ml_flip_kernel(PrnnArgs a) {
+    using S = GruStack<T, NFULL, NL, 1>;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const char* img = S::stage(lds, a.wimg);
+    const int lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
+    const int64_t gw = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const int64_t nw = (int64_t)gridDim.x * WAVES;
+    const int N = a.N;
+    // tiles are ordered longest chain first (i ascending); every wave strides through them, so each
+    // wave receives the same mix of lengths
+    for (int64_t tile = gw; tile < a.ntiles; tile += nw) {
+        const int i = (int)(tile / a.nsb);
+        const int64_t sb = tile - (int64_t)i * a.nsb;
+        const int64_t s = sb * kChains + c;
+        const bool valid = s < a.ns;
+        const int64_t sc = valid ? s : a.ns - 1;
+        T h[S::NL][S::KT];
+        {
+            const T* src = reinterpret_cast<const T*>(a.hck) + (((int64_t)i * a.nsb + sb) * S::ROW) * 64 + lane;
+#pragma unroll
+            for (int l = 0; l < S::NL; ++l)
+#pragma unroll
+                for (int kt = 0; kt < S::KT; ++kt) h[l][kt] = src[(l * S::KT + kt) * 64];
+        }
+        // Site n consumes spin n-1 and its head needs spin n: one coalesced 4-byte load per site, fetched a site
+        // ahead (branch-free loop body, so the scheduler can interleave MFMA and VALU work across the whole step).
+        auto spin = [&](int n) { return (int)((a.bits[(int64_t)(n >> 5) * a.ns + sc] >> (n & 31)) & 1); };
+        int sig_in = 1 - spin(i);                  // the flipped spin feeds site i+1
+        double lp = 0.0;
+        for (int n = i + 1; n < N; ++n) {
+            const int sig = spin(n);
+            S::template step<false>(img, a.wimg, sig_in, h, lane, a.ablate);
+            if (!S::ablated(a.ablate, 4)) {
+                T z[1];
+                S::head(img, h, lane, z);
                 T lp0, lp1;
                 log_softmax2(z[0], lp0, lp1);
                 lp += (double)(sig ? lp1 : lp0);

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -326,6 +327,26 @@ inline int launch_shrinking(rnnwf_handle* h, TimerId id, Kern kern, size_t lds, 
     const int wpb = (int)std::max<int64_t>(1, std::min<int64_t>(WAVES, (items + slots - 1) / slots));
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + wpb - 1) / wpb, slots));
     return timed_launch(h, id, kern, grid, wpb * 64, lds, args...);
+}
+
+// The kernels a family is built for: one row per shape (element type, layers, NFULL) with the waves per workgroup of its kernels.
+template <typename T_, int NL_, int NFULL_, int WAVES_>
+struct KernelRow {
+    using T = T_;
+    static constexpr int NL = NL_, NFULL = NFULL_, WAVES = WAVES_;
+};
+template <class... Rows> struct KernelTable {};
+
+// fn(K<T, NFULL, NL, WAVES>()) for the row of this handle's shape; false (fn not called) for a shape without kernels
+template <template <typename, int, int, int> class K, class Fn, class... Rows>
+inline bool with_kernels(KernelTable<Rows...>, const rnnwf_handle* h, Fn&& fn) {
+    auto hit = [&](auto row) {
+        using R = decltype(row);
+        if (std::is_same<typename R::T, double>::value != (bool)h->f64 || R::NL != h->NL || R::NFULL != h->NFULL) return false;
+        fn(K<typename R::T, R::NFULL, R::NL, R::WAVES>());
+        return true;
+    };
+    return (hit(Rows()) || ...);
 }
 
 }  // namespace rnnwf

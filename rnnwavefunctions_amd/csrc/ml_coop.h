@@ -1,7 +1,7 @@
 // ml_coop.h - the base pass of STACKED GRU layers (sampling / teacher-forced, all N sites in sequence) with the gate tiles of every
 // layer split over NFULL + 1 waves per block of 16 chains - the stacked counterpart of gru_kernels.h: coop_base_pass.
 //
-// Why: the one-wave-per-block kernels (ml_kernels.h: prnn_ml_base_kernel, crnn_ml_kernels.h) run 130 f32-input MFMAs for the first
+// Why: the one-wave-per-block kernels (gru_kernels.h: prnn_ml_base_kernel, crnn_kernels.h: crnn_ml_base_kernel) run 130 f32-input MFMAs for the first
 // layer and 260 for every layer above per site and chain block - 12 500 MFMA cycles per site with two layers of 50 units, on 625 of
 // the chip's 1 024 SIMDs at config 2's size, the others idle: 0.78 ms of an 8.5 ms step (profiles/r04_z_bench_cfg2_l2.json).  Here a
 // block's products are spread over four waves (= four SIMDs) and three blocks share a workgroup and its image in LDS, so every SIMD

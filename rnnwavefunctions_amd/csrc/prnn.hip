@@ -5,7 +5,6 @@
 #include <type_traits>
 
 #include "gru_kernels.h"
-#include "ml_kernels.h"
 #include "models.h"
 #include "pack.h"
 
@@ -13,140 +12,72 @@ using namespace rnnwf;
 
 namespace {
 
-template <typename T, int NFULL, int WAVES>
+// The kernels of one shape: NL == 1 one GRU layer, NL > 1 stacked layers.
+template <typename T, int NFULL, int NL, int WAVES>
 struct Launch {
+    using S = GruStack<T, NFULL, NL, 1>;
     using L = GruLayout<T, NFULL, 1>;
-    // fewer 16-chain blocks than SIMDs: the cooperative kernel (NFULL + 1 waves per block) cuts the per-site latency
-    static int base_coop(rnnwf_handle* h, const PrnnArgs& a) {
-        if constexpr (std::is_same<T, float>::value && NFULL <= 4) {
-            const size_t lds = L::BYTES + (size_t)2 * L::KT * 64 * 4 + 2 * 64 * 4;
-            return launch_persistent(h, kTimerBase, prnn_base_coop_kernel<NFULL>, (NFULL + 1) * 64, lds, a.nsb, 1, a);
-        }
-        return 0;
-    }
+    static constexpr bool F32 = std::is_same<T, float>::value;
     static int base(rnnwf_handle* h, const PrnnArgs& a) {
-        // f32 models of 37..52 units: the cooperative kernel on the bf16 matrix core, for every batch size (a batch and its
-        // shards always take the same kernel); RNNWF_BASE=f32 / RNNWF_NO_COOP=1 keep the f32-input-MFMA kernels
-        if (std::is_same<T, float>::value && NFULL <= 3 && base_bf_available(h)) return prnn_base_coop_bf(h, a);
-        if (std::is_same<T, float>::value && NFULL <= 4 && a.nsb <= (int64_t)4 * h->cu_count && !h->knobs.no_coop)
-            return base_coop(h, a);
-        return plain(h, a);
+        if constexpr (NL > 1) {
+            // all layers' images resident in LDS (f32, up to 52 units): the gate tiles of every layer spread over NFULL + 1 waves per block
+            // of 16 chains (ml_coop.h) - for every batch size, its accumulation order is not the one-wave kernel's; RNNWF_NO_COOP=1 keeps that one
+            if constexpr (F32 && MlCoopLayout<NFULL, NL, 1>::FITS && S::SPILL == 0) {
+                if (!h->knobs.no_coop) {
+                    using ML = MlCoopLayout<NFULL, NL, 1>;
+                    return launch_persistent(h, kTimerBase, prnn_base_coop_kernel<NFULL, false, NL>, ML::THREADS, ML::LDS, a.nsb, ML::NB, a);
+                }
+            }
+            return launch_shrinking<WAVES>(h, kTimerBase, prnn_ml_base_kernel<T, NFULL, NL, WAVES>, S::LDS_BYTES, a.nsb, a);
+        } else {
+            // f32 models of 37..52 units: the cooperative kernel on the bf16 matrix core, for every batch size (a batch and its
+            // shards always take the same kernel); RNNWF_BASE=f32 / RNNWF_NO_COOP=1 keep the f32-input-MFMA kernels
+            if (F32 && NFULL <= 3 && base_bf_available(h)) return prnn_base_coop_bf(h, a);
+            // fewer 16-chain blocks than SIMDs: the cooperative kernel (NFULL + 1 waves per block) cuts the per-site latency
+            if constexpr (F32 && NFULL <= 4) {
+                if (a.nsb <= (int64_t)4 * h->cu_count && !h->knobs.no_coop) {
+                    const size_t lds = L::BYTES + (size_t)2 * L::KT * 64 * 4 + 2 * 64 * 4;
+                    return launch_persistent(h, kTimerBase, prnn_base_coop_kernel<NFULL>, (NFULL + 1) * 64, lds, a.nsb, 1, a);
+                }
+            }
+            return plain(h, a);
+        }
     }
     // the one-wave-per-block kernel whatever the batch size
     static int plain(rnnwf_handle* h, const PrnnArgs& a) {
-        return launch_persistent(h, kTimerBase, prnn_base_kernel<T, NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, a.nsb, WAVES, a);
+        if constexpr (NL > 1) return h->fail(RNNWF_ERR_INVALID, "stacked layers: no one-wave base pass");
+        else return launch_persistent(h, kTimerBase, prnn_base_kernel<T, NFULL, WAVES>, WAVES * 64, S::LDS_BYTES, a.nsb, WAVES, a);
     }
     static int flip(rnnwf_handle* h, const PrnnArgs& a) {
-        return launch_persistent(h, kTimerFlip, prnn_flip_kernel<T, NFULL, WAVES>, WAVES * 64, L::LDS_BYTES, a.ntiles, WAVES, a);
+        if constexpr (NL > 1) return launch_persistent(h, kTimerFlip, prnn_ml_flip_kernel<T, NFULL, NL, WAVES>, WAVES * 64, S::LDS_BYTES, a.ntiles, WAVES, a);
+        else return launch_persistent(h, kTimerFlip, prnn_flip_kernel<T, NFULL, WAVES>, WAVES * 64, S::LDS_BYTES, a.ntiles, WAVES, a);
     }
-    static std::vector<char> pack(const rnnwf_handle* h) { return pack_gru_image<T, NFULL, 1>(h); }
-    static size_t hck_bytes_per_block() { return (size_t)L::KT * 64 * sizeof(T); }
-    static double mfma_flops_per_step() { return (double)L::NT * L::KT * 2048.0; }
-};
-
-// stacked layers: same interface, kernels of ml_kernels.h
-template <typename T, int NFULL, int NL, int WAVES>
-struct MLaunchL {
-    using M = MlCore<NFULL, NL, T>;
-    static int base(rnnwf_handle* h, const PrnnArgs& a) {
-        // all layers' images resident in LDS (f32, up to 52 units): the gate tiles of every layer spread over NFULL + 1 waves per block
-        // of 16 chains (ml_coop.h) - for every batch size, its accumulation order is not the one-wave kernel's; RNNWF_NO_COOP=1 keeps that one
-        if constexpr (std::is_same<T, float>::value && MlCoopLayout<NFULL, NL, 1>::FITS && M::SPILL == 0) {
-            if (!h->knobs.no_coop) {
-                using ML = MlCoopLayout<NFULL, NL, 1>;
-                return launch_persistent(h, kTimerBase, prnn_base_coop_kernel<NFULL, false, NL>, ML::THREADS, ML::LDS, a.nsb, ML::NB, a);
-            }
-        }
-        return launch_shrinking<WAVES>(h, kTimerBase, prnn_ml_base_kernel<T, NFULL, NL, WAVES>, M::BYTES, a.nsb, a);
-    }
-    static int flip(rnnwf_handle* h, const PrnnArgs& a) {
-        return launch_persistent(h, kTimerFlip, prnn_ml_flip_kernel<T, NFULL, NL, WAVES>, WAVES * 64, M::BYTES, a.ntiles, WAVES, a);
-    }
-    static int plain(rnnwf_handle* h, const PrnnArgs&) { return h->fail(RNNWF_ERR_INVALID, "stacked layers: no one-wave base pass"); }
     static std::vector<char> pack(const rnnwf_handle* h) {
         std::vector<char> img = pack_gru_image<T, NFULL, 1>(h);
-        for (int l = 1; l < NL; ++l) {
-            const std::vector<char> up = pack_upper_image<NFULL, T>(h, l);
-            img.insert(img.end(), up.begin(), up.end());
-        }
+        if constexpr (NL > 1)
+            for (int l = 1; l < NL; ++l) {
+                const std::vector<char> up = pack_upper_image<NFULL, T>(h, l);
+                img.insert(img.end(), up.begin(), up.end());
+            }
         return img;
     }
-    static size_t hck_bytes_per_block() { return (size_t)NL * M::KT * 64 * sizeof(T); }
-    static double mfma_flops_per_step() {
-        return ((double)M::C0::L::NT + 2.0 * (NL - 1) * M::CU::U::NT) * M::KT * 2048.0;
-    }
+    static size_t hck_bytes_per_block() { return (size_t)S::ROW * 64 * sizeof(T); }
+    static double mfma_flops_per_step() { return ((double)L::NT + 2.0 * (NL - 1) * UpperLayout<NFULL, T>::NT) * L::KT * 2048.0; }
 };
 
-// fn(K()) for this handle's launch class K, false (fn not called) for a shape without kernels: the one place that maps
-// (dtype, layers, NFULL) to an instantiation <element type, NFULL, [layers,] waves per workgroup>
+// (element type, layers, NFULL) -> waves per workgroup: every shape with kernels
+template <typename T, int NL, int NFULL, int WAVES> using R = KernelRow<T, NL, NFULL, WAVES>;
+using Kernels = KernelTable<
+    R<double, 1, 1, 4>, R<double, 1, 2, 4>, R<double, 1, 3, 4>, R<double, 1, 4, 8>, R<double, 1, 6, 4>,
+    R<double, 2, 1, 4>, R<double, 2, 2, 8>, R<double, 2, 3, 4>, R<double, 2, 4, 4>,
+    R<double, 3, 1, 4>, R<double, 3, 2, 4>, R<double, 3, 3, 4>, R<double, 3, 4, 4>,
+    R<double, 4, 1, 4>, R<double, 4, 2, 4>, R<double, 4, 3, 4>, R<double, 4, 4, 4>,
+    R<float, 1, 1, 4>, R<float, 1, 2, 4>, R<float, 1, 3, 4>, R<float, 1, 4, 4>, R<float, 1, 6, 8>, R<float, 1, 8, 4>, R<float, 1, 12, 4>, R<float, 1, 16, 4>,
+    R<float, 2, 1, 4>, R<float, 2, 2, 4>, R<float, 2, 3, 8>, R<float, 2, 4, 4>, R<float, 2, 6, 4>,
+    R<float, 3, 1, 4>, R<float, 3, 2, 8>, R<float, 3, 3, 8>, R<float, 3, 4, 4>, R<float, 3, 6, 4>,
+    R<float, 4, 1, 4>, R<float, 4, 2, 4>, R<float, 4, 3, 4>, R<float, 4, 4, 4>, R<float, 4, 6, 4>>;
 template <class Fn>
-bool with_launch(const rnnwf_handle* h, Fn&& fn) {
-    const int nf = h->NFULL;
-    if (h->f64) {
-        switch (h->NL) {
-            case 2: switch (nf) {
-                case 1: fn(MLaunchL<double, 1, 2, 4>()); return true;
-                case 2: fn(MLaunchL<double, 2, 2, 8>()); return true;
-                case 3: fn(MLaunchL<double, 3, 2, 4>()); return true;
-                case 4: fn(MLaunchL<double, 4, 2, 4>()); return true;
-            } return false;
-            case 3: switch (nf) {
-                case 1: fn(MLaunchL<double, 1, 3, 4>()); return true;
-                case 2: fn(MLaunchL<double, 2, 3, 4>()); return true;
-                case 3: fn(MLaunchL<double, 3, 3, 4>()); return true;
-                case 4: fn(MLaunchL<double, 4, 3, 4>()); return true;
-            } return false;
-            case 4: switch (nf) {
-                case 1: fn(MLaunchL<double, 1, 4, 4>()); return true;
-                case 2: fn(MLaunchL<double, 2, 4, 4>()); return true;
-                case 3: fn(MLaunchL<double, 3, 4, 4>()); return true;
-                case 4: fn(MLaunchL<double, 4, 4, 4>()); return true;
-            } return false;
-        }
-        switch (nf) {
-            case 1: fn(Launch<double, 1, 4>()); return true;
-            case 2: fn(Launch<double, 2, 4>()); return true;
-            case 3: fn(Launch<double, 3, 4>()); return true;
-            case 4: fn(Launch<double, 4, 8>()); return true;
-            case 6: fn(Launch<double, 6, 4>()); return true;
-        }
-        return false;
-    }
-    switch (h->NL) {
-        case 2: switch (nf) {
-            case 1: fn(MLaunchL<float, 1, 2, 4>()); return true;
-            case 2: fn(MLaunchL<float, 2, 2, 4>()); return true;
-            case 3: fn(MLaunchL<float, 3, 2, 8>()); return true;
-            case 4: fn(MLaunchL<float, 4, 2, 4>()); return true;
-            case 6: fn(MLaunchL<float, 6, 2, 4>()); return true;
-        } return false;
-        case 3: switch (nf) {
-            case 1: fn(MLaunchL<float, 1, 3, 4>()); return true;
-            case 2: fn(MLaunchL<float, 2, 3, 8>()); return true;
-            case 3: fn(MLaunchL<float, 3, 3, 8>()); return true;
-            case 4: fn(MLaunchL<float, 4, 3, 4>()); return true;
-            case 6: fn(MLaunchL<float, 6, 3, 4>()); return true;
-        } return false;
-        case 4: switch (nf) {
-            case 1: fn(MLaunchL<float, 1, 4, 4>()); return true;
-            case 2: fn(MLaunchL<float, 2, 4, 4>()); return true;
-            case 3: fn(MLaunchL<float, 3, 4, 4>()); return true;
-            case 4: fn(MLaunchL<float, 4, 4, 4>()); return true;
-            case 6: fn(MLaunchL<float, 6, 4, 4>()); return true;
-        } return false;
-    }
-    switch (nf) {
-        case 1: fn(Launch<float, 1, 4>()); return true;
-        case 2: fn(Launch<float, 2, 4>()); return true;
-        case 3: fn(Launch<float, 3, 4>()); return true;
-        case 4: fn(Launch<float, 4, 4>()); return true;
-        case 6: fn(Launch<float, 6, 8>()); return true;
-        case 8: fn(Launch<float, 8, 4>()); return true;
-        case 12: fn(Launch<float, 12, 4>()); return true;
-        case 16: fn(Launch<float, 16, 4>()); return true;
-    }
-    return false;
-}
+bool with_launch(const rnnwf_handle* h, Fn&& fn) { return with_kernels<Launch>(Kernels(), h, fn); }
 
 int no_kernel(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "no pRNN kernel for NFULL=%d f64=%d", h->NFULL, (int)h->f64); }
 int launch_base(rnnwf_handle* h, const PrnnArgs& a) {

@@ -31,7 +31,7 @@ Bounds, none taken from a kernel (FACTOR = 16 as tests/autograd_reference.py):
   E_loc       |e - e_ref| <= sum_k |H_k| |r_k| (FACTOR y_b + 2^-24) + 2^-24 |e_ref| + N 2^-53 (|diag| + sum_k |H_k| |r_k|),
               r_k = exp(d64[k]).  First term: what the ratio bound lets through to first order, and `coef` cast to float; second:
               the complex64 output; third: the sum.  FOUND in the sources: every swap kernel's store (crnn_swap_kernel,
-              crnn_split_kernels.h, crnn_ml_kernels.h) forms exp(dre) * coef, cos and sin in double and writes a double2;
+              crnn_ml_swap_kernel, crnn_split_kernels.h) forms exp(dre) * coef, cos and sin in double and writes a double2;
               j1j2_eloc_kernel adds diag and the 2 N slots in double in bond order and casts once to float2; the enumerate kernel
               sums the diagonal in double.  So the summation term carries 2^-53 as stated (it is 2^-24 of the second term and
               decides nothing).
@@ -141,7 +141,7 @@ def case(cid):
 
 
 def tile_of_engine(engine):
-    """Items per swap tile: 32 on the bf16x3 engine (crnn_split_kernels.h), 16 on the f32-input MFMA (crnn_kernels.h, crnn_ml_kernels.h)."""
+    """Items per swap tile: 32 on the bf16x3 engine (crnn_split_kernels.h), 16 on the f32-input MFMA (crnn_kernels.h)."""
     return 32 if engine == "bf16x3" else 16
 
 

@@ -128,7 +128,7 @@ def case(cid):
 
 
 def tile_of_engine(engine):
-    """Chains per flip tile: 32 on the bf16x3 engine (split_kernels.h), 16 on the f32-input MFMA (gru_kernels.h, ml_kernels.h)."""
+    """Chains per flip tile: 32 on the bf16x3 engine (split_kernels.h), 16 on the f32-input MFMA (gru_kernels.h)."""
     return 32 if engine == "bf16x3" else 16
 
 

@@ -101,7 +101,7 @@ def test_every_draw_against_float64_conditionals(cid, family, shape, units, ns, 
 
 BIG_SEED = 0x9E3779B97F4A7C15
 # family, lattice, units, kernel scale, environment: the one-wave and the cooperative GRU base kernels (gru_kernels.h, both sites), the
-# stack (ml_kernels.h), the complex model's two kernels and its stack (crnn_kernels.h, crnn_ml_kernels.h), the 2D RNN, the LSTM, and
+# stack (gru_kernels.h), the complex model's two kernels and its stack (crnn_kernels.h), the 2D RNN, the LSTM, and
 # the float64 GRU.  Scales as in the table above (2D RNN 1.25).
 EDGE_MODELS = [
     ("gru", (40, 1), (50,), 3.0, {}),
