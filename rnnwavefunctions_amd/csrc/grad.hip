@@ -1,6 +1,8 @@
-// grad.hip - host side of the VMC-cost gradient: the shared driver (grad_device), rnnwf_vmc_gradient,
+// grad.hip - host side of the VMC-cost gradient: the shared driver (grad_device, grad_bwd_image), rnnwf_vmc_gradient,
 // the flat-gradient probe, rnnwf_get_grad / rnnwf_get_grads_flat, and the gradient hooks (models.h: Gradient) of the GRU RNNs
 // (f32 1D positive / parity / complex, f64 2D-lattice GRU; one layer or a stack).  The 2D RNN's hooks live in mdrnn.hip.
+// Every layer's backward image comes from pack_bwd_side, every layer's tensors from unpack_cell, every backward pass - the 2D RNN's
+// too - is launched by backward_launch (tn_gemm.h).
 #include <algorithm>
 
 #include "grad_kernels.h"
@@ -13,6 +15,71 @@ using namespace rnnwf;
 
 namespace {
 
+// One backward operand [NTO][KBG][64] x 16 B at A: in the A fragment of output tile t (hidden unit kout receives dL/dh), k-step
+// kk = (gate g, unit quad kt) holds weight(g, kout, u), the weight from pre-activation (gate g, unit u) back to unit kout.
+// S: double, or Lin - the device re-pack tables of train.hip are this code run over Lin (pack_value.h).
+template <typename T, int NFULL, class S, class W>
+void pack_bwd_side(T* A, int H, W&& weight) {
+    using G = GradLayout<NFULL, T>;
+    for (int t = 0; t < G::NTO; ++t)
+        for (int row = 0; row < 16; ++row) {
+            int q, r;
+            row_to_qr<T>(row, q, r);
+            if (t == NFULL && r != 0) continue;
+            const int kout = t < NFULL ? 16 * t + 4 * r + q : 16 * NFULL + q;
+            if (kout >= H) continue;
+            for (int kq = 0; kq < 4; ++kq) {
+                const int lane = (kq << 4) | row;
+                for (int kk = 0; kk < G::KB; ++kk) {
+                    const int g = kk / G::KT, kt = kk % G::KT, u = 4 * kt + kq;
+                    if (u >= H) continue;
+                    PackSink<S>::put(&A[(((size_t)t * G::KBG + kk / G::VW) * 64 + lane) * G::VW + (kk % G::VW)], weight(g, kout, u));
+                }
+            }
+        }
+}
+
+// One GRU cell's tensors (TF names under `pre`) from its dW image [PCOLS][qcols]: unit u's P rows (gate tiles, dy tiles) against
+// the Q columns of the `nin` input rows (xcol(i)), of the recurrent state (hoff + col_of_unit) and of the constant 1 (onecol).
+template <typename T, int NFULL, class XCol>
+void unpack_cell(rnnwf_handle* h, const T* dW, int qcols, const std::string& pre, int nin, XCol&& xcol, int hoff, int onecol) {
+    const int H = h->H;
+    constexpr int NT = GradLayout<NFULL, T>::NT;
+    auto at = [&](int prow, int col) { return (double)dW[(size_t)prow * qcols + col]; };
+    auto& gWg = h->grads[pre + "gates/kernel"];
+    auto& gbg = h->grads[pre + "gates/bias"];
+    auto& gWci = h->grads[pre + "candidate/input_projection/kernel"];
+    auto& gbci = h->grads[pre + "candidate/input_projection/bias"];
+    auto& gWch = h->grads[pre + "candidate/hidden_projection/kernel"];
+    auto& gbch = h->grads[pre + "candidate/hidden_projection/bias"];
+    gWg.assign((size_t)(nin + H) * 2 * H, 0.0); gbg.assign(2 * H, 0.0);
+    gWci.assign((size_t)nin * H, 0.0); gbci.assign(H, 0.0);
+    gWch.assign((size_t)H * H, 0.0); gbch.assign(H, 0.0);
+    for (int u = 0; u < H; ++u) {
+        const int m = u / 16, r = (u % 16) / 4, q = u % 4;
+        const bool full = u < 16 * NFULL;
+        const int uq = u - 16 * NFULL;                       // remainder units: lane quarter = uq
+        int prow[3];
+        for (int g = 0; g < 3; ++g) prow[g] = full ? (g * NFULL + m) * 16 + 4 * q + r : (NT - 1) * 16 + 4 * uq + g;
+        const int prow_y = full ? (NT + m) * 16 + 4 * q + r : (NT + NFULL) * 16 + 4 * uq;
+        for (int k = 0; k < H; ++k) {
+            const int ch = hoff + col_of_unit(NFULL, k);
+            gWg[(size_t)(nin + k) * 2 * H + u] = at(prow[0], ch);
+            gWg[(size_t)(nin + k) * 2 * H + H + u] = at(prow[1], ch);
+            gWch[(size_t)k * H + u] = at(prow[2], ch);
+        }
+        for (int i = 0; i < nin; ++i) {
+            gWg[(size_t)i * 2 * H + u] = at(prow[0], xcol(i));
+            gWg[(size_t)i * 2 * H + H + u] = at(prow[1], xcol(i));
+            gWci[(size_t)i * H + u] = at(prow_y, xcol(i));
+        }
+        gbg[u] = at(prow[0], onecol);
+        gbg[H + u] = at(prow[1], onecol);
+        gbch[u] = at(prow[2], onecol);
+        gbci[u] = at(prow_y, onecol);
+    }
+}
+
 template <typename T, int NFULL, int WAVES, int NOUT>
 struct GLaunch {
     using L = GruLayout<T, NFULL, NOUT>;
@@ -22,34 +89,16 @@ struct GLaunch {
 
     template <class S = double>
     static std::vector<char> pack_bwd(const rnnwf_handle* h) {
-        using Out = PackSink<S>;
-        const int H = h->H;
+        const size_t H = h->H;
         std::vector<char> img(G::BWD_BYTES, 0);
-        Out::begin(img);
+        PackSink<S>::begin(img);
         const std::string pre = kGruPre;
         const auto Wg = pvs<S>(h, pre + "gates/kernel");                         // [2+H, 2H]
         const auto Wch = pvs<S>(h, pre + "candidate/hidden_projection/kernel");  // [H, H]
-        T* A = reinterpret_cast<T*>(img.data());
-        for (int t = 0; t < G::NTO; ++t)
-            for (int row = 0; row < 16; ++row) {
-                int q, r;
-                row_to_qr<T>(row, q, r);
-                if (t == NFULL && r != 0) continue;
-                const int kout = t < NFULL ? 16 * t + 4 * r + q : 16 * NFULL + q;   // hidden unit receiving dL/dh
-                if (kout >= H) continue;
-                for (int kq = 0; kq < 4; ++kq) {
-                    const int lane = (kq << 4) | row;
-                    for (int kk = 0; kk < G::KB; ++kk) {
-                        const int g = kk / G::KT, kt = kk % G::KT, u = 4 * kt + kq;  // pre-activation (gate g, unit u)
-                        if (u >= H) continue;
-                        S w;
-                        if (g == 0) w = Wg[(size_t)(2 + kout) * 2 * H + u];
-                        else if (g == 1) w = Wg[(size_t)(2 + kout) * 2 * H + H + u];
-                        else w = Wch[(size_t)kout * H + u];
-                        Out::put(&A[(((size_t)t * G::KBG + kk / G::VW) * 64 + lane) * G::VW + (kk % G::VW)], w);
-                    }
-                }
-            }
+        pack_bwd_side<T, NFULL, S>(reinterpret_cast<T*>(img.data()), h->H, [&](int g, int kout, int u) -> S {
+            if (g == 2) return Wch[kout * H + u];
+            return Wg[(2 + kout) * 2 * H + g * H + u];
+        });
         return img;
     }
 
@@ -57,57 +106,28 @@ struct GLaunch {
     static constexpr int WIDE = (std::is_same<T, float>::value && NOUT == 3 && WAVES == 4) ? (NFULL == 8 ? 0 : NFULL == 12 ? 1 : NFULL == 16 ? 3 : -1)
                               : (std::is_same<T, float>::value && NOUT == 1 && WAVES == 4) ? (NFULL == 8 ? 4 : NFULL == 12 ? 5 : NFULL == 16 ? 6 : -1)
                               : (std::is_same<T, double>::value && NOUT == 1 && WAVES == 4 && NFULL == 6) ? 2 : -1;
-    static const void* kernel() {
+    static GradKernel kernel() {
         if constexpr (WIDE >= 0) return grad_wide_kernel(WIDE);
-        else return (const void*)gru_bwd_kernel<T, NFULL, WAVES, NOUT>;
-    }
-    static void launch(unsigned grid, size_t lds, hipStream_t stream, const GradArgs& a) {
-        if constexpr (WIDE >= 0) grad_wide_launch(WIDE, grid, lds, stream, a);
-        else gru_bwd_kernel<T, NFULL, WAVES, NOUT><<<grid, WAVES * 64, lds, stream>>>(a);
+        else return gru_bwd_kernel<T, NFULL, WAVES, NOUT>;
     }
 
     // small batches: two waves per block of 16 chains (grad_kernels.h: GradPair) while every pair still gets SIMDs of its own
     static constexpr bool PAIR_OK = WIDE < 0 && std::is_same<T, float>::value && WAVES == 4 && GradPair<T, NFULL, NOUT>::FITS;
-    static int run_pair(rnnwf_handle* h, GradArgs a, int64_t R, void* dW) {
+
+    // one pass of `kern` (per_wg 16-chain blocks per workgroup), then dW += P^T Q
+    static int run_kernel(rnnwf_handle* h, GradKernel kern, int threads, size_t lds, int per_wg, const GradArgs& a, int64_t R, void* dW) {
+        if (int rc = backward_launch<T>(h, kern, threads, lds, a.nsb, per_wg, NOUT * G::HEAD_ROW, (T*)a.head_grad, a)) return rc;
+        return tn_gemm_launch<T, G::PCOLS / 16, G::QCOLS / 16>(h, (const T*)a.P, (const T*)a.Q, R, (T*)dW);
+    }
+    static int run(rnnwf_handle* h, const GradArgs& a, int64_t R, void* dW) {
         if constexpr (PAIR_OK) {
             using GP = GradPair<T, NFULL, NOUT>;
-            const auto kern = gru_bwd_kernel<T, NFULL, 2 * GP::NB, NOUT, true>;
-            unsigned grid = 0;
-            if (int rc = persistent_grid(h, kern, 2 * GP::NB * 64, GP::LDS, a.nsb, GP::NB, &grid)) return rc;
-            constexpr int HN = NOUT * G::HEAD_ROW;
-            T* part = nullptr;
-            if (int rc = head_part_alloc<T>(h, (size_t)grid * GP::NB, HN, &part)) return rc;
-            a.head_part = part;
-            {
-                TimedLaunch tl(h, kTimerBackprop);
-                kern<<<grid, 2 * GP::NB * 64, GP::LDS, h->stream>>>(a);
-                head_reduce_launch<T>(h, (size_t)grid * GP::NB, HN, (T*)a.head_grad);
-            }
-            RNNWF_HIP(h, hipGetLastError());
-            return tn_gemm_launch<T, G::PCOLS / 16, G::QCOLS / 16>(h, (const T*)a.P, (const T*)a.Q, R, (T*)dW);
+            if (a.nsb <= (int64_t)GP::NB * h->cu_count && !h->knobs.no_coop)
+                return run_kernel(h, gru_bwd_kernel<T, NFULL, 2 * GP::NB, NOUT, true>, 2 * GP::NB * 64, GP::LDS, GP::NB, a, R, dW);
         }
-        return RNNWF_ERR_INVALID;
-    }
-
-    static int run(rnnwf_handle* h, GradArgs a, int64_t R, void* dW) {
-        if constexpr (PAIR_OK)
-            if (a.nsb <= (int64_t)GradPair<T, NFULL, NOUT>::NB * h->cu_count && !h->knobs.no_coop) return run_pair(h, a, R, dW);
-        const size_t lds = LDS;
-        if (lds > 160 * 1024)
-            return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: forward + backward weight images (%zu B) exceed the 160 KB LDS", lds);
-        unsigned grid = 0;
-        if (int rc = persistent_grid(h, kernel(), WAVES * 64, lds, a.nsb, WAVES, &grid)) return rc;
-        constexpr int HN = NOUT * G::HEAD_ROW;
-        T* part = nullptr;
-        if (int rc = head_part_alloc<T>(h, (size_t)grid * WAVES, HN, &part)) return rc;
-        a.head_part = part;
-        {
-            TimedLaunch tl(h, kTimerBackprop);
-            launch(grid, lds, h->stream, a);
-            head_reduce_launch<T>(h, (size_t)grid * WAVES, HN, (T*)a.head_grad);
-        }
-        RNNWF_HIP(h, hipGetLastError());
-        return tn_gemm_launch<T, G::PCOLS / 16, G::QCOLS / 16>(h, (const T*)a.P, (const T*)a.Q, R, (T*)dW);
+        if (LDS > 160 * 1024)
+            return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: forward + backward weight images (%zu B) exceed the 160 KB LDS", LDS);
+        return run_kernel(h, kernel(), WAVES * 64, LDS, WAVES, a, R, dW);
     }
 
     // dW image [PCOLS][QCOLS] + head gradients -> TF-named gradient arrays
@@ -115,23 +135,10 @@ struct GLaunch {
         const T* dW = (const T*)dW_;
         const T* hg = dW + head_off;
         const int H = h->H;
-        const int NT = G::NT;
-        auto col_of_unit = [&](int k) { return k < 16 * NFULL ? 16 * (k / 16) + 4 * (k % 4) + (k % 16) / 4 : 16 * NFULL + 4 * (k - 16 * NFULL); };
-        const int xcol = 16 * NFULL + 1, onecol = 16 * NFULL + 3;
-        auto at = [&](int prow, int col) { return (double)dW[(size_t)prow * G::QCOLS + col]; };
-        const std::string pre = kGruPre;
-        auto& gWg = h->grads[pre + "gates/kernel"];
-        auto& gbg = h->grads[pre + "gates/bias"];
-        auto& gWci = h->grads[pre + "candidate/input_projection/kernel"];
-        auto& gbci = h->grads[pre + "candidate/input_projection/bias"];
-        auto& gWch = h->grads[pre + "candidate/hidden_projection/kernel"];
-        auto& gbch = h->grads[pre + "candidate/hidden_projection/bias"];
+        unpack_cell<T, NFULL>(h, dW, G::QCOLS, kGruPre, 2, [](int sgm) { return 16 * NFULL + 1 + sgm; }, 0, 16 * NFULL + 3);
         const char* amp = NOUT == 1 ? "wf_dense" : "wf_dense_ampl";
         auto& gWd = h->grads[std::string(amp) + "/kernel"];
         auto& gbd = h->grads[std::string(amp) + "/bias"];
-        gWg.assign((size_t)(2 + H) * 2 * H, 0.0); gbg.assign(2 * H, 0.0);
-        gWci.assign((size_t)2 * H, 0.0); gbci.assign(H, 0.0);
-        gWch.assign((size_t)H * H, 0.0); gbch.assign(H, 0.0);
         gWd.assign((size_t)H * 2, 0.0); gbd.assign(2, 0.0);
         std::vector<double>* gWp = nullptr;
         std::vector<double>* gbp = nullptr;
@@ -142,27 +149,6 @@ struct GLaunch {
             gbp->assign(2, 0.0);
         }
         for (int u = 0; u < H; ++u) {
-            const int m = u / 16, r = (u % 16) / 4, q = u % 4;
-            const bool full = u < 16 * NFULL;
-            const int uq = u - 16 * NFULL;                       // remainder units: lane quarter = uq
-            int prow[3];
-            for (int g = 0; g < 3; ++g) prow[g] = full ? (g * NFULL + m) * 16 + 4 * q + r : (NT - 1) * 16 + 4 * uq + g;
-            const int prow_y = full ? (NT + m) * 16 + 4 * q + r : (NT + NFULL) * 16 + 4 * uq;
-            for (int k = 0; k < H; ++k) {
-                const int col = col_of_unit(k);
-                gWg[(size_t)(2 + k) * 2 * H + u] = at(prow[0], col);
-                gWg[(size_t)(2 + k) * 2 * H + H + u] = at(prow[1], col);
-                gWch[(size_t)k * H + u] = at(prow[2], col);
-            }
-            for (int sgm = 0; sgm < 2; ++sgm) {
-                gWg[(size_t)sgm * 2 * H + u] = at(prow[0], xcol + sgm);
-                gWg[(size_t)sgm * 2 * H + H + u] = at(prow[1], xcol + sgm);
-                gWci[(size_t)sgm * H + u] = at(prow_y, xcol + sgm);
-            }
-            gbg[u] = at(prow[0], onecol);
-            gbg[H + u] = at(prow[1], onecol);
-            gbch[u] = at(prow[2], onecol);
-            gbci[u] = at(prow_y, onecol);
             // head: the image holds the logit difference z1 - z0, so d/dWd[:,1] = +v and d/dWd[:,0] = -v
             const double v = hg[u];          // slot 4 kt + q == unit index
             gWd[(size_t)u * 2 + 1] = v;
@@ -203,39 +189,18 @@ struct MLGrad {
 
     template <class S = double>
     static std::vector<char> pack_upper_bwd(const rnnwf_handle* h, int layer) {
-        using Out = PackSink<S>;
-        const int H = h->H;
+        const size_t H = h->H;
         std::vector<char> img(GU::BWD_BYTES, 0);
-        Out::begin(img);
+        PackSink<S>::begin(img);
         const std::string pre = "multi_rnn_cell/cell_" + std::to_string(layer) + "/cudnn_compatible_gru_cell/";
         const auto Wg = pvs<S>(h, pre + "gates/kernel");                         // [H + H, 2H]
         const auto Wci = pvs<S>(h, pre + "candidate/input_projection/kernel");   // [H, H]
         const auto Wch = pvs<S>(h, pre + "candidate/hidden_projection/kernel");  // [H, H]
-        for (int side = 0; side < 2; ++side) {                                // 0: H side (-> dh), 1: X side (-> dx)
-            T* A = reinterpret_cast<T*>(img.data() + side * GU::SIDE_BYTES);
-            for (int t = 0; t < GU::NTO; ++t)
-                for (int row = 0; row < 16; ++row) {
-                    int q, r;
-                    row_to_qr<T>(row, q, r);
-                    if (t == NFULL && r != 0) continue;
-                    const int kout = t < NFULL ? 16 * t + 4 * r + q : 16 * NFULL + q;
-                    if (kout >= H) continue;
-                    const size_t grow = side == 0 ? (size_t)H + kout : (size_t)kout;   // row of the gates kernel
-                    for (int kq = 0; kq < 4; ++kq) {
-                        const int lane = (kq << 4) | row;
-                        for (int kk = 0; kk < GU::KB; ++kk) {
-                            const int g = kk / GU::KT, kt = kk % GU::KT, u = 4 * kt + kq;
-                            if (u >= H) continue;
-                            S w;
-                            if (g == 0) w = Wg[grow * 2 * H + u];
-                            else if (g == 1) w = Wg[grow * 2 * H + H + u];
-                            else if (side == 0) w = Wch[(size_t)kout * H + u];
-                            else w = Wci[(size_t)kout * H + u];
-                            Out::put(&A[(((size_t)t * GU::KBG + kk / GU::VW) * 64 + lane) * GU::VW + (kk % GU::VW)], w);
-                        }
-                    }
-                }
-        }
+        for (int side = 0; side < 2; ++side)                                  // 0: H side (-> dh), 1: X side (-> dx)
+            pack_bwd_side<T, NFULL, S>(reinterpret_cast<T*>(img.data() + side * GU::SIDE_BYTES), h->H, [&](int g, int kout, int u) -> S {
+                if (g == 2) return (side == 0 ? Wch : Wci)[kout * H + u];
+                return Wg[((side == 0 ? H : 0) + kout) * 2 * H + g * H + u];      // the gates kernel's rows: x, then h
+            });
         return img;
     }
 
@@ -276,25 +241,11 @@ struct MLGrad {
     }
 
     template <bool TOP>
-    static int upper_pass(rnnwf_handle* h, UpperGradArgs a) {
-        const auto kern = gru_upper_bwd_kernel<T, NFULL, WAVES, TOP, NOUT>;
+    static int upper_pass(rnnwf_handle* h, const UpperGradArgs& a) {
         const size_t lds = GU::WIDE ? GU::HEAD_BYTES : U::BYTES + GU::BWD_BYTES + (TOP ? GU::HEAD_BYTES : 0);
         if (lds > 160 * 1024) return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: stacked-layer images (%zu B) exceed the 160 KB LDS", lds);
-        unsigned grid = 0;
-        if (int rc = persistent_grid(h, kern, WAVES * 64, lds, a.nsb, WAVES, &grid)) return rc;
-        constexpr int HN = NOUT * GU::HEAD_ROW;
-        if (TOP) {
-            T* part = nullptr;
-            if (int rc = head_part_alloc<T>(h, (size_t)grid * WAVES, HN, &part)) return rc;
-            a.head_part = part;
-        }
-        {
-            TimedLaunch tl(h, kTimerBackprop);
-            kern<<<grid, WAVES * 64, lds, h->stream>>>(a);
-            if (TOP) head_reduce_launch<T>(h, (size_t)grid * WAVES, HN, (T*)a.head_grad);
-        }
-        RNNWF_HIP(h, hipGetLastError());
-        return 0;
+        return backward_launch<T>(h, gru_upper_bwd_kernel<T, NFULL, WAVES, TOP, NOUT>, WAVES * 64, lds, a.nsb, WAVES, NOUT * GU::HEAD_ROW,
+                                  TOP ? (T*)a.head_grad : nullptr, a);
     }
 
     // every kernel of the gradient on the resident batch, added into the cleared h->gradW
@@ -326,98 +277,51 @@ struct MLGrad {
 
     // one backward pass per layer, top first, over the resident checkpoints of the chains in `bits`; everything is ADDED to gradW
     static int passes(rnnwf_handle* h, const GradCost& c, const uint32_t* bits, const double* wfac) {
-        const int N = h->N;
-        const int64_t ns = h->last_ns, R = ns * N, nsb = (ns + kChains - 1) / kChains;
+        const int64_t R = h->last_ns * h->N;
         T* dW = (T*)h->gradW.p;
+        // the batch, the chains in `bits` and the cost's weights: the same in every pass
+        auto fill = [&](auto& a) {
+            grad_batch_args(h, &a);
+            a.bits = bits;
+            a.eloc = (const double*)h->eloc.p;
+            a.eloc_c = (const float2*)h->eloc.p;
+            a.mean_e = c.mean_e;
+            a.mean_im = c.mean_im;
+            a.inv_norm = c.inv_norm;
+            a.mom = c.mom;
+        };
         const void* dh_in = nullptr;
         if constexpr (NL > 1) {
-            const char* bwd = (const char*)h->wbwd.p;
             for (int l = NL - 1; l >= 1; --l) {
-                UpperGradArgs a{};
-                a.wup = (const char*)h->wimg.p + L0::BYTES + (size_t)(l - 1) * U::BYTES;
-                a.wbwd = bwd + G0::G::BWD_BYTES + (size_t)(l - 1) * GU::BWD_BYTES;
-                a.whead = (const char*)h->wimg.p + L0::OFF_WD;
-                a.N = N; a.layer = l; a.hck_nl = NL;
-                a.ns = ns; a.nsb = nsb;
-                a.bits = bits;
-                a.wfac = wfac;
-                a.hck = h->hck.p;
-                a.eloc = (const double*)h->eloc.p;
-                a.eloc_c = (const float2*)h->eloc.p;
-                a.mean_e = c.mean_e;
-                a.mean_im = c.mean_im;
-                a.inv_norm = c.inv_norm;
-                a.mom = c.mom;
-                a.dh_in = dh_in;
-                a.dx_out = h->gradDX[(NL - 1 - l) & 1].p;
-                a.P = h->gradP.p;
-                a.Q = h->gradQ.p;
-                a.head_grad = dW + DW0;
-                if (l == NL - 1) { if (int rc = upper_pass<true>(h, a)) return rc; }
-                else { if (int rc = upper_pass<false>(h, a)) return rc; }
-                if (int rc = tn_gemm_launch<T, GU::PCOLS / 16, GU::QCOLS / 16>(h, (const T*)a.P, (const T*)a.Q, R, dW + DW0 + HEAD + (size_t)(l - 1) * DWU))
+                UpperGradArgs u{};
+                fill(u);
+                u.wup = (const char*)h->wimg.p + L0::BYTES + (size_t)(l - 1) * U::BYTES;
+                u.wbwd = (const char*)h->wbwd.p + G0::G::BWD_BYTES + (size_t)(l - 1) * GU::BWD_BYTES;
+                u.whead = (const char*)h->wimg.p + L0::OFF_WD;
+                u.layer = l;
+                u.wfac = wfac;
+                u.dh_in = dh_in;
+                u.dx_out = h->gradDX[(NL - 1 - l) & 1].p;
+                u.head_grad = dW + DW0;
+                if (int rc = l == NL - 1 ? upper_pass<true>(h, u) : upper_pass<false>(h, u)) return rc;
+                if (int rc = tn_gemm_launch<T, GU::PCOLS / 16, GU::QCOLS / 16>(h, (const T*)u.P, (const T*)u.Q, R, dW + DW0 + HEAD + (size_t)(l - 1) * DWU))
                     return rc;
-                dh_in = a.dx_out;
+                dh_in = u.dx_out;
             }
         }
         GradArgs a{};
+        fill(a);
         a.wimg = h->wimg.p;
-        a.wbwd = h->wbwd.p;
-        a.N = N; a.ns = ns; a.nsb = nsb;
-        a.bits = bits;
         a.wfac = NL > 1 ? nullptr : wfac;                  // a stack: w_s only weights the head terms, on the top layer
-        a.hck = h->hck.p;
-        a.eloc = (const double*)h->eloc.p;
-        a.eloc_c = (const float2*)h->eloc.p;
-        a.mean_e = c.mean_e;
-        a.mean_im = c.mean_im;
-        a.inv_norm = c.inv_norm;
-        a.mom = c.mom;
-        a.P = h->gradP.p;
-        a.Q = h->gradQ.p;
         a.head_grad = dW + (NL > 1 ? DW_FLOATS : DW0);     // a stack: the scratch row (layer 0 has no head term there; its adds are zeros)
         a.dh_in = dh_in;
-        a.hck_nl = NL;
         return G0::run(h, a, R, dW);
     }
 
     static void unpack_upper(rnnwf_handle* h, const T* dW, int layer) {
-        const int H = h->H;
-        const int NT = GU::NT;
-        auto col_of_unit = [&](int k) { return k < 16 * NFULL ? 16 * (k / 16) + 4 * (k % 4) + (k % 16) / 4 : 16 * NFULL + 4 * (k - 16 * NFULL); };
-        const int hoff = 16 * GU::NTO, onecol = hoff + 16 * NFULL + 1;
-        auto at = [&](int prow, int col) { return (double)dW[(size_t)prow * GU::QCOLS + col]; };
-        const std::string pre = "multi_rnn_cell/cell_" + std::to_string(layer) + "/cudnn_compatible_gru_cell/";
-        auto& gWg = h->grads[pre + "gates/kernel"];
-        auto& gbg = h->grads[pre + "gates/bias"];
-        auto& gWci = h->grads[pre + "candidate/input_projection/kernel"];
-        auto& gbci = h->grads[pre + "candidate/input_projection/bias"];
-        auto& gWch = h->grads[pre + "candidate/hidden_projection/kernel"];
-        auto& gbch = h->grads[pre + "candidate/hidden_projection/bias"];
-        gWg.assign((size_t)2 * H * 2 * H, 0.0); gbg.assign(2 * H, 0.0);
-        gWci.assign((size_t)H * H, 0.0); gbci.assign(H, 0.0);
-        gWch.assign((size_t)H * H, 0.0); gbch.assign(H, 0.0);
-        for (int u = 0; u < H; ++u) {
-            const int m = u / 16, r = (u % 16) / 4, q = u % 4;
-            const bool full = u < 16 * NFULL;
-            const int uq = u - 16 * NFULL;
-            int prow[3];
-            for (int g = 0; g < 3; ++g) prow[g] = full ? (g * NFULL + m) * 16 + 4 * q + r : (NT - 1) * 16 + 4 * uq + g;
-            const int prow_y = full ? (NT + m) * 16 + 4 * q + r : (NT + NFULL) * 16 + 4 * uq;
-            for (int k = 0; k < H; ++k) {
-                const int cx = col_of_unit(k), ch = hoff + col_of_unit(k);
-                gWg[(size_t)k * 2 * H + u] = at(prow[0], cx);
-                gWg[(size_t)k * 2 * H + H + u] = at(prow[1], cx);
-                gWg[(size_t)(H + k) * 2 * H + u] = at(prow[0], ch);
-                gWg[(size_t)(H + k) * 2 * H + H + u] = at(prow[1], ch);
-                gWci[(size_t)k * H + u] = at(prow_y, cx);
-                gWch[(size_t)k * H + u] = at(prow[2], ch);
-            }
-            gbg[u] = at(prow[0], onecol);
-            gbg[H + u] = at(prow[1], onecol);
-            gbch[u] = at(prow[2], onecol);
-            gbci[u] = at(prow_y, onecol);
-        }
+        const int hoff = 16 * GU::NTO;
+        unpack_cell<T, NFULL>(h, dW, GU::QCOLS, "multi_rnn_cell/cell_" + std::to_string(layer) + "/cudnn_compatible_gru_cell/", h->H,
+                              [](int k) { return col_of_unit(NFULL, k); }, hoff, hoff + 16 * NFULL + 1);
     }
 };
 
@@ -495,6 +399,17 @@ const Gradient* rnnwf::gru_gradient() {
     return &g;
 }
 
+// the family's backward image in h->wbwd, packed and uploaded when the committed parameters changed since the last one
+int rnnwf::grad_bwd_image(rnnwf_handle* h) {
+    if (h->wbwd_valid) return 0;
+    std::vector<char> img;
+    if (int rc = h->family->gradient->pack(h, &img)) return rc;
+    if (int rc = ensure(h, h->wbwd, img.size())) return rc;
+    if (int rc = upload(h, h->wbwd.p, img.data(), img.size())) return rc;
+    h->wbwd_valid = true;
+    return 0;
+}
+
 // The gradient's kernels on the batch of the last rnnwf_vmc_step: back-propagation through time + weight-gradient GEMMs, the
 // result (the family's dW images and head rows) left in h->gradW.
 int rnnwf::grad_device(rnnwf_handle* h, double mean_energy, double mean_energy_im, double norm, const double* mom_dev, GradImage* out) {
@@ -505,13 +420,7 @@ int rnnwf::grad_device(rnnwf_handle* h, double mean_energy, double mean_energy_i
     const Gradient& g = *h->family->gradient;
     GradImage im;
     if (int rc = g.layout(h, &im)) return rc;
-    if (!h->wbwd_valid) {
-        std::vector<char> img;
-        if (int rc = g.pack(h, &img)) return rc;
-        if (int rc = ensure(h, h->wbwd, img.size())) return rc;
-        if (int rc = upload(h, h->wbwd.p, img.data(), img.size())) return rc;
-        h->wbwd_valid = true;
-    }
+    if (int rc = grad_bwd_image(h)) return rc;
     const size_t bytes = im.alloc * (im.f64 ? 8 : 4);
     if (int rc = ensure(h, h->gradW, bytes)) return rc;
     RNNWF_HIP(h, hipMemsetAsync(h->gradW.p, 0, bytes, h->stream));

@@ -10,6 +10,8 @@
 //                     operand).  It writes, per (site, chain), the row  P = [d a_r | d a_u | d q | d y]  and the
 //                     row  Q = [h_in | x one-hot | 1]; head gradients are summed in registers, one row per wave,
 //                     and head_reduce_kernel adds the rows.
+//                     fetch_row is what it shares with gru_upper_bwd_kernel (ml_grad_kernels.h) as a function; the rest of
+//                     what the two have in common is written out in each ("Backward kernels").
 //   tn_gemm_kernel  : dW = P^T Q over all R = N*ns rows (tall-skinny TN GEMM on the f32 / f64 MFMA; operands are read
 //                     straight from the row-major arrays, which already have the A/B fragment shape); every block
 //                     stores its partial fragments, tn_reduce_kernel adds them in a fixed order.
@@ -39,12 +41,12 @@ struct GradStream {
 };
 
 struct GradArgs {
-    const void* wimg;          // forward image (GruLayout<float, NFULL, 1>)
+    const void* wimg;          // forward image (GruLayout<T, NFULL, NOUT>)
     const void* wbwd;          // backward A fragments (GradLayout::BWD_BYTES)
     int32_t N;
     int64_t ns, nsb;
     const uint32_t* bits;
-    const void* hck;           // [N-1][nsb][KT][64] T, state after each site
+    const void* hck;           // [N][nsb][hck_nl][KT][64] T: every layer's state after each site (the last site's is read by upper layers only)
     const double* eloc;        // [ns] f64 (positive RNN) ...
     const float2* eloc_c;      // ... or [ns] complex64 (complex RNN)
     double mean_e, mean_im, inv_norm;   // w_s = (E_s - mean) * inv_norm  (real and imaginary part separately)
@@ -61,6 +63,21 @@ struct GradArgs {
     const void* dh_in;         // [N][nsb][KT][64] T or nullptr
     int32_t hck_nl;            // layers per checkpoint entry (0 or 1: single layer)
 };
+
+// Shared by gru_bwd_kernel and gru_upper_bwd_kernel; the other pieces the two kernels have in common stay written out in each
+// ("Backward kernels").
+// Checkpoint row `row` of rows[.][KT][64] into this lane's registers; zeros where there is none (the state before site 0).
+template <typename T, int KT>
+__device__ __forceinline__ void fetch_row(T (&dst)[KT], const T* rows, int64_t row, int lane, bool present = true) {
+    if (present) {
+        const T* src = rows + row * KT * 64 + lane;
+#pragma unroll
+        for (int k = 0; k < KT; ++k) dst[k] = src[k * 64];
+    } else {
+#pragma unroll
+        for (int k = 0; k < KT; ++k) dst[k] = T(0);
+    }
+}
 
 // Head-row sums of one wave over its chains, stored (not added) to row = part[global wave][NOUT][HEAD_ROW]: slot 4 k + q is a unit
 // slot, 4 KT the bias, the rest zero.  head_reduce_kernel adds the waves' rows in a fixed order: no atomics, the gradient is
@@ -199,14 +216,7 @@ __global__ void __launch_bounds__(WAVES * 64) gru_bwd_kernel(GradArgs a) {
         // fetched 32 sites ahead) and the input state of site n - 1 is fetched while site n is worked on
         uint32_t wcur = word((N - 1) >> 5), wlow = N > 32 ? word(((N - 1) >> 5) - 1) : 0u;
         auto fetch_state = [&](int n, T (&dst)[KT]) {           // h_in of site n = state after site n - 1 (zero at n = 0)
-            if (n > 0) {
-                const T* src = reinterpret_cast<const T*>(a.hck) + (((int64_t)(n - 1) * a.nsb + sb) * hck_nl * KT) * 64 + lane;
-#pragma unroll
-                for (int k = 0; k < KT; ++k) dst[k] = src[k * 64];
-            } else {
-#pragma unroll
-                for (int k = 0; k < KT; ++k) dst[k] = T(0);
-            }
+            fetch_row(dst, reinterpret_cast<const T*>(a.hck), ((int64_t)(n - 1) * a.nsb + sb) * hck_nl, lane, n > 0);
         };
         T hpf[KT];
         if (fwd_role) fetch_state(N - 1, hpf);

@@ -9,29 +9,17 @@
 
 namespace rnnwf {
 
-const void* grad_wide_kernel(int which) {
+GradKernel grad_wide_kernel(int which) {
     switch (which) {
-        case 0: return (const void*)gru_bwd_kernel<float, 8, 4, 3>;
-        case 1: return (const void*)gru_bwd_kernel<float, 12, 4, 3>;
-        case 2: return (const void*)gru_bwd_kernel<double, 6, 4, 1>;
-        case 3: return (const void*)gru_bwd_kernel<float, 16, 4, 3>;
-        case 4: return (const void*)gru_bwd_kernel<float, 8, 4, 1>;
-        case 5: return (const void*)gru_bwd_kernel<float, 12, 4, 1>;
-        case 6: return (const void*)gru_bwd_kernel<float, 16, 4, 1>;
+        case 0: return gru_bwd_kernel<float, 8, 4, 3>;
+        case 1: return gru_bwd_kernel<float, 12, 4, 3>;
+        case 2: return gru_bwd_kernel<double, 6, 4, 1>;
+        case 3: return gru_bwd_kernel<float, 16, 4, 3>;
+        case 4: return gru_bwd_kernel<float, 8, 4, 1>;
+        case 5: return gru_bwd_kernel<float, 12, 4, 1>;
+        case 6: return gru_bwd_kernel<float, 16, 4, 1>;
     }
     return nullptr;
-}
-
-void grad_wide_launch(int which, unsigned grid, size_t lds, hipStream_t stream, const GradArgs& a) {
-    switch (which) {
-        case 0: gru_bwd_kernel<float, 8, 4, 3><<<grid, 256, lds, stream>>>(a); break;
-        case 1: gru_bwd_kernel<float, 12, 4, 3><<<grid, 256, lds, stream>>>(a); break;
-        case 2: gru_bwd_kernel<double, 6, 4, 1><<<grid, 256, lds, stream>>>(a); break;
-        case 3: gru_bwd_kernel<float, 16, 4, 3><<<grid, 256, lds, stream>>>(a); break;
-        case 4: gru_bwd_kernel<float, 8, 4, 1><<<grid, 256, lds, stream>>>(a); break;
-        case 5: gru_bwd_kernel<float, 12, 4, 1><<<grid, 256, lds, stream>>>(a); break;
-        case 6: gru_bwd_kernel<float, 16, 4, 1><<<grid, 256, lds, stream>>>(a); break;
-    }
 }
 
 }  // namespace rnnwf

@@ -129,4 +129,8 @@ template <typename T> inline void row_to_qr(int row, int& q, int& r);
 template <> inline void row_to_qr<float>(int row, int& q, int& r) { q = row >> 2; r = row & 3; }
 template <> inline void row_to_qr<double>(int row, int& q, int& r) { q = row & 3; r = row >> 2; }
 
+// column of hidden unit k in a row kept in unit-fragment order (the gradient's P / Q rows): the nfull full tiles by (tile,
+// register, lane quarter), then the remainder units, one per lane quarter
+inline int col_of_unit(int nfull, int k) { return k < 16 * nfull ? 16 * (k / 16) + 4 * (k % 4) + (k % 16) / 4 : 16 * nfull + 4 * (k - 16 * nfull); }
+
 }  // namespace rnnwf

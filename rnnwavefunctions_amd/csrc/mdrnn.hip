@@ -357,17 +357,11 @@ struct MGrad {
         a.head_grad = (double*)h->gradW.p + (size_t)G::PCOLS * G::QCOLS;
         a.vert_pos = m.vert_pos;
         a.row_first = m.row_first;
-        unsigned grid = 0;
+        unsigned grid = 0;                                  // the ring is sized by the grid backward_launch will use
         if (int rc = persistent_grid(h, mdrnn_bwd_kernel<NFULL, WAVES>, WAVES * 64, G::BYTES, a.nsb, WAVES, &grid)) return rc;
         if (int rc = ensure(h, h->rowbuf, (size_t)grid * WAVES * 2 * a.Nx * G::KT * 64 * 8)) return rc;
         a.ring = (double*)h->rowbuf.p;
-        if (int rc = head_part_alloc<double>(h, (size_t)grid * WAVES, 2 * G::HEAD_ROW, &a.head_part)) return rc;
-        {
-            TimedLaunch tl(h, kTimerBackprop);
-            mdrnn_bwd_kernel<NFULL, WAVES><<<grid, WAVES * 64, G::BYTES, h->stream>>>(a);
-            head_reduce_launch<double>(h, (size_t)grid * WAVES, 2 * G::HEAD_ROW, a.head_grad);
-        }
-        RNNWF_HIP(h, hipGetLastError());
+        if (int rc = backward_launch<double>(h, mdrnn_bwd_kernel<NFULL, WAVES>, WAVES * 64, G::BYTES, a.nsb, WAVES, 2 * G::HEAD_ROW, a.head_grad, a)) return rc;
         return tn_gemm_launch<double, G::PCOLS / 16, G::QCOLS / 16>(h, a.P, a.Q, R, (double*)h->gradW.p);
     }
 
@@ -376,7 +370,6 @@ struct MGrad {
         const double* dW = (const double*)img;
         const double* hg = dW + (size_t)G::PCOLS * G::QCOLS;
         const int H = h->H;
-        auto col_of_unit = [&](int k) { return k < 16 * NFULL ? 16 * (k / 16) + 4 * (k % 4) + (k % 16) / 4 : 16 * NFULL + 4 * (k - 16 * NFULL); };
         const int xcol = 16 * NFULL + 1, onecol = 16 * NFULL + 3, voff = 16 * G::NT;
         auto at = [&](int prow, int col) { return dW[(size_t)prow * G::QCOLS + col]; };
         auto& gWh = h->grads["Wh_rnn_0"];
@@ -390,10 +383,10 @@ struct MGrad {
         gUh.assign((size_t)2 * H, 0.0); gUv.assign((size_t)2 * H, 0.0);
         gb.assign(H, 0.0); gWd.assign((size_t)H * 2, 0.0); gbd.assign(2, 0.0);
         for (int u = 0; u < H; ++u) {
-            const int prow = col_of_unit(u);            // P uses the same tile / quarter / register order as Q
+            const int prow = col_of_unit(NFULL, u);            // P uses the same tile / quarter / register order as Q
             for (int k = 0; k < H; ++k) {
-                gWh[(size_t)k * H + u] = at(prow, col_of_unit(k));
-                gWv[(size_t)k * H + u] = at(prow, voff + col_of_unit(k));
+                gWh[(size_t)k * H + u] = at(prow, col_of_unit(NFULL, k));
+                gWv[(size_t)k * H + u] = at(prow, voff + col_of_unit(NFULL, k));
             }
             for (int sg = 0; sg < 2; ++sg) {
                 gUh[(size_t)sg * H + u] = at(prow, xcol + sg);

@@ -8,46 +8,43 @@
 // with both products on the f32 MFMA.  dL/dh_n comes from the head (top layer) or from the pass of the layer above.
 // Weight gradients are P^T Q with the same P rows as the first layer and Q = [x | h_{n-1}, 1].
 // One pass needs only this layer's images in LDS: forward 67 KB + two backward operands 80 KB at 50 units.
+// Layout constants and checkpoint-row fetch come from grad_kernels.h; the site loop is this kernel's own.
 #pragma once
 #include "grad_kernels.h"
 
 namespace rnnwf {
 
+// GradLayout with two backward operands and Q = [x | h_{n-1}]
 template <int NFULL, int NOUT = 1, typename T = float>
-struct UpperGradLayout {
-    static constexpr int KT = 4 * NFULL + 1;
-    static constexpr int NT = 3 * NFULL + 1;
-    static constexpr int NTO = NFULL + 1;
-    static constexpr int PCOLS = 16 * (NT + NTO);         // as GradLayout: [gate rows in image order | dy]
-    static constexpr int QCOLS = 32 * NTO;                // [x | h_{n-1} with the constant 1 in a spare slot]
-    static constexpr int KB = 3 * KT;
-    static constexpr int VW = 16 / (int)sizeof(T);        // k-steps per 16-byte LDS vector
-    static constexpr int KBG = (KB + VW - 1) / VW;
-    static constexpr size_t SIDE_BYTES = (size_t)NTO * KBG * 64 * 16;    // [NTO][KBG][64] x 16 B
-    static constexpr size_t BWD_BYTES = 2 * SIDE_BYTES;                  // H side (-> dh), X side (-> dx)
-    static constexpr int WD_Q = ((NOUT * KT + 3) / 4) * 4;               // GruLayout<T, NFULL, NOUT>::WD_Q
+struct UpperGradLayout : GradLayout<NFULL, T> {
+    using B = GradLayout<NFULL, T>;
+    static constexpr int QCOLS = 32 * B::NTO;             // [x | h_{n-1} with the constant 1 in a spare slot]
+    static constexpr size_t SIDE_BYTES = B::BWD_BYTES;    // [NTO][KBG][64] x 16 B
+    static constexpr size_t BWD_BYTES = 2 * SIDE_BYTES;   // H side (-> dh), X side (-> dx)
+    static constexpr int WD_Q = GruLayout<T, NFULL, NOUT>::WD_Q;
     static constexpr size_t HEAD_BYTES = ((size_t)4 * WD_Q * sizeof(T) + 32 + 15) / 16 * 16;   // [4 q][KT][NOUT] + bias (OFF_WD .. end of the image)
-    static constexpr int HEAD_ROW = 4 * KT + 4;                          // as GradLayout::HEAD_ROW
     // forward image + both backward operands + head rows beyond the 160 KB of LDS (53..100 units): read through L2 instead
     static constexpr bool WIDE = UpperLayout<NFULL, T>::BYTES + BWD_BYTES + HEAD_BYTES > 160 * 1024;
     static constexpr size_t LDS_BYTES = WIDE ? HEAD_BYTES : UpperLayout<NFULL, T>::BYTES + BWD_BYTES + HEAD_BYTES;
 };
 
+// The fields of GradArgs under the same names (the cost's are read by the top layer's pass only), and what an upper pass adds.
+// Not GradArgs itself: with the merged struct every instantiation of the kernel loaded its arguments in other groups.
 struct UpperGradArgs {
-    const void* wup;           // forward image of this layer (UpperLayout)
+    const void* wup;           // forward image of this layer (UpperLayout<NFULL, T>)
     const void* wbwd;          // UpperGradLayout::BWD_BYTES
     const void* whead;         // OFF_WD section of the first layer's image (head weights), top layer only
     int32_t N, layer, hck_nl;
     int64_t ns, nsb;
     const uint32_t* bits;
-    const void* hck;           // [N][nsb][NL][KT][64] T
-    const double* eloc;        // [ns] f64 (positive RNN) ...
-    const float2* eloc_c;      // ... or [ns] complex64 (complex RNN)
+    const void* hck;           // [N][nsb][hck_nl][KT][64] T, as GradArgs::hck
+    const double* eloc;
+    const float2* eloc_c;
     double mean_e, mean_im, inv_norm;
-    const double* mom;         // device-resident training: the step's moments on the device (grad_kernels.h: GradArgs::mom), nullptr: the fields above
-    const double* wfac;        // [ns] extra factor of w_s or nullptr (parity-symmetric model: the direction's share of P_sym)
+    const double* mom;
+    const double* wfac;
     const void* dh_in;         // [N][nsb][KT][64] T from the layer above (nullptr: top layer, head)
-    void* dx_out;              // [N][nsb][KT][64] T
+    void* dx_out;              // [N][nsb][KT][64] T: dL/dx of every site, the dh_in of the pass below
     void* P;
     void* Q;
     void* head_grad;           // [NOUT][HEAD_ROW] T (top layer; written by head_reduce_kernel)
@@ -135,19 +132,8 @@ __global__ void __launch_bounds__(WAVES * 64) gru_upper_bwd_kernel(UpperGradArgs
         // the inputs of site n - 1 (state of the layer below at that site, this layer's state before it) are fetched while
         // site n is worked on
         auto fetch_inputs = [&](int n, T (&xd)[KT], T (&hd)[KT]) {
-            {
-                const T* src = hck + ((((int64_t)n * a.nsb + sb) * a.hck_nl + a.layer - 1) * KT) * 64 + lane;
-#pragma unroll
-                for (int k = 0; k < KT; ++k) xd[k] = src[k * 64];
-            }
-            if (n > 0) {
-                const T* src = hck + ((((int64_t)(n - 1) * a.nsb + sb) * a.hck_nl + a.layer) * KT) * 64 + lane;
-#pragma unroll
-                for (int k = 0; k < KT; ++k) hd[k] = src[k * 64];
-            } else {
-#pragma unroll
-                for (int k = 0; k < KT; ++k) hd[k] = T(0);
-            }
+            fetch_row(xd, hck, ((int64_t)n * a.nsb + sb) * a.hck_nl + a.layer - 1, lane);
+            fetch_row(hd, hck, ((int64_t)(n - 1) * a.nsb + sb) * a.hck_nl + a.layer, lane, n > 0);
         };
         T xpf[KT], hpf[KT];
         fetch_inputs(N - 1, xpf, hpf);

@@ -146,8 +146,9 @@ int crnn_base_coop_bf(rnnwf_handle* h, const CrnnArgs& a);
 // ---- gradient (grad.hip) ---------------------------------------------------------------------------
 // grad_wide.hip: backward kernels compiled in their own translation unit (index: grad.hip, GLaunch::WIDE)
 struct GradArgs;
-const void* grad_wide_kernel(int which);
-void grad_wide_launch(int which, unsigned grid, size_t lds, hipStream_t stream, const GradArgs& a);
+using GradKernel = void (*)(GradArgs);
+GradKernel grad_wide_kernel(int which);
+int grad_bwd_image(rnnwf_handle* h);                    // grad.hip: the backward image, re-packed when stale
 // forward weight-image tables into the active PackTrace, for device training: the 2D RNN's (mdrnn.hip), a stack's [layer 0 | upper layers]
 int mdrnn_pack_table(rnnwf_handle* h);
 int grad_stack_forward_table(rnnwf_handle* h);

@@ -9,6 +9,7 @@
 #include "sr_kernels.h"
 #include "sr_solve_kernels.h"
 #include "models.h"
+#include "tn_gemm.h"
 
 using namespace rnnwf;
 
@@ -92,27 +93,15 @@ int sr_build_shape(rnnwf_handle* h) {
     const int N = h->N;
     const int64_t ns = h->last_ns, R = ns * N, nsb = (ns + kChains - 1) / kChains;
     if (int rc = sr_table(h, S::D)) return rc;
-    if (!h->wbwd_valid) {                                  // the backward image, as grad_device packs it
-        std::vector<char> img;
-        if (int rc = h->family->gradient->pack(h, &img)) return rc;
-        if (int rc = ensure(h, h->wbwd, img.size())) return rc;
-        if (int rc = upload(h, h->wbwd.p, img.data(), img.size())) return rc;
-        h->wbwd_valid = true;
-    }
+    if (int rc = grad_bwd_image(h)) return rc;
     if (int rc = ensure(h, h->gradP, (size_t)R * G::PCOLS * sizeof(T))) return rc;
     if (int rc = ensure(h, h->gradQ, (size_t)R * G::QCOLS * sizeof(T))) return rc;
     if (int rc = ensure(h, h->srHead, (size_t)ns * G::HEAD_ROW * sizeof(T))) return rc;
     if (int rc = ensure(h, h->srJ, (size_t)ns * S::D * sizeof(T))) return rc;
     GradArgs a{};
+    grad_batch_args(h, &a);                                // (one layer: sr_refuse)
     a.wimg = h->wimg.p;
-    a.wbwd = h->wbwd.p;
-    a.N = N; a.ns = ns; a.nsb = nsb;
-    a.bits = (const uint32_t*)h->bits.p;
-    a.hck = h->hck.p;
-    a.P = h->gradP.p;
-    a.Q = h->gradQ.p;
     a.head_part = h->srHead.p;                             // [ns][HEAD_ROW]: one row per chain (gru_bwd_kernel<SR>)
-    a.hck_nl = 1;
     constexpr size_t lds = L::LDS_BYTES + (GradStream<T, NFULL, 1>::value ? 0 : G::BWD_BYTES);
     static_assert(lds <= 160 * 1024, "forward + backward weight images exceed the LDS");
     if (int rc = launch_persistent(h, kTimerBackprop, gru_bwd_kernel<T, NFULL, 4, 1, false, true>, 4 * 64, lds, nsb, 4, a)) return rc;

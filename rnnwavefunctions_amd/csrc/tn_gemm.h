@@ -1,5 +1,6 @@
 // tn_gemm.h - host side of the two fixed-order reductions of the gradient: the weight-gradient product  dW += P^T Q
-// (grad_kernels.h: tn_gemm_kernel + tn_reduce_kernel) and the head rows (head_reduce_kernel).
+// (grad_kernels.h: tn_gemm_kernel + tn_reduce_kernel) and the head rows (head_reduce_kernel), and the launch of a backward pass
+// (backward_launch), which ends in the latter.
 #pragma once
 #include <algorithm>
 
@@ -54,6 +55,42 @@ inline int head_part_alloc(rnnwf_handle* h, size_t waves, int n, T** out) {
 template <typename T>
 inline void head_reduce_launch(rnnwf_handle* h, size_t waves, int n, T* head_grad) {
     head_reduce_kernel<T><<<(n + 63) / 64, 1024, 0, h->stream>>>((const T*)h->gradHeadPart.p, (int)waves, n, head_grad);
+}
+
+// What every backward pass of the GRU families reads of the resident batch (A: GradArgs, UpperGradArgs): the spins, the checkpoints
+// of its hck_nl layers, the backward images, the P / Q rows.
+template <class A>
+inline void grad_batch_args(rnnwf_handle* h, A* a) {
+    a->wbwd = h->wbwd.p;
+    a->N = h->N;
+    a->ns = h->last_ns;
+    a->nsb = (h->last_ns + kChains - 1) / kChains;
+    a->bits = (const uint32_t*)h->bits.p;
+    a->hck = h->hck.p;
+    a->hck_nl = h->NL;
+    a->P = h->gradP.p;
+    a->Q = h->gradQ.p;
+}
+
+// One backward pass: the persistent grid of `kern` (per_wg 16-chain blocks per workgroup; persistent_grid, for a caller that sizes
+// a buffer by it first), room for one head row of head_n entries per block slot of the grid in a.head_part, then - inside the
+// back-propagation timer - the kernel and the head rows' reduction into head_grad.  head_grad == nullptr: a pass without head rows.
+template <typename T, typename Kern, typename Args>
+inline int backward_launch(rnnwf_handle* h, Kern kern, int threads, size_t lds, int64_t nsb, int per_wg, int head_n, T* head_grad, Args a) {
+    unsigned grid = 0;
+    if (int rc = persistent_grid(h, kern, threads, lds, nsb, per_wg, &grid)) return rc;
+    if (head_grad) {
+        T* part = nullptr;
+        if (int rc = head_part_alloc<T>(h, (size_t)grid * per_wg, head_n, &part)) return rc;
+        a.head_part = part;
+    }
+    {
+        TimedLaunch tl(h, kTimerBackprop);
+        kern<<<grid, threads, lds, h->stream>>>(a);
+        if (head_grad) head_reduce_launch<T>(h, (size_t)grid * per_wg, head_n, head_grad);
+    }
+    RNNWF_HIP(h, hipGetLastError());
+    return 0;
 }
 
 }  // namespace rnnwf
