@@ -39,11 +39,11 @@ struct KernelTimer {
 
 // Environment switches, read ONCE in rnnwf_create (never on the per-step path).
 struct Knobs {
-    int engine = 0;               // RNNWF_ENGINE: 0 default, 1 "f32" (f32-input MFMA everywhere), 2 "bf16x3" (pinned), 3 "bf16x3-serial" (pinned, 4-wave kernel without the ping-pong: A/B), 4 "bf16x3-hipcc" (pinned; 69..100 units: the compiler-scheduled riders step instead of the generated asm block: A/B), 5 "bf16x3-asm32" (pinned; 69..100 units: the 32x32x16 asm step instead of the 16x16x32 one: A/B), 7 "bf16x3-n16" (pinned; 37..52 units, positive RNN: the 16x16x32 riders form instead of the 32x32x16 ping-pong kernel: A/B, 10 % slower)
+    int engine = 0;               // RNNWF_ENGINE: 0 default, 1 "f32" (f32-input MFMA everywhere), 2 "bf16x3" (pinned); any other value is refused.  The measured-negative
+                                  // kernel variants and their A/B switches (four engines, the 2D RNN's prefetch) were removed after commit f88b60d: DESIGN.md 10
     bool no_coop = false;         // RNNWF_NO_COOP=1: base pass always on the one-wave-per-block kernel
     bool base_f32 = false;        // RNNWF_BASE=f32: the base pass keeps the f32-input MFMA (no bf16 cooperative kernel): A/B, and the
                                   // bit-identity test of the two f32 kernels
-    bool md_prefetch = false;     // RNNWF_MDRNN_PREFETCH=1: the MDRNN flip pass with the LDS-DMA prefetch of the vertical state (measured 1.7 % slower at config 4; A/B only)
     size_t state_budget = 0;      // RNNWF_STATE_BUDGET_MB << 20 (0: the family's default)
     int ablate = 0, ablate_base = 0;   // RNNWF_ABLATE / RNNWF_ABLATE_BASE: only in -DRNNWF_DIAGNOSTICS builds (tools/)
 };

@@ -22,29 +22,7 @@ struct MLaunch {
         return launch_persistent(h, kTimerBase, mdrnn_base_kernel<NFULL, WAVES>, WAVES * 64, L::BYTES, a.nsb, WAVES, a);
     }
     static constexpr size_t FLIP_LDS = L::BYTES + (size_t)WAVES * L::WORDS_BYTES;     // image + the waves' spin words
-#ifdef RNNWF_DIAGNOSTICS      // measured negative (profiles/r03_d_cfg4_prefetch.md), kept for A/B runs of tools/ only: not in the release library
-    // prefetching variant (mdrnn_flip_pf_kernel): one 8-wave workgroup per CU, a staging slot per wave behind the spin words
-    static constexpr int PF_WAVES = 8;
-    static constexpr size_t PF_LDS = L::BYTES + (size_t)PF_WAVES * L::WORDS_BYTES + (size_t)PF_WAVES * ((L::KT + 1) / 2) * 1024;
-    static constexpr bool PF_FITS = PF_LDS <= 160 * 1024;
-    static int flip_pf(rnnwf_handle* h, MdArgs a) {
-        if constexpr (PF_FITS) {
-            const auto kern = mdrnn_flip_pf_kernel<NFULL, PF_WAVES>;
-            unsigned grid = 0;
-            if (int rc = persistent_grid(h, kern, PF_WAVES * 64, PF_LDS, a.ntiles, PF_WAVES, &grid)) return rc;
-            const size_t ring_bytes = (size_t)grid * PF_WAVES * a.Nx * ((L::KT + 1) / 2) * 64 * 16;
-            if (int rc = ensure(h, h->rowbuf, ring_bytes)) return rc;
-            a.ring = (double*)h->rowbuf.p;
-            a.ablate = h->knobs.ablate;
-            return timed_launch(h, kTimerFlip, kern, grid, PF_WAVES * 64, PF_LDS, a);
-        }
-        return 0;
-    }
-#endif
     static int flip(rnnwf_handle* h, MdArgs a) {
-#ifdef RNNWF_DIAGNOSTICS
-        if (PF_FITS && NFULL == 3 && h->knobs.md_prefetch) return flip_pf(h, a);      // A/B only: measured slower (profiles/r03_d_cfg4_prefetch.md)
-#endif
         const auto kern = mdrnn_flip_kernel<NFULL, WAVES>;
         unsigned grid = 0;
         if (int rc = persistent_grid(h, kern, WAVES * 64, FLIP_LDS, a.ntiles, WAVES, &grid)) return rc;

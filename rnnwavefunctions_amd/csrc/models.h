@@ -105,7 +105,7 @@ struct CrnnArgs;
 int prnn_split_flip(rnnwf_handle* h, const PrnnArgs& a);
 double prnn_split_flops_per_step(rnnwf_handle* h);      // MFMA flops issued per 32-chain wave-step
 int prnn_split_pack(rnnwf_handle* h, std::vector<char>& simg);
-// split_stream.hip: the same pass at 69..100 units (classic layout, w3 fragments read through L2)
+// split_stream.hip: the same pass at 53..100 units (the riders form; above 68 units the w3 fragments are read through L2)
 int prnn_split_flip_stream(rnnwf_handle* h, const PrnnArgs& a, int kt16);
 double prnn_split_stream_flops_per_step(rnnwf_handle* h);
 int prnn_split_stream_pack(rnnwf_handle* h, std::vector<char>& simg);
@@ -118,10 +118,7 @@ size_t prnn_hck_bytes_per_block(rnnwf_handle* h);
 int crnn_plain_base(rnnwf_handle* h, const CrnnArgs& a);
 CrnnArgs crnn_base_args(rnnwf_handle* h, int64_t ns);
 size_t crnn_hck_bytes_per_block(rnnwf_handle* h);
-// the 16x16x32 form at 37..52 units (split_stream.hip; image in h->wsplit16)
-int prnn_split_flip_16n(rnnwf_handle* h, const PrnnArgs& a, int kt16);
-double prnn_split_16n_flops_per_step();
-int prnn_split_16n_pack(rnnwf_handle* h);
+// split_stream.hip: the complex RNN's swap pass at 53..100 units
 int crnn_split_swap_stream(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles, int kt16);
 double crnn_split_stream_flops_per_step(rnnwf_handle* h);
 int crnn_split_stream_pack(rnnwf_handle* h, std::vector<char>& simg);

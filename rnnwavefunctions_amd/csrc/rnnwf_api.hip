@@ -91,17 +91,10 @@ size_t rnnwf::state_budget_bytes(const rnnwf_handle* h, size_t dflt) {
 // Returns nullptr, or the offending setting: a value this build does not know is refused (rnnwf_create fails), never ignored.
 static const char* read_knobs(Knobs& k) {
     if (const char* e = getenv("RNNWF_ENGINE")) {
-        k.engine = !strcmp(e, "f32") ? 1 : !strcmp(e, "bf16x3") ? 2 : -1;
-#ifdef RNNWF_DIAGNOSTICS      // measured negatives kept for A/B runs (docs/history): the release library holds one kernel per model and width class
-        if (const char* e2 = getenv("RNNWF_MDRNN_PREFETCH")) k.md_prefetch = !strcmp(e2, "1");
-        if (k.engine < 0) k.engine = !strcmp(e, "bf16x3-serial") ? 3 : !strcmp(e, "bf16x3-hipcc") ? 4 : !strcmp(e, "bf16x3-asm32") ? 5 : !strcmp(e, "bf16x3-n16") ? 7 : -1;
-#endif
+        k.engine = !strcmp(e, "f32") ? 1 : !strcmp(e, "bf16x3") ? 2 : -1;      // one kernel per model and width class: nothing else to select
         if (k.engine < 0 && *e) return "RNNWF_ENGINE (this build knows: f32, bf16x3)";
         if (k.engine < 0) k.engine = 0;
     }
-#ifdef RNNWF_DIAGNOSTICS
-    if (const char* e = getenv("RNNWF_MDRNN_PREFETCH")) k.md_prefetch = !strcmp(e, "1");
-#endif
     if (const char* e = getenv("RNNWF_NO_COOP")) k.no_coop = atoi(e) != 0;
     if (const char* e = getenv("RNNWF_BASE")) k.base_f32 = !strcmp(e, "f32");
     if (const char* e = getenv("RNNWF_STATE_BUDGET_MB")) {

@@ -52,7 +52,7 @@ int read_stamps(rnnwf_handle* h, Launch&& launch, size_t waves, int words, const
 }
 #endif
 
-// ---- bf16x3 engine for the flip pass (f32 models; above 68 units: split_stream.hip) ----------------------
+// ---- bf16x3 engine for the flip pass (f32 models; above 52 units: split_stream.hip) ----------------------
 template <int NF32, int RJ, int WAVES, int MODE>
 struct SLaunch {
     using L = SplitLayout<NF32, RJ, 1, MODE>;
@@ -87,7 +87,7 @@ struct SLaunch {
     static double mfma_flops_per_step() { return (double)L::NT * L::KS * 32768.0; }   // per 32-chain wave-step
 };
 
-// ---- bf16x3 engine for the swap pass (num_units <= 68) ---------------------------------------------------
+// ---- bf16x3 engine for the swap pass (num_units <= 52) ---------------------------------------------------
 template <int NF32, int RJ, int WAVES, int MODE>
 struct CSLaunch {
     using L = SplitLayout<NF32, RJ, 3, MODE>;
@@ -120,24 +120,12 @@ bool with_layout(const rnnwf_handle* h, Fn&& fn) {
             if (h->H <= 50) fn(K<1, 9, 4, 2>());
             else fn(K<1, 10, 4, 0>());
             return true;
-        case 4: fn(K<2, 2, 4, 0>()); return true;
     }
     return false;
 }
 
-
-// widths served by the riders form (split_stream.hip): 53..100 units (53..68: RNNWF_ENGINE=bf16x3-serial selects the padded
-// serial kernel of round 1 instead, for A/B runs: 5.55 against 4.56 ms at N=80, 64 units, 10 000 samples)
-bool riders(const rnnwf_handle* h) { return h->NFULL == 6 || (h->NFULL == 4 && h->knobs.engine != 3); }      // (engine 3: diagnostics builds only)
-// 37..52 units, positive RNN: RNNWF_ENGINE=bf16x3-n16 runs the flip pass in the 16x16x32 riders form (split_stream.hip:
-// prnn_flip_riders16n_asm_kernel) instead of the 32x32x16 ping-pong kernel - built and measured in round 3, 10 % slower
-bool riders16n(const rnnwf_handle* h) {
-#ifdef RNNWF_DIAGNOSTICS
-    return h->NFULL == 3 && h->model != RNNWF_MODEL_CRNN_U1 && h->knobs.engine == 7;
-#else
-    return false;
-#endif
-}
+// widths served by the riders form (split_stream.hip): 53..100 units; every caller of with_layout asks this first
+bool riders(const rnnwf_handle* h) { return h->NFULL == 4 || h->NFULL == 6; }
 
 }  // namespace
 
@@ -324,18 +312,11 @@ int rnnwf::prnn_split_flip(rnnwf_handle* h, const PrnnArgs& a) {
     const int kt16 = 4 * h->NFULL + 1;
     if (riders(h)) return prnn_split_flip_stream(h, a, kt16);
     int rc = 0;
-#ifdef RNNWF_DIAGNOSTICS
-    if (riders16n(h)) return prnn_split_flip_16n(h, a, kt16);
-    if (h->knobs.engine == 3 && with_layout<SLaunch>(h, [&](auto k) { rc = decltype(k)::flip(h, a, kt16); })) return rc;   // RNNWF_ENGINE=bf16x3-serial: A/B only
-#endif
     if (with_layout<SLaunch>(h, [&](auto k) { rc = decltype(k)::flip_pp(h, a, kt16); })) return rc;
     return h->fail(RNNWF_ERR_INVALID, "no bf16x3 kernel for NFULL=%d", h->NFULL);
 }
 double rnnwf::prnn_split_flops_per_step(rnnwf_handle* h) {
     if (riders(h)) return prnn_split_stream_flops_per_step(h);
-#ifdef RNNWF_DIAGNOSTICS
-    if (riders16n(h)) return prnn_split_16n_flops_per_step();
-#endif
     double f = 0;
     with_layout<SLaunch>(h, [&](auto k) { f = decltype(k)::mfma_flops_per_step(); });
     return f;
@@ -344,11 +325,6 @@ double rnnwf::prnn_split_flops_per_step(rnnwf_handle* h) {
 
 int rnnwf::prnn_split_pack(rnnwf_handle* h, std::vector<char>& simg) {
     if (riders(h)) return prnn_split_stream_pack(h, simg);
-#ifdef RNNWF_DIAGNOSTICS
-    if (riders16n(h)) {
-        if (int rc = prnn_split_16n_pack(h)) return rc;
-    }
-#endif
     if (with_layout<SLaunch>(h, [&](auto k) { simg = decltype(k)::pack(h); })) return 0;
     return h->fail(RNNWF_ERR_INVALID, "no bf16x3 layout for NFULL=%d", h->NFULL);
 }
@@ -357,9 +333,6 @@ int rnnwf::crnn_split_swap(rnnwf_handle* h, const CrnnArgs& a, int64_t max_tiles
     const int kt16 = 4 * h->NFULL + 1;
     if (riders(h)) return crnn_split_swap_stream(h, a, max_tiles, kt16);
     int rc = 0;
-#ifdef RNNWF_DIAGNOSTICS
-    if (h->knobs.engine == 3 && with_layout<CSLaunch>(h, [&](auto k) { rc = decltype(k)::swap(h, a, max_tiles, kt16); })) return rc;   // RNNWF_ENGINE=bf16x3-serial: A/B only
-#endif
     if (with_layout<CSLaunch>(h, [&](auto k) { rc = decltype(k)::swap_pp(h, a, max_tiles, kt16); })) return rc;
     return h->fail(RNNWF_ERR_INVALID, "no bf16x3 cRNN kernel for NFULL=%d", h->NFULL);
 }

@@ -445,9 +445,9 @@ def test_both_flip_engines_agree_with_the_f64_oracle(N, H, ns, monkeypatch):
 
 
 def test_release_library_refuses_engine_switches_it_does_not_hold(monkeypatch):
-    """The measured negatives of rounds 1-3 (RNNWF_ENGINE=bf16x3-serial / -hipcc / -asm32 / -n16, RNNWF_MDRNN_PREFETCH) live in the
-    -DRNNWF_DIAGNOSTICS build of tools/ only; the release library holds one kernel per model and width class and refuses a
-    value it does not know instead of silently running something else."""
+    """The measured negatives of rounds 1-3 (four alternative bf16x3 engines and the 2D RNN's prefetching flip kernel, once selected
+    through the values below) are gone from every build; the library holds one kernel per model and width class and
+    refuses a value it does not know instead of silently running something else."""
     from rnnwavefunctions_amd import _lib
     for bad in ("bf16x3-n16", "bf16x3-serial", "bf16x3-hipcc", "bf16x3-asm32", "fp8"):
         monkeypatch.setenv("RNNWF_ENGINE", bad)

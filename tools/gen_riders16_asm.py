@@ -2,8 +2,12 @@
 """Generates rnnwavefunctions_amd/csrc/split_riders16_asm.h: the whole wave-step of the bf16x3 flip pass at 69..100 units on
 v_mfma_f32_16x16x32_bf16 (csrc/split16_core.h explains the layout) as ONE hand-scheduled inline-asm block.
 
-Same machinery as tools/gen_riders_asm.py (the 32x32x16 form: emission with hazard padding, counted waits, fragment rings, rider
-streams list-scheduled into the slots behind the MFMAs); what differs is the shape: 19 tiles of 16 rows x 19 k-steps x 2 chain sets =
+Why by hand: one wave per SIMD leaves only the issue cycles between its own MFMAs for ~1 000 VALU / transcendental instructions, the
+fragment reads (LDS) and loads (L2) and their waits; they fit only if the riders are spread evenly and never wait on each other.
+Everything is static, decided here: the MFMA order (block 0 k-major - the state parts h2 / h3 appear while it runs - then tile by
+tile), every register, two A-fragment rings in AGPRs (LDS-fed and streamed) with counted waits, and the rider streams (split, gate
+batches stage by stage over eight units) list-scheduled into the slots behind the MFMAs under an issue-cycle budget, subject to
+readiness.  tools/riders_asm_lib.py emits with hazard padding.  The shape: 19 tiles of 16 rows x 19 k-steps x 2 chain sets =
 722 MFMAs of 16 cycles, every A fragment read once for both sets, the state of set X in v(64 + 25 X) .. and the operand quads per set.
 
 Register map:
@@ -17,14 +21,12 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import gen_riders_asm as G   # noqa: E402
-from gen_riders_asm import Ins, valu, trans, V, A, VQ, AQ   # noqa: E402
+from riders_asm_lib import Emitter, Ins, valu, trans, V, A, VQ, AQ, ORD5, MFMA_ISSUE   # noqa: E402
 
 NT, NOCT, NJ, NJA = 19, 3, 25, 24
 KS = 6 * NOCT + 1
 LDS_REG = NT * 2 * NOCT * 1024
 XCP = 28
-ORD5 = G.ORD5
 RING_L = int(os.environ.get("RIDERS_RING_L", "10"))       # quads; the two rings share a152..a255 (26 quads)
 RING_S = int(os.environ.get("RIDERS_RING_S", "14"))
 assert RING_L + RING_S <= 26
@@ -49,9 +51,9 @@ def aringL(r): return 152 + 4 * r
 def aringS(r): return 152 + 4 * RING_L + 4 * r
 
 
-class Step16(G.Step):
+class Step16(Emitter):
     def __init__(self, order23="tile", budget=10):
-        G.Step.__init__(self, 1, order23, budget)
+        Emitter.__init__(self, order23, budget)
         self.L = layout()
 
     def lds_frag_addr(self, t, kind, idx):
@@ -295,7 +297,7 @@ class Step16(G.Step):
                 areg = aringS(spos[f] % RING_S) if k[0] == "S" else aringL(lpos[f] % RING_L)
                 d = aacc(t, X, 0)
                 mf = Ins("v_mfma_f32_16x16x32_bf16 a[%d:%d], %s, %s, a[%d:%d]" % (d, d + 3, AQ(areg), VQ(bq), d, d + 3),
-                         G.MFMA_ISSUE, ["v%d" % (bq + n) for n in range(4)], (), "mfma")
+                         MFMA_ISSUE, ["v%d" % (bq + n) for n in range(4)], (), "mfma")
                 if X == 0:
                     if k[0] == "S":
                         mf.vm_need = ("S", spos[f])

@@ -1,11 +1,11 @@
-# usage (GPU box, repo root): bash tools/refresh_cfg5.sh  -> full GPU suite, config-5 bench lines of the three step variants (default 16x16x32 asm,
-# RNNWF_ENGINE=bf16x3-asm32, bf16x3-hipcc; written to $OUT_DIR, default bench_out/), FETCH_SIZE / WRITE_SIZE passes and rocprofv3 stats of the default kernel
+# usage (GPU box, repo root): bash tools/refresh_cfg5.sh  -> full GPU suite, the config-5 bench line of the default engine (the 16x16x32 asm step;
+# written to $OUT_DIR, default bench_out/), FETCH_SIZE / WRITE_SIZE passes and rocprofv3 stats of the default kernel
 timeout -k 10 700 python -m pytest tests -m gpu -q -x > gpurun_out/r03_n_tests.log 2>&1; echo "tests rc=$?"; tail -5 gpurun_out/r03_n_tests.log
 O=${OUT_DIR:-bench_out}; mkdir -p $O          # the config-5 bench lines (--full: they carry the parity leg)
-for e in default bf16x3-asm32 bf16x3-hipcc; do if [ $e = default ]; then unset RNNWF_ENGINE; else export RNNWF_ENGINE=$e; fi; timeout -k 10 200 python bench.py --full --workload cfg5 --steps 5 --warmup 2 --no-cpu-baseline --no-alt-engine > $O/cfg5_$e.json 2> $O/cfg5_$e.err; python -c "
+e=default; unset RNNWF_ENGINE; timeout -k 10 200 python bench.py --full --workload cfg5 --steps 5 --warmup 2 --no-cpu-baseline --no-alt-engine > $O/cfg5_$e.json 2> $O/cfg5_$e.err; python -c "
 import json
 d=json.load(open('$O/cfg5_$e.json')); print('$e', d['value'], d['ms_per_step'], d['roofline']['kernel'], d['roofline']['avg_launch_ms'], d['roofline']['frac'], d['roofline']['mfma_issue_frac'], d['parity']['max_abs_dE_per_site'])
-"; done; unset RNNWF_ENGINE
+"
 R=$GRAFT_REPO_ROOT; cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/gpurun_out/r03_n_pmc_cfg5_$c -- python3 $R/bench.py --workload cfg5 --steps 3 --warmup 1 --no-cpu-baseline --no-alt-engine --no-parity > $R/gpurun_out/r03_n_pmc_cfg5_$c.log 2>&1; done
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/r03_n_prof_cfg5 -- python3 $R/bench.py --workload cfg5 --steps 4 --warmup 2 --train 3 --no-cpu-baseline --no-alt-engine --no-parity > $R/gpurun_out/r03_n_prof_cfg5.log 2>&1
