@@ -157,7 +157,8 @@ def test_run_1dtfim_reaches_the_exact_ground_state_energy():
     ("tfim", dict(systemsize=8, num_units=10, numsamples=100, learningrate=5e-3, num_layers=3, parity_symmetric=True)),
     ("j1j2", dict(systemsize=10, num_units=10, numsamples=200, learningrate=5e-4, J2_=0.2, num_layers=2)),
     ("j1j2", dict(systemsize=24, num_units=44, numsamples=2000, learningrate=5e-4, J2_=0.5, num_layers=2)),
-    # the float64 GRU on the 2D lattice (2DTFIM_1DRNN), whose driver adapts the learning rate every iteration
+    # the float64 GRU on the 2D lattice (2DTFIM_1DRNN), whose driver adapts the learning rate every iteration.  20 and 10 units are
+    # BOTH width class NFULL 1 (<= 20 units): the float64 rows above it are test_gpu_train_images.py's
     ("2d1d", dict(systemsize_x=3, systemsize_y=3, num_units=20, numsamples=100, learningrate=1e-3)),
     ("2d1d", dict(systemsize_x=4, systemsize_y=3, num_units=10, numsamples=100, learningrate=1e-3, num_layers=2)),
     # the 2D RNN (2DTFIM_2DRNN): 2 + 2 padded units of the 4-unit remainder tile, a full tile, the driver's 50 units
