@@ -449,6 +449,24 @@ int rnnwf_sr_solve(rnnwf_handle* h, double diag_shift, double* y);
 int rnnwf_sr_direction(rnnwf_handle* h, double diag_shift, double* out_direction);
 /* samples of the resident batch (what sizes the five calls above), 0 without one */
 int64_t rnnwf_resident_samples(const rnnwf_handle* h);
+/* rnnwf_sr_train_steps: K whole minSR iterations (1 <= K <= 1024) with ONE host synchronisation, the counterpart of rnnwf_train_steps.
+ * Iteration k = 0 .. K-1, all on the handle's stream: the fused VMC step of numsamples samples drawn with step index step0 + k (its
+ * moments into row k of `moments`, [K][4] as rnnwf_vmc_step returns them); the Jacobian, the Gram matrix, the Cholesky solve with
+ * diag_shifts[k] and dO^T y exactly as rnnwf_sr_direction runs them; theta_i <- theta_i - learning_rates[k] delta_i on the flat float64
+ * parameters of the device (the product and the difference each rounded once, then rounded to float32 for GRU1D: the arithmetic of
+ * rnnwavefunctions_amd/sr.py's train_tfim, so the trajectory equals that host loop's bit for bit); every weight image rebuilt on the device.
+ * Afterwards, as after rnnwf_train_steps: no batch is resident, rnnwf_get_param and rnnwf_commit_params see the device's parameters,
+ * Adam's moments and step count are untouched.
+ * Refused before anything is launched or changed, leaving parameters, resident batch and Jacobian as they were: RNNWF_ERR_INVALID
+ * "rnnwf_sr_train_steps: <why>" for the handles of the list above, bad arguments (K, numsamples < 1, a null pointer), the wrong number of
+ * couplings, a diag_shifts[k] that is not positive and finite, a learning_rates[k] that is not finite; RNNWF_ERR_STATE for uncommitted
+ * parameters; RNNWF_ERR_NOMEM "... ns too large for the SR workspace" for numsamples (the factor counted).
+ * A pivot that is not positive and finite in iteration k: that iteration's update and all later ones are not stored (theta stays what it
+ * was before iteration k, the later iterations sample it again), `moments` is filled for all K rows, and the call returns
+ * RNNWF_ERR_NUMERIC "rnnwf_sr_train_steps: iteration <k>: pivot <index> ... (diag_shift ..., ... samples)" after its synchronisation.  */
+int rnnwf_sr_train_steps(rnnwf_handle* h, int32_t K, int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset,
+                         const double* couplings, int64_t n_couplings, const double* learning_rates, const double* diag_shifts,
+                         double* moments);
 
 /* ---- multi-GPU: one RCCL all-reduce of the energy moments -------------------------------------
  * The reference is single-process; these add the one data-parallel collective of SURVEY.md 8e.

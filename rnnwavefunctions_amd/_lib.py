@@ -84,6 +84,7 @@ PROTOTYPES = {
     "rnnwf_sr_apply": (C.c_int, [_P, _F64P, _F64P]),
     "rnnwf_sr_solve": (C.c_int, [_P, _F64, _F64P]),
     "rnnwf_sr_direction": (C.c_int, [_P, _F64, _F64P]),
+    "rnnwf_sr_train_steps": (C.c_int, [_P, _I32, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _I64, _F64P, _F64P, _F64P]),
     "rnnwf_resident_samples": (_I64, [_P]),
     "rnnwf_timing_enable": (C.c_int, [_P, _I32]),
     "rnnwf_timing_reset": (C.c_int, [_P]),
@@ -398,6 +399,19 @@ class NativeWavefunction:
         out = np.empty(self.num_params(), dtype=np.float64)
         self._check(self.lib.rnnwf_sr_direction(self.h, float(diag_shift), out.ctypes.data_as(_F64P)))
         return out
+
+    def sr_train_steps(self, K, numsamples, seed, step0, couplings, learning_rates, diag_shifts, sample_offset=0):
+        """K whole minSR iterations (sample, local energies, Jacobian, Gram matrix, solve, theta -= lr delta, re-pack of the weight
+        images) on the device with one host synchronisation (rnnwf_sr_train_steps); iteration k draws with step index step0 + k.
+        learning_rates and diag_shifts: one value per iteration, or a scalar for all K.  Returns the (K, 4) moments of the K batches."""
+        K = int(K)
+        c, cp = _f64(couplings)
+        lr, lrp = _f64(np.broadcast_to(np.asarray(learning_rates, dtype=np.float64), (max(K, 0),)))
+        lam, lamp = _f64(np.broadcast_to(np.asarray(diag_shifts, dtype=np.float64), (max(K, 0),)))
+        mom = np.empty((max(K, 0), 4), dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_train_steps(self.h, K, int(numsamples), seed, step0, sample_offset, cp, c.size, lrp, lamp,
+                                                  mom.ctypes.data_as(_F64P)))
+        return mom
 
     # -- device-resident training iteration (rnnwf_train_steps; single-layer float32 GRU models) ------------------
     def device_training_supported(self):

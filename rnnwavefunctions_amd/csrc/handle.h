@@ -141,8 +141,9 @@ struct rnnwf_handle {
     rnnwf::DevBuf renyi;          // rnnwf_renyi2_swap, rnnwf_renyi2_regions, rnnwf_pauli_step: tables, per-site terms, tails, log-ratios and partial sums of one pass
     // stochastic reconfiguration (sr.hip): the per-sample log-derivatives J[sr_ns][D] in image order, the chains' head rows, how many
     // parameters read each image element, column sums [mean | J^T y], the centred Gram matrix, the weights y, and the workspace of the
-    // device solve: [ns][ns] Cholesky factor | eps row [ns] | y [ns] | pivot status word | diagonal blocks (sr_solve_kernels.h)
-    rnnwf::DevBuf srJ, srHead, srMask, srCol, srGram, srY, srFac;
+    // device solve: [ns][ns] Cholesky factor | eps row [ns] | y [ns] | pivot status word | diagonal blocks (sr_solve_kernels.h);
+    // srStat: rnnwf_sr_train_steps' pivot status of one call, [0] sticky (1 + the first iteration with a bad pivot), [1 + k] iteration k's word
+    rnnwf::DevBuf srJ, srHead, srMask, srCol, srGram, srY, srFac, srStat;
     bool sr_valid = false;        // srJ belongs to the resident batch and the committed parameters (cleared where either changes)
     int64_t sr_ns = 0;
     std::vector<int32_t> sr_sidx; // grad_flat_probe's table, probed once

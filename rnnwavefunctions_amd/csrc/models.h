@@ -78,6 +78,8 @@ const Gradient* gru_gradient();   // grad.hip: the GRU hooks of gru_family and c
 // the fused VMC step behind rnnwf_vmc_step and rnnwf_train_steps (rnnwf_api.hip); out_samples, out_eloc, moments may be nullptr
 int vmc_step(rnnwf_handle* h, int64_t ns, const Draw& draw, const double* couplings, int32_t* out_samples, void* out_eloc,
              double* moments);
+// RNNWF_ERR_NOMEM "<what>: ... exceed the state budget of one pass" where vmc_step would refuse ns samples (rnnwf_api.hip)
+int refuse_past_budget(rnnwf_handle* h, int64_t ns, const char* what);
 // the batch just computed stays on the device (h->bits, h->hck, h->eloc) for rnnwf_vmc_gradient (rnnwf_api.hip): h->last_ns and
 // h->sr_valid change together.  ns = 0: no batch is resident
 void keep_resident(rnnwf_handle* h, int64_t ns);
@@ -153,6 +155,10 @@ int grad_stack_forward_table(rnnwf_handle* h);
 void train_params_changed_on_host(rnnwf_handle* h);           // rnnwf_set_param / rnnwf_commit_params: the device copy is stale
 int train_sync_params_to_host(rnnwf_handle* h);               // before the host reads its copy (rnnwf_get_param, checkpoints)
 int train_allreduce_grads_device(rnnwf_handle* h);           // 1: gradient all-reduced in-stream on the device, 0: not available
+// for rnnwf_sr_train_steps (sr.hip), whose iterations update the same flat parameters and re-pack the same images:
+int train_prepare(rnnwf_handle* h);                          // the tables built and the flat parameters current on the device
+// theta_i <- round_T(theta_i - lr (+-col[|gidx_i| - 1])) unless *hold != 0 (both on the device), then the re-pack of every image
+int train_apply_direction(rnnwf_handle* h, const double* col, size_t col_count, double lr, const long long* hold);
 void grad_invalidate(rnnwf_handle* h);
 // bytes of per-site hidden states one pass may hold; RNNWF_STATE_BUDGET_MB (read at rnnwf_create) overrides the
 // default (tests use it to drive the multi-pass path at small sizes)

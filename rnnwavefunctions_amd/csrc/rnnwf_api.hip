@@ -251,7 +251,7 @@ extern "C" int rnnwf_destroy(rnnwf_handle* h) {
                       &h->train.P, &h->train.M, &h->train.V, &h->train.G, &h->train.gidx, &h->train.img[0].table, &h->train.img[1].table,
                       &h->train.img[2].table, &h->train.img[3].table, &h->train.img[4].table, &h->train.img[5].table, &h->train.img[6].table,
                       &h->train.img[7].table, &h->train.combo,
-                      &h->srJ, &h->srHead, &h->srMask, &h->srCol, &h->srGram, &h->srY, &h->srFac};
+                      &h->srJ, &h->srHead, &h->srMask, &h->srCol, &h->srGram, &h->srY, &h->srFac, &h->srStat};
     static_assert(RNNWF_MAX_LAYERS == 4, "wsplit_up has RNNWF_MAX_LAYERS - 1 entries");
     for (DevBuf* b : bufs) free_buf(*b);
     for (auto& t : h->timers) {
@@ -535,7 +535,7 @@ void rnnwf::keep_resident(rnnwf_handle* h, int64_t ns) {
     h->sr_valid = false;          // a new batch: its log-derivatives are not built yet (sr.hip)
 }
 
-static int refuse_past_budget(rnnwf_handle* h, int64_t ns, const char* what) {
+int rnnwf::refuse_past_budget(rnnwf_handle* h, int64_t ns, const char* what) {
     if (ns <= h->family->max_chains_per_pass(h)) return 0;
     return h->fail(RNNWF_ERR_NOMEM, "%s: %lld samples exceed the state budget of one pass; split the batch", what, (long long)ns);
 }

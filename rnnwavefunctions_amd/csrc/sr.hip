@@ -1,5 +1,6 @@
 // sr.hip - stochastic reconfiguration (docs/sr.md): rnnwf_log_derivatives, rnnwf_sr_gram, rnnwf_sr_apply, rnnwf_sr_solve,
-// rnnwf_sr_direction on the resident batch of the one-layer positive GRU (GRU1D, GRU1D_F64; up to 68 units).  The per-sample
+// rnnwf_sr_direction on the resident batch of the one-layer positive GRU (GRU1D, GRU1D_F64; up to 68 units), and rnnwf_sr_train_steps,
+// K whole minSR iterations on batches it draws itself (the update and the images' re-pack are train.hip's).  The per-sample
 // log-derivatives J[ns][D] stay on the device in the order of the gradient image (grad.hip) and are read through the table
 // grad_flat_probe builds; the ns x ns solve is the caller's (rnnwf_sr_gram + rnnwf_sr_apply) or the device's (rnnwf_sr_solve,
 // rnnwf_sr_direction: blocked f64 Cholesky, sr_solve_kernels.h).
@@ -16,6 +17,7 @@ using namespace rnnwf;
 namespace {
 
 constexpr int64_t kSrMaxSamples = 4096;
+constexpr int kSrMaxSteps = 1024;          // iterations of one rnnwf_sr_train_steps call: the rows of train.hip's pinned moments table (kMaxSteps)
 
 // 0, or RNNWF_ERR_INVALID "<entry>: <why>" for a handle these entry points do not serve; called before anything is touched
 int sr_refuse(rnnwf_handle* h, const char* entry) {
@@ -51,12 +53,8 @@ int64_t sr_image_size(rnnwf_handle* h) {
     return D;
 }
 
-// refusals, then the state checks every entry point shares; `factor`: the entry also holds the ns x ns Cholesky factor
-int sr_ready(rnnwf_handle* h, const char* entry, bool factor = false) {
-    if (int rc = sr_refuse(h, entry)) return rc;
-    if (!h->committed) return h->fail(RNNWF_ERR_STATE, "%s: parameters not committed (call rnnwf_commit_params)", entry);
-    if (h->last_ns <= 0) return h->fail(RNNWF_ERR_STATE, "%s: call rnnwf_vmc_step first (its samples, states and E_loc are reused)", entry);
-    const int64_t ns = h->last_ns;
+// RNNWF_ERR_NOMEM unless the workspace of a batch of ns samples fits; `factor`: with the ns x ns Cholesky factor
+int sr_workspace(rnnwf_handle* h, const char* entry, int64_t ns, bool factor) {
     const size_t es = h->f64 ? 8 : 4;
     // the factor's workspace: ns^2 doubles, eps, y, the status word and the diagonal blocks (sr_solve_device), all counted
     const size_t nb = (size_t)(ns + kSrNB - 1) / kSrNB;
@@ -65,6 +63,19 @@ int sr_ready(rnnwf_handle* h, const char* entry, bool factor = false) {
     if (ns > kSrMaxSamples || need > state_budget_bytes(h, kDefaultStateBudget))
         return h->fail(RNNWF_ERR_NOMEM, "%s: ns too large for the SR workspace (%lld samples: Jacobian + Gram matrix%s take %zu bytes; at most %lld samples)",
                        entry, (long long)ns, factor ? " + Cholesky factor" : "", need, (long long)kSrMaxSamples);
+    return 0;
+}
+
+int sr_committed(rnnwf_handle* h, const char* entry) {
+    return h->committed ? 0 : h->fail(RNNWF_ERR_STATE, "%s: parameters not committed (call rnnwf_commit_params)", entry);
+}
+
+// refusals, then the state checks every entry point on the resident batch shares; `factor`: the entry also holds the ns x ns Cholesky factor
+int sr_ready(rnnwf_handle* h, const char* entry, bool factor = false) {
+    if (int rc = sr_refuse(h, entry)) return rc;
+    if (int rc = sr_committed(h, entry)) return rc;
+    if (h->last_ns <= 0) return h->fail(RNNWF_ERR_STATE, "%s: call rnnwf_vmc_step first (its samples, states and E_loc are reused)", entry);
+    if (int rc = sr_workspace(h, entry, h->last_ns, factor)) return rc;
     RNNWF_HIP(h, hipSetDevice(h->cfg.device));
     return 0;
 }
@@ -168,13 +179,43 @@ int sr_solve_device(rnnwf_handle* h, double diag_shift) {
     return 0;
 }
 
-// the checks and the device work both solving entries share, up to y on the device
-int sr_solve_common(rnnwf_handle* h, const char* entry, double diag_shift) {
+int sr_check_shift(rnnwf_handle* h, const char* entry, double diag_shift) {
     if (!(diag_shift > 0.0) || !std::isfinite(diag_shift)) return h->fail(RNNWF_ERR_INVALID, "%s: diag_shift must be positive and finite", entry);
-    if (int rc = sr_ready(h, entry, true)) return rc;
+    return 0;
+}
+
+// the device work the solving entries share once their checks have passed, up to y on the device
+int sr_solve_queue(rnnwf_handle* h, double diag_shift) {
     if (int rc = sr_build(h)) return rc;
     if (int rc = sr_gram_device(h)) return rc;
     return sr_solve_device(h, diag_shift);
+}
+
+int sr_solve_common(rnnwf_handle* h, const char* entry, double diag_shift) {
+    if (int rc = sr_check_shift(h, entry, diag_shift)) return rc;
+    if (int rc = sr_ready(h, entry, true)) return rc;
+    return sr_solve_queue(h, diag_shift);
+}
+
+// behind sr_solve_queue: dO^T y = J^T (y - mean y), as rnnwf_sr_apply, with the centring on the device; the direction's image is
+// left in sr_direction_image(h), nothing is synchronised
+double* sr_direction_image(rnnwf_handle* h) { return (double*)h->srCol.p + sr_image_size(h); }
+
+int sr_direction_queue(rnnwf_handle* h) {
+    const int64_t ns = h->sr_ns, D = sr_image_size(h);
+    if (int rc = ensure(h, h->srY, (size_t)ns * 8)) return rc;
+    if (int rc = timed_launch(h, kTimerGemm, sr_centre_kernel, 1, 256, 0, (const double*)sr_y(h), ns, (double*)h->srY.p, (long long*)nullptr)) return rc;
+    double* col = sr_direction_image(h);
+    return h->f64 ? sr_colsum<double>(h, D, (const double*)h->srY.p, 1.0, col) : sr_colsum<float>(h, D, (const double*)h->srY.p, 1.0, col);
+}
+
+// rnnwf_sr_train_steps: iteration k's pivot status word into its slot of the call's table, and into the sticky word when that is
+// still clear (sr_centre_kernel clears the solve's own word at the start of every iteration)
+__global__ void sr_record_status_kernel(const long long* __restrict__ status, int k, long long* __restrict__ table) {
+    if (blockIdx.x || threadIdx.x) return;
+    const long long s = *status;
+    table[1 + k] = s;
+    if (s && !table[0]) table[0] = k + 1;
 }
 
 int sr_pivot_error(rnnwf_handle* h, const char* entry, long long status, double diag_shift) {
@@ -273,12 +314,9 @@ extern "C" int rnnwf_sr_direction(rnnwf_handle* h, double diag_shift, double* ou
     if (!h) return RNNWF_ERR_INVALID;
     if (!out_direction) return h->fail(RNNWF_ERR_INVALID, "rnnwf_sr_direction: bad arguments");
     if (int rc = sr_solve_common(h, "rnnwf_sr_direction", diag_shift)) return rc;
-    const int64_t ns = h->sr_ns, D = sr_image_size(h);
-    // dO^T y = J^T (y - mean y), as rnnwf_sr_apply, with the centring on the device
-    if (int rc = ensure(h, h->srY, (size_t)ns * 8)) return rc;
-    if (int rc = timed_launch(h, kTimerGemm, sr_centre_kernel, 1, 256, 0, (const double*)sr_y(h), ns, (double*)h->srY.p, (long long*)nullptr)) return rc;
-    double* col = (double*)h->srCol.p + D;
-    if (int rc = h->f64 ? sr_colsum<double>(h, D, (const double*)h->srY.p, 1.0, col) : sr_colsum<float>(h, D, (const double*)h->srY.p, 1.0, col)) return rc;
+    if (int rc = sr_direction_queue(h)) return rc;
+    const int64_t D = sr_image_size(h);
+    const double* col = sr_direction_image(h);
     if (int rc = ensure_staging(h, (size_t)(D + 1) * 8)) return rc;
     RNNWF_HIP(h, hipMemcpyAsync(h->staging, col, (size_t)D * 8, hipMemcpyDeviceToHost, h->stream));
     RNNWF_HIP(h, hipMemcpyAsync((double*)h->staging + D, sr_status(h), 8, hipMemcpyDeviceToHost, h->stream));
@@ -286,5 +324,62 @@ extern "C" int rnnwf_sr_direction(rnnwf_handle* h, double diag_shift, double* ou
     const long long status = ((const long long*)h->staging)[D];
     if (status) return sr_pivot_error(h, "rnnwf_sr_direction", status, diag_shift);
     sr_gather(h->sr_sidx, (const double*)h->staging, out_direction);
+    return RNNWF_OK;
+}
+
+// K whole minSR iterations with one host synchronisation (docs/sr.md, "Iterations on the device"): per iteration the fused VMC step,
+// the Jacobian, the Gram matrix, the solve with diag_shifts[k] and dO^T y as rnnwf_sr_direction queues them, then train.hip's update
+// theta <- theta - learning_rates[k] delta on the flat device parameters and the re-pack of every weight image.  The iteration's
+// moments go to row k of train.hip's pinned table, its pivot status to h->srStat; from a bad pivot on nothing more is stored.
+extern "C" int rnnwf_sr_train_steps(rnnwf_handle* h, int32_t K, int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset,
+                                    const double* couplings, int64_t n_couplings, const double* learning_rates, const double* diag_shifts,
+                                    double* moments) {
+    if (!h) return RNNWF_ERR_INVALID;
+    const char* entry = "rnnwf_sr_train_steps";
+    if (int rc = sr_refuse(h, entry)) return rc;
+    if (int rc = sr_committed(h, entry)) return rc;
+    if (K < 1 || K > kSrMaxSteps || numsamples < 1 || !couplings || !learning_rates || !diag_shifts || !moments)
+        return h->fail(RNNWF_ERR_INVALID, "%s: bad arguments (1 <= K <= %d)", entry, kSrMaxSteps);
+    if (n_couplings != (int64_t)h->family->coupl_per_site * h->N + h->family->coupl_tail)
+        return h->fail(RNNWF_ERR_INVALID, "%s: wrong number of couplings", entry);
+    for (int k = 0; k < K; ++k) {
+        if (int rc = sr_check_shift(h, entry, diag_shifts[k])) return rc;
+        if (!std::isfinite(learning_rates[k])) return h->fail(RNNWF_ERR_INVALID, "%s: learning_rate must be finite", entry);
+    }
+    if (int rc = sr_workspace(h, entry, numsamples, true)) return rc;
+    if (int rc = refuse_past_budget(h, numsamples, entry)) return rc;
+    // nothing was touched so far: a refused call leaves the parameters, the resident batch and its Jacobian as they were
+    RNNWF_HIP(h, hipSetDevice(h->cfg.device));
+    if (int rc = train_prepare(h)) return rc;
+    const int64_t D = sr_image_size(h);
+    if (int rc = sr_table(h, D)) return rc;                 // (its check: the flat table train.hip applies the direction through reads an image of D elements)
+    if (int rc = ensure(h, h->srStat, (size_t)(kSrMaxSteps + 1) * 8)) return rc;
+    if (int rc = ensure_staging(h, (size_t)(kSrMaxSteps + 1) * 8)) return rc;
+    long long* stat = (long long*)h->srStat.p;
+    RNNWF_HIP(h, hipMemsetAsync(stat, 0, (size_t)(K + 1) * 8, h->stream));
+    int rc = 0;
+    for (int k = 0; k < K && !rc; ++k) {
+        h->moments_direct = (double*)h->train.mom_host_dev + 4 * k;      // as rnnwf_train_steps: the moments kernel writes the pinned row itself
+        rc = vmc_step(h, numsamples, Draw{seed, step0 + (uint64_t)k, sample_offset}, couplings, nullptr, nullptr, nullptr);
+        h->moments_direct = nullptr;
+        if (!rc) rc = sr_solve_queue(h, diag_shifts[k]);
+        if (!rc) rc = timed_launch(h, kTimerGemm, sr_record_status_kernel, 1, 64, 0, (const long long*)sr_status(h), k, stat);
+        if (!rc) rc = sr_direction_queue(h);
+        if (!rc) rc = train_apply_direction(h, sr_direction_image(h), (size_t)D, learning_rates[k], stat);
+        h->sr_valid = false;                                               // the Jacobian belongs to the parameters before the update
+    }
+    if (!rc && hipMemcpyAsync(h->staging, stat, (size_t)(K + 1) * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+        rc = h->fail(RNNWF_ERR_HIP, "%s: status download failed", entry);
+    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = h->fail(RNNWF_ERR_HIP, "%s: stream synchronisation failed", entry);
+    h->last_ns = 0;                       // the resident batch belongs to the weights before the last update
+    if (rc) return rc;
+    memcpy(moments, h->train.mom_host, (size_t)K * 4 * sizeof(double));
+    const long long* st = (const long long*)h->staging;
+    if (st[0]) {
+        const int k = (int)st[0] - 1;
+        char where[64];
+        snprintf(where, sizeof where, "%s: iteration %d", entry, k);
+        return sr_pivot_error(h, where, st[1 + k], diag_shifts[k]);
+    }
     return RNNWF_OK;
 }

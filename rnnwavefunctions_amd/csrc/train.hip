@@ -14,6 +14,8 @@
 // The arithmetic is the host path's, operation for operation (IEEE f64, no contraction), so a trajectory equals the host-Adam
 // one bit for bit (tests/test_gpu_training.py).  Supported: every model of the four drivers - the positive, parity-symmetric, complex
 // and float64 GRU with one layer or a stack, and the 2D RNN (rnnwf_device_training_supported answers for a handle).
+// Stochastic reconfiguration's iterations (sr.hip: rnnwf_sr_train_steps) run on the same state: train_prepare, then per iteration
+// train_apply_direction (apply_direction_kernel in place of adam_kernel, the same re-pack).
 #include <cmath>
 
 #include "models.h"
@@ -94,6 +96,19 @@ __global__ void adam_kernel(double* __restrict__ P, double* __restrict__ M, doub
     M[i] = m;
     V[i] = v;
     const double p = __dsub_rn(P[i], __ddiv_rn(__dmul_rn(lr_t, m), __dadd_rn(__dsqrt_rn(v), eps)));
+    P[i] = f32 ? (double)(float)p : p;
+}
+
+// sr.py: train_tfim - theta = (theta - learningrate * delta).astype(dtype), delta the minSR direction gathered from its image `col`
+// through the table of the flat gradient (sr.hip: sr_gather).  *hold != 0 (an earlier pivot of this call failed): nothing is stored
+__global__ void apply_direction_kernel(double* __restrict__ P, int64_t n, const int32_t* __restrict__ sidx, const double* __restrict__ col,
+                                       double lr, int f32, const long long* __restrict__ hold) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || *hold) return;
+    const int32_t k = sidx[i];
+    const double d = k > 0 ? col[k - 1] : k < 0 ? -col[-k - 1] : 0.0;
+    const double p = __dsub_rn(P[i], __dmul_rn(lr, d));       // two roundings, as NumPy's (adam_kernel's note)
     P[i] = f32 ? (double)(float)p : p;
 }
 
@@ -274,6 +289,8 @@ int ensure_combo(rnnwf_handle* h) {
     return 0;
 }
 
+int launch_repack(rnnwf_handle* h);
+
 int launch_update(rnnwf_handle* h, double lr_t, double b1, double b2, double eps) {
     TrainState& t = h->train;
     const unsigned blocks = (unsigned)((t.nparams + 255) / 256);
@@ -293,6 +310,12 @@ int launch_update(rnnwf_handle* h, double lr_t, double b1, double b2, double eps
                                                                 eps, f32, (const int32_t*)t.gidx.p, (const float*)h->gradW.p);
     }
     RNNWF_HIP(h, hipGetLastError());
+    return launch_repack(h);
+}
+
+// every weight image rebuilt from the flat parameters, one launch
+int launch_repack(rnnwf_handle* h) {
+    TrainState& t = h->train;
     if (int rc = ensure_combo(h)) return rc;
     RepackPlan plan{};
     plan.nimg = t.nimg;
@@ -340,6 +363,24 @@ int rnnwf::train_allreduce_grads_device(rnnwf_handle* h) {
         off += (int64_t)kv.second.slot.size();
     }
     return 1;
+}
+
+int rnnwf::train_prepare(rnnwf_handle* h) {
+    if (int rc = build(h)) return rc;
+    return params_to_device(h);
+}
+
+// One minSR update from the direction's image `col` (col_count doubles on the device, the order of the dW image) and the images'
+// re-pack, queued on the stream; the backward image must have been packed once (its table is added here on first use)
+int rnnwf::train_apply_direction(rnnwf_handle* h, const double* col, size_t col_count, double lr, const long long* hold) {
+    TrainState& t = h->train;
+    if (!t.supported || t.host_newer) return h->fail(RNNWF_ERR_STATE, "device training: train_apply_direction without train_prepare");
+    if (col_count != t.dw_count) return h->fail(RNNWF_ERR_STATE, "device training: direction image of %zu elements, the gradient's has %zu", col_count, t.dw_count);
+    if (int rc = ensure_bwd_image(h)) return rc;
+    apply_direction_kernel<<<(unsigned)((t.nparams + 255) / 256), 256, 0, h->stream>>>((double*)t.P.p, t.nparams, (const int32_t*)t.gidx.p, col, lr,
+                                                                                      h->f64 ? 0 : 1, hold);
+    RNNWF_HIP(h, hipGetLastError());
+    return launch_repack(h);
 }
 
 void rnnwf::train_params_changed_on_host(rnnwf_handle* h) {

@@ -73,13 +73,25 @@ def unflatten_params(wf, flat, like, scope="RNNwavefunction"):
     return out
 
 
+def _check_device_steps(device_steps):
+    if device_steps is None:
+        return None
+    if isinstance(device_steps, bool) or not isinstance(device_steps, (int, np.integer)) or device_steps < 1:
+        raise ValueError("device_steps must be None or an integer >= 1, got %r" % (device_steps,))
+    return int(device_steps)
+
+
 def train_tfim(wf, Jz, Bx, params, numsteps=100, numsamples=500, learningrate=1e-2, diag_shift=1e-3, seed=111, scope="RNNwavefunction",
-               solver="host"):
+               solver="host", device_steps=None):
     """Minimise the 1D / raster TFIM energy of `wf` (a NativeWavefunction of GRU1D or GRU1D_F64 with one layer, holding `params`)
     by minSR: vmc_step (samples, local energies, moments; the batch stays resident) -> minsr_direction -> theta -= lr delta ->
     set_params_flat.  Returns (meanEnergy, varEnergy), one entry per iteration 0..numsteps like training.minimize_hamiltonian; the
     trained parameters are left in train_tfim.last_params.  The parameters keep the dtype of `params` (float32 models round every
-    update to float32, as the Adam drivers do).  `solver` as in minsr_direction."""
+    update to float32, as the Adam drivers do).  `solver` as in minsr_direction.
+    device_steps=K (an integer >= 1): the numsteps + 1 iterations run on the device in chunks of at most K with one host
+    synchronisation each (wf.sr_train_steps: the device solver, `solver` is ignored) - the same energies, variances and parameters,
+    bit for bit, as solver="device" gives with the loop below."""
+    device_steps = _check_device_steps(device_steps)
     _check_shift(diag_shift)
     _check_solver(solver)
     if int(numsteps) < 0 or int(numsamples) < 2:
@@ -92,6 +104,17 @@ def train_tfim(wf, Jz, Bx, params, numsteps=100, numsamples=500, learningrate=1e
     theta = flatten_params(wf, params, scope).astype(dtype).astype(np.float64)
     wf.set_params_flat(theta)
     meanEnergy, varEnergy = [], []
+    if device_steps:
+        total = int(numsteps) + 1
+        chunk = min(device_steps, 1024)                      # one call takes at most 1024 iterations
+        for it in range(0, total, chunk):
+            mom = wf.sr_train_steps(min(chunk, total - it), int(numsamples), seed, it, couplings, float(learningrate), float(diag_shift))
+            for s1, s2, n, _ in mom:
+                meanE = s1 / n
+                meanEnergy.append(meanE)
+                varEnergy.append(s2 / n - meanE ** 2)
+        train_tfim.last_params = wf.get_params_dict(params, scope)
+        return meanEnergy, varEnergy
     for it in range(int(numsteps) + 1):
         s1, s2, n, _ = wf.vmc_step(int(numsamples), seed, it, couplings)["moments"]
         meanE = s1 / n
