@@ -122,7 +122,8 @@ def prnn_log_probability(params, samples, scope="RNNwavefunction", dtype=np.floa
 
 
 def prnn_paritysym_log_probability(params, samples, scope="RNNwavefunction", dtype=np.float32):
-    """1DTFIM/RNNwavefunction_paritysym.py:122-145: log(0.5 (P(s) + P(reversed s)))."""
+    """1DTFIM/RNNwavefunction_paritysym.py:122-145: log(0.5 (P(s) + P(reversed s))).  As written there, so it underflows where the
+    reference does: inexact below log P = -708, -inf below -745 (the library does not: tests/parity_reference.py)."""
     samples = np.asarray(samples)
     lp1 = prnn_log_probability(params, samples, scope, dtype)
     lp2 = prnn_log_probability(params, samples[:, ::-1], scope, dtype)      # :125

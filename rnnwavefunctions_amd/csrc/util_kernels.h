@@ -108,11 +108,16 @@ __global__ void __launch_bounds__(1024) moments_kernel(const TE* __restrict__ e,
     }
 }
 
-// parity-symmetric combination log(0.5 (exp(a) + exp(b)))  (RNNwavefunction_paritysym.py:145)
-__global__ void parity_combine_kernel(const double* __restrict__ a, const double* __restrict__ b, int64_t n,
-                                      double* __restrict__ out) {
+// parity-symmetric combination log(0.5 (exp(a) + exp(b)))  (RNNwavefunction_paritysym.py:145) from the difference alone: a and b are
+// ABSOLUTE log-probabilities, and exp(a) is subnormal below -708 and zero below -745 (an untrained chain of 1 075 sites).  Symmetric in
+// (a, b); a == b gives a exactly (log(1) = 0), -inf for two -inf without forming inf - inf; one -inf gives the other - ln 2; NaN stays.
+// Reads element i before it writes it: out may be a (prnn.hip runs it in place), hence no __restrict__.
+__global__ void parity_combine_kernel(const double* a, const double* b, int64_t n, double* out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = log(0.5 * (exp(a[i]) + exp(b[i])));
+    if (i >= n) return;
+    const double x = a[i], y = b[i];
+    const double d = x == y ? 0.0 : fabs(x - y);           // NaN in either: d, and through it the sum, is NaN (fmax alone would drop it)
+    out[i] = fmax(x, y) + log(0.5 * (1.0 + exp(-d)));
 }
 
 // Parity-symmetric model, gradient: log P_sym = log(0.5 (P_F + P_R)) gives  d log P_sym = aF d log P_F + aR d log P_R  with the shares
