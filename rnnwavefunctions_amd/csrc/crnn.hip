@@ -7,6 +7,7 @@
 #include "crnn_kernels.h"
 #include "models.h"
 #include "pack.h"
+#include "shapes.h"
 
 using namespace rnnwf;
 
@@ -52,27 +53,14 @@ struct CLaunch {
         if constexpr (NL > 1) return launch_persistent(h, kTimerFlip, crnn_ml_swap_kernel<NFULL, NL, WAVES>, WAVES * 64, S::LDS_BYTES, max_tiles, WAVES, a);
         else return launch_persistent(h, kTimerFlip, crnn_swap_kernel<NFULL, WAVES>, WAVES * 64, S::LDS_BYTES, max_tiles, WAVES, a);
     }
-    static std::vector<char> pack(const rnnwf_handle* h) {
-        std::vector<char> img = pack_gru_image<T, NFULL, 3>(h);
-        if constexpr (NL > 1)
-            for (int l = 1; l < NL; ++l) {
-                const std::vector<char> up = pack_upper_image<NFULL>(h, l);
-                img.insert(img.end(), up.begin(), up.end());
-            }
-        return img;
-    }
+    static std::vector<char> pack(const rnnwf_handle* h) { return pack_gru_stack<T, NFULL, NL, 3>(h); }
+    static void pack_table(const rnnwf_handle* h) { pack_gru_stack<T, NFULL, NL, 3, Lin>(h); }
     static size_t hck_bytes_per_block() { return (size_t)S::ROW * 64 * sizeof(T); }
 };
 
-// (layers, NFULL) -> waves per workgroup: every shape with kernels
-template <int NL, int NFULL, int WAVES> using R = KernelRow<float, NL, NFULL, WAVES>;
-using Kernels = KernelTable<
-    R<1, 1, 4>, R<1, 2, 4>, R<1, 3, 4>, R<1, 4, 4>, R<1, 6, 8>, R<1, 8, 4>, R<1, 12, 4>, R<1, 16, 4>,
-    R<2, 1, 4>, R<2, 2, 4>, R<2, 3, 8>, R<2, 4, 4>, R<2, 6, 4>,
-    R<3, 1, 4>, R<3, 2, 8>, R<3, 3, 8>, R<3, 4, 4>, R<3, 6, 4>,
-    R<4, 1, 4>, R<4, 2, 4>, R<4, 3, 4>, R<4, 4, 4>, R<4, 6, 4>>;
+// every shape with kernels: shapes.h
 template <class Fn>
-bool with_launch(const rnnwf_handle* h, Fn&& fn) { return with_kernels<CLaunch>(Kernels(), h, fn); }
+bool with_launch(const rnnwf_handle* h, Fn&& fn) { return with_kernels<CLaunch>(CrnnKernels(), h, fn); }
 
 int no_kernel(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "no cRNN kernel for NFULL=%d", h->NFULL); }
 int launch_base(rnnwf_handle* h, const CrnnArgs& a) {
@@ -238,6 +226,11 @@ int pack_image(rnnwf_handle* h, std::vector<char>& img) {
     return with_launch(h, [&](auto k) { img = decltype(k)::pack(h); }) ? 0 : no_kernel(h);
 }
 
+// device-resident training (train.hip): the table of the image pack_image returns
+int pack_table(rnnwf_handle* h) {
+    return with_launch(h, [&](auto k) { decltype(k)::pack_table(h); }) ? 0 : no_kernel(h);
+}
+
 }  // namespace
 
 int rnnwf::crnn_log_amp(rnnwf_handle* h, const int32_t* samples, int64_t B, float* out_re_im, double* out_logp) {
@@ -298,7 +291,7 @@ size_t rnnwf::crnn_hck_bytes_per_block(rnnwf_handle* h) { return hck_bytes_per_b
 
 const Family* rnnwf::crnn_family() {
     static const Family f = {
-        "complex RNN", pack_image, log_prob_pass, nullptr, energy, max_chains_per_pass, nullptr, count_work,
+        "complex RNN", pack_image, pack_table, log_prob_pass, nullptr, energy, max_chains_per_pass, nullptr, count_work,
         3, 2,               // J1, J2, Bz per site; periodic, marshall
         true, false, gru_gradient(),    // complex64 E_loc; the base pass alone keeps no states
     };

@@ -18,21 +18,9 @@ struct CPauliLaunch {
     static double mfma_flops_per_step() { return (double)L::NT * L::KT * 2048.0; }
 };
 
-// the one-layer rows of crnn.hip's with_launch, with its waves per workgroup
+// the one-layer rows of the complex RNN's table (shapes.h), with its waves per workgroup
 template <class Fn>
-bool with_crnn1(const rnnwf_handle* h, Fn&& fn) {
-    switch (h->NFULL) {
-        case 1: fn(CPauliLaunch<1, 4>()); return true;
-        case 2: fn(CPauliLaunch<2, 4>()); return true;
-        case 3: fn(CPauliLaunch<3, 4>()); return true;
-        case 4: fn(CPauliLaunch<4, 4>()); return true;
-        case 6: fn(CPauliLaunch<6, 8>()); return true;
-        case 8: fn(CPauliLaunch<8, 4>()); return true;
-        case 12: fn(CPauliLaunch<12, 4>()); return true;
-        case 16: fn(CPauliLaunch<16, 4>()); return true;
-    }
-    return false;
-}
+bool with_crnn1(const rnnwf_handle* h, Fn&& fn) { return with_width_kernels<CPauliLaunch>(CrnnKernels(), h, fn); }
 
 // whole 16-chain blocks per pass within the state budget: per block the checkpoints and the pass's `bytes_per_block` beside them
 inline int64_t crnn_blocks_per_pass(rnnwf_handle* h, size_t bytes_per_block) {

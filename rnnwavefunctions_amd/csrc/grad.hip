@@ -10,6 +10,7 @@
 #include "ml_grad_kernels.h"
 #include "models.h"
 #include "pack.h"
+#include "shapes.h"
 
 using namespace rnnwf;
 
@@ -102,17 +103,16 @@ struct GLaunch {
         return img;
     }
 
-    // the wide shapes, whose kernels live in grad_wide.hip's translation unit (see there): -1 otherwise
-    static constexpr int WIDE = (std::is_same<T, float>::value && NOUT == 3 && WAVES == 4) ? (NFULL == 8 ? 0 : NFULL == 12 ? 1 : NFULL == 16 ? 3 : -1)
-                              : (std::is_same<T, float>::value && NOUT == 1 && WAVES == 4) ? (NFULL == 8 ? 4 : NFULL == 12 ? 5 : NFULL == 16 ? 6 : -1)
-                              : (std::is_same<T, double>::value && NOUT == 1 && WAVES == 4 && NFULL == 6) ? 2 : -1;
-    static GradKernel kernel() {
-        if constexpr (WIDE >= 0) return grad_wide_kernel(WIDE);
+    // the wide shapes' kernels live in grad_wide.hip's translation unit (see there)
+    static constexpr bool WIDE = kGradWide<T, NFULL>;
+    static_assert(!WIDE || WAVES == kGradWaves, "grad_wide.hip instantiates its kernels at kGradWaves waves per workgroup");
+    static GradKernel kernel(const rnnwf_handle* h) {
+        if constexpr (WIDE) return grad_wide_kernel(h);
         else return gru_bwd_kernel<T, NFULL, WAVES, NOUT>;
     }
 
     // small batches: two waves per block of 16 chains (grad_kernels.h: GradPair) while every pair still gets SIMDs of its own
-    static constexpr bool PAIR_OK = WIDE < 0 && std::is_same<T, float>::value && WAVES == 4 && GradPair<T, NFULL, NOUT>::FITS;
+    static constexpr bool PAIR_OK = !WIDE && std::is_same<T, float>::value && WAVES == 4 && GradPair<T, NFULL, NOUT>::FITS;
 
     // one pass of `kern` (per_wg 16-chain blocks per workgroup), then dW += P^T Q
     static int run_kernel(rnnwf_handle* h, GradKernel kern, int threads, size_t lds, int per_wg, const GradArgs& a, int64_t R, void* dW) {
@@ -127,7 +127,7 @@ struct GLaunch {
         }
         if (LDS > 160 * 1024)
             return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: forward + backward weight images (%zu B) exceed the 160 KB LDS", LDS);
-        return run_kernel(h, kernel(), WAVES * 64, LDS, WAVES, a, R, dW);
+        return run_kernel(h, kernel(h), WAVES * 64, LDS, WAVES, a, R, dW);
     }
 
     // dW image [PCOLS][QCOLS] + head gradients -> TF-named gradient arrays
@@ -223,16 +223,6 @@ struct MLGrad {
         }
         pack_trace().shift = base;
     }
-    // the table of a stack's forward buffer [layer 0 | upper layers] (grad_stack_forward_table)
-    static void pack_forward_table(const rnnwf_handle* h) {
-        const size_t base = pack_trace().shift;
-        pack_gru_image<T, NFULL, NOUT, Lin>(h);
-        for (int l = 1; l < NL; ++l) {
-            pack_trace().shift = base + L0::BYTES + (size_t)(l - 1) * U::BYTES;
-            pack_upper_image<NFULL, T, Lin>(h, l);
-        }
-        pack_trace().shift = base;
-    }
     // dW image + head rows (host copy of h->gradW) -> TF-named gradient arrays
     static void unpack(rnnwf_handle* h, const void* img) {
         const T* dW = (const T*)img;
@@ -325,38 +315,16 @@ struct MLGrad {
     }
 };
 
-// fn(K()) for this handle's gradient class K: the widths of each model, one layer (f32 8..16 and the float64 GRU's 6: kernels in
-// grad_wide.hip, GLaunch::WIDE) or a stack
-template <int NL, int NOUT, typename T, class Fn>
-int gru_widths(rnnwf_handle* h, Fn&& fn) {
-    constexpr bool f32 = std::is_same<T, float>::value;
-    switch (h->NFULL) {
-        case 1: return fn(MLGrad<1, NL, 4, NOUT, T>());
-        case 2: return fn(MLGrad<2, NL, 4, NOUT, T>());
-        case 3: return fn(MLGrad<3, NL, 4, NOUT, T>());
-        case 4: return fn(MLGrad<4, NL, 4, NOUT, T>());
-        case 6: if constexpr (f32 || NL == 1) return fn(MLGrad<6, NL, 4, NOUT, T>()); break;
-        case 8: if constexpr (f32 && NL == 1) return fn(MLGrad<8, NL, 4, NOUT, T>()); break;
-        case 12: if constexpr (f32 && NL == 1) return fn(MLGrad<12, NL, 4, NOUT, T>()); break;
-        case 16: if constexpr (f32 && NL == 1) return fn(MLGrad<16, NL, 4, NOUT, T>()); break;
-    }
-    return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: no gradient kernel for NFULL=%d with %d layers", h->NFULL, NL);
-}
-template <int NL, class Fn>
-int gru_models(rnnwf_handle* h, Fn&& fn) {
-    if (h->model == RNNWF_MODEL_CRNN_U1) return gru_widths<NL, 3, float>(h, fn);
-    if (h->model == RNNWF_MODEL_GRU1D_F64) return gru_widths<NL, 1, double>(h, fn);
-    return gru_widths<NL, 1, float>(h, fn);
-}
+// rc = fn(K()) for this handle's gradient class K: one per row of the family's forward table (shapes.h), at kGradWaves waves per
+// workgroup whatever the forward kernels' (the kernels of f32 8..16 and the float64 GRU's 6 are in grad_wide.hip: GLaunch::WIDE)
+template <typename T, int NFULL, int NL, int> using PGrad = MLGrad<NFULL, NL, kGradWaves, 1, T>;      // positive GRU, f32 and f64
+template <typename T, int NFULL, int NL, int> using CGrad = MLGrad<NFULL, NL, kGradWaves, 3, T>;      // complex RNN
 template <class Fn>
 int with_gru_grad(rnnwf_handle* h, Fn&& fn) {
-    switch (h->NL) {
-        case 1: return gru_models<1>(h, fn);
-        case 2: return gru_models<2>(h, fn);
-        case 3: return gru_models<3>(h, fn);
-        case 4: return gru_models<4>(h, fn);
-    }
-    return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: no gradient kernel for %d layers", h->NL);
+    int rc = 0;
+    auto call = [&](auto k) { rc = fn(k); };
+    if (h->model == RNNWF_MODEL_CRNN_U1 ? with_kernels<CGrad>(CrnnKernels(), h, call) : with_kernels<PGrad>(GruKernels(), h, call)) return rc;
+    return h->fail(RNNWF_ERR_INVALID, "rnnwf_vmc_gradient: no gradient kernel for NFULL=%d with %d layers", h->NFULL, h->NL);
 }
 
 int grad_layout(rnnwf_handle* h, GradImage* out) {
@@ -441,11 +409,6 @@ extern "C" int rnnwf_vmc_gradient(rnnwf_handle* h, double mean_energy, double me
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));
     h->family->gradient->unpack(h, h->staging);
     return RNNWF_OK;
-}
-
-// table of a stack's forward buffer [layer 0 | upper layers] into the active PackTrace (train.hip; the layouts live here)
-int rnnwf::grad_stack_forward_table(rnnwf_handle* h) {
-    return with_gru_grad(h, [&](auto k) { decltype(k)::pack_forward_table(h); return 0; });
 }
 
 // Where every entry of the flat gradient (order and shapes of rnnwf_get_grads_flat) sits in the h->gradW image: the family's

@@ -6,20 +6,30 @@
 // where the 68-unit one takes 1.6).  This unit is compiled WITHOUT that option (accumulators in AGPRs), which the pass survives.
 #include "grad_kernels.h"
 #include "models.h"
+#include "shapes.h"
 
 namespace rnnwf {
 
-GradKernel grad_wide_kernel(int which) {
-    switch (which) {
-        case 0: return gru_bwd_kernel<float, 8, 4, 3>;
-        case 1: return gru_bwd_kernel<float, 12, 4, 3>;
-        case 2: return gru_bwd_kernel<double, 6, 4, 1>;
-        case 3: return gru_bwd_kernel<float, 16, 4, 3>;
-        case 4: return gru_bwd_kernel<float, 8, 4, 1>;
-        case 5: return gru_bwd_kernel<float, 12, 4, 1>;
-        case 6: return gru_bwd_kernel<float, 16, 4, 1>;
-    }
-    return nullptr;
+namespace {
+// the kernel of a one-layer row with NOUT head rows, where the row is a wide one (models.h: kGradWide)
+template <int NOUT>
+struct Wide {
+    template <typename T, int NFULL, int>
+    struct Row {
+        static GradKernel kernel() {
+            if constexpr (kGradWide<T, NFULL>) return gru_bwd_kernel<T, NFULL, kGradWaves, NOUT>;
+            else return nullptr;
+        }
+    };
+};
+}  // namespace
+
+GradKernel grad_wide_kernel(const rnnwf_handle* h) {
+    GradKernel kern = nullptr;
+    auto pick = [&](auto row) { kern = decltype(row)::kernel(); };
+    if (h->model == RNNWF_MODEL_CRNN_U1) with_layer_kernels<Wide<3>::Row>(CrnnKernels(), h, pick);
+    else with_layer_kernels<Wide<1>::Row>(GruKernels(), h, pick);
+    return kern;
 }
 
 }  // namespace rnnwf

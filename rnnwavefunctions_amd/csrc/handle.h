@@ -331,23 +331,53 @@ inline int launch_shrinking(rnnwf_handle* h, TimerId id, Kern kern, size_t lds, 
 }
 
 // The kernels a family is built for: one row per shape (element type, layers, NFULL) with the waves per workgroup of its kernels.
+// The families' tables are in shapes.h; every width-class dispatch of the host code walks one of them.
 template <typename T_, int NL_, int NFULL_, int WAVES_>
 struct KernelRow {
     using T = T_;
     static constexpr int NL = NL_, NFULL = NFULL_, WAVES = WAVES_;
+    static bool serves(const rnnwf_handle* h) { return std::is_same<T, double>::value == (bool)h->f64 && NL == h->NL && NFULL == h->NFULL; }
 };
+// A row of the bf16x3 engine (f32 models, one layer; the callers ask for no other handle): width class NFULL runs on
+// SplitLayout<NF32, RJ, ., MODE> (split_core.h) with WAVES waves per workgroup; HMIN <= num_units <= HMAX where a width class has two
+// layouts.  MODE 3: the riders form (split_stream.hip)
+template <int NFULL_, int NF32_, int RJ_, int WAVES_, int MODE_, int HMIN_ = 0, int HMAX_ = 1 << 30>
+struct SplitRow {
+    static constexpr int NFULL = NFULL_, NF32 = NF32_, RJ = RJ_, WAVES = WAVES_, MODE = MODE_, HMIN = HMIN_, HMAX = HMAX_;
+    static bool serves(const rnnwf_handle* h) { return NFULL == h->NFULL && HMIN <= h->H && h->H <= HMAX; }
+};
+template <class R> struct Riders : std::bool_constant<R::MODE == 3> {};
+template <class R> struct NotRiders : std::bool_constant<R::MODE != 3> {};
 template <class... Rows> struct KernelTable {};
 
-// fn(K<T, NFULL, NL, WAVES>()) for the row of this handle's shape; false (fn not called) for a shape without kernels
-template <template <typename, int, int, int> class K, class Fn, class... Rows>
-inline bool with_kernels(KernelTable<Rows...>, const rnnwf_handle* h, Fn&& fn) {
+// fn(Row()) for the row of this handle's shape among the rows Keep admits (no code of another row is instantiated); false (fn not
+// called) for a shape without kernels
+template <class R> struct AnyRow : std::true_type {};
+template <class R> struct OneLayer : std::bool_constant<R::NL == 1> {};
+template <template <class> class Keep = AnyRow, class Fn, class... Rows>
+inline bool with_row(KernelTable<Rows...>, const rnnwf_handle* h, Fn&& fn) {
     auto hit = [&](auto row) {
-        using R = decltype(row);
-        if (std::is_same<typename R::T, double>::value != (bool)h->f64 || R::NL != h->NL || R::NFULL != h->NFULL) return false;
-        fn(K<typename R::T, R::NFULL, R::NL, R::WAVES>());
-        return true;
+        if constexpr (Keep<decltype(row)>::value)
+            if (decltype(row)::serves(h)) return fn(row), true;
+        return false;
     };
     return (hit(Rows()) || ...);
+}
+
+// the same with fn(K<T, NFULL, NL, WAVES>()): a family's launch class of the row
+template <template <typename, int, int, int> class K, class Table, class Fn>
+inline bool with_kernels(Table t, const rnnwf_handle* h, Fn&& fn) {
+    return with_row(t, h, [&](auto r) { fn(K<typename decltype(r)::T, decltype(r)::NFULL, decltype(r)::NL, decltype(r)::WAVES>()); });
+}
+// one-layer passes: fn(K<T, NFULL, WAVES>()) for the handle's row among the table's one-layer rows; false for a stack as well
+template <template <typename, int, int> class K, class Table, class Fn>
+inline bool with_layer_kernels(Table t, const rnnwf_handle* h, Fn&& fn) {
+    return with_row<OneLayer>(t, h, [&](auto r) { fn(K<typename decltype(r)::T, decltype(r)::NFULL, decltype(r)::WAVES>()); });
+}
+// the same with fn(K<NFULL, WAVES>()): families of one element type
+template <template <int, int> class K, class Table, class Fn>
+inline bool with_width_kernels(Table t, const rnnwf_handle* h, Fn&& fn) {
+    return with_row<OneLayer>(t, h, [&](auto r) { fn(K<decltype(r)::NFULL, decltype(r)::WAVES>()); });
 }
 
 }  // namespace rnnwf

@@ -7,6 +7,7 @@
 #include "lstm_kernels.h"
 #include "models.h"
 #include "pack.h"
+#include "shapes.h"
 
 using namespace rnnwf;
 
@@ -78,12 +79,15 @@ std::vector<char> pack_lstm_image(const rnnwf_handle* h) {
     return img;
 }
 
-// WAVES: waves per workgroup of the flip pass; BWAVES: of the base pass.  The image takes most of a CU's LDS (one workgroup per
+// WAVES: waves per workgroup of the flip pass (shapes.h); BWAVES: of the base pass - at 68 units one wave per SIMD: with its
+// checkpoint stores and sampler beside h, c and h' it needs more than the 256 registers of two waves per SIMD (scratch otherwise); it
+// is the short pass (N steps per chain against the flip pass's N (N - 1) / 2).  The image takes most of a CU's LDS (one workgroup per
 // CU from 37 units up): both passes shrink their workgroups for small batches (handle.h: launch_shrinking; the run script's 4x4 /
 // 500 samples would sit on 60 of 256 CUs in full-size workgroups)
-template <int NFULL, int WAVES, int BWAVES = WAVES>
+template <int NFULL, int WAVES>
 struct LLaunch {
     using L = LstmLayout<NFULL>;
+    static constexpr int BWAVES = NFULL == 4 ? 4 : WAVES;
     static int base(rnnwf_handle* h, const LstmArgs& a) {
         return launch_shrinking<BWAVES>(h, kTimerBase, lstm_base_kernel<NFULL, BWAVES>, L::BYTES, a.nsb, a);
     }
@@ -95,20 +99,9 @@ struct LLaunch {
     static double mfma_flops_per_step() { return (double)L::NT * L::KT * 2048.0; }
 };
 
-// fn(K()) for this handle's launch class K, false (fn not called) for a width without kernels.  NFULL 1..4 (<= 20, 36, 52, 68
-// units); 8 waves where one workgroup fills a CU's LDS (two per SIMD).  The base pass at 68 units runs one wave per SIMD: with
-// its checkpoint stores and sampler beside h, c and h' it needs more than the 256 registers of two waves per SIMD (scratch
-// otherwise); it is the short pass (N steps per chain against the flip pass's N (N - 1) / 2).
+// fn(K()) for this handle's launch class K, false (fn not called) for a width without kernels
 template <class Fn>
-bool with_launch(const rnnwf_handle* h, Fn&& fn) {
-    switch (h->NFULL) {
-        case 1: fn(LLaunch<1, 4>()); return true;
-        case 2: fn(LLaunch<2, 4>()); return true;
-        case 3: fn(LLaunch<3, 8>()); return true;
-        case 4: fn(LLaunch<4, 8, 4>()); return true;
-    }
-    return false;
-}
+bool with_launch(const rnnwf_handle* h, Fn&& fn) { return with_width_kernels<LLaunch>(LstmKernels(), h, fn); }
 
 int no_kernel(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "no LSTM kernel for NFULL=%d (one layer, <= 68 units)", h->NFULL); }
 int launch_base(rnnwf_handle* h, const LstmArgs& a) {
@@ -189,7 +182,7 @@ int pack_image(rnnwf_handle* h, std::vector<char>& img) {
 
 const Family* rnnwf::lstm_family() {
     static const Family f = {
-        "LSTM cell", pack_image, log_prob_pass, nullptr, eloc_on_device, max_chains_per_pass, nullptr, nullptr,
+        "LSTM cell", pack_image, nullptr, log_prob_pass, nullptr, eloc_on_device, max_chains_per_pass, nullptr, nullptr,
         1, 1,                 // Jz per site; Bx
         false, false, nullptr,  // float64 E_loc; the base pass alone keeps no states; no gradient (nothing stays resident)
     };

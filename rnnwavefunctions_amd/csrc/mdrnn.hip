@@ -8,6 +8,7 @@
 #include "mdrnn_kernels.h"
 #include "models.h"
 #include "pack.h"
+#include "shapes.h"
 
 using namespace rnnwf;
 
@@ -114,19 +115,10 @@ struct MLaunch {
     }
 };
 
-// fn(K<NFULL, 4>()) for the handle's width, false (fn not called) for a width without kernels: K = MLaunch (the forward passes) or
-// MGrad (the gradient)
+// fn(K<NFULL, WAVES>()) for the handle's row of shapes.h, false (fn not called) for a width without kernels: K = MLaunch (the forward
+// passes) or MGrad (the gradient)
 template <template <int, int> class K, class Fn>
-bool with_width(const rnnwf_handle* h, Fn&& fn) {
-    switch (h->NFULL) {
-        case 1: fn(K<1, 4>()); return true;
-        case 2: fn(K<2, 4>()); return true;
-        case 3: fn(K<3, 4>()); return true;
-        case 4: fn(K<4, 4>()); return true;
-        case 5: fn(K<5, 4>()); return true;
-    }
-    return false;
-}
+bool with_width(const rnnwf_handle* h, Fn&& fn) { return with_width_kernels<K>(MdKernels(), h, fn); }
 
 int no_kernel(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "MDRNN: num_units > 84 is not implemented on gfx950 yet"); }
 int launch_base(rnnwf_handle* h, const MdArgs& a) {
@@ -255,6 +247,10 @@ int site_maps(rnnwf_handle* h, const int32_t** col_of_pos, const int32_t** pos_o
 int pack_image(rnnwf_handle* h, std::vector<char>& img) {
     if (h->N > 256) return h->fail(RNNWF_ERR_INVALID, "MDRNN: lattices above 256 sites are not implemented");
     return with_width<MLaunch>(h, [&](auto k) { img = decltype(k)::template pack<double>(h); }) ? 0 : no_kernel(h);
+}
+// device-resident training (train.hip): the table of that image
+int pack_table(rnnwf_handle* h) {
+    return with_width<MLaunch>(h, [&](auto k) { decltype(k)::template pack<Lin>(h); }) ? 0 : no_kernel(h);
 }
 
 }  // namespace
@@ -405,14 +401,9 @@ void grad_unpack(rnnwf_handle* h, const void* img) {
 const Family* rnnwf::mdrnn_family() {
     static const Gradient g = {grad_layout, grad_pack, grad_launch, grad_unpack};
     static const Family f = {
-        "2D RNN", pack_image, log_prob_pass, nullptr, eloc_on_device, max_chains_per_pass, site_maps, nullptr,
+        "2D RNN", pack_image, pack_table, log_prob_pass, nullptr, eloc_on_device, max_chains_per_pass, site_maps, nullptr,
         1, 1,               // Jz per site; Bx
         false, true, &g,    // float64 E_loc; the base pass alone keeps every site's state
     };
     return &f;
-}
-
-// device-resident training (train.hip): the forward image's table
-int rnnwf::mdrnn_pack_table(rnnwf_handle* h) {
-    return with_width<MLaunch>(h, [&](auto k) { decltype(k)::template pack<Lin>(h); }) ? 0 : 1;
 }

@@ -21,18 +21,9 @@ struct MdLaunch {
     static double mfma_flops_per_step() { return (double)NFULL * 2 * L::KT * 2048.0; }
 };
 
-// the rows of mdrnn.hip's with_width
+// the rows of the 2D RNN's table (shapes.h), as mdrnn.hip's with_width
 template <class Fn>
-bool with_md_width(const rnnwf_handle* h, Fn&& fn) {
-    switch (h->NFULL) {
-        case 1: fn(MdLaunch<1, 4>()); return true;
-        case 2: fn(MdLaunch<2, 4>()); return true;
-        case 3: fn(MdLaunch<3, 4>()); return true;
-        case 4: fn(MdLaunch<4, 4>()); return true;
-        case 5: fn(MdLaunch<5, 4>()); return true;
-    }
-    return false;
-}
+bool with_md_width(const rnnwf_handle* h, Fn&& fn) { return with_width_kernels<MdLaunch>(MdKernels(), h, fn); }
 
 // 0, or RNNWF_ERR_INVALID for another model or a width without kernels; gru_entry: the entry point that serves the GRU models
 inline int md_refuse(rnnwf_handle* h, const char* entry, const char* gru_entry) {

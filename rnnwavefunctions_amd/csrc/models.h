@@ -29,6 +29,9 @@ struct Gradient;
 struct Family {
     const char* name;
     int (*pack_image)(rnnwf_handle* h, std::vector<char>& img);
+    // the table of that image over Lin into the active PackTrace, from the same row of the family's shape table (shapes.h): what
+    // device-resident training replays (train.hip); nullptr for a family without a gradient
+    int (*pack_table)(rnnwf_handle* h);
     // base pass alone: log P of ns chains -> h->out_lp (spins drawn into h->bits when `draw`)
     int (*base)(rnnwf_handle* h, int64_t ns, const Draw* draw);
     // parity model: h->out_lp <- log P symmetrised over the reversed chains of the spins in h->samples_i32; nullptr for the others
@@ -141,16 +144,22 @@ bool base_bf_available(const rnnwf_handle* h);
 int base_bf_pack(rnnwf_handle* h);
 int prnn_base_coop_bf(rnnwf_handle* h, const PrnnArgs& a);
 int crnn_base_coop_bf(rnnwf_handle* h, const CrnnArgs& a);
+// device-resident training (train.hip): the tables of the engine's images over Lin into the active PackTrace, from the rows of
+// shapes.h their host packers take - h->wsplit of one layer; of a stack, layer 0 -> h->wsplit, l >= 1 -> h->wsplit_up[l - 1]; h->wbasebf
+int split_pack_table(rnnwf_handle* h);
+int stack_pack_table(rnnwf_handle* h, int layer);
+int base_bf_pack_table(rnnwf_handle* h);
 
 // ---- gradient (grad.hip) ---------------------------------------------------------------------------
-// grad_wide.hip: backward kernels compiled in their own translation unit (index: grad.hip, GLaunch::WIDE)
+// grad_wide.hip: the backward kernels of the wide one-layer shapes, compiled in their own translation unit - the rows of the GRU
+// families' tables (shapes.h) that kGradWide picks: f32 from NFULL = 8 (101 units), f64 at NFULL = 6 (69..100 units).  Every
+// gradient kernel of the GRUs runs kGradWaves waves per workgroup, whatever the forward kernels of its row run
 struct GradArgs;
 using GradKernel = void (*)(GradArgs);
-GradKernel grad_wide_kernel(int which);
+constexpr int kGradWaves = 4;
+template <typename T, int NFULL> constexpr bool kGradWide = sizeof(T) == 4 ? NFULL >= 8 : NFULL == 6;
+GradKernel grad_wide_kernel(const rnnwf_handle* h);     // nullptr for another shape
 int grad_bwd_image(rnnwf_handle* h);                    // grad.hip: the backward image, re-packed when stale
-// forward weight-image tables into the active PackTrace, for device training: the 2D RNN's (mdrnn.hip), a stack's [layer 0 | upper layers]
-int mdrnn_pack_table(rnnwf_handle* h);
-int grad_stack_forward_table(rnnwf_handle* h);
 // ---- device-resident training (train.hip) ------------------------------------------------------------
 void train_params_changed_on_host(rnnwf_handle* h);           // rnnwf_set_param / rnnwf_commit_params: the device copy is stale
 int train_sync_params_to_host(rnnwf_handle* h);               // before the host reads its copy (rnnwf_get_param, checkpoints)

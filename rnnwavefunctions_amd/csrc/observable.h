@@ -13,6 +13,7 @@
 #include "chain_kernels.h"
 #include "gru_kernels.h"
 #include "models.h"
+#include "shapes.h"
 
 namespace rnnwf {
 
@@ -24,34 +25,12 @@ struct Gru1Launch {
     static double mfma_flops_per_step() { return (double)L::NT * L::KT * 2048.0; }
 };
 
-// fn(K()) for this handle's launch class K, false (fn not called) for a width without kernels.  The one-layer rows of prnn.hip's
-// table with its flip pass's waves per workgroup - except f64 at 53..68 units (NFULL = 6): 4, not 8.  At 8 the swap kernel spills 20
-// bytes per lane to scratch (profiles/renyi_kernel_resources.txt); at these rows no kernel of the four passes uses scratch
-// (profiles/{renyi,corr,renyi_regions,pauli}_kernel_resources.txt).  The rows are every width rnnwf_create accepts for these models.
+// fn(K()) for this handle's launch class K, false (fn not called) for a width without kernels: the one-layer rows of the positive
+// GRU's table at the waves per workgroup shapes.h gives these passes (kGru1Waves).  The rows are every width rnnwf_create accepts
+// for these models.
+template <typename T, int NFULL, int WAVES> using Gru1Row = Gru1Launch<T, NFULL, kGru1Waves<T, NFULL, WAVES>>;
 template <class Fn>
-bool with_gru1(const rnnwf_handle* h, Fn&& fn) {
-    if (!h->f64) {
-        switch (h->NFULL) {
-            case 1: fn(Gru1Launch<float, 1, 4>()); return true;
-            case 2: fn(Gru1Launch<float, 2, 4>()); return true;
-            case 3: fn(Gru1Launch<float, 3, 4>()); return true;
-            case 4: fn(Gru1Launch<float, 4, 4>()); return true;
-            case 6: fn(Gru1Launch<float, 6, 8>()); return true;
-            case 8: fn(Gru1Launch<float, 8, 4>()); return true;
-            case 12: fn(Gru1Launch<float, 12, 4>()); return true;
-            case 16: fn(Gru1Launch<float, 16, 4>()); return true;
-        }
-        return false;
-    }
-    switch (h->NFULL) {
-        case 1: fn(Gru1Launch<double, 1, 4>()); return true;
-        case 2: fn(Gru1Launch<double, 2, 4>()); return true;
-        case 3: fn(Gru1Launch<double, 3, 4>()); return true;
-        case 4: fn(Gru1Launch<double, 4, 4>()); return true;
-        case 6: fn(Gru1Launch<double, 6, 4>()); return true;
-    }
-    return false;
-}
+bool with_gru1(const rnnwf_handle* h, Fn&& fn) { return with_layer_kernels<Gru1Row>(GruKernels(), h, fn); }
 
 inline bool has_kernel(const rnnwf_handle* h) { return with_gru1(h, [](auto) {}); }
 

@@ -214,4 +214,21 @@ std::vector<char> pack_upper_image(const rnnwf_handle* h, int layer) {
     return img;
 }
 
+// The forward buffer of a shape, [layer 0 | layers 1 .. NL - 1].  S = Lin: the same images once more over Lin, the table of the whole
+// buffer for device-resident training (pack_value.h; the active PackTrace's shift moves along)
+template <typename T, int NFULL, int NL, int NOUT, class S = double>
+std::vector<char> pack_gru_stack(const rnnwf_handle* h) {
+    std::vector<char> img = pack_gru_image<T, NFULL, NOUT, S>(h);
+    if constexpr (NL > 1) {
+        const size_t base = pack_trace().shift;
+        for (int l = 1; l < NL; ++l) {
+            pack_trace().shift = base + img.size();
+            const std::vector<char> up = pack_upper_image<NFULL, T, S>(h, l);
+            img.insert(img.end(), up.begin(), up.end());
+        }
+        pack_trace().shift = base;
+    }
+    return img;
+}
+
 }  // namespace rnnwf

@@ -7,6 +7,7 @@
 #include "gru_kernels.h"
 #include "models.h"
 #include "pack.h"
+#include "shapes.h"
 
 using namespace rnnwf;
 
@@ -52,32 +53,15 @@ struct Launch {
         if constexpr (NL > 1) return launch_persistent(h, kTimerFlip, prnn_ml_flip_kernel<T, NFULL, NL, WAVES>, WAVES * 64, S::LDS_BYTES, a.ntiles, WAVES, a);
         else return launch_persistent(h, kTimerFlip, prnn_flip_kernel<T, NFULL, WAVES>, WAVES * 64, S::LDS_BYTES, a.ntiles, WAVES, a);
     }
-    static std::vector<char> pack(const rnnwf_handle* h) {
-        std::vector<char> img = pack_gru_image<T, NFULL, 1>(h);
-        if constexpr (NL > 1)
-            for (int l = 1; l < NL; ++l) {
-                const std::vector<char> up = pack_upper_image<NFULL, T>(h, l);
-                img.insert(img.end(), up.begin(), up.end());
-            }
-        return img;
-    }
+    static std::vector<char> pack(const rnnwf_handle* h) { return pack_gru_stack<T, NFULL, NL, 1>(h); }
+    static void pack_table(const rnnwf_handle* h) { pack_gru_stack<T, NFULL, NL, 1, Lin>(h); }
     static size_t hck_bytes_per_block() { return (size_t)S::ROW * 64 * sizeof(T); }
     static double mfma_flops_per_step() { return ((double)L::NT + 2.0 * (NL - 1) * UpperLayout<NFULL, T>::NT) * L::KT * 2048.0; }
 };
 
-// (element type, layers, NFULL) -> waves per workgroup: every shape with kernels
-template <typename T, int NL, int NFULL, int WAVES> using R = KernelRow<T, NL, NFULL, WAVES>;
-using Kernels = KernelTable<
-    R<double, 1, 1, 4>, R<double, 1, 2, 4>, R<double, 1, 3, 4>, R<double, 1, 4, 8>, R<double, 1, 6, 4>,
-    R<double, 2, 1, 4>, R<double, 2, 2, 8>, R<double, 2, 3, 4>, R<double, 2, 4, 4>,
-    R<double, 3, 1, 4>, R<double, 3, 2, 4>, R<double, 3, 3, 4>, R<double, 3, 4, 4>,
-    R<double, 4, 1, 4>, R<double, 4, 2, 4>, R<double, 4, 3, 4>, R<double, 4, 4, 4>,
-    R<float, 1, 1, 4>, R<float, 1, 2, 4>, R<float, 1, 3, 4>, R<float, 1, 4, 4>, R<float, 1, 6, 8>, R<float, 1, 8, 4>, R<float, 1, 12, 4>, R<float, 1, 16, 4>,
-    R<float, 2, 1, 4>, R<float, 2, 2, 4>, R<float, 2, 3, 8>, R<float, 2, 4, 4>, R<float, 2, 6, 4>,
-    R<float, 3, 1, 4>, R<float, 3, 2, 8>, R<float, 3, 3, 8>, R<float, 3, 4, 4>, R<float, 3, 6, 4>,
-    R<float, 4, 1, 4>, R<float, 4, 2, 4>, R<float, 4, 3, 4>, R<float, 4, 4, 4>, R<float, 4, 6, 4>>;
+// every shape with kernels: shapes.h
 template <class Fn>
-bool with_launch(const rnnwf_handle* h, Fn&& fn) { return with_kernels<Launch>(Kernels(), h, fn); }
+bool with_launch(const rnnwf_handle* h, Fn&& fn) { return with_kernels<Launch>(GruKernels(), h, fn); }
 
 int no_kernel(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "no pRNN kernel for NFULL=%d f64=%d", h->NFULL, (int)h->f64); }
 int launch_base(rnnwf_handle* h, const PrnnArgs& a) {
@@ -251,6 +235,11 @@ int pack_image(rnnwf_handle* h, std::vector<char>& img) {
     return with_launch(h, [&](auto k) { img = decltype(k)::pack(h); }) ? 0 : no_kernel(h);
 }
 
+// device-resident training (train.hip): the table of the image pack_image returns
+int pack_table(rnnwf_handle* h) {
+    return with_launch(h, [&](auto k) { decltype(k)::pack_table(h); }) ? 0 : no_kernel(h);
+}
+
 }  // namespace
 
 // Teacher-forced base pass with checkpoints over the resident spins (h->bits, or the reversed ones in h->bits2), log P of every
@@ -274,7 +263,7 @@ size_t rnnwf::prnn_hck_bytes_per_block(rnnwf_handle* h) { return hck_bytes_per_b
 
 const Family* rnnwf::gru_family() {
     static const Family f = {
-        "GRU cell", pack_image, log_prob_pass, symmetrise, eloc_on_device, max_chains_per_pass, nullptr, nullptr,
+        "GRU cell", pack_image, pack_table, log_prob_pass, symmetrise, eloc_on_device, max_chains_per_pass, nullptr, nullptr,
         1, 1,                // Jz per site; Bx
         false, false, gru_gradient(),   // float64 E_loc; the base pass alone keeps no states
     };

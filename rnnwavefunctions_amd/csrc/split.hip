@@ -11,6 +11,7 @@
 #include "models.h"
 #include "pack.h"
 #include "pack_split.h"
+#include "shapes.h"
 #include "split_kernels.h"
 
 using namespace rnnwf;
@@ -109,23 +110,16 @@ struct CSLaunch {
     static double mfma_flops_per_step() { return (double)L::NT * L::KS * 32768.0; }
 };
 
-// fn(K<NF32, RJ, WAVES, MODE>()) for the handle's width, false (fn not called) for a width without kernels: K = SLaunch (positive
-// RNN) or CSLaunch (complex RNN), which share the bf16x3 layouts of each width
+// fn(K<NF32, RJ, WAVES, MODE>()) for the handle's row of the bf16x3 table (shapes.h) among those of this translation unit (MODE 0..2),
+// false (fn not called) for a width without kernels here: K = SLaunch (positive RNN) or CSLaunch (complex RNN), which share the
+// bf16x3 layouts of each width
 template <template <int, int, int, int> class K, class Fn>
 bool with_layout(const rnnwf_handle* h, Fn&& fn) {
-    switch (h->NFULL) {
-        case 1: fn(K<0, 10, 4, 1>()); return true;
-        case 2: fn(K<1, 2, 4, 1>()); return true;
-        case 3:
-            if (h->H <= 50) fn(K<1, 9, 4, 2>());
-            else fn(K<1, 10, 4, 0>());
-            return true;
-    }
-    return false;
+    return with_row<NotRiders>(SplitKernels(), h, [&](auto r) { fn(K<decltype(r)::NF32, decltype(r)::RJ, decltype(r)::WAVES, decltype(r)::MODE>()); });
 }
 
-// widths served by the riders form (split_stream.hip): 53..100 units; every caller of with_layout asks this first
-bool riders(const rnnwf_handle* h) { return h->NFULL == 4 || h->NFULL == 6; }
+// widths served by the riders form (split_stream.hip: the table's MODE 3 rows, 53..100 units); every caller of with_layout asks this first
+bool riders(const rnnwf_handle* h) { return with_row<Riders>(SplitKernels(), h, [](auto) {}); }
 
 }  // namespace
 
@@ -134,6 +128,7 @@ namespace {
 template <int NFULL>
 struct BfBase {
     using B = BaseBfLayout<NFULL>;
+    static constexpr int NF = NFULL;
     template <int NOUT> static size_t lds_bytes() {
         return GruLayout<float, NFULL, NOUT>::BYTES + B::BYTES + (size_t)B::NB * (B::PB_BYTES + (size_t)2 * (4 * NFULL + 1) * 64 * 4 + 2 * 64 * 4);
     }
@@ -171,6 +166,12 @@ struct BfBase {
         return timed_launch(h, kTimerBase, kern, grid, threads, lds, a);
     }
 };
+// fn(BfBase<NFULL>()) for the handle's row of the cooperative bf16 base pass's table (shapes.h); false for a width without kernels
+template <class Fn>
+bool with_bf_base(const rnnwf_handle* h, Fn&& fn) {
+    return with_row(BaseBfKernels(), h, [&](auto row) { fn(BfBase<decltype(row)::NFULL>()); });
+}
+int no_bf_base(rnnwf_handle* h) { return h->fail(RNNWF_ERR_INVALID, "no bf16 cooperative base kernel for NFULL=%d", h->NFULL); }
 }  // namespace
 
 bool rnnwf::base_bf_available(const rnnwf_handle* h) { return h->base_bf; }
@@ -181,12 +182,7 @@ int rnnwf::base_bf_pack(rnnwf_handle* h) {
     // (config 1) the f32 cooperative kernel is 9 % faster - its image is three times smaller to stage - so narrower models keep it
     if (h->f64 || h->NL != 1 || h->NFULL != 3 || h->knobs.base_f32 || h->knobs.no_coop || h->knobs.engine == 1) return 0;
     std::vector<char> img;
-    switch (h->NFULL) {
-        case 1: img = pack_base_bf_image<1>(h); break;
-        case 2: img = pack_base_bf_image<2>(h); break;
-        case 3: img = pack_base_bf_image<3>(h); break;
-        default: return 0;
-    }
+    if (!with_bf_base(h, [&](auto b) { img = pack_base_bf_image<decltype(b)::NF>(h); })) return 0;
     if (int rc = ensure(h, h->wbasebf, img.size())) return rc;
     if (int rc = upload(h, h->wbasebf.p, img.data(), img.size())) return rc;
     h->base_bf = true;
@@ -196,25 +192,36 @@ int rnnwf::base_bf_pack(rnnwf_handle* h) {
 int rnnwf::prnn_base_coop_bf(rnnwf_handle* h, const PrnnArgs& a0) {
     PrnnArgs a = a0;
     a.wbf = h->wbasebf.p;
-    switch (h->NFULL) {
-        case 1: return BfBase<1>::launch(h, a, prnn_base_coop_kernel<1, true>, BfBase<1>::lds_bytes<1>());
-        case 2: return BfBase<2>::launch(h, a, prnn_base_coop_kernel<2, true>, BfBase<2>::lds_bytes<1>());
-        case 3: return BfBase<3>::launch(h, a, prnn_base_coop_kernel<3, true>, BfBase<3>::lds_bytes<1>());
-    }
-    return h->fail(RNNWF_ERR_INVALID, "no bf16 cooperative base kernel for NFULL=%d", h->NFULL);
+    int rc = 0;
+    return with_bf_base(h, [&](auto b) {
+        using B = decltype(b);
+        rc = B::launch(h, a, prnn_base_coop_kernel<B::NF, true>, B::template lds_bytes<1>());
+    }) ? rc : no_bf_base(h);
 }
 
 int rnnwf::crnn_base_coop_bf(rnnwf_handle* h, const CrnnArgs& a0) {
     CrnnArgs a = a0;
     a.wbf = h->wbasebf.p;
-    switch (h->NFULL) {
-        case 1: return BfBase<1>::launch(h, a, crnn_base_coop_kernel<1, true>, BfBase<1>::lds_bytes<3>());
-        case 2: return BfBase<2>::launch(h, a, crnn_base_coop_kernel<2, true>, BfBase<2>::lds_bytes<3>());
-        case 3: return BfBase<3>::launch(h, a, crnn_base_coop_kernel<3, true>, BfBase<3>::lds_bytes<3>());
-    }
-    return h->fail(RNNWF_ERR_INVALID, "no bf16 cooperative base kernel for NFULL=%d", h->NFULL);
+    int rc = 0;
+    return with_bf_base(h, [&](auto b) {
+        using B = decltype(b);
+        rc = B::launch(h, a, crnn_base_coop_kernel<B::NF, true>, B::template lds_bytes<3>());
+    }) ? rc : no_bf_base(h);
 }
 
+// ---- device-resident training (train.hip): the tables of the engine's images over Lin into the active PackTrace, each from the row
+// its host packer takes (pack_value.h); != 0: no such row ---------------------------------------------------------------------
+int rnnwf::base_bf_pack_table(rnnwf_handle* h) {             // h->wbasebf
+    return with_bf_base(h, [&](auto b) { pack_base_bf_image<decltype(b)::NF, Lin>(h); }) ? 0 : 1;
+}
+int rnnwf::split_pack_table(rnnwf_handle* h) {               // h->wsplit of one layer, the riders rows too
+    const bool cplx = h->model == RNNWF_MODEL_CRNN_U1;
+    return with_row(SplitKernels(), h, [&](auto row) {
+        using R = decltype(row);
+        if (cplx) pack_split_image<R::NF32, R::RJ, 3, R::MODE, Lin>(h);
+        else pack_split_image<R::NF32, R::RJ, 1, R::MODE, Lin>(h);
+    }) ? 0 : 1;
+}
 
 // ---- stacked layers on the bf16x3 engine: a pipeline of one kernel per layer (split_core.h: SplitUpperLayout) -----------------
 namespace {
@@ -252,6 +259,18 @@ int rnnwf::stack_pack(rnnwf_handle* h) {
 }
 template int rnnwf::stack_pack<1>(rnnwf_handle*);
 template int rnnwf::stack_pack<3>(rnnwf_handle*);
+// the table of one of those images: layer 0 -> h->wsplit, layer l >= 1 -> h->wsplit_up[l - 1]
+int rnnwf::stack_pack_table(rnnwf_handle* h, int layer) {
+    const bool cplx = h->model == RNNWF_MODEL_CRNN_U1, top = layer == h->NL - 1;
+    if (layer == 0) {
+        if (cplx) pack_split_image<kStackNF32, kStackRJ, 3, 2, Lin>(h);
+        else pack_split_image<kStackNF32, kStackRJ, 1, 2, Lin>(h);
+    } else {
+        if (cplx) pack_split_upper_image<kStackNF32, kStackRJ, 3, Lin>(h, layer, top);
+        else pack_split_upper_image<kStackNF32, kStackRJ, 1, Lin>(h, layer, top);
+    }
+    return 0;
+}
 
 namespace {
 // The layer pipeline over `tiles` 32-chain tiles: first (the first layer's kernel, STACK form), then one upper kernel per further layer -

@@ -10,6 +10,7 @@
 #include "sr_kernels.h"
 #include "sr_solve_kernels.h"
 #include "models.h"
+#include "shapes.h"
 #include "tn_gemm.h"
 
 using namespace rnnwf;
@@ -17,6 +18,7 @@ using namespace rnnwf;
 namespace {
 
 constexpr int64_t kSrMaxSamples = 4096;
+constexpr int kSrMaxNFULL = 4;             // up to 68 units
 constexpr int kSrMaxSteps = 1024;          // iterations of one rnnwf_sr_train_steps call: the rows of train.hip's pinned moments table (kMaxSteps)
 
 // 0, or RNNWF_ERR_INVALID "<entry>: <why>" for a handle these entry points do not serve; called before anything is touched
@@ -29,21 +31,18 @@ int sr_refuse(rnnwf_handle* h, const char* entry) {
         case RNNWF_MODEL_LSTM1D_F64: why = "not implemented for the LSTM cell"; break;
         default:
             if (h->NL > 1) why = "not implemented for stacked layers (one GRU layer only)";
-            else if (h->NFULL > 4) why = "not implemented for layers wider than 68 units";
+            else if (h->NFULL > kSrMaxNFULL) why = "not implemented for layers wider than 68 units";
             else if (h->comm) why = "not implemented for a handle with a communicator";
     }
     return why ? h->fail(RNNWF_ERR_INVALID, "%s: %s", entry, why) : 0;
 }
 
+// fn(SrShape<T, NFULL>()) for the handle's row among the one-layer rows of the positive GRU's table up to kSrMaxNFULL (shapes.h)
+template <class R> struct SrRow : std::bool_constant<R::NL == 1 && R::NFULL <= kSrMaxNFULL> {};
 template <class Fn>
 int with_sr_shape(rnnwf_handle* h, Fn&& fn) {
-    const bool f64 = h->model == RNNWF_MODEL_GRU1D_F64;
-    switch (h->NFULL) {
-        case 1: return f64 ? fn(SrShape<double, 1>()) : fn(SrShape<float, 1>());
-        case 2: return f64 ? fn(SrShape<double, 2>()) : fn(SrShape<float, 2>());
-        case 3: return f64 ? fn(SrShape<double, 3>()) : fn(SrShape<float, 3>());
-        case 4: return f64 ? fn(SrShape<double, 4>()) : fn(SrShape<float, 4>());
-    }
+    int rc = 0;
+    if (with_row<SrRow>(GruKernels(), h, [&](auto r) { rc = fn(SrShape<typename decltype(r)::T, decltype(r)::NFULL>()); })) return rc;
     return h->fail(RNNWF_ERR_INVALID, "stochastic reconfiguration: no kernel for NFULL=%d", h->NFULL);
 }
 

@@ -112,52 +112,9 @@ __global__ void apply_direction_kernel(double* __restrict__ P, int64_t n, const 
     P[i] = f32 ? (double)(float)p : p;
 }
 
-// ---- tables: the host packers once more, over Lin ----------------------------------------------------------------------
-template <int NOUT>
-int wimg_table(rnnwf_handle* h) {
-    switch (h->NFULL) {
-        case 1: pack_gru_image<float, 1, NOUT, Lin>(h); return 0;
-        case 2: pack_gru_image<float, 2, NOUT, Lin>(h); return 0;
-        case 3: pack_gru_image<float, 3, NOUT, Lin>(h); return 0;
-        case 4: pack_gru_image<float, 4, NOUT, Lin>(h); return 0;
-        case 6: pack_gru_image<float, 6, NOUT, Lin>(h); return 0;
-        case 8: pack_gru_image<float, 8, NOUT, Lin>(h); return 0;
-        case 12: pack_gru_image<float, 12, NOUT, Lin>(h); return 0;
-        case 16: pack_gru_image<float, 16, NOUT, Lin>(h); return 0;
-    }
-    return 1;
-}
-// the layouts of split.hip / split_stream.hip (SPLIT_DISPATCH, RLaunch), by width class
-template <int NOUT>
-int wsplit_table(rnnwf_handle* h) {
-    switch (h->NFULL) {
-        case 1: pack_split_image<0, 10, NOUT, 1, Lin>(h); return 0;
-        case 2: pack_split_image<1, 2, NOUT, 1, Lin>(h); return 0;
-        case 3: if (h->H <= 50) pack_split_image<1, 9, NOUT, 2, Lin>(h); else pack_split_image<1, 10, NOUT, 0, Lin>(h); return 0;
-        case 4: pack_split_image<2, 2, NOUT, 3, Lin>(h); return 0;
-        case 6: pack_split_image<3, 2, NOUT, 3, Lin>(h); return 0;
-    }
-    return 1;
-}
-int wimg_table_f64(rnnwf_handle* h) {
-    switch (h->NFULL) {
-        case 1: pack_gru_image<double, 1, 1, Lin>(h); return 0;
-        case 2: pack_gru_image<double, 2, 1, Lin>(h); return 0;
-        case 3: pack_gru_image<double, 3, 1, Lin>(h); return 0;
-        case 4: pack_gru_image<double, 4, 1, Lin>(h); return 0;
-        case 6: pack_gru_image<double, 6, 1, Lin>(h); return 0;
-    }
-    return 1;
-}
-int wbasebf_table(rnnwf_handle* h) {
-    switch (h->NFULL) {
-        case 1: pack_base_bf_image<1, Lin>(h); return 0;
-        case 2: pack_base_bf_image<2, Lin>(h); return 0;
-        case 3: pack_base_bf_image<3, Lin>(h); return 0;
-    }
-    return 1;
-}
-
+// ---- tables: the host packers once more, over Lin.  Which packer an image takes is its family's knowledge - the row of its shape
+// table (shapes.h) the forward path launches from: Family::pack_table (h->wimg), Gradient::pack (h->wbwd), split.hip's
+// split_pack_table / stack_pack_table / base_bf_pack_table (the bf16x3 engine's images) - never restated here -------------------
 template <typename Fn>
 int add_image(rnnwf_handle* h, DevBuf* target, Fn&& run_packer) {
     TrainState& t = h->train;
@@ -193,8 +150,6 @@ int build(rnnwf_handle* h) {
     if (int rc = require_gradient(h, "device-resident training")) return rc;
     if (t.built) return t.supported ? 0 : h->fail(RNNWF_ERR_INVALID, "device-resident training is not available for this model: %s", t.why.c_str());
     t.built = true;
-    const bool md = h->model == RNNWF_MODEL_MDRNN2D;
-    const bool cplx = h->model == RNNWF_MODEL_CRNN_U1;
     t.nparams = rnnwf_num_params(h);
     for (DevBuf* b : {&t.P, &t.M, &t.V, &t.G})
         if (int rc = ensure(h, *b, (size_t)t.nparams * 8)) return rc;
@@ -215,31 +170,18 @@ int build(rnnwf_handle* h) {
     RNNWF_HIP(h, hipMemcpy(t.gidx.p, sidx.data(), sidx.size() * 4, hipMemcpyHostToDevice));
     // images (the backward image's table is added on first use: its buffer exists once the gradient has packed it on the host)
     t.nimg = 0;
-    if (md) {
-        if (int rc = add_image(h, &h->wimg, [&] { return mdrnn_pack_table(h); })) return rc;
-    } else if (h->NL > 1) {
-        // a stack: the forward buffer holds [layer 0 | upper layers] (grad.hip knows the layouts); on the bf16x3 engine (37..50 units)
-        // the layer pipeline's images beside it (split.hip: stack_pack)
-        if (int rc = add_image(h, &h->wimg, [&] { return grad_stack_forward_table(h); })) return rc;
-        if (h->engine_split) {
-            if (int rc = add_image(h, &h->wsplit, [&] { if (cplx) pack_split_image<1, 9, 3, 2, Lin>(h); else pack_split_image<1, 9, 1, 2, Lin>(h); return 0; })) return rc;
-            for (int l = 1; l < h->NL; ++l) {
-                const bool top = l == h->NL - 1;
-                if (int rc = add_image(h, &h->wsplit_up[l - 1], [&] {
-                        if (cplx) pack_split_upper_image<1, 9, 3, Lin>(h, l, top); else pack_split_upper_image<1, 9, 1, Lin>(h, l, top);
-                        return 0; })) return rc;
-            }
-        }
-    } else {
-        if (int rc = add_image(h, &h->wimg, [&] { return h->f64 ? wimg_table_f64(h) : cplx ? wimg_table<3>(h) : wimg_table<1>(h); })) return rc;
-        if (h->engine_split) {
-            if (int rc = add_image(h, &h->wsplit, [&] { return cplx ? wsplit_table<3>(h) : wsplit_table<1>(h); })) return rc;
-            if (h->NFULL == 6 && !cplx && h->wsplit16.p)
-                if (int rc = add_image(h, &h->wsplit16, [&] { pack_split16_image<1, Lin>(h); return 0; })) return rc;
-        }
+    if (int rc = add_image(h, &h->wimg, [&] { return h->family->pack_table(h); })) return rc;
+    if (h->engine_split && h->NL > 1) {
+        // a stack on the bf16x3 engine: the layer pipeline's images (split.hip: stack_pack)
+        for (int l = 0; l < h->NL; ++l)
+            if (int rc = add_image(h, l ? &h->wsplit_up[l - 1] : &h->wsplit, [&] { return stack_pack_table(h, l); })) return rc;
+    } else if (h->engine_split) {
+        if (int rc = add_image(h, &h->wsplit, [&] { return split_pack_table(h); })) return rc;
+        if (h->wsplit16.p)                                     // the positive RNN's 16x16x32 form (split_stream.hip)
+            if (int rc = add_image(h, &h->wsplit16, [&] { pack_split16_image<1, Lin>(h); return 0; })) return rc;
     }
     if (h->base_bf)
-        if (int rc = add_image(h, &h->wbasebf, [&] { return wbasebf_table(h); })) return rc;
+        if (int rc = add_image(h, &h->wbasebf, [&] { return base_bf_pack_table(h); })) return rc;
     t.supported = true;
     return 0;
 }
