@@ -468,6 +468,25 @@ int rnnwf_sr_train_steps(rnnwf_handle* h, int32_t K, int64_t numsamples, uint64_
                          const double* couplings, int64_t n_couplings, const double* learning_rates, const double* diag_shifts,
                          double* moments);
 
+/* ---- stochastic reconfiguration for the complex RNN (CRNN_U1; docs/sr_complex.md) ------------------------------------------------
+ * psi = sqrt(P) e^{i phi}, theta real:  O[s][k] = d log psi(sigma_s) / d theta_k = 1/2 d log P / d theta_k + i d phi / d theta_k,
+ * eps_s = E_loc,s - mean E (complex).  S = Re(dO^H dO) / ns and F = Re(dO^H eps) / ns; with the stacked real matrix
+ * Obar = [Re dO ; Im dO] (2 ns x nparams) and ebar = [Re eps ; Im eps], each half centred with its own mean, S = Obar^T Obar / ns,
+ * F = Obar^T ebar / ns (2 F is the gradient rnnwf_vmc_gradient returns) and the minSR direction is
+ *   delta = Obar^T (Obar Obar^T + ns lambda I)^-1 ebar  =  (S + lambda I)^-1 F:
+ * the five calls above on a system of order 2 ns, rows [0, ns) the real parts and rows [ns, 2 ns) the imaginary parts.
+ * rnnwf_log_derivatives_complex: out_re_im (2, ns, nparams) f64 = [Re O ; Im O] (not centred), or NULL.  rnnwf_sr_gram_complex: gram
+ * (2 ns, 2 ns) f64 = Obar Obar^T, exactly symmetric; eps (2 ns,) f64 = ebar.  rnnwf_sr_apply_complex: y (2 ns,) -> Obar^T y (each half of y
+ * is centred).  rnnwf_sr_solve_complex: y (2 ns,) of (gram + ns diag_shift I) y = ebar.  rnnwf_sr_direction_complex: delta (nparams,).
+ * The complex RNN with one layer of at most 68 units; ns <= RNNWF_SR_COMPLEX_MAX_SAMPLES.  Refusals, state rules, workspace check (with
+ * 2 ns rows), pivot status and error codes as for the five calls above; RNNWF_ERR_INVALID "<entry>: <why>" for every other model.  */
+#define RNNWF_SR_COMPLEX_MAX_SAMPLES 2048
+int rnnwf_log_derivatives_complex(rnnwf_handle* h, double* out_re_im, int64_t ns, int64_t nparams);
+int rnnwf_sr_gram_complex(rnnwf_handle* h, double* gram, double* eps);
+int rnnwf_sr_apply_complex(rnnwf_handle* h, const double* y, double* out_direction);
+int rnnwf_sr_solve_complex(rnnwf_handle* h, double diag_shift, double* y);
+int rnnwf_sr_direction_complex(rnnwf_handle* h, double diag_shift, double* out_direction);
+
 /* ---- multi-GPU: one RCCL all-reduce of the energy moments -------------------------------------
  * The reference is single-process; these add the one data-parallel collective of SURVEY.md 8e.
  * One process per GPU: rank 0 calls rnnwf_comm_unique_id and ships the 128 bytes to the other

@@ -17,6 +17,7 @@ ABI_VERSION = 1
 MAX_LAYERS = 4
 UNIQUE_ID_BYTES = 128
 SR_BLOCK = 32          # block width of the device Cholesky solve (kSrNB in csrc/sr_solve_kernels.h)
+SR_COMPLEX_MAX_SAMPLES = 2048    # RNNWF_SR_COMPLEX_MAX_SAMPLES: the complex RNN's minSR system has 2 ns <= 4096 rows
 
 
 class Config(C.Structure):
@@ -85,6 +86,11 @@ PROTOTYPES = {
     "rnnwf_sr_solve": (C.c_int, [_P, _F64, _F64P]),
     "rnnwf_sr_direction": (C.c_int, [_P, _F64, _F64P]),
     "rnnwf_sr_train_steps": (C.c_int, [_P, _I32, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _I64, _F64P, _F64P, _F64P]),
+    "rnnwf_log_derivatives_complex": (C.c_int, [_P, _F64P, _I64, _I64]),
+    "rnnwf_sr_gram_complex": (C.c_int, [_P, _F64P, _F64P]),
+    "rnnwf_sr_apply_complex": (C.c_int, [_P, _F64P, _F64P]),
+    "rnnwf_sr_solve_complex": (C.c_int, [_P, _F64, _F64P]),
+    "rnnwf_sr_direction_complex": (C.c_int, [_P, _F64, _F64P]),
     "rnnwf_resident_samples": (_I64, [_P]),
     "rnnwf_timing_enable": (C.c_int, [_P, _I32]),
     "rnnwf_timing_reset": (C.c_int, [_P]),
@@ -412,6 +418,47 @@ class NativeWavefunction:
         self._check(self.lib.rnnwf_sr_train_steps(self.h, K, int(numsamples), seed, step0, sample_offset, cp, c.size, lrp, lamp,
                                                   mom.ctypes.data_as(_F64P)))
         return mom
+
+    # -- stochastic reconfiguration for the complex RNN: rnnwf_*_complex (docs/sr_complex.md) ------
+    def log_derivatives_complex(self):
+        """(ns, num_params) complex128: O[s, k] = d log psi(sigma_s) / d theta_k = 1/2 d log P / d theta_k + i d phi / d theta_k on the
+        resident batch, theta (real) in the flat order of _layout()."""
+        ns, n = self.resident_samples(), self.num_params()
+        out = np.empty((2, ns, n), dtype=np.float64)
+        self._check(self.lib.rnnwf_log_derivatives_complex(self.h, out.ctypes.data_as(_F64P), ns, n))
+        return out[0] + 1j * out[1]
+
+    def sr_gram_complex(self):
+        """(gram, eps): Obar Obar^T (2 ns, 2 ns) for Obar = [Re dO ; Im dO] and eps = [Re (E_loc - mean E) ; Im (E_loc - mean E)]
+        (2 ns,) of the resident batch, float64, each half centred with its own mean; gram is exactly symmetric."""
+        n = 2 * self.resident_samples()
+        gram, eps = np.empty((n, n), dtype=np.float64), np.empty(n, dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_gram_complex(self.h, gram.ctypes.data_as(_F64P), eps.ctypes.data_as(_F64P)))
+        return gram, eps
+
+    def sr_apply_complex(self, y):
+        """(num_params,) float64: Obar^T y for y (2 ns,) = [weights of the real rows ; weights of the imaginary rows]."""
+        yv, yp = _f64(y)
+        ns = self.resident_samples()
+        if ns > 0 and yv.shape != (2 * ns,):
+            raise ValueError("sr_apply_complex: y must have shape (%d,), two entries per sample of the resident batch, got %r"
+                             % (2 * ns, yv.shape))
+        out = np.empty(self.num_params(), dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_apply_complex(self.h, yp if ns > 0 else None, out.ctypes.data_as(_F64P)))
+        return out
+
+    def sr_solve_complex(self, diag_shift):
+        """(2 ns,) float64: y of (Obar Obar^T + ns diag_shift I) y = eps, factorised and solved on the device; y is not centred."""
+        y = np.empty(2 * self.resident_samples(), dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_solve_complex(self.h, float(diag_shift), y.ctypes.data_as(_F64P)))
+        return y
+
+    def sr_direction_complex(self, diag_shift):
+        """(num_params,) float64: the minSR direction Obar^T (Obar Obar^T + ns diag_shift I)^-1 eps of the resident batch, everything
+        on the device (rnnwf_sr_direction_complex), in the flat order of _layout()."""
+        out = np.empty(self.num_params(), dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_direction_complex(self.h, float(diag_shift), out.ctypes.data_as(_F64P)))
+        return out
 
     # -- device-resident training iteration (rnnwf_train_steps; single-layer float32 GRU models) ------------------
     def device_training_supported(self):

@@ -62,6 +62,8 @@ struct GradArgs {
     // the layer above instead of from the head, and hck holds hck_nl layers per (site, block)
     const void* dh_in;         // [N][nsb][KT][64] T or nullptr
     int32_t hck_nl;            // layers per checkpoint entry (0 or 1: single layer)
+    int32_t sr_im;             // unit-weight mode (SR) of the complex RNN: 0 seeds (w, w_im) = (1, 0), the rows of d Re log psi; 1 seeds
+                               // (0, 1), those of d Im log psi (in the struct's tail padding: the other fields stay where they were)
 };
 
 // Shared by gru_bwd_kernel and gru_upper_bwd_kernel; the other pieces the two kernels have in common stay written out in each
@@ -133,11 +135,13 @@ struct GradPair {
     static constexpr bool FITS = !GruLayout<T, NFULL, NOUT>::SPILL && LDS <= 160 * 1024;
 };
 
-// SR (sr.hip: the per-sample log-derivatives; NOUT = 1, no PAIR): unit weights w_s = 1 (no E_loc, no wfac) and the head row of every
-// chain kept on its own, head_part = [ns][HEAD_ROW] - slot 4 k + q a unit, 4 KT the bias - instead of one sum per wave.
+// SR (sr.hip: the per-sample log-derivatives; no PAIR): unit weights w_s = 1 (no E_loc, no wfac) and the head rows of every
+// chain kept on their own, head_part = [ns][NOUT][HEAD_ROW] - slot 4 k + q a unit, 4 KT the bias - instead of one sum per wave.
+// Complex RNN (NOUT = 3): one launch per seed (GradArgs::sr_im), (w, w_im) = (1, 0) for d Re log psi = 1/2 d log P and (0, 1) for
+// d Im log psi = d phi; the Q rows are the same for both.
 template <typename T, int NFULL, int WAVES, int NOUT, bool PAIR = false, bool SR = false>
 __global__ void __launch_bounds__(WAVES * 64) gru_bwd_kernel(GradArgs a) {
-    static_assert(!SR || (NOUT == 1 && !PAIR), "per-sample head rows: positive RNN, one wave per 16-chain block (no forward / backward wave pair)");
+    static_assert(!SR || !PAIR, "per-sample head rows: one wave per 16-chain block (no forward / backward wave pair)");
     using C = GruCore<T, NFULL, NOUT>;
     using G = GradLayout<NFULL, T>;
     using V4 = typename C::V4;
@@ -196,10 +200,16 @@ __global__ void __launch_bounds__(WAVES * 64) gru_bwd_kernel(GradArgs a) {
         const int64_t sc = valid ? s : a.ns - 1;
         T w = T(0), w_im = T(0);
         if constexpr (SR) {
-            if (valid) w = T(1);
-            gb[0] = HA(0);
+            if (valid) {
+                w = NOUT == 3 && a.sr_im ? T(0) : T(1);
+                w_im = NOUT == 3 && a.sr_im ? T(1) : T(0);
+            }
 #pragma unroll
-            for (int k = 0; k < KT; ++k) hg[0][k] = HA(0);
+            for (int o = 0; o < NOUT; ++o) {
+                gb[o] = HA(0);
+#pragma unroll
+                for (int k = 0; k < KT; ++k) hg[o][k] = HA(0);
+            }
         } else if (valid) {
             const double mean_e = a.mom ? a.mom[0] / a.mom[2] : a.mean_e, mean_im = a.mom ? a.mom[3] / a.mom[2] : a.mean_im;
             const double inv_norm = a.mom ? a.inv_norm / a.mom[2] : a.inv_norm;
@@ -372,10 +382,13 @@ __global__ void __launch_bounds__(WAVES * 64) gru_bwd_kernel(GradArgs a) {
         }
         if constexpr (SR) {
             if (valid) {
-                T* row = reinterpret_cast<T*>(a.head_part) + s * G::HEAD_ROW;
 #pragma unroll
-                for (int k = 0; k < KT; ++k) row[4 * k + q] = (T)hg[0][k];
-                row[4 * KT + q] = q == 0 ? (T)gb[0] : T(0);
+                for (int o = 0; o < NOUT; ++o) {
+                    T* row = reinterpret_cast<T*>(a.head_part) + (s * NOUT + o) * G::HEAD_ROW;
+#pragma unroll
+                    for (int k = 0; k < KT; ++k) row[4 * k + q] = (T)hg[o][k];
+                    row[4 * KT + q] = q == 0 ? (T)gb[o] : T(0);
+                }
             }
         }
     }

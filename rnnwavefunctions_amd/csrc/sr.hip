@@ -4,6 +4,8 @@
 // log-derivatives J[ns][D] stay on the device in the order of the gradient image (grad.hip) and are read through the table
 // grad_flat_probe builds; the ns x ns solve is the caller's (rnnwf_sr_gram + rnnwf_sr_apply) or the device's (rnnwf_sr_solve,
 // rnnwf_sr_direction: blocked f64 Cholesky, sr_solve_kernels.h).
+// The complex RNN (CRNN_U1, one layer, up to 68 units) has the same five calls as rnnwf_*_complex (docs/sr_complex.md): J[2 ns][D_c]
+// = [Re O ; Im O], each half centred with its own mean, and the same solve path on a system of order 2 ns.
 #include <cmath>
 #include <cstring>
 
@@ -17,13 +19,33 @@ using namespace rnnwf;
 
 namespace {
 
-constexpr int64_t kSrMaxSamples = 4096;
+constexpr int64_t kSrMaxSamples = 4096;   // the largest order of the Gram matrix and the solve
+static_assert(2 * RNNWF_SR_COMPLEX_MAX_SAMPLES == kSrMaxSamples, "the complex RNN's system has 2 ns rows");
 constexpr int kSrMaxNFULL = 4;             // up to 68 units
 constexpr int kSrMaxSteps = 1024;          // iterations of one rnnwf_sr_train_steps call: the rows of train.hip's pinned moments table (kMaxSteps)
 
+// An entry point: its name, and whether it is one of the complex RNN's (rnnwf_*_complex, docs/sr_complex.md).  Which handles an entry
+// serves depends on the entry; once it has accepted a handle, the handle's model decides everything else (sr_halves).
+struct SrEntry {
+    const char* name;
+    bool complex;
+};
+
+// the row blocks of J with a column mean of their own: [Re O ; Im O] for the complex RNN, whose system has 2 ns rows
+int64_t sr_halves(const rnnwf_handle* h) { return h->model == RNNWF_MODEL_CRNN_U1 ? 2 : 1; }
+int64_t sr_order(const rnnwf_handle* h) { return sr_halves(h) * h->sr_ns; }
+
 // 0, or RNNWF_ERR_INVALID "<entry>: <why>" for a handle these entry points do not serve; called before anything is touched
-int sr_refuse(rnnwf_handle* h, const char* entry) {
+int sr_refuse(rnnwf_handle* h, const SrEntry& e) {
+    const char* entry = e.name;
     const char* why = nullptr;
+    if (e.complex) {
+        if (h->model != RNNWF_MODEL_CRNN_U1) why = "only for the complex RNN (RNNWF_MODEL_CRNN_U1)";
+        else if (h->NL > 1) why = "not implemented for stacked layers (one GRU layer only)";
+        else if (h->NFULL > kSrMaxNFULL) why = "not implemented for layers wider than 68 units";
+        else if (h->comm) why = "not implemented for a handle with a communicator";
+        return why ? h->fail(RNNWF_ERR_INVALID, "%s: %s", entry, why) : 0;
+    }
     switch (h->model) {
         case RNNWF_MODEL_GRU1D_PARITY: why = "not implemented for the parity model (its symmetrised P has two directions per sample)"; break;
         case RNNWF_MODEL_CRNN_U1: why = "not implemented for the complex RNN"; break;
@@ -37,12 +59,16 @@ int sr_refuse(rnnwf_handle* h, const char* entry) {
     return why ? h->fail(RNNWF_ERR_INVALID, "%s: %s", entry, why) : 0;
 }
 
-// fn(SrShape<T, NFULL>()) for the handle's row among the one-layer rows of the positive GRU's table up to kSrMaxNFULL (shapes.h)
+// fn(SrShape<T, NFULL, NOUT>()) for the handle's row among the one-layer rows of its family's table up to kSrMaxNFULL (shapes.h):
+// the positive GRU's (NOUT 1) or the complex RNN's (NOUT 3)
 template <class R> struct SrRow : std::bool_constant<R::NL == 1 && R::NFULL <= kSrMaxNFULL> {};
 template <class Fn>
 int with_sr_shape(rnnwf_handle* h, Fn&& fn) {
     int rc = 0;
-    if (with_row<SrRow>(GruKernels(), h, [&](auto r) { rc = fn(SrShape<typename decltype(r)::T, decltype(r)::NFULL>()); })) return rc;
+    const bool hit = h->model == RNNWF_MODEL_CRNN_U1
+        ? with_row<SrRow>(CrnnKernels(), h, [&](auto r) { rc = fn(SrShape<typename decltype(r)::T, decltype(r)::NFULL, 3>()); })
+        : with_row<SrRow>(GruKernels(), h, [&](auto r) { rc = fn(SrShape<typename decltype(r)::T, decltype(r)::NFULL>()); });
+    if (hit) return rc;
     return h->fail(RNNWF_ERR_INVALID, "stochastic reconfiguration: no kernel for NFULL=%d", h->NFULL);
 }
 
@@ -55,13 +81,14 @@ int64_t sr_image_size(rnnwf_handle* h) {
 // RNNWF_ERR_NOMEM unless the workspace of a batch of ns samples fits; `factor`: with the ns x ns Cholesky factor
 int sr_workspace(rnnwf_handle* h, const char* entry, int64_t ns, bool factor) {
     const size_t es = h->f64 ? 8 : 4;
-    // the factor's workspace: ns^2 doubles, eps, y, the status word and the diagonal blocks (sr_solve_device), all counted
-    const size_t nb = (size_t)(ns + kSrNB - 1) / kSrNB;
-    const size_t fac = factor ? ((size_t)ns * ns + 2 * (size_t)ns + 1 + nb * kSrNB * kSrNB) * 8 : 0;
-    const size_t need = (size_t)ns * (size_t)sr_image_size(h) * es + (size_t)ns * ns * 8 + fac;
-    if (ns > kSrMaxSamples || need > state_budget_bytes(h, kDefaultStateBudget))
+    const size_t n = (size_t)(sr_halves(h) * ns);              // rows of J, order of the Gram matrix and of the solve
+    // the factor's workspace: n^2 doubles, eps, y, the status word and the diagonal blocks (sr_solve_device), all counted
+    const size_t nb = (n + kSrNB - 1) / kSrNB;
+    const size_t fac = factor ? (n * n + 2 * n + 1 + nb * kSrNB * kSrNB) * 8 : 0;
+    const size_t need = n * (size_t)sr_image_size(h) * es + n * n * 8 + fac;
+    if ((int64_t)n > kSrMaxSamples || need > state_budget_bytes(h, kDefaultStateBudget))
         return h->fail(RNNWF_ERR_NOMEM, "%s: ns too large for the SR workspace (%lld samples: Jacobian + Gram matrix%s take %zu bytes; at most %lld samples)",
-                       entry, (long long)ns, factor ? " + Cholesky factor" : "", need, (long long)kSrMaxSamples);
+                       entry, (long long)ns, factor ? " + Cholesky factor" : "", need, (long long)(kSrMaxSamples / sr_halves(h)));
     return 0;
 }
 
@@ -69,9 +96,10 @@ int sr_committed(rnnwf_handle* h, const char* entry) {
     return h->committed ? 0 : h->fail(RNNWF_ERR_STATE, "%s: parameters not committed (call rnnwf_commit_params)", entry);
 }
 
-// refusals, then the state checks every entry point on the resident batch shares; `factor`: the entry also holds the ns x ns Cholesky factor
-int sr_ready(rnnwf_handle* h, const char* entry, bool factor = false) {
-    if (int rc = sr_refuse(h, entry)) return rc;
+// refusals, then the state checks every entry point on the resident batch shares; `factor`: the entry also holds the Cholesky factor
+int sr_ready(rnnwf_handle* h, const SrEntry& e, bool factor = false) {
+    const char* entry = e.name;
+    if (int rc = sr_refuse(h, e)) return rc;
     if (int rc = sr_committed(h, entry)) return rc;
     if (h->last_ns <= 0) return h->fail(RNNWF_ERR_STATE, "%s: call rnnwf_vmc_step first (its samples, states and E_loc are reused)", entry);
     if (int rc = sr_workspace(h, entry, h->last_ns, factor)) return rc;
@@ -95,29 +123,36 @@ int sr_table(rnnwf_handle* h, int64_t D) {
     return 0;
 }
 
-template <typename T, int NFULL>
+template <class S>
 int sr_build_shape(rnnwf_handle* h) {
-    using S = SrShape<T, NFULL>;
+    using T = typename S::Elem;
     using G = typename S::G;
-    using L = GruLayout<T, NFULL, 1>;
+    constexpr int NFULL = S::NF, NOUT = S::NOUT;
+    using L = GruLayout<T, NFULL, NOUT>;
     const int N = h->N;
     const int64_t ns = h->last_ns, R = ns * N, nsb = (ns + kChains - 1) / kChains;
     if (int rc = sr_table(h, S::D)) return rc;
     if (int rc = grad_bwd_image(h)) return rc;
     if (int rc = ensure(h, h->gradP, (size_t)R * G::PCOLS * sizeof(T))) return rc;
     if (int rc = ensure(h, h->gradQ, (size_t)R * G::QCOLS * sizeof(T))) return rc;
-    if (int rc = ensure(h, h->srHead, (size_t)ns * G::HEAD_ROW * sizeof(T))) return rc;
-    if (int rc = ensure(h, h->srJ, (size_t)ns * S::D * sizeof(T))) return rc;
+    if (int rc = ensure(h, h->srHead, (size_t)ns * NOUT * G::HEAD_ROW * sizeof(T))) return rc;
+    if (int rc = ensure(h, h->srJ, (size_t)sr_halves(h) * ns * S::D * sizeof(T))) return rc;
     GradArgs a{};
     grad_batch_args(h, &a);                                // (one layer: sr_refuse)
     a.wimg = h->wimg.p;
-    a.head_part = h->srHead.p;                             // [ns][HEAD_ROW]: one row per chain (gru_bwd_kernel<SR>)
-    constexpr size_t lds = L::LDS_BYTES + (GradStream<T, NFULL, 1>::value ? 0 : G::BWD_BYTES);
+    a.head_part = h->srHead.p;                             // [ns][NOUT][HEAD_ROW]: the head rows of every chain (gru_bwd_kernel<SR>)
+    constexpr size_t lds = L::LDS_BYTES + (GradStream<T, NFULL, NOUT>::value ? 0 : G::BWD_BYTES);
     static_assert(lds <= 160 * 1024, "forward + backward weight images exceed the LDS");
-    if (int rc = launch_persistent(h, kTimerBackprop, gru_bwd_kernel<T, NFULL, 4, 1, false, true>, 4 * 64, lds, nsb, 4, a)) return rc;
-    if (int rc = launch_persistent(h, kTimerGemm, sr_outer_kernel<T, NFULL>, S::WAVES * 64, 0, ns, 1, (const T*)h->gradP.p, (const T*)h->gradQ.p,
-                                   (const T*)h->srHead.p, (const uint8_t*)h->srMask.p, N, ns, (T*)h->srJ.p))
-        return rc;
+    // complex RNN: one backward pass and one outer-product pass per seed, Re O into the rows [0, ns) and Im O into [ns, 2 ns).  Both
+    // go through the same P, Q and head rows - the second pass starts after the first half is written (one stream); Q is the same twice
+    for (int half = 0; half < (int)sr_halves(h); ++half) {
+        a.sr_im = half;
+        if (int rc = launch_persistent(h, kTimerBackprop, gru_bwd_kernel<T, NFULL, 4, NOUT, false, true>, 4 * 64, lds, nsb, 4, a)) return rc;
+        if (int rc = launch_persistent(h, kTimerGemm, sr_outer_kernel<T, NFULL, NOUT>, S::WAVES * 64, 0, ns, 1, (const T*)h->gradP.p,
+                                       (const T*)h->gradQ.p, (const T*)h->srHead.p, (const uint8_t*)h->srMask.p, N, ns,
+                                       (T*)h->srJ.p + (size_t)half * ns * S::D))
+            return rc;
+    }
     h->sr_ns = ns;
     h->sr_valid = true;
     return 0;
@@ -127,54 +162,64 @@ int sr_build_shape(rnnwf_handle* h) {
 int sr_build(rnnwf_handle* h) {
     if (h->sr_valid && h->sr_ns == h->last_ns) return 0;
     h->sr_valid = false;
-    return with_sr_shape(h, [&](auto s) { return sr_build_shape<typename decltype(s)::Elem, decltype(s)::NF>(h); });
+    return with_sr_shape(h, [&](auto s) { return sr_build_shape<decltype(s)>(h); });
 }
 
-template <typename T>
-int sr_colsum(rnnwf_handle* h, int64_t D, const double* w, double scale, double* out) {
-    return launch_persistent(h, kTimerGemm, sr_colsum_kernel<T>, 256, 0, (D + 63) / 64, 1, (const T*)h->srJ.p, h->sr_ns, D, w, scale, out);
+// out[k] = scale sum_s w_s J[row0 + s][k] over `rows` rows of the resident Jacobian
+int sr_colsum(rnnwf_handle* h, int64_t D, int64_t row0, int64_t rows, const double* w, double scale, double* out) {
+    return h->f64 ? launch_persistent(h, kTimerGemm, sr_colsum_kernel<double>, 256, 0, (D + 63) / 64, 1, (const double*)h->srJ.p + row0 * D, rows, D,
+                                      w, scale, out)
+                  : launch_persistent(h, kTimerGemm, sr_colsum_kernel<float>, 256, 0, (D + 63) / 64, 1, (const float*)h->srJ.p + row0 * D, rows, D,
+                                      w, scale, out);
 }
 
-// the column mean and the centred Gram matrix of the resident Jacobian, into h->srCol[0 .. D) and h->srGram
+template <typename T, bool HALVES>
+int sr_gram_launch(rnnwf_handle* h, int64_t n, int64_t D, const double* mean) {
+    const int64_t nb = (n + 31) / 32, nblocks = nb * (nb + 1) / 2;
+    return launch_persistent(h, kTimerGemm, sr_gram_kernel<T, HALVES>, 256, 0, nblocks, 1, (const T*)h->srJ.p, mean, (const uint8_t*)h->srMask.p, n, D,
+                             nblocks, (double*)h->srGram.p);
+}
+
+// the column mean(s) and the centred Gram matrix of the resident Jacobian, into h->srCol[0 .. halves D) and h->srGram; h->srCol has
+// room for one more image behind the means (sr_direction_image)
 int sr_gram_device(rnnwf_handle* h) {
-    const int64_t ns = h->sr_ns, D = sr_image_size(h);
-    if (int rc = ensure(h, h->srCol, (size_t)2 * D * 8)) return rc;
-    if (int rc = ensure(h, h->srGram, (size_t)ns * ns * 8)) return rc;
+    const int64_t ns = h->sr_ns, halves = sr_halves(h), n = sr_order(h), D = sr_image_size(h);
+    if (int rc = ensure(h, h->srCol, (size_t)(halves + 1) * D * 8)) return rc;
+    if (int rc = ensure(h, h->srGram, (size_t)n * n * 8)) return rc;
     double* mean = (double*)h->srCol.p;
-    if (int rc = h->f64 ? sr_colsum<double>(h, D, nullptr, 1.0 / (double)ns, mean) : sr_colsum<float>(h, D, nullptr, 1.0 / (double)ns, mean)) return rc;
-    const int64_t nb = (ns + 31) / 32, nblocks = nb * (nb + 1) / 2;
-    if (int rc = h->f64 ? launch_persistent(h, kTimerGemm, sr_gram_kernel<double>, 256, 0, nblocks, 1, (const double*)h->srJ.p, (const double*)mean,
-                                            (const uint8_t*)h->srMask.p, ns, D, nblocks, (double*)h->srGram.p)
-                        : launch_persistent(h, kTimerGemm, sr_gram_kernel<float>, 256, 0, nblocks, 1, (const float*)h->srJ.p, (const double*)mean,
-                                            (const uint8_t*)h->srMask.p, ns, D, nblocks, (double*)h->srGram.p))
-        return rc;
-    return 0;
+    for (int64_t half = 0; half < halves; ++half)
+        if (int rc = sr_colsum(h, D, half * ns, ns, nullptr, 1.0 / (double)ns, mean + half * D)) return rc;
+    if (halves == 2) return sr_gram_launch<float, true>(h, n, D, mean);         // (the complex RNN is float32)
+    return h->f64 ? sr_gram_launch<double, false>(h, n, D, mean) : sr_gram_launch<float, false>(h, n, D, mean);
 }
 
-// (gram + ns diag_shift I) y = eps on the device: eps from the resident local energies into the eps row of the workspace, per
-// panel the diagonal factorisation + panel solve and the trailing update, then the backward sweep.  Leaves y and the pivot
+// (gram + ns diag_shift I) y = eps on the device, of order n = sr_order: eps from the resident local energies into the eps row of the
+// workspace, per panel the diagonal factorisation + panel solve and the trailing update, then the backward sweep.  Leaves y and the pivot
 // status word behind the eps row (sr_y / sr_status), the factors of the diagonal blocks behind those; nothing is synchronised here.
-double* sr_y(rnnwf_handle* h) { return (double*)h->srFac.p + (size_t)h->sr_ns * h->sr_ns + (size_t)h->sr_ns; }
-long long* sr_status(rnnwf_handle* h) { return (long long*)(sr_y(h) + h->sr_ns); }
+double* sr_y(rnnwf_handle* h) { return (double*)h->srFac.p + (size_t)sr_order(h) * sr_order(h) + (size_t)sr_order(h); }
+long long* sr_status(rnnwf_handle* h) { return (long long*)(sr_y(h) + sr_order(h)); }
 
 int sr_solve_device(rnnwf_handle* h, double diag_shift) {
-    const int64_t ns = h->sr_ns;
-    const int nb = (int)((ns + kSrNB - 1) / kSrNB);
-    if (int rc = ensure(h, h->srFac, ((size_t)ns * ns + 2 * (size_t)ns + 1 + (size_t)nb * kSrNB * kSrNB) * 8)) return rc;
+    const int64_t ns = h->sr_ns, n = sr_order(h);
+    const int nb = (int)((n + kSrNB - 1) / kSrNB);
+    if (int rc = ensure(h, h->srFac, ((size_t)n * n + 2 * (size_t)n + 1 + (size_t)nb * kSrNB * kSrNB) * 8)) return rc;
     double* F = (double*)h->srFac.p;
     double* Ld = (double*)(sr_status(h) + 1);                // the factorised diagonal blocks
     const double* gram = (const double*)h->srGram.p;
-    const double shift = (double)ns * diag_shift;
-    if (int rc = timed_launch(h, kTimerGemm, sr_centre_kernel, 1, 256, 0, (const double*)h->eloc.p, ns, F + (size_t)ns * ns, sr_status(h))) return rc;
+    const double shift = (double)ns * diag_shift;            // ns, not the order: the shift of S = O^T O / ns
+    if (int rc = sr_halves(h) == 2
+            ? timed_launch(h, kTimerGemm, sr_centre_complex_kernel, 2, 256, 0, (const float2*)h->eloc.p, ns, F + (size_t)n * n, sr_status(h))
+            : timed_launch(h, kTimerGemm, sr_centre_kernel, 1, 256, 0, (const double*)h->eloc.p, ns, F + (size_t)n * n, sr_status(h)))
+        return rc;
     for (int k = 0; k < nb; ++k) {
         const double* src = k == 0 ? gram : F;
-        if (int rc = launch_persistent(h, kTimerGemm, sr_chol_panel_kernel, 256, 0, nb - k, 1, src, F, ns, k, shift, Ld, sr_status(h))) return rc;
+        if (int rc = launch_persistent(h, kTimerGemm, sr_chol_panel_kernel, 256, 0, nb - k, 1, src, F, n, k, shift, Ld, sr_status(h))) return rc;
         const int64_t m = nb - k - 1, nitems = m * (m + 1) / 2 + m;
         if (nitems > 0)
-            if (int rc = launch_persistent(h, kTimerGemm, sr_chol_update_kernel, 256, 0, nitems, 1, src, F, ns, k, nitems)) return rc;
+            if (int rc = launch_persistent(h, kTimerGemm, sr_chol_update_kernel, 256, 0, nitems, 1, src, F, n, k, nitems)) return rc;
     }
     for (int k = nb - 1; k >= 0; --k)
-        if (int rc = launch_persistent(h, kTimerGemm, sr_chol_back_kernel, 64, 0, k + 1, 1, F, (const double*)Ld, ns, k, sr_y(h))) return rc;
+        if (int rc = launch_persistent(h, kTimerGemm, sr_chol_back_kernel, 64, 0, k + 1, 1, F, (const double*)Ld, n, k, sr_y(h))) return rc;
     return 0;
 }
 
@@ -190,22 +235,24 @@ int sr_solve_queue(rnnwf_handle* h, double diag_shift) {
     return sr_solve_device(h, diag_shift);
 }
 
-int sr_solve_common(rnnwf_handle* h, const char* entry, double diag_shift) {
-    if (int rc = sr_check_shift(h, entry, diag_shift)) return rc;
-    if (int rc = sr_ready(h, entry, true)) return rc;
+int sr_solve_common(rnnwf_handle* h, const SrEntry& e, double diag_shift) {
+    if (int rc = sr_check_shift(h, e.name, diag_shift)) return rc;
+    if (int rc = sr_ready(h, e, true)) return rc;
     return sr_solve_queue(h, diag_shift);
 }
 
-// behind sr_solve_queue: dO^T y = J^T (y - mean y), as rnnwf_sr_apply, with the centring on the device; the direction's image is
-// left in sr_direction_image(h), nothing is synchronised
-double* sr_direction_image(rnnwf_handle* h) { return (double*)h->srCol.p + sr_image_size(h); }
+// behind sr_solve_queue: dO^T y = J^T (y - mean y), as rnnwf_sr_apply, with the centring on the device (each half of y with its own
+// mean); the direction's image is left in sr_direction_image(h), nothing is synchronised
+double* sr_direction_image(rnnwf_handle* h) { return (double*)h->srCol.p + sr_halves(h) * sr_image_size(h); }
 
 int sr_direction_queue(rnnwf_handle* h) {
-    const int64_t ns = h->sr_ns, D = sr_image_size(h);
-    if (int rc = ensure(h, h->srY, (size_t)ns * 8)) return rc;
-    if (int rc = timed_launch(h, kTimerGemm, sr_centre_kernel, 1, 256, 0, (const double*)sr_y(h), ns, (double*)h->srY.p, (long long*)nullptr)) return rc;
-    double* col = sr_direction_image(h);
-    return h->f64 ? sr_colsum<double>(h, D, (const double*)h->srY.p, 1.0, col) : sr_colsum<float>(h, D, (const double*)h->srY.p, 1.0, col);
+    const int64_t ns = h->sr_ns, n = sr_order(h), D = sr_image_size(h);
+    if (int rc = ensure(h, h->srY, (size_t)n * 8)) return rc;
+    for (int64_t half = 0; half < sr_halves(h); ++half)
+        if (int rc = timed_launch(h, kTimerGemm, sr_centre_kernel, 1, 256, 0, (const double*)sr_y(h) + half * ns, ns, (double*)h->srY.p + half * ns,
+                                  (long long*)nullptr))
+            return rc;
+    return sr_colsum(h, D, 0, n, (const double*)h->srY.p, 1.0, sr_direction_image(h));
 }
 
 // rnnwf_sr_train_steps: iteration k's pivot status word into its slot of the call's table, and into the sticky word when that is
@@ -235,59 +282,77 @@ void sr_gather(const std::vector<int32_t>& sidx, const T* img, double* flat) {
 
 extern "C" int64_t rnnwf_resident_samples(const rnnwf_handle* h) { return h ? h->last_ns : 0; }
 
-extern "C" int rnnwf_log_derivatives(rnnwf_handle* h, double* out, int64_t ns, int64_t nparams) {
+// ---- the five calls on the resident batch, each behind the positive GRU's entry and the complex RNN's (docs/sr_complex.md) ---------
+// Below the refusal the two run the same code on sr_halves(h) row blocks of ns rows: n = sr_order(h) rows of J, a Gram matrix and a
+// solve of order n, y and eps of n entries ([Re ; Im] for the complex RNN).
+
+static int sr_log_derivatives(rnnwf_handle* h, const SrEntry& e, double* out, int64_t ns, int64_t nparams) {
     if (!h) return RNNWF_ERR_INVALID;
-    if (int rc = sr_ready(h, "rnnwf_log_derivatives")) return rc;
+    if (int rc = sr_ready(h, e)) return rc;
     if (out && (ns != h->last_ns || nparams != rnnwf_num_params(h)))
-        return h->fail(RNNWF_ERR_INVALID, "rnnwf_log_derivatives: the resident batch has %lld samples and the model %lld parameters, caller passed %lld and %lld",
+        return h->fail(RNNWF_ERR_INVALID, "%s: the resident batch has %lld samples and the model %lld parameters, caller passed %lld and %lld", e.name,
                        (long long)h->last_ns, (long long)rnnwf_num_params(h), (long long)ns, (long long)nparams);
     if (int rc = sr_build(h)) return rc;
     if (!out) return RNNWF_OK;
-    const int64_t D = sr_image_size(h);
-    const size_t bytes = (size_t)h->sr_ns * D * (h->f64 ? 8 : 4);
+    const int64_t D = sr_image_size(h), n = sr_order(h);
+    const size_t bytes = (size_t)n * D * (h->f64 ? 8 : 4);
     if (int rc = ensure_staging(h, bytes)) return rc;
     RNNWF_HIP(h, hipMemcpyAsync(h->staging, h->srJ.p, bytes, hipMemcpyDeviceToHost, h->stream));
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    for (int64_t s = 0; s < h->sr_ns; ++s) {
+    for (int64_t s = 0; s < n; ++s) {
         if (h->f64) sr_gather(h->sr_sidx, (const double*)h->staging + s * D, out + s * nparams);
         else sr_gather(h->sr_sidx, (const float*)h->staging + s * D, out + s * nparams);
     }
     return RNNWF_OK;
 }
 
-extern "C" int rnnwf_sr_gram(rnnwf_handle* h, double* gram, double* eps) {
+// v[s] -= the mean of the ns entries, the sum taken in order
+static void sr_centre_host(double* v, int64_t ns) {
+    double sum = 0.0;
+    for (int64_t s = 0; s < ns; ++s) sum += v[s];
+    const double mean = sum / (double)ns;
+    for (int64_t s = 0; s < ns; ++s) v[s] -= mean;
+}
+
+static int sr_gram(rnnwf_handle* h, const SrEntry& e, double* gram, double* eps) {
     if (!h) return RNNWF_ERR_INVALID;
-    if (int rc = sr_ready(h, "rnnwf_sr_gram")) return rc;
-    if (!gram || !eps) return h->fail(RNNWF_ERR_INVALID, "rnnwf_sr_gram: bad arguments");
+    if (int rc = sr_ready(h, e)) return rc;
+    if (!gram || !eps) return h->fail(RNNWF_ERR_INVALID, "%s: bad arguments", e.name);
     if (int rc = sr_build(h)) return rc;
     if (int rc = sr_gram_device(h)) return rc;
-    const int64_t ns = h->sr_ns;
-    RNNWF_HIP(h, hipMemcpyAsync(gram, h->srGram.p, (size_t)ns * ns * 8, hipMemcpyDeviceToHost, h->stream));
-    RNNWF_HIP(h, hipMemcpyAsync(eps, h->eloc.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream));
-    RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    double sum = 0.0;
-    for (int64_t s = 0; s < ns; ++s) sum += eps[s];
-    const double mean_e = sum / (double)ns;
-    for (int64_t s = 0; s < ns; ++s) eps[s] -= mean_e;
+    const int64_t ns = h->sr_ns, n = sr_order(h);
+    RNNWF_HIP(h, hipMemcpyAsync(gram, h->srGram.p, (size_t)n * n * 8, hipMemcpyDeviceToHost, h->stream));
+    if (sr_halves(h) == 2) {                                  // complex64 local energies -> [Re eps ; Im eps]
+        if (int rc = ensure_staging(h, (size_t)ns * sizeof(float2))) return rc;
+        RNNWF_HIP(h, hipMemcpyAsync(h->staging, h->eloc.p, (size_t)ns * sizeof(float2), hipMemcpyDeviceToHost, h->stream));
+        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
+        const float2* el = (const float2*)h->staging;
+        for (int64_t s = 0; s < ns; ++s) {
+            eps[s] = (double)el[s].x;
+            eps[ns + s] = (double)el[s].y;
+        }
+    } else {
+        RNNWF_HIP(h, hipMemcpyAsync(eps, h->eloc.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream));
+        RNNWF_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    for (int64_t half = 0; half < sr_halves(h); ++half) sr_centre_host(eps + half * ns, ns);
     return RNNWF_OK;
 }
 
-extern "C" int rnnwf_sr_apply(rnnwf_handle* h, const double* y, double* out_direction) {
+static int sr_apply(rnnwf_handle* h, const SrEntry& e, const double* y, double* out_direction) {
     if (!h) return RNNWF_ERR_INVALID;
-    if (int rc = sr_ready(h, "rnnwf_sr_apply")) return rc;
-    if (!y || !out_direction) return h->fail(RNNWF_ERR_INVALID, "rnnwf_sr_apply: bad arguments");
+    if (int rc = sr_ready(h, e)) return rc;
+    if (!y || !out_direction) return h->fail(RNNWF_ERR_INVALID, "%s: bad arguments", e.name);
     if (int rc = sr_build(h)) return rc;
-    const int64_t ns = h->sr_ns, D = sr_image_size(h);
-    // dO^T y = J^T (y - mean y): the centring moves from the ns x D matrix to the ns weights
-    double sum = 0.0;
-    for (int64_t s = 0; s < ns; ++s) sum += y[s];
-    std::vector<double> yc((size_t)ns);
-    for (int64_t s = 0; s < ns; ++s) yc[(size_t)s] = y[s] - sum / (double)ns;
-    if (int rc = ensure(h, h->srY, (size_t)ns * 8)) return rc;
-    if (int rc = ensure(h, h->srCol, (size_t)2 * D * 8)) return rc;
-    if (int rc = upload(h, h->srY.p, yc.data(), (size_t)ns * 8)) return rc;
-    double* col = (double*)h->srCol.p + D;
-    if (int rc = h->f64 ? sr_colsum<double>(h, D, (const double*)h->srY.p, 1.0, col) : sr_colsum<float>(h, D, (const double*)h->srY.p, 1.0, col)) return rc;
+    const int64_t ns = h->sr_ns, n = sr_order(h), D = sr_image_size(h);
+    // dO^T y = J^T (y - mean y): the centring moves from the rows of the matrix to the weights (each half with its own mean)
+    std::vector<double> yc(y, y + n);
+    for (int64_t half = 0; half < sr_halves(h); ++half) sr_centre_host(yc.data() + half * ns, ns);
+    if (int rc = ensure(h, h->srY, (size_t)n * 8)) return rc;
+    if (int rc = ensure(h, h->srCol, (size_t)(sr_halves(h) + 1) * D * 8)) return rc;
+    if (int rc = upload(h, h->srY.p, yc.data(), (size_t)n * 8)) return rc;
+    double* col = sr_direction_image(h);
+    if (int rc = sr_colsum(h, D, 0, n, (const double*)h->srY.p, 1.0, col)) return rc;
     if (int rc = ensure_staging(h, (size_t)D * 8)) return rc;
     RNNWF_HIP(h, hipMemcpyAsync(h->staging, col, (size_t)D * 8, hipMemcpyDeviceToHost, h->stream));
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));
@@ -295,24 +360,24 @@ extern "C" int rnnwf_sr_apply(rnnwf_handle* h, const double* y, double* out_dire
     return RNNWF_OK;
 }
 
-extern "C" int rnnwf_sr_solve(rnnwf_handle* h, double diag_shift, double* y) {
+static int sr_solve(rnnwf_handle* h, const SrEntry& e, double diag_shift, double* y) {
     if (!h) return RNNWF_ERR_INVALID;
-    if (!y) return h->fail(RNNWF_ERR_INVALID, "rnnwf_sr_solve: bad arguments");
-    if (int rc = sr_solve_common(h, "rnnwf_sr_solve", diag_shift)) return rc;
-    const int64_t ns = h->sr_ns;
-    if (int rc = ensure_staging(h, (size_t)(ns + 1) * 8)) return rc;
-    RNNWF_HIP(h, hipMemcpyAsync(h->staging, sr_y(h), (size_t)(ns + 1) * 8, hipMemcpyDeviceToHost, h->stream));      // y | status
+    if (!y) return h->fail(RNNWF_ERR_INVALID, "%s: bad arguments", e.name);
+    if (int rc = sr_solve_common(h, e, diag_shift)) return rc;
+    const int64_t n = sr_order(h);
+    if (int rc = ensure_staging(h, (size_t)(n + 1) * 8)) return rc;
+    RNNWF_HIP(h, hipMemcpyAsync(h->staging, sr_y(h), (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, h->stream));      // y | status
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));
-    const long long status = ((const long long*)h->staging)[ns];
-    if (status) return sr_pivot_error(h, "rnnwf_sr_solve", status, diag_shift);
-    memcpy(y, h->staging, (size_t)ns * 8);
+    const long long status = ((const long long*)h->staging)[n];
+    if (status) return sr_pivot_error(h, e.name, status, diag_shift);
+    memcpy(y, h->staging, (size_t)n * 8);
     return RNNWF_OK;
 }
 
-extern "C" int rnnwf_sr_direction(rnnwf_handle* h, double diag_shift, double* out_direction) {
+static int sr_direction(rnnwf_handle* h, const SrEntry& e, double diag_shift, double* out_direction) {
     if (!h) return RNNWF_ERR_INVALID;
-    if (!out_direction) return h->fail(RNNWF_ERR_INVALID, "rnnwf_sr_direction: bad arguments");
-    if (int rc = sr_solve_common(h, "rnnwf_sr_direction", diag_shift)) return rc;
+    if (!out_direction) return h->fail(RNNWF_ERR_INVALID, "%s: bad arguments", e.name);
+    if (int rc = sr_solve_common(h, e, diag_shift)) return rc;
     if (int rc = sr_direction_queue(h)) return rc;
     const int64_t D = sr_image_size(h);
     const double* col = sr_direction_image(h);
@@ -321,9 +386,37 @@ extern "C" int rnnwf_sr_direction(rnnwf_handle* h, double diag_shift, double* ou
     RNNWF_HIP(h, hipMemcpyAsync((double*)h->staging + D, sr_status(h), 8, hipMemcpyDeviceToHost, h->stream));
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));
     const long long status = ((const long long*)h->staging)[D];
-    if (status) return sr_pivot_error(h, "rnnwf_sr_direction", status, diag_shift);
+    if (status) return sr_pivot_error(h, e.name, status, diag_shift);
     sr_gather(h->sr_sidx, (const double*)h->staging, out_direction);
     return RNNWF_OK;
+}
+
+extern "C" int rnnwf_log_derivatives(rnnwf_handle* h, double* out, int64_t ns, int64_t nparams) {
+    return sr_log_derivatives(h, {"rnnwf_log_derivatives", false}, out, ns, nparams);
+}
+extern "C" int rnnwf_sr_gram(rnnwf_handle* h, double* gram, double* eps) { return sr_gram(h, {"rnnwf_sr_gram", false}, gram, eps); }
+extern "C" int rnnwf_sr_apply(rnnwf_handle* h, const double* y, double* out_direction) {
+    return sr_apply(h, {"rnnwf_sr_apply", false}, y, out_direction);
+}
+extern "C" int rnnwf_sr_solve(rnnwf_handle* h, double diag_shift, double* y) { return sr_solve(h, {"rnnwf_sr_solve", false}, diag_shift, y); }
+extern "C" int rnnwf_sr_direction(rnnwf_handle* h, double diag_shift, double* out_direction) {
+    return sr_direction(h, {"rnnwf_sr_direction", false}, diag_shift, out_direction);
+}
+
+extern "C" int rnnwf_log_derivatives_complex(rnnwf_handle* h, double* out_re_im, int64_t ns, int64_t nparams) {
+    return sr_log_derivatives(h, {"rnnwf_log_derivatives_complex", true}, out_re_im, ns, nparams);
+}
+extern "C" int rnnwf_sr_gram_complex(rnnwf_handle* h, double* gram, double* eps) {
+    return sr_gram(h, {"rnnwf_sr_gram_complex", true}, gram, eps);
+}
+extern "C" int rnnwf_sr_apply_complex(rnnwf_handle* h, const double* y, double* out_direction) {
+    return sr_apply(h, {"rnnwf_sr_apply_complex", true}, y, out_direction);
+}
+extern "C" int rnnwf_sr_solve_complex(rnnwf_handle* h, double diag_shift, double* y) {
+    return sr_solve(h, {"rnnwf_sr_solve_complex", true}, diag_shift, y);
+}
+extern "C" int rnnwf_sr_direction_complex(rnnwf_handle* h, double diag_shift, double* out_direction) {
+    return sr_direction(h, {"rnnwf_sr_direction_complex", true}, diag_shift, out_direction);
 }
 
 // K whole minSR iterations with one host synchronisation (docs/sr.md, "Iterations on the device"): per iteration the fused VMC step,
@@ -335,7 +428,7 @@ extern "C" int rnnwf_sr_train_steps(rnnwf_handle* h, int32_t K, int64_t numsampl
                                     double* moments) {
     if (!h) return RNNWF_ERR_INVALID;
     const char* entry = "rnnwf_sr_train_steps";
-    if (int rc = sr_refuse(h, entry)) return rc;
+    if (int rc = sr_refuse(h, SrEntry{entry, false})) return rc;
     if (int rc = sr_committed(h, entry)) return rc;
     if (K < 1 || K > kSrMaxSteps || numsamples < 1 || !couplings || !learning_rates || !diag_shifts || !moments)
         return h->fail(RNNWF_ERR_INVALID, "%s: bad arguments (1 <= K <= %d)", entry, kSrMaxSteps);

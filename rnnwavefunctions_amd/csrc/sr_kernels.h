@@ -2,6 +2,8 @@
 //
 //   J[ns][D],  D = PCOLS QCOLS + HEAD_ROW:  row s = O_s = d log psi(sigma_s) / d theta = 1/2 d log P / d theta  in IMAGE order, the
 //   order of the gradient image h->gradW ([dW | head row], grad.hip), element type of the model.
+//   Complex RNN (docs/sr_complex.md): J[2 ns][D_c], D_c = PCOLS QCOLS + 3 HEAD_ROW, row s = Re O_s, row ns + s = Im O_s; the rows
+//   [0, ns) and [ns, 2 ns) are centred with their own column means (HALVES).
 //
 //   sr_outer_kernel  : O_s = 1/2 sum_n p_{n ns + s} (x) q_{n ns + s} from the rows gru_bwd_kernel<SR> left in P and Q (unit weights),
 //                      plus 1/2 of the sample's head row; image elements that no parameter reads (padding) are written as zeros.
@@ -17,11 +19,11 @@ namespace rnnwf {
 // One workgroup per sample; wave w owns the P tiles w, w + WAVES, ... (14 x 4 tiles at 50 units would be 224 accumulator registers in
 // one wave): 8 waves where 4 would own more than 112 registers of full rows of tiles, and the Q tiles are taken QCH at a time so that
 // a pass holds at most 64 accumulator registers - the N rows of P are read again per pass, from L2.
-template <typename T, int NFULL>
+template <typename T, int NFULL, int NOUT_ = 1>
 struct SrShape {
     using Elem = T;
     using G = GradLayout<NFULL, T>;
-    static constexpr int NF = NFULL;
+    static constexpr int NF = NFULL, NOUT = NOUT_;         // NOUT 3: the complex RNN's three head rows
     static constexpr int PT = G::PCOLS / 16, QT = G::QCOLS / 16;
     static constexpr int FRAG_REGS = 4 * (int)sizeof(T) / 4;
     static constexpr int WAVES = ((PT + 3) / 4) * QT * FRAG_REGS > 112 ? 8 : 4;
@@ -29,15 +31,19 @@ struct SrShape {
     static constexpr int QCH = 64 / (MP * FRAG_REGS) < 1 ? 1 : 64 / (MP * FRAG_REGS) > QT ? QT : 64 / (MP * FRAG_REGS);
     static constexpr int PASSES = (QT + QCH - 1) / QCH;
     static constexpr int64_t DW0 = (int64_t)G::PCOLS * G::QCOLS;
-    static constexpr int64_t D = DW0 + G::HEAD_ROW;
+    static constexpr int64_t D = DW0 + NOUT * G::HEAD_ROW;
+    static_assert(NOUT * G::HEAD_ROW <= WAVES * 64, "one thread per head element");
 };
 
 // K = N is short: the last group of four sites is padded with zeros (its rows are read from site 0 and zeroed), no branch.
-template <typename T, int NFULL>
-__global__ void __launch_bounds__((SrShape<T, NFULL>::WAVES * 64)) sr_outer_kernel(const T* __restrict__ P, const T* __restrict__ Q,
-                                                                                 const T* __restrict__ head, const uint8_t* __restrict__ used,
-                                                                                 int N, int64_t ns, T* __restrict__ J) {
-    using S = SrShape<T, NFULL>;
+// NOUT = 3 (complex RNN): P holds the rows of one seed of gru_bwd_kernel<SR>, which already carry the 1/2 of log a = 1/2 log p
+// (no factor here), head its three head rows, J the first row of that seed's half.
+template <typename T, int NFULL, int NOUT = 1>
+__global__ void __launch_bounds__((SrShape<T, NFULL, NOUT>::WAVES * 64)) sr_outer_kernel(const T* __restrict__ P, const T* __restrict__ Q,
+                                                                                       const T* __restrict__ head, const uint8_t* __restrict__ used,
+                                                                                       int N, int64_t ns, T* __restrict__ J) {
+    using S = SrShape<T, NFULL, NOUT>;
+    const T scale = NOUT == 1 ? T(0.5) : T(1);
     using G = typename S::G;
     using V4 = typename Frag<T>::V4;
     constexpr int PT = S::PT, QT = S::QT, MP = S::MP, WAVES = S::WAVES, QCH = S::QCH;
@@ -89,14 +95,14 @@ __global__ void __launch_bounds__((SrShape<T, NFULL>::WAVES * 64)) sr_outer_kern
                     for (int rr = 0; rr < 4; ++rr) {
                         const int fr = sizeof(T) == 4 ? 4 * lk + rr : lk + 4 * rr;      // C/D fragment row of (lane quarter lk, register rr)
                         const int idx = (16 * pt + fr) * G::QCOLS + 16 * (t0 + t) + li;
-                        out[idx] = used[idx] ? T(0.5) * acc[i][t][rr] : T(0);
+                        out[idx] = used[idx] ? scale * acc[i][t][rr] : T(0);
                     }
                 }
             }
         }
-        if ((int)threadIdx.x < G::HEAD_ROW) {
+        if ((int)threadIdx.x < NOUT * G::HEAD_ROW) {
             const int idx = (int)S::DW0 + threadIdx.x;
-            out[idx] = used[idx] ? T(0.5) * head[s * G::HEAD_ROW + threadIdx.x] : T(0);
+            out[idx] = used[idx] ? scale * head[s * NOUT * G::HEAD_ROW + threadIdx.x] : T(0);
         }
     }
 }
@@ -127,7 +133,8 @@ __global__ void __launch_bounds__(256) sr_colsum_kernel(const T* __restrict__ J,
 // Element (r, c), r >= c, is stored to (r, c) and (c, r): symmetric by construction.  D is a multiple of 4.
 // mult[k]: how many flat parameters read image element k (0 padding, 2 the head's logit-difference row, which the two columns of
 // wf_dense share with opposite signs) - the product is the flat-order one, sum over PARAMETERS.
-template <typename T>
+// HALVES (complex RNN): ns is the order 2 x samples; the rows from ns / 2 on are centred with the second mean vector, mean + D.
+template <typename T, bool HALVES = false>
 __global__ void __launch_bounds__(256) sr_gram_kernel(const T* __restrict__ J, const double* __restrict__ mean, const uint8_t* __restrict__ mult,
                                                       int64_t ns, int64_t D, int64_t nblocks, double* __restrict__ gram) {
     typedef double V4 __attribute__((ext_vector_type(4)));
@@ -142,6 +149,8 @@ __global__ void __launch_bounds__(256) sr_gram_kernel(const T* __restrict__ J, c
         const int64_t bj = item - bi * (bi + 1) / 2;
         const T* arow[2];
         const T* brow[2];
+        const double* amean[2];
+        const double* bmean[2];
         bool aok[2], bok[2];
 #pragma unroll
         for (int x = 0; x < 2; ++x) {
@@ -150,6 +159,8 @@ __global__ void __launch_bounds__(256) sr_gram_kernel(const T* __restrict__ J, c
             bok[x] = rb < ns;
             arow[x] = J + (aok[x] ? ra : 0) * D;                   // rows past ns are read from row 0 and zeroed
             brow[x] = J + (bok[x] ? rb : 0) * D;
+            amean[x] = mean + (HALVES && 2 * ra >= ns ? D : 0);
+            bmean[x] = mean + (HALVES && 2 * rb >= ns ? D : 0);
         }
         V4 acc[2][2];
 #pragma unroll
@@ -160,7 +171,15 @@ __global__ void __launch_bounds__(256) sr_gram_kernel(const T* __restrict__ J, c
             const int64_t k = 16 * ks + 4 * lk;
             const bool kok = k < D;
             const int64_t kc = kok ? k : 0;
-            const V4 m = *reinterpret_cast<const V4*>(mean + kc);
+            V4 ma[2], mb[2];
+            ma[0] = *reinterpret_cast<const V4*>(amean[0] + kc);
+            if constexpr (HALVES) {
+                ma[1] = *reinterpret_cast<const V4*>(amean[1] + kc);
+                mb[0] = *reinterpret_cast<const V4*>(bmean[0] + kc);
+                mb[1] = *reinterpret_cast<const V4*>(bmean[1] + kc);
+            } else {
+                ma[1] = mb[0] = mb[1] = ma[0];
+            }
             const uchar4 mu4 = *reinterpret_cast<const uchar4*>(mult + kc);
             const double mu[4] = {(double)mu4.x, (double)mu4.y, (double)mu4.z, (double)mu4.w};
             double av[2][4], bv[2][4];
@@ -170,8 +189,8 @@ __global__ void __launch_bounds__(256) sr_gram_kernel(const T* __restrict__ J, c
                 const T4 b = *reinterpret_cast<const T4*>(brow[x] + kc);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    av[x][j] = aok[x] && kok ? ((double)a[j] - m[j]) * mu[j] : 0.0;
-                    bv[x][j] = bok[x] && kok ? (double)b[j] - m[j] : 0.0;
+                    av[x][j] = aok[x] && kok ? ((double)a[j] - ma[x][j]) * mu[j] : 0.0;
+                    bv[x][j] = bok[x] && kok ? (double)b[j] - mb[x][j] : 0.0;
                 }
             }
 #pragma unroll

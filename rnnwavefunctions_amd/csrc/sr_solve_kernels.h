@@ -47,6 +47,29 @@ __global__ void __launch_bounds__(256) sr_centre_kernel(const double* __restrict
     if (status && t == 0) *status = 0;
 }
 
+// The complex RNN's stacked eps (docs/sr_complex.md): workgroup b = 0 / 1 takes the real / imaginary parts of the ns resident
+// float2 local energies and writes out[b ns + s], centred with that half's own mean in the order and the arithmetic of
+// sr_centre_kernel (reference element subtracted first: a constant E_loc gives exact zeros); workgroup 0 clears the status word.
+__global__ void __launch_bounds__(256) sr_centre_complex_kernel(const float2* __restrict__ in, int64_t ns, double* __restrict__ out,
+                                                                long long* __restrict__ status) {
+    __shared__ double part[256];
+    const int t = threadIdx.x;
+    const bool im = blockIdx.x != 0;
+    auto at = [&](int64_t s) { return (double)(im ? in[s].y : in[s].x); };
+    const double ref = at(0);
+    double v = 0.0;
+    for (int64_t s = t; s < ns; s += 256) v += at(s) - ref;
+    part[t] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (t < w) part[t] += part[t + w];
+        __syncthreads();
+    }
+    const double mean = part[0] / (double)ns;
+    for (int64_t s = t; s < ns; s += 256) out[(im ? ns : 0) + s] = (at(s) - ref) - mean;
+    if (status && t == 0 && !im) *status = 0;
+}
+
 // the 32 x 32 diagonal block of panel k, shifted, into LDS (rows past ns: identity) and its Cholesky factor in place (lower triangle)
 __device__ __forceinline__ void sr_factor_diagonal(const double* src, int64_t ns, int64_t c0, double shift, bool record,
                                                    long long* __restrict__ status, double (*Ls)[kSrNB + 1]) {

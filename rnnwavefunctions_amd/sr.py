@@ -124,3 +124,61 @@ def train_tfim(wf, Jz, Bx, params, numsteps=100, numsamples=500, learningrate=1e
         wf.set_params_flat(theta)
     train_tfim.last_params = unflatten_params(wf, theta, params, scope)
     return meanEnergy, varEnergy
+
+
+# ---- the complex RNN (docs/sr_complex.md) ---------------------------------------------------------------------------------------
+# psi = sqrt(P) e^{i phi} with real parameters: O = 1/2 d log P + i d phi, eps = E_loc - mean E complex,
+#     S = Re(dO^H dO) / ns,  F = Re(dO^H eps) / ns,  delta = (S + lambda I)^-1 F = Obar^T (Obar Obar^T + ns lambda I)^-1 ebar
+# for the stacked real Obar = [Re dO ; Im dO] (2 ns rows) and ebar = [Re eps ; Im eps]: the positive model's solve on order 2 ns.
+
+def minsr_direction_complex(wf, diag_shift, solver="host"):
+    """delta (num_params,) float64 on the resident batch of the complex RNN `wf`, flat order of wf._layout().  solver "host": the
+    (2 ns, 2 ns) Gram matrix to the host, LAPACK Cholesky, sr_apply_complex; "device": wf.sr_direction_complex."""
+    lam = _check_shift(diag_shift)
+    if _check_solver(solver) == "device":
+        return wf.sr_direction_complex(lam)
+    gram, eps = wf.sr_gram_complex()
+    ns = gram.shape[0] // 2
+    if ns == 0:
+        raise ValueError("minsr_direction_complex: no resident batch")
+    # solve_shifted shifts by (order) x lambda; the system's shift is ns lambda = (2 ns) (lambda / 2)
+    return wf.sr_apply_complex(solve_shifted(gram, eps, lam / 2.0))
+
+
+def qgt_complex(wf):
+    """S = Re(dO^H dO) / ns (num_params, num_params) float64 from the per-sample log-derivatives of the resident batch of the complex
+    RNN: the quantum geometric tensor for real parameters.  For diagnostics and small models."""
+    o = wf.log_derivatives_complex()
+    d = o - o.mean(axis=0)
+    return (d.real.T @ d.real + d.imag.T @ d.imag) / o.shape[0]
+
+
+def train_j1j2(wf, J1, J2, Bz, params, numsteps=100, numsamples=500, learningrate=1e-2, diag_shift=1e-3, seed=111,
+               scope="RNNwavefunction", Marshall_sign=False, solver="device"):
+    """Minimise the open J1-J2 chain's energy of `wf` (a NativeWavefunction of CRNN_U1 with one layer, holding `params`) by minSR:
+    the fused J1-J2 vmc_step (samples of the zero-magnetisation sector, complex local energies, moments; the batch stays resident) ->
+    minsr_direction_complex -> theta -= lr delta -> set_params_flat, the host loop of train_tfim.  J1, J2, Bz: scalars or one entry
+    per site.  `Marshall_sign` reaches the local energies exactly as training.run_J1J2 passes it on (through the reference's
+    `periodic` slot: True selects the periodic chain without a Marshall sign).  Returns (meanEnergy, varEnergy) as run_J1J2 does,
+    one entry per iteration 0..numsteps: meanEnergy complex, varEnergy the variance of the real part; the trained parameters are
+    left in train_j1j2.last_params and keep the dtype of `params`."""
+    _check_shift(diag_shift)
+    _check_solver(solver)
+    if int(numsteps) < 0 or int(numsamples) < 2:
+        raise ValueError("numsteps must be >= 0 and numsamples >= 2, got %r and %r" % (numsteps, numsamples))
+    N = wf.N
+    j1, j2, bz = (np.broadcast_to(np.asarray(v, dtype=np.float64), (N,)) for v in (J1, J2, Bz))
+    periodic = 1.0 if Marshall_sign else 0.0          # run_J1J2's couplings: [J1 | J2 | Bz | periodic, marshall = 0]
+    couplings = np.concatenate([j1, j2, bz, [periodic, 0.0]])
+    dtype = next(iter(params.values())).dtype
+    theta = flatten_params(wf, params, scope).astype(dtype).astype(np.float64)
+    wf.set_params_flat(theta)
+    meanEnergy, varEnergy = [], []
+    for it in range(int(numsteps) + 1):
+        s1, s2, n, si = wf.vmc_step(int(numsamples), seed, it, couplings)["moments"]
+        meanEnergy.append(complex(s1 / n, si / n))
+        varEnergy.append(s2 / n - (s1 / n) ** 2)
+        theta = (theta - learningrate * minsr_direction_complex(wf, diag_shift, solver)).astype(dtype).astype(np.float64)
+        wf.set_params_flat(theta)
+    train_j1j2.last_params = unflatten_params(wf, theta, params, scope)
+    return meanEnergy, varEnergy
