@@ -9,6 +9,13 @@
 // accumulated in f32, smallest terms first.  bf16 x bf16 products are exact in f32; the dropped terms
 // (w2 h3, w3 h2, w3 h3) are below 2^-24 of |w h| each - the size of one f32 rounding.  So the result has f32
 // accuracy (tests: same tolerances as the f32-MFMA engine, both compared with the float64 oracle).
+// Order of the six products into an accumulator: the one-wave steps below (step, step_stream) go product by product,
+//        w3 h1, w2 h2, w1 h3, w2 h1, w1 h2, w1 h1                                   (all quads of one, then the next);
+// the ping-pong kernels' generated segment (split_mfma_asm.h) goes weight part by weight part, so that every weight
+// fragment is read from LDS once and multiplies all its state parts from the same registers:
+//        w3: h1 | w2: h2, h1 | w1: h3, h2, h1      per quad (quad 0's products, then quad 1's ...), then the special k-step.
+// Inside a weight part the smaller state part comes first, the weight parts run from the smallest up, and w1 h1 of the
+// last quad is still the last regular term; the two orders differ in f32 rounding only (tests/test_gpu_pp_fragment_order.py).
 //
 // Shapes: v_mfma_f32_32x32x16_bf16, 32 chains per wave (columns = lane & 31), 32-row tiles.  Lane (c, hh = lane>>5),
 // accumulator register rho of a tile holds row (rho & 3) + 8 (rho >> 2) + 4 hh.  The lane therefore owns, for its
@@ -29,7 +36,7 @@
 //     three parts are exactly three k-steps each (no padding at all: 18 k-steps for the six products) plus ONE special
 //     unit (48 + hh) whose six products {w1 h1, w1 h2, w1 h3, w2 h1, w2 h2, w3 h1} fill six of the eight K entries of
 //     a 19th k-step.  95 MFMAs per 32-chain wave-step instead of 120; A fragments stay shared between products
-//     (image 50 KB instead of 60 KB).
+//     (image 50 KB instead of 60 KB: 50 fragments, which the ping-pong kernels read once each per wave-step).
 //  3  the same K-packing at 69 <= num_units <= 100 (config 5): 48 aligned units per lane half (6 k-steps per part) + TWO
 //     special units whose 12 products fill two extra k-steps: 38 k-steps x 10 tiles = 380 MFMAs (mode 0 would need 420).
 //     Its 200 KB of fragments exceed LDS: the regular w3 fragments stay in global memory (STREAM, step_stream below).

@@ -5,7 +5,8 @@
 // MFMA segment ran at 51 cycles per MFMA (every fragment read sunk to just before its MFMA: an LDS round trip per
 // MFMA) and the VALU segment at 5 100 cycles for 470 instructions (register-starved: exp -> add -> rcp chains issued
 // back to back, each instruction waiting for the one before).  Hence:
-//   * MFMA segment  = split_mfma_asm.h (generated): one asm block, fragment reads two k-steps ahead, counted waits;
+//   * MFMA segment  = split_mfma_asm.h (generated): one asm block, every weight fragment read once and used by all its
+//     products (50 reads per 95 MFMAs), reads two fragment sets ahead, counted waits;
 //   * VALU segment  = below: every formula is evaluated STAGE by STAGE over a batch of units (all exp2, then all adds,
 //     then all rcp ...), stages pinned with sched_barrier(0), so consecutive instructions are independent and a
 //     dependent one is >= 12 issue slots behind its operand.

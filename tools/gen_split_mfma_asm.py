@@ -2,63 +2,70 @@
 """Generates rnnwavefunctions_amd/csrc/split_mfma_asm.h: the MFMA segment of the bf16x3 GRU step as ONE hand-scheduled
 inline-asm block per K-packed layout (split_core.h, MODE 2).
 
-Why by hand: the segment is 95 v_mfma_f32_32x32x16_bf16 fed by 95 ds_read_b128 of weight fragments.  hipcc, short of
-registers, sinks every fragment read to just in front of the MFMA that consumes it, so each MFMA waits out an LDS
-round trip (in-kernel stamps, tools/stamps.py: 51 cycles per MFMA instead of 32).  Here the reads run TWO k-steps
-(9-10 MFMAs, ~300 cycles) ahead through a ring of two fragment sets, every wait is a counted `s_waitcnt lgkmcnt(8)`,
-and nothing but MFMAs, reads and waits is issued, which leaves the SIMD's vector issue to the partner wave's VALU
-segment (prnn_flip_pp_kernel).
+Why by hand: the segment is 95 v_mfma_f32_32x32x16_bf16.  hipcc, short of registers, sinks every fragment read to just in
+front of the MFMA that consumes it, so each MFMA waits out an LDS round trip (in-kernel stamps, tools/stamps.py: 51 cycles
+per MFMA instead of 32).  Here the reads run ahead through a ring of two fragment sets, every wait is a counted
+`s_waitcnt lgkmcnt(n)`, and nothing but MFMAs, reads and waits is issued, which leaves the SIMD's vector issue to the
+partner wave's VALU segment (prnn_flip_pp_kernel).
 
-Schedule, MFMA m = (k-step k, tile t):   wait until fragment m has landed;  MFMA m;  read fragment m - 1 + 2 NT into the
-registers MFMA m - 1 consumed.
+Each weight fragment is read ONCE per block: 50 ds_read_b128 (5 tiles x 3 parts x 3 quads + 5 special) feed the 95 MFMAs.
+A set is the five tiles' fragments of one (weight part, quad); all products of that set - w1: h3, h2, h1;  w2: h2, h1;
+w3: h1 - are issued from the same registers, tile 0..4 per state part, so an accumulator is never written by two
+consecutive MFMAs.  The sets run w3, w2, w1 (quads 0..NQ-1 inside each), then the special k-step.
+
+Schedule: wait until the fragment has landed (first use only);  MFMA;  once the MFMA after a fragment's last one has issued,
+read the fragment of the set two further on into its registers.
 """
 import os
 import sys
 
-ORD = [(2, 0), (1, 1), (0, 2), (1, 0), (0, 1), (0, 0)]       # (weight part, state part), smallest products first
+# (weight part, state parts it multiplies): one GROUP per (weight part, quad).  Groups run w3, w2, w1 and, inside a group, from
+# the smallest state part to the largest, so w1 h1 of the last quad is the last regular term into every accumulator.
+PARTS = [(2, (0,)), (1, (1, 0)), (0, (2, 1, 0))]
 
 
 def gen_body(NT, NQ, zero=()):
     """(declarations, asm body, outputs, inputs) of one block; tiles in `zero` start from 0 (first MFMA with the inline constant
     as C, early-clobber output) instead of accumulating on their incoming value."""
-    KS = 6 * NQ + 1
     NB = 3 * NQ + 1
+    # groups: (A offset of tile t, B quads the set multiplies); the special k-step is the last group, one product
+    groups = []
+    for p, hs in PARTS:
+        for q in range(NQ):
+            groups.append(([((t * 3 + p) * NQ + q) * 1024 for t in range(NT)], [h * NQ + q for h in hs]))
+    groups.append(([(NT * 3 * NQ + t) * 1024 for t in range(NT)], [3 * NQ]))
+    RING = 2                                   # fragment sets; set g % RING holds group g
 
-    def a_off(t, k):
-        if k < 6 * NQ:
-            return ((t * 3 + ORD[k // NQ][0]) * NQ + k % NQ) * 1024
-        return (NT * 3 * NQ + t) * 1024
-
-    def b_idx(k):
-        return ORD[k // NQ][1] * NQ + k % NQ if k < 6 * NQ else 3 * NQ
-
-    total = KS * NT
-    RING = 2                                   # fragment sets; set k % RING holds k-step k
     lines = []
-    for k in range(min(RING, KS)):
+    seq = {}                                   # (group, tile) -> position of its read in the wave's LDS queue
+    def read(g, t):
+        seq[(g, t)] = len(seq)
+        lines.append("ds_read_b128 %%[f%d_%d], %%[aa] offset:%d" % (g % RING, t, groups[g][0][t]))
+
+    for g in range(min(RING, len(groups))):
         for t in range(NT):
-            lines.append("ds_read_b128 %%[f%d_%d], %%[aa] offset:%d" % (k % RING, t, a_off(t, k)))
-    issued = min(RING, KS) * NT
-
-    def read(r):                               # read of fragment index r = k NT + t
-        k, t = divmod(r, NT)
-        return "ds_read_b128 %%[f%d_%d], %%[aa] offset:%d" % (k % RING, t, a_off(t, k))
-
-    for m in range(total):
-        k, t = divmod(m, NT)
-        lines.append("s_waitcnt lgkmcnt(%d)" % (issued - m - 1))
-        if k == 0 and t in zero:
-            lines.append("v_mfma_f32_32x32x16_bf16 %%[c%d], %%[f%d_%d], %%[b%d], 0" % (t, k % RING, t, b_idx(k)))
-        else:
-            lines.append("v_mfma_f32_32x32x16_bf16 %%[c%d], %%[f%d_%d], %%[b%d], %%[c%d]" % (t, k % RING, t, b_idx(k), t))
-        # the register set of fragment m - 1 is free once MFMA m has issued (MFMA m - 1 started >= 32 cycles ago and
-        # has long read its operands): refill it with the fragment RING k-steps further on
-        r = m - 1 + RING * NT
-        if m >= 1 and r < total:
-            lines.append(read(r))
-            issued += 1
-    r = total - 1 + RING * NT
-    assert issued == total, (issued, total)
+            read(g, t)
+    started = set()
+    refill = None                              # fragment whose last MFMA was the previous one
+    nmfma = 0
+    for g, (_, bs) in enumerate(groups):
+        for i, b in enumerate(bs):
+            for t in range(NT):                # always all tiles before the same accumulator again
+                if i == 0:                     # LDS returns in order: at most this many younger reads still in flight
+                    lines.append("s_waitcnt lgkmcnt(%d)" % (len(seq) - seq[(g, t)] - 1))
+                c = "%%[c%d]" % t
+                if t in zero and t not in started:
+                    c = "0"
+                started.add(t)
+                lines.append("v_mfma_f32_32x32x16_bf16 %%[c%d], %%[f%d_%d], %%[b%d], %s" % (t, g % RING, t, b, c))
+                nmfma += 1
+                # the registers of a fragment are free once the MFMA AFTER its last one has issued (that last MFMA started
+                # >= 32 cycles ago and has long read its operands): refill them with the group RING further on
+                if refill is not None and refill[0] + RING < len(groups):
+                    read(refill[0] + RING, refill[1])
+                refill = (g, t) if i == len(bs) - 1 else None
+    assert len(seq) == len(groups) * NT and nmfma == (6 * NQ + 1) * NT, (len(seq), nmfma)
+    assert all(int(l.split("(")[1][:-1]) <= 15 for l in lines if l.startswith("s_waitcnt"))
     # the accumulators are read by VALU code right behind this block (only a barrier in between): an 8-pass MFMA's
     # result needs >= 10 wait states before a VALU read, and the assembler inserts none inside inline asm
     lines += ["s_nop 7", "s_nop 7"]
@@ -102,7 +109,7 @@ def gen(NT, NQ):
 
 
 HEADER = '''// GENERATED by tools/gen_split_mfma_asm.py - do not edit (edit the generator).
-// MFMA segment of the bf16x3 GRU step, hand-scheduled: fragment reads two k-steps ahead of their MFMAs, counted waits.
+// MFMA segment of the bf16x3 GRU step, hand-scheduled: every weight fragment read once, two sets ahead of its MFMAs, counted waits.
 #pragma once
 
 namespace rnnwf {
