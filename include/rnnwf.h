@@ -487,6 +487,19 @@ int rnnwf_sr_apply_complex(rnnwf_handle* h, const double* y, double* out_directi
 int rnnwf_sr_solve_complex(rnnwf_handle* h, double diag_shift, double* y);
 int rnnwf_sr_direction_complex(rnnwf_handle* h, double diag_shift, double* out_direction);
 
+/* ---- stochastic reconfiguration for the 2D RNN (MDRNN2D; docs/sr_2d.md) -----------------------------------------------------------
+ * psi = sqrt(P) real and positive: the conventions, arguments, state rules, workspace check (ns <= 4096), pivot status and error
+ * codes of the positive model's five calls, on the resident batch of the last rnnwf_vmc_step / rnnwf_load_batch of an MDRNN2D handle
+ * at every width its gradient serves (up to 84 units).  O[s][k] = 1/2 d log P(sigma_s) / d theta_k in the flat order of
+ * rnnwf_set_params_flat; 2 F = 2 dO^T eps / ns is the gradient rnnwf_vmc_gradient returns for this model.
+ * RNNWF_ERR_INVALID "<entry>: only for the 2D RNN (RNNWF_MODEL_MDRNN2D)" for every other model; a handle with a communicator is
+ * refused.  The positive model's and the complex RNN's entries keep refusing this model.                                        */
+int rnnwf_log_derivatives_2d(rnnwf_handle* h, double* out, int64_t ns, int64_t nparams);
+int rnnwf_sr_gram_2d(rnnwf_handle* h, double* gram, double* eps);
+int rnnwf_sr_apply_2d(rnnwf_handle* h, const double* y, double* out_direction);
+int rnnwf_sr_solve_2d(rnnwf_handle* h, double diag_shift, double* y);
+int rnnwf_sr_direction_2d(rnnwf_handle* h, double diag_shift, double* out_direction);
+
 /* ---- multi-GPU: one RCCL all-reduce of the energy moments -------------------------------------
  * The reference is single-process; these add the one data-parallel collective of SURVEY.md 8e.
  * One process per GPU: rank 0 calls rnnwf_comm_unique_id and ships the 128 bytes to the other

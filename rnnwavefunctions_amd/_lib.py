@@ -91,6 +91,11 @@ PROTOTYPES = {
     "rnnwf_sr_apply_complex": (C.c_int, [_P, _F64P, _F64P]),
     "rnnwf_sr_solve_complex": (C.c_int, [_P, _F64, _F64P]),
     "rnnwf_sr_direction_complex": (C.c_int, [_P, _F64, _F64P]),
+    "rnnwf_log_derivatives_2d": (C.c_int, [_P, _F64P, _I64, _I64]),
+    "rnnwf_sr_gram_2d": (C.c_int, [_P, _F64P, _F64P]),
+    "rnnwf_sr_apply_2d": (C.c_int, [_P, _F64P, _F64P]),
+    "rnnwf_sr_solve_2d": (C.c_int, [_P, _F64, _F64P]),
+    "rnnwf_sr_direction_2d": (C.c_int, [_P, _F64, _F64P]),
     "rnnwf_resident_samples": (_I64, [_P]),
     "rnnwf_timing_enable": (C.c_int, [_P, _I32]),
     "rnnwf_timing_reset": (C.c_int, [_P]),
@@ -458,6 +463,46 @@ class NativeWavefunction:
         on the device (rnnwf_sr_direction_complex), in the flat order of _layout()."""
         out = np.empty(self.num_params(), dtype=np.float64)
         self._check(self.lib.rnnwf_sr_direction_complex(self.h, float(diag_shift), out.ctypes.data_as(_F64P)))
+        return out
+
+    # -- stochastic reconfiguration for the 2D RNN: rnnwf_*_2d (docs/sr_2d.md) ----------------------
+    def log_derivatives_2d(self):
+        """(ns, num_params) float64: O[s, k] = 1/2 d log P(sigma_s) / d theta_k on the resident batch of the 2D RNN, theta in the flat
+        order of _layout()."""
+        ns, n = self.resident_samples(), self.num_params()
+        out = np.empty((ns, n), dtype=np.float64)
+        self._check(self.lib.rnnwf_log_derivatives_2d(self.h, out.ctypes.data_as(_F64P), ns, n))
+        return out
+
+    def sr_gram_2d(self):
+        """(gram, eps): the centred Gram matrix dO dO^T (ns, ns) and eps = E_loc - mean E (ns,) of the resident batch of the 2D RNN,
+        float64; gram is exactly symmetric."""
+        ns = self.resident_samples()
+        gram, eps = np.empty((ns, ns), dtype=np.float64), np.empty(ns, dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_gram_2d(self.h, gram.ctypes.data_as(_F64P), eps.ctypes.data_as(_F64P)))
+        return gram, eps
+
+    def sr_apply_2d(self, y):
+        """(num_params,) float64: dO^T y for y of one entry per sample of the resident batch of the 2D RNN."""
+        yv, yp = _f64(y)
+        ns = self.resident_samples()
+        if ns > 0 and yv.shape != (ns,):
+            raise ValueError("sr_apply_2d: y must have shape (%d,), one entry per sample of the resident batch, got %r" % (ns, yv.shape))
+        out = np.empty(self.num_params(), dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_apply_2d(self.h, yp if ns > 0 else None, out.ctypes.data_as(_F64P)))
+        return out
+
+    def sr_solve_2d(self, diag_shift):
+        """(ns,) float64: y of (dO dO^T + ns diag_shift I) y = eps, factorised and solved on the device; y is not centred."""
+        y = np.empty(self.resident_samples(), dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_solve_2d(self.h, float(diag_shift), y.ctypes.data_as(_F64P)))
+        return y
+
+    def sr_direction_2d(self, diag_shift):
+        """(num_params,) float64: the minSR direction dO^T (dO dO^T + ns diag_shift I)^-1 eps of the resident batch of the 2D RNN,
+        everything on the device (rnnwf_sr_direction_2d), in the flat order of _layout()."""
+        out = np.empty(self.num_params(), dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_direction_2d(self.h, float(diag_shift), out.ctypes.data_as(_F64P)))
         return out
 
     # -- device-resident training iteration (rnnwf_train_steps; single-layer float32 GRU models) ------------------

@@ -307,7 +307,10 @@ struct MGrad {
         return img;
     }
 
-    static int launch(rnnwf_handle* h, const GradCost& c) {
+    // What a backward pass over the resident batch reads and writes, whatever its weights: the site maps, the spins and states, the
+    // P / Q rows and the per-wave ring in HBM, sized by the persistent grid of `kern` - the kernel these arguments are launched with
+    template <class Kern>
+    static int backward_args(rnnwf_handle* h, Kern kern, MdGradArgs* out) {
         Maps m;
         if (int rc = get_maps(h, &m)) return rc;
         const int N = h->N;
@@ -322,21 +325,36 @@ struct MGrad {
         a.nsb = (ns + kChains - 1) / kChains;
         a.bits = (const uint32_t*)h->bits.p;
         a.hs = (const double*)h->hck.p;
+        a.P = (double*)h->gradP.p;
+        a.Q = (double*)h->gradQ.p;
+        a.vert_pos = m.vert_pos;
+        a.row_first = m.row_first;
+        unsigned grid = 0;                                  // the ring is sized by the grid backward_launch will use
+        if (int rc = persistent_grid(h, kern, WAVES * 64, G::BYTES, a.nsb, WAVES, &grid)) return rc;
+        if (int rc = ensure(h, h->rowbuf, (size_t)grid * WAVES * 2 * a.Nx * G::KT * 64 * 8)) return rc;
+        a.ring = (double*)h->rowbuf.p;
+        *out = a;
+        return 0;
+    }
+
+    static int launch(rnnwf_handle* h, const GradCost& c) {
+        MdGradArgs a{};
+        if (int rc = backward_args(h, mdrnn_bwd_kernel<NFULL, WAVES>, &a)) return rc;
         a.eloc = (const double*)h->eloc.p;
         a.mean_e = c.mean_e;
         a.inv_norm = c.inv_norm;
         a.mom = c.mom;
-        a.P = (double*)h->gradP.p;
-        a.Q = (double*)h->gradQ.p;
         a.head_grad = (double*)h->gradW.p + (size_t)G::PCOLS * G::QCOLS;
-        a.vert_pos = m.vert_pos;
-        a.row_first = m.row_first;
-        unsigned grid = 0;                                  // the ring is sized by the grid backward_launch will use
-        if (int rc = persistent_grid(h, mdrnn_bwd_kernel<NFULL, WAVES>, WAVES * 64, G::BYTES, a.nsb, WAVES, &grid)) return rc;
-        if (int rc = ensure(h, h->rowbuf, (size_t)grid * WAVES * 2 * a.Nx * G::KT * 64 * 8)) return rc;
-        a.ring = (double*)h->rowbuf.p;
         if (int rc = backward_launch<double>(h, mdrnn_bwd_kernel<NFULL, WAVES>, WAVES * 64, G::BYTES, a.nsb, WAVES, 2 * G::HEAD_ROW, a.head_grad, a)) return rc;
-        return tn_gemm_launch<double, G::PCOLS / 16, G::QCOLS / 16>(h, a.P, a.Q, R, (double*)h->gradW.p);
+        return tn_gemm_launch<double, G::PCOLS / 16, G::QCOLS / 16>(h, a.P, a.Q, (int64_t)a.ns * a.N, (double*)h->gradW.p);
+    }
+
+    // stochastic reconfiguration (sr.hip): the same pass with unit weights, every chain's two head rows into head_rows [ns][2][HEAD_ROW]
+    static int sr_backward(rnnwf_handle* h, double* head_rows) {
+        MdGradArgs a{};
+        if (int rc = backward_args(h, mdrnn_bwd_kernel<NFULL, WAVES, true>, &a)) return rc;
+        a.head_part = head_rows;
+        return backward_launch<double>(h, mdrnn_bwd_kernel<NFULL, WAVES, true>, WAVES * 64, G::BYTES, a.nsb, WAVES, 0, (double*)nullptr, a);
     }
 
     // dW image [PCOLS][QCOLS], then the two head rows -> TF-named gradient arrays
@@ -397,6 +415,11 @@ void grad_unpack(rnnwf_handle* h, const void* img) {
 }
 
 }  // namespace
+
+int rnnwf::mdrnn_sr_backward(rnnwf_handle* h, double* head_rows) {
+    int rc = 0;
+    return with_width<MGrad>(h, [&](auto k) { rc = decltype(k)::sr_backward(h, head_rows); }) ? rc : no_grad_kernel(h);
+}
 
 const Family* rnnwf::mdrnn_family() {
     static const Gradient g = {grad_layout, grad_pack, grad_launch, grad_unpack};

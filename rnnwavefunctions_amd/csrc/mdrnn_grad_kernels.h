@@ -42,12 +42,15 @@ struct MdGradArgs {
     double* P;
     double* Q;
     double* head_grad;             // [2][HEAD_ROW], zeroed before the launch (written by head_reduce_kernel)
-    double* head_part;             // [waves of the grid][2][HEAD_ROW]: every wave's head-row sums
+    double* head_part;             // [waves of the grid][2][HEAD_ROW]: every wave's head-row sums; SR: [ns][2][HEAD_ROW], every chain's
     const int32_t* vert_pos;
     const int32_t* row_first;
 };
 
-template <int NFULL, int WAVES>
+// SR (sr.hip: the per-sample log-derivatives, docs/sr_2d.md): unit weights w_s = 1 - eloc, mean_e, inv_norm and mom are not read - and
+// the two head rows of every chain kept on their own, head_part = [ns][2][HEAD_ROW] (slot 4 k + q a unit, 4 KT the bias), instead
+// of one sum per wave: lane (c, q) holds the units 4 k + q of chain c in hg[.][k], so the rows are stored without a reduction.
+template <int NFULL, int WAVES, bool SR = false>
 __global__ void __launch_bounds__(WAVES * 64) mdrnn_bwd_kernel(MdGradArgs a) {
     using G = MdGradLayout<NFULL>;
     using C = MdCore<NFULL>;
@@ -77,8 +80,16 @@ __global__ void __launch_bounds__(WAVES * 64) mdrnn_bwd_kernel(MdGradArgs a) {
         const int64_t s = sb * kChains + c;
         const bool valid = s < a.ns;
         const int64_t sc = valid ? s : a.ns - 1;
-        const double mean_e = a.mom ? a.mom[0] / a.mom[2] : a.mean_e, inv_norm = a.mom ? a.inv_norm / a.mom[2] : a.inv_norm;
-        const double w = valid ? (a.eloc[sc] - mean_e) * inv_norm : 0.0;
+        double w;
+        if constexpr (SR) {
+            w = valid ? 1.0 : 0.0;
+            gb[0] = gb[1] = 0.0;
+#pragma unroll
+            for (int k = 0; k < KT; ++k) hg[0][k] = hg[1][k] = 0.0;
+        } else {
+            const double mean_e = a.mom ? a.mom[0] / a.mom[2] : a.mean_e, inv_norm = a.mom ? a.inv_norm / a.mom[2] : a.inv_norm;
+            w = valid ? (a.eloc[sc] - mean_e) * inv_norm : 0.0;
+        }
         double carry[KT];
 #pragma unroll
         for (int k = 0; k < KT; ++k) carry[k] = 0.0;
@@ -179,8 +190,19 @@ __global__ void __launch_bounds__(WAVES * 64) mdrnn_bwd_kernel(MdGradArgs a) {
                 for (int r = 0; r < 4; ++r) carry[4 * m + r] = first ? (turn ? acc[NT + m][r] : 0.0) : acc[m][r];
             carry[KT - 1] = first ? (turn ? acc[NT + NFULL][0] : 0.0) : acc[NFULL][0];
         }
+        if constexpr (SR) {
+            if (valid) {
+#pragma unroll
+                for (int o = 0; o < 2; ++o) {
+                    double* row = a.head_part + (s * 2 + o) * G::HEAD_ROW;
+#pragma unroll
+                    for (int k = 0; k < KT; ++k) row[4 * k + q] = hg[o][k];
+                    row[4 * KT + q] = q == 0 ? gb[o] : 0.0;
+                }
+            }
+        }
     }
-    store_head_part<double, 2, KT>(a.head_part + (size_t)gw * 2 * G::HEAD_ROW, G::HEAD_ROW, hg, gb, c, q);
+    if constexpr (!SR) store_head_part<double, 2, KT>(a.head_part + (size_t)gw * 2 * G::HEAD_ROW, G::HEAD_ROW, hg, gb, c, q);
 }
 
 }  // namespace rnnwf

@@ -160,6 +160,9 @@ constexpr int kGradWaves = 4;
 template <typename T, int NFULL> constexpr bool kGradWide = sizeof(T) == 4 ? NFULL >= 8 : NFULL == 6;
 GradKernel grad_wide_kernel(const rnnwf_handle* h);     // nullptr for another shape
 int grad_bwd_image(rnnwf_handle* h);                    // grad.hip: the backward image, re-packed when stale
+// mdrnn.hip, for stochastic reconfiguration (sr.hip): the 2D RNN's backward pass over the resident batch with unit weights - the rows
+// of P and Q as the gradient leaves them (h->gradP, h->gradQ), every chain's two head rows into head_rows [ns][2][HEAD_ROW]
+int mdrnn_sr_backward(rnnwf_handle* h, double* head_rows);
 // ---- device-resident training (train.hip) ------------------------------------------------------------
 void train_params_changed_on_host(rnnwf_handle* h);           // rnnwf_set_param / rnnwf_commit_params: the device copy is stale
 int train_sync_params_to_host(rnnwf_handle* h);               // before the host reads its copy (rnnwf_get_param, checkpoints)

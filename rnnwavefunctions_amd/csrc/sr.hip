@@ -6,6 +6,8 @@
 // rnnwf_sr_direction: blocked f64 Cholesky, sr_solve_kernels.h).
 // The complex RNN (CRNN_U1, one layer, up to 68 units) has the same five calls as rnnwf_*_complex (docs/sr_complex.md): J[2 ns][D_c]
 // = [Re O ; Im O], each half centred with its own mean, and the same solve path on a system of order 2 ns.
+// The 2D RNN (MDRNN2D, float64, up to 84 units) has them as rnnwf_*_2d (docs/sr_2d.md): J[ns][D_2] in the order of its gradient image,
+// from mdrnn_bwd_kernel's unit-weight mode (mdrnn.hip: mdrnn_sr_backward); one row block, everything behind J as for the positive GRU.
 #include <cmath>
 #include <cstring>
 
@@ -24,11 +26,13 @@ static_assert(2 * RNNWF_SR_COMPLEX_MAX_SAMPLES == kSrMaxSamples, "the complex RN
 constexpr int kSrMaxNFULL = 4;             // up to 68 units
 constexpr int kSrMaxSteps = 1024;          // iterations of one rnnwf_sr_train_steps call: the rows of train.hip's pinned moments table (kMaxSteps)
 
-// An entry point: its name, and whether it is one of the complex RNN's (rnnwf_*_complex, docs/sr_complex.md).  Which handles an entry
-// serves depends on the entry; once it has accepted a handle, the handle's model decides everything else (sr_halves).
+// An entry point: its name, and the family it belongs to - the positive GRU's, the complex RNN's (rnnwf_*_complex, docs/sr_complex.md)
+// or the 2D RNN's (rnnwf_*_2d, docs/sr_2d.md).  Which handles an entry serves depends on the entry; once it has accepted a handle, the
+// handle's model decides everything else (sr_halves, with_sr_shape).
+enum SrFamily { kSrPositive, kSrComplex, kSr2D };
 struct SrEntry {
     const char* name;
-    bool complex;
+    SrFamily family;
 };
 
 // the row blocks of J with a column mean of their own: [Re O ; Im O] for the complex RNN, whose system has 2 ns rows
@@ -39,7 +43,12 @@ int64_t sr_order(const rnnwf_handle* h) { return sr_halves(h) * h->sr_ns; }
 int sr_refuse(rnnwf_handle* h, const SrEntry& e) {
     const char* entry = e.name;
     const char* why = nullptr;
-    if (e.complex) {
+    if (e.family == kSr2D) {
+        if (h->model != RNNWF_MODEL_MDRNN2D) why = "only for the 2D RNN (RNNWF_MODEL_MDRNN2D)";
+        else if (h->comm) why = "not implemented for a handle with a communicator";
+        return why ? h->fail(RNNWF_ERR_INVALID, "%s: %s", entry, why) : 0;
+    }
+    if (e.family == kSrComplex) {
         if (h->model != RNNWF_MODEL_CRNN_U1) why = "only for the complex RNN (RNNWF_MODEL_CRNN_U1)";
         else if (h->NL > 1) why = "not implemented for stacked layers (one GRU layer only)";
         else if (h->NFULL > kSrMaxNFULL) why = "not implemented for layers wider than 68 units";
@@ -60,12 +69,14 @@ int sr_refuse(rnnwf_handle* h, const SrEntry& e) {
 }
 
 // fn(SrShape<T, NFULL, NOUT>()) for the handle's row among the one-layer rows of its family's table up to kSrMaxNFULL (shapes.h):
-// the positive GRU's (NOUT 1) or the complex RNN's (NOUT 3)
+// the positive GRU's (NOUT 1) or the complex RNN's (NOUT 3); fn(MdSrShape<NFULL>()) for every row of the 2D RNN's table
 template <class R> struct SrRow : std::bool_constant<R::NL == 1 && R::NFULL <= kSrMaxNFULL> {};
 template <class Fn>
 int with_sr_shape(rnnwf_handle* h, Fn&& fn) {
     int rc = 0;
-    const bool hit = h->model == RNNWF_MODEL_CRNN_U1
+    const bool hit = h->model == RNNWF_MODEL_MDRNN2D
+        ? with_row<OneLayer>(MdKernels(), h, [&](auto r) { rc = fn(MdSrShape<decltype(r)::NFULL>()); })
+        : h->model == RNNWF_MODEL_CRNN_U1
         ? with_row<SrRow>(CrnnKernels(), h, [&](auto r) { rc = fn(SrShape<typename decltype(r)::T, decltype(r)::NFULL, 3>()); })
         : with_row<SrRow>(GruKernels(), h, [&](auto r) { rc = fn(SrShape<typename decltype(r)::T, decltype(r)::NFULL>()); });
     if (hit) return rc;
@@ -123,32 +134,45 @@ int sr_table(rnnwf_handle* h, int64_t D) {
     return 0;
 }
 
-template <class S>
-int sr_build_shape(rnnwf_handle* h) {
-    using T = typename S::Elem;
-    using G = typename S::G;
-    constexpr int NFULL = S::NF, NOUT = S::NOUT;
+// The backward pass over the resident batch in its unit-weight mode: the rows of P and Q, every chain's head rows into h->srHead.
+// GRU families: gru_bwd_kernel<SR>; `half` is the complex RNN's seed
+template <typename T, int NFULL, int NOUT>
+int sr_backward(rnnwf_handle* h, SrShape<T, NFULL, NOUT>, int half) {
+    using G = GradLayout<NFULL, T>;
     using L = GruLayout<T, NFULL, NOUT>;
-    const int N = h->N;
-    const int64_t ns = h->last_ns, R = ns * N, nsb = (ns + kChains - 1) / kChains;
-    if (int rc = sr_table(h, S::D)) return rc;
-    if (int rc = grad_bwd_image(h)) return rc;
+    const int64_t ns = h->last_ns, R = ns * h->N, nsb = (ns + kChains - 1) / kChains;
     if (int rc = ensure(h, h->gradP, (size_t)R * G::PCOLS * sizeof(T))) return rc;
     if (int rc = ensure(h, h->gradQ, (size_t)R * G::QCOLS * sizeof(T))) return rc;
-    if (int rc = ensure(h, h->srHead, (size_t)ns * NOUT * G::HEAD_ROW * sizeof(T))) return rc;
-    if (int rc = ensure(h, h->srJ, (size_t)sr_halves(h) * ns * S::D * sizeof(T))) return rc;
     GradArgs a{};
     grad_batch_args(h, &a);                                // (one layer: sr_refuse)
     a.wimg = h->wimg.p;
     a.head_part = h->srHead.p;                             // [ns][NOUT][HEAD_ROW]: the head rows of every chain (gru_bwd_kernel<SR>)
+    a.sr_im = half;
     constexpr size_t lds = L::LDS_BYTES + (GradStream<T, NFULL, NOUT>::value ? 0 : G::BWD_BYTES);
     static_assert(lds <= 160 * 1024, "forward + backward weight images exceed the LDS");
+    return launch_persistent(h, kTimerBackprop, gru_bwd_kernel<T, NFULL, 4, NOUT, false, true>, 4 * 64, lds, nsb, 4, a);
+}
+// 2D RNN: mdrnn_bwd_kernel<SR> behind the set-up of its gradient launch (the site maps, the ring in HBM)
+template <int NFULL>
+int sr_backward(rnnwf_handle* h, MdSrShape<NFULL>, int) {
+    return mdrnn_sr_backward(h, (double*)h->srHead.p);
+}
+
+template <class S>
+int sr_build_shape(rnnwf_handle* h) {
+    using T = typename S::Elem;
+    using G = typename S::G;
+    const int N = h->N;
+    const int64_t ns = h->last_ns;
+    if (int rc = sr_table(h, S::D)) return rc;
+    if (int rc = grad_bwd_image(h)) return rc;
+    if (int rc = ensure(h, h->srHead, (size_t)ns * S::NOUT * G::HEAD_ROW * sizeof(T))) return rc;
+    if (int rc = ensure(h, h->srJ, (size_t)sr_halves(h) * ns * S::D * sizeof(T))) return rc;
     // complex RNN: one backward pass and one outer-product pass per seed, Re O into the rows [0, ns) and Im O into [ns, 2 ns).  Both
     // go through the same P, Q and head rows - the second pass starts after the first half is written (one stream); Q is the same twice
     for (int half = 0; half < (int)sr_halves(h); ++half) {
-        a.sr_im = half;
-        if (int rc = launch_persistent(h, kTimerBackprop, gru_bwd_kernel<T, NFULL, 4, NOUT, false, true>, 4 * 64, lds, nsb, 4, a)) return rc;
-        if (int rc = launch_persistent(h, kTimerGemm, sr_outer_kernel<T, NFULL, NOUT>, S::WAVES * 64, 0, ns, 1, (const T*)h->gradP.p,
+        if (int rc = sr_backward(h, S(), half)) return rc;
+        if (int rc = launch_persistent(h, kTimerGemm, sr_outer_kernel<S>, S::WAVES * 64, 0, ns, 1, (const T*)h->gradP.p,
                                        (const T*)h->gradQ.p, (const T*)h->srHead.p, (const uint8_t*)h->srMask.p, N, ns,
                                        (T*)h->srJ.p + (size_t)half * ns * S::D))
             return rc;
@@ -282,8 +306,8 @@ void sr_gather(const std::vector<int32_t>& sidx, const T* img, double* flat) {
 
 extern "C" int64_t rnnwf_resident_samples(const rnnwf_handle* h) { return h ? h->last_ns : 0; }
 
-// ---- the five calls on the resident batch, each behind the positive GRU's entry and the complex RNN's (docs/sr_complex.md) ---------
-// Below the refusal the two run the same code on sr_halves(h) row blocks of ns rows: n = sr_order(h) rows of J, a Gram matrix and a
+// ---- the five calls on the resident batch, each behind the positive GRU's entry, the complex RNN's (docs/sr_complex.md) and the 2D
+// RNN's (docs/sr_2d.md).  Below the refusal the three run the same code on sr_halves(h) row blocks of ns rows: n = sr_order(h) rows of J, a Gram matrix and a
 // solve of order n, y and eps of n entries ([Re ; Im] for the complex RNN).
 
 static int sr_log_derivatives(rnnwf_handle* h, const SrEntry& e, double* out, int64_t ns, int64_t nparams) {
@@ -392,31 +416,43 @@ static int sr_direction(rnnwf_handle* h, const SrEntry& e, double diag_shift, do
 }
 
 extern "C" int rnnwf_log_derivatives(rnnwf_handle* h, double* out, int64_t ns, int64_t nparams) {
-    return sr_log_derivatives(h, {"rnnwf_log_derivatives", false}, out, ns, nparams);
+    return sr_log_derivatives(h, {"rnnwf_log_derivatives", kSrPositive}, out, ns, nparams);
 }
-extern "C" int rnnwf_sr_gram(rnnwf_handle* h, double* gram, double* eps) { return sr_gram(h, {"rnnwf_sr_gram", false}, gram, eps); }
+extern "C" int rnnwf_sr_gram(rnnwf_handle* h, double* gram, double* eps) { return sr_gram(h, {"rnnwf_sr_gram", kSrPositive}, gram, eps); }
 extern "C" int rnnwf_sr_apply(rnnwf_handle* h, const double* y, double* out_direction) {
-    return sr_apply(h, {"rnnwf_sr_apply", false}, y, out_direction);
+    return sr_apply(h, {"rnnwf_sr_apply", kSrPositive}, y, out_direction);
 }
-extern "C" int rnnwf_sr_solve(rnnwf_handle* h, double diag_shift, double* y) { return sr_solve(h, {"rnnwf_sr_solve", false}, diag_shift, y); }
+extern "C" int rnnwf_sr_solve(rnnwf_handle* h, double diag_shift, double* y) { return sr_solve(h, {"rnnwf_sr_solve", kSrPositive}, diag_shift, y); }
 extern "C" int rnnwf_sr_direction(rnnwf_handle* h, double diag_shift, double* out_direction) {
-    return sr_direction(h, {"rnnwf_sr_direction", false}, diag_shift, out_direction);
+    return sr_direction(h, {"rnnwf_sr_direction", kSrPositive}, diag_shift, out_direction);
 }
 
 extern "C" int rnnwf_log_derivatives_complex(rnnwf_handle* h, double* out_re_im, int64_t ns, int64_t nparams) {
-    return sr_log_derivatives(h, {"rnnwf_log_derivatives_complex", true}, out_re_im, ns, nparams);
+    return sr_log_derivatives(h, {"rnnwf_log_derivatives_complex", kSrComplex}, out_re_im, ns, nparams);
 }
 extern "C" int rnnwf_sr_gram_complex(rnnwf_handle* h, double* gram, double* eps) {
-    return sr_gram(h, {"rnnwf_sr_gram_complex", true}, gram, eps);
+    return sr_gram(h, {"rnnwf_sr_gram_complex", kSrComplex}, gram, eps);
 }
 extern "C" int rnnwf_sr_apply_complex(rnnwf_handle* h, const double* y, double* out_direction) {
-    return sr_apply(h, {"rnnwf_sr_apply_complex", true}, y, out_direction);
+    return sr_apply(h, {"rnnwf_sr_apply_complex", kSrComplex}, y, out_direction);
 }
 extern "C" int rnnwf_sr_solve_complex(rnnwf_handle* h, double diag_shift, double* y) {
-    return sr_solve(h, {"rnnwf_sr_solve_complex", true}, diag_shift, y);
+    return sr_solve(h, {"rnnwf_sr_solve_complex", kSrComplex}, diag_shift, y);
 }
 extern "C" int rnnwf_sr_direction_complex(rnnwf_handle* h, double diag_shift, double* out_direction) {
-    return sr_direction(h, {"rnnwf_sr_direction_complex", true}, diag_shift, out_direction);
+    return sr_direction(h, {"rnnwf_sr_direction_complex", kSrComplex}, diag_shift, out_direction);
+}
+
+extern "C" int rnnwf_log_derivatives_2d(rnnwf_handle* h, double* out, int64_t ns, int64_t nparams) {
+    return sr_log_derivatives(h, {"rnnwf_log_derivatives_2d", kSr2D}, out, ns, nparams);
+}
+extern "C" int rnnwf_sr_gram_2d(rnnwf_handle* h, double* gram, double* eps) { return sr_gram(h, {"rnnwf_sr_gram_2d", kSr2D}, gram, eps); }
+extern "C" int rnnwf_sr_apply_2d(rnnwf_handle* h, const double* y, double* out_direction) {
+    return sr_apply(h, {"rnnwf_sr_apply_2d", kSr2D}, y, out_direction);
+}
+extern "C" int rnnwf_sr_solve_2d(rnnwf_handle* h, double diag_shift, double* y) { return sr_solve(h, {"rnnwf_sr_solve_2d", kSr2D}, diag_shift, y); }
+extern "C" int rnnwf_sr_direction_2d(rnnwf_handle* h, double diag_shift, double* out_direction) {
+    return sr_direction(h, {"rnnwf_sr_direction_2d", kSr2D}, diag_shift, out_direction);
 }
 
 // K whole minSR iterations with one host synchronisation (docs/sr.md, "Iterations on the device"): per iteration the fused VMC step,
@@ -428,7 +464,7 @@ extern "C" int rnnwf_sr_train_steps(rnnwf_handle* h, int32_t K, int64_t numsampl
                                     double* moments) {
     if (!h) return RNNWF_ERR_INVALID;
     const char* entry = "rnnwf_sr_train_steps";
-    if (int rc = sr_refuse(h, SrEntry{entry, false})) return rc;
+    if (int rc = sr_refuse(h, SrEntry{entry, kSrPositive})) return rc;
     if (int rc = sr_committed(h, entry)) return rc;
     if (K < 1 || K > kSrMaxSteps || numsamples < 1 || !couplings || !learning_rates || !diag_shifts || !moments)
         return h->fail(RNNWF_ERR_INVALID, "%s: bad arguments (1 <= K <= %d)", entry, kSrMaxSteps);

@@ -4,6 +4,7 @@
 //   order of the gradient image h->gradW ([dW | head row], grad.hip), element type of the model.
 //   Complex RNN (docs/sr_complex.md): J[2 ns][D_c], D_c = PCOLS QCOLS + 3 HEAD_ROW, row s = Re O_s, row ns + s = Im O_s; the rows
 //   [0, ns) and [ns, 2 ns) are centred with their own column means (HALVES).
+//   2D RNN (docs/sr_2d.md): J[ns][D_2], D_2 = PCOLS QCOLS + 2 HEAD_ROW of MdGradLayout, from the rows mdrnn_bwd_kernel<SR> left.
 //
 //   sr_outer_kernel  : O_s = 1/2 sum_n p_{n ns + s} (x) q_{n ns + s} from the rows gru_bwd_kernel<SR> left in P and Q (unit weights),
 //                      plus 1/2 of the sample's head row; image elements that no parameter reads (padding) are written as zeros.
@@ -13,41 +14,71 @@
 // Every sum has a fixed order (no atomics): the same batch gives the same bits.
 #pragma once
 #include "grad_kernels.h"
+#include "mdrnn_grad_kernels.h"
 
 namespace rnnwf {
 
-// One workgroup per sample; wave w owns the P tiles w, w + WAVES, ... (14 x 4 tiles at 50 units would be 224 accumulator registers in
-// one wave): 8 waves where 4 would own more than 112 registers of full rows of tiles, and the Q tiles are taken QCH at a time so that
-// a pass holds at most 64 accumulator registers - the N rows of P are read again per pass, from L2.
-template <typename T, int NFULL, int NOUT_ = 1>
-struct SrShape {
+// One workgroup per sample; the P tiles go round the waves (14 x 4 tiles at 50 units would be 224 accumulator registers in one wave)
+// and the Q tiles are taken QCH at a time so that a pass holds at most 64 accumulator registers - the N rows of P are read again per
+// pass, from L2.
+// The tiles of a gradient image G (GradLayout, or MdGradLayout of the 2D RNN: P and Q of different widths, two head rows) over the
+// WAVES = WP x WQ waves of a workgroup: wave w owns the P tiles wp, wp + WP, ... (wp = w mod WP) and the QW consecutive Q tiles from
+// wq QW on (wq = w / WP), taken QCH at a time.  WQ = 1: every wave owns every Q tile.  HALF: the rows carry d log P, O = 1/2 of them.
+template <typename T, class G_, int NOUT_, int WAVES_, int WQ_, bool HALF_>
+struct SrTiles {
     using Elem = T;
-    using G = GradLayout<NFULL, T>;
-    static constexpr int NF = NFULL, NOUT = NOUT_;         // NOUT 3: the complex RNN's three head rows
+    using G = G_;
+    static constexpr int NOUT = NOUT_;                     // head rows: 1, 3 (complex RNN) or 2 (2D RNN)
+    static constexpr bool HALF = HALF_;
     static constexpr int PT = G::PCOLS / 16, QT = G::QCOLS / 16;
     static constexpr int FRAG_REGS = 4 * (int)sizeof(T) / 4;
-    static constexpr int WAVES = ((PT + 3) / 4) * QT * FRAG_REGS > 112 ? 8 : 4;
-    static constexpr int MP = (PT + WAVES - 1) / WAVES;
-    static constexpr int QCH = 64 / (MP * FRAG_REGS) < 1 ? 1 : 64 / (MP * FRAG_REGS) > QT ? QT : 64 / (MP * FRAG_REGS);
-    static constexpr int PASSES = (QT + QCH - 1) / QCH;
+    static constexpr int WAVES = WAVES_, WQ = WQ_, WP = WAVES / WQ;
+    static constexpr int MP = (PT + WP - 1) / WP;
+    static constexpr int QW = (QT + WQ - 1) / WQ;
+    static constexpr int QCH = 64 / (MP * FRAG_REGS) < 1 ? 1 : 64 / (MP * FRAG_REGS) > QW ? QW : 64 / (MP * FRAG_REGS);
+    static constexpr int PASSES = (QW + QCH - 1) / QCH;
     static constexpr int64_t DW0 = (int64_t)G::PCOLS * G::QCOLS;
     static constexpr int64_t D = DW0 + NOUT * G::HEAD_ROW;
+    static_assert(WP * WQ == WAVES && WP <= PT && (WQ - 1) * QW < QT, "every wave owns a tile");
+    static_assert(MP * QCH * FRAG_REGS <= 64 || QCH == 1, "at most 64 accumulator registers per pass");
     static_assert(NOUT * G::HEAD_ROW <= WAVES * 64, "one thread per head element");
+};
+
+// The GRU families: 8 waves where 4 would own more than 112 registers of full rows of tiles; no split of the Q tiles.
+template <typename T, int NFULL>
+constexpr int kSrGruWaves = ((GradLayout<NFULL, T>::PCOLS / 16 + 3) / 4) * (GradLayout<NFULL, T>::QCOLS / 16) * (4 * (int)sizeof(T) / 4) > 112 ? 8 : 4;
+template <typename T, int NFULL, int NOUT_ = 1>            // NOUT 3: the complex RNN's three head rows, which carry their 1/2 already
+struct SrShape : SrTiles<T, GradLayout<NFULL, T>, NOUT_, kSrGruWaves<T, NFULL>, 1, NOUT_ == 1> {
+    static constexpr int NF = NFULL;
+};
+// The 2D RNN (docs/sr_2d.md): NT x 2 NT tiles of 8 registers.  Two rows of waves share the P tiles, the Q tiles are split over
+// two (up to 52 units) or four (53..84 units: eight waves) columns of waves.
+template <int NFULL>
+struct MdSrShape : SrTiles<double, MdGradLayout<NFULL>, 2, NFULL <= 3 ? 4 : 8, NFULL <= 3 ? 2 : 4, true> {
+    static constexpr int NF = NFULL;
 };
 
 // K = N is short: the last group of four sites is padded with zeros (its rows are read from site 0 and zeroed), no branch.
 // NOUT = 3 (complex RNN): P holds the rows of one seed of gru_bwd_kernel<SR>, which already carry the 1/2 of log a = 1/2 log p
 // (no factor here), head its three head rows, J the first row of that seed's half.
-template <typename T, int NFULL, int NOUT = 1>
-__global__ void __launch_bounds__((SrShape<T, NFULL, NOUT>::WAVES * 64)) sr_outer_kernel(const T* __restrict__ P, const T* __restrict__ Q,
-                                                                                       const T* __restrict__ head, const uint8_t* __restrict__ used,
-                                                                                       int N, int64_t ns, T* __restrict__ J) {
-    using S = SrShape<T, NFULL, NOUT>;
-    const T scale = NOUT == 1 ? T(0.5) : T(1);
+template <class S>
+__global__ void __launch_bounds__((S::WAVES * 64)) sr_outer_kernel(const typename S::Elem* __restrict__ P, const typename S::Elem* __restrict__ Q,
+                                                                 const typename S::Elem* __restrict__ head, const uint8_t* __restrict__ used,
+                                                                 int N, int64_t ns, typename S::Elem* __restrict__ J) {
+    using T = typename S::Elem;
+    constexpr int NOUT = S::NOUT;
+    const T scale = S::HALF ? T(0.5) : T(1);
     using G = typename S::G;
     using V4 = typename Frag<T>::V4;
-    constexpr int PT = S::PT, QT = S::QT, MP = S::MP, WAVES = S::WAVES, QCH = S::QCH;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    constexpr int PT = S::PT, MP = S::MP, WP = S::WP, QCH = S::QCH, QW = S::QW;
+    constexpr bool SPLIT = S::WQ > 1;                      // the Q tiles are split over columns of waves
+    const int lane = threadIdx.x & 63;
+    const int wid = SPLIT ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;      // SPLIT: in a scalar register
+    const int wave = SPLIT ? wid % WP : wid;
+    // this wave's Q tiles are q0 .. q0 + qn - 1; the last column of waves may own fewer than QW: it skips a pass without a tile of
+    // its own (a branch the whole wave takes) and multiplies its last tile again for the missing tiles of a pass it has one in
+    const int q0 = SPLIT ? (wid / WP) * QW : 0;
+    const int qn = SPLIT ? (S::QT - q0 < QW ? S::QT - q0 : QW) : QW;
     const int li = lane & 15, lk = lane >> 4;
     const int kgroups = (N + 3) / 4;
     for (int64_t s = blockIdx.x; s < ns; s += gridDim.x) {
@@ -55,6 +86,7 @@ __global__ void __launch_bounds__((SrShape<T, NFULL, NOUT>::WAVES * 64)) sr_oute
 #pragma unroll
         for (int pass = 0; pass < S::PASSES; ++pass) {
             const int t0 = pass * QCH;
+            if (SPLIT && t0 >= qn) continue;
             V4 acc[MP][QCH];
 #pragma unroll
             for (int i = 0; i < MP; ++i)
@@ -65,13 +97,19 @@ __global__ void __launch_bounds__((SrShape<T, NFULL, NOUT>::WAVES * 64)) sr_oute
                 const bool ok = n < N;
                 const int64_t row = (int64_t)(ok ? n : 0) * ns + s;
                 const T* prow = P + row * G::PCOLS + li;
-                const T* qrow = Q + row * G::QCOLS + li;
+                const T* qrow = Q + row * G::QCOLS + 16 * q0 + li;
                 T qv[QCH], pv[MP];
 #pragma unroll
-                for (int t = 0; t < QCH; ++t) qv[t] = t0 + t < QT ? qrow[16 * (t0 + t)] : T(0);
+                for (int t = 0; t < QCH; ++t) {
+                    if constexpr (SPLIT) {                            // a tile past the wave's share: the last one again, dropped on store
+                        qv[t] = qrow[16 * (t0 + t < qn ? t0 + t : qn - 1)];
+                    } else {
+                        qv[t] = t0 + t < QW ? qrow[16 * (t0 + t)] : T(0);
+                    }
+                }
 #pragma unroll
                 for (int i = 0; i < MP; ++i) {
-                    const int pt = wave + WAVES * i;              // a wave without an i-th tile multiplies the last tile again and drops it
+                    const int pt = wave + WP * i;                 // a wave without an i-th tile multiplies the last tile again and drops it
                     pv[i] = prow[16 * (pt < PT ? pt : PT - 1)];
                 }
 #pragma unroll
@@ -81,20 +119,20 @@ __global__ void __launch_bounds__((SrShape<T, NFULL, NOUT>::WAVES * 64)) sr_oute
                     const T p = ok ? pv[i] : T(0);
 #pragma unroll
                     for (int t = 0; t < QCH; ++t)
-                        if (t0 + t < QT) acc[i][t] = Frag<T>::mfma(p, qv[t], acc[i][t]);
+                        if (t0 + t < QW) acc[i][t] = Frag<T>::mfma(p, qv[t], acc[i][t]);
                 }
             }
 #pragma unroll
             for (int i = 0; i < MP; ++i) {
-                const int pt = wave + WAVES * i;
+                const int pt = wave + WP * i;
                 if (pt >= PT) continue;
 #pragma unroll
                 for (int t = 0; t < QCH; ++t) {
-                    if (t0 + t >= QT) continue;
+                    if (t0 + t >= QW || t0 + t >= qn) continue;
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {
                         const int fr = sizeof(T) == 4 ? 4 * lk + rr : lk + 4 * rr;      // C/D fragment row of (lane quarter lk, register rr)
-                        const int idx = (16 * pt + fr) * G::QCOLS + 16 * (t0 + t) + li;
+                        const int idx = (16 * pt + fr) * G::QCOLS + 16 * (q0 + t0 + t) + li;
                         out[idx] = used[idx] ? scale * acc[i][t][rr] : T(0);
                     }
                 }

@@ -40,22 +40,31 @@ def _check_solver(solver):
     return solver
 
 
+def _real_direction(wf, suffix, diag_shift, solver):
+    """the direction of a real positive wave function through the facade methods sr_gram / sr_apply / sr_direction + suffix
+    ("" the positive GRU's, "_2d" the 2D RNN's)"""
+    lam = _check_shift(diag_shift)
+    if _check_solver(solver) == "device":
+        return getattr(wf, "sr_direction" + suffix)(lam)
+    gram, eps = getattr(wf, "sr_gram" + suffix)()
+    return getattr(wf, "sr_apply" + suffix)(solve_shifted(gram, eps, diag_shift))
+
+
+def _real_qgt(o):
+    d = o - o.mean(axis=0)
+    return d.T @ d / o.shape[0]
+
+
 def minsr_direction(wf, diag_shift, solver="host"):
     """delta (num_params,) float64 on the resident batch of `wf` (the last vmc_step / load_batch), flat order of wf._layout().
     solver "host": Gram matrix to the host, LAPACK Cholesky, sr_apply; "device": wf.sr_direction, the whole direction on the device."""
-    lam = _check_shift(diag_shift)
-    if _check_solver(solver) == "device":
-        return wf.sr_direction(lam)
-    gram, eps = wf.sr_gram()
-    return wf.sr_apply(solve_shifted(gram, eps, diag_shift))
+    return _real_direction(wf, "", diag_shift, solver)
 
 
 def qgt(wf):
     """S = dO^T dO / ns (num_params, num_params) float64 from the per-sample log-derivatives of the resident batch: the quantum
     geometric tensor of a real positive wave function.  For diagnostics and small models (it holds num_params^2 doubles)."""
-    o = wf.log_derivatives()
-    d = o - o.mean(axis=0)
-    return d.T @ d / o.shape[0]
+    return _real_qgt(wf.log_derivatives())
 
 
 def flatten_params(wf, params, scope="RNNwavefunction"):
@@ -79,6 +88,19 @@ def _check_device_steps(device_steps):
     if isinstance(device_steps, bool) or not isinstance(device_steps, (int, np.integer)) or device_steps < 1:
         raise ValueError("device_steps must be None or an integer >= 1, got %r" % (device_steps,))
     return int(device_steps)
+
+
+def _real_host_loop(wf, suffix, theta, dtype, couplings, numsteps, numsamples, learningrate, diag_shift, seed, solver, meanEnergy, varEnergy):
+    """iterations 0..numsteps of vmc_step (step = iteration) -> _real_direction -> theta -= lr delta, rounded to `dtype` ->
+    set_params_flat; appends every iteration's energy and variance, returns the last theta"""
+    for it in range(int(numsteps) + 1):
+        s1, s2, n, _ = wf.vmc_step(int(numsamples), seed, it, couplings)["moments"]
+        meanE = s1 / n
+        meanEnergy.append(meanE)
+        varEnergy.append(s2 / n - meanE ** 2)
+        theta = (theta - learningrate * _real_direction(wf, suffix, diag_shift, solver)).astype(dtype).astype(np.float64)
+        wf.set_params_flat(theta)
+    return theta
 
 
 def train_tfim(wf, Jz, Bx, params, numsteps=100, numsamples=500, learningrate=1e-2, diag_shift=1e-3, seed=111, scope="RNNwavefunction",
@@ -115,13 +137,7 @@ def train_tfim(wf, Jz, Bx, params, numsteps=100, numsamples=500, learningrate=1e
                 varEnergy.append(s2 / n - meanE ** 2)
         train_tfim.last_params = wf.get_params_dict(params, scope)
         return meanEnergy, varEnergy
-    for it in range(int(numsteps) + 1):
-        s1, s2, n, _ = wf.vmc_step(int(numsamples), seed, it, couplings)["moments"]
-        meanE = s1 / n
-        meanEnergy.append(meanE)
-        varEnergy.append(s2 / n - meanE ** 2)
-        theta = (theta - learningrate * minsr_direction(wf, diag_shift, solver)).astype(dtype).astype(np.float64)
-        wf.set_params_flat(theta)
+    theta = _real_host_loop(wf, "", theta, dtype, couplings, numsteps, numsamples, learningrate, diag_shift, seed, solver, meanEnergy, varEnergy)
     train_tfim.last_params = unflatten_params(wf, theta, params, scope)
     return meanEnergy, varEnergy
 
@@ -181,4 +197,46 @@ def train_j1j2(wf, J1, J2, Bz, params, numsteps=100, numsamples=500, learningrat
         theta = (theta - learningrate * minsr_direction_complex(wf, diag_shift, solver)).astype(dtype).astype(np.float64)
         wf.set_params_flat(theta)
     train_j1j2.last_params = unflatten_params(wf, theta, params, scope)
+    return meanEnergy, varEnergy
+
+
+# ---- the 2D RNN (docs/sr_2d.md) ---------------------------------------------------------------------------------------------------
+# psi = sqrt(P) real and positive on the zig-zag path of the square lattice: the positive model's formulas and solve, on the
+# rnnwf_*_2d entries of an MDRNN2D handle.
+
+def minsr_direction_2d(wf, diag_shift, solver="host"):
+    """delta (num_params,) float64 on the resident batch of the 2D RNN `wf`, flat order of wf._layout().  solver "host": the Gram
+    matrix to the host, LAPACK Cholesky, sr_apply_2d; "device": wf.sr_direction_2d."""
+    return _real_direction(wf, "_2d", diag_shift, solver)
+
+
+def qgt_2d(wf):
+    """S = dO^T dO / ns (num_params, num_params) float64 from the per-sample log-derivatives of the resident batch of the 2D RNN.
+    For diagnostics and small models."""
+    return _real_qgt(wf.log_derivatives_2d())
+
+
+def train_tfim2d(wf, Jz, Bx, params, numsteps=100, numsamples=500, learningrate=1e-2, diag_shift=1e-3, seed=111, scope="RNNwavefunction",
+                 solver="device"):
+    """Minimise the square-lattice TFIM energy of `wf` (a NativeWavefunction of MDRNN2D holding `params`) by minSR, the host loop of
+    train_tfim: vmc_step (samples, local energies, moments; the batch stays resident) -> minsr_direction_2d -> theta -= lr delta ->
+    set_params_flat.  Jz: a scalar or one entry per site in the order of vmc_step's couplings.  The batches are drawn as
+    training.run_2DTFIM_2DRNN draws them (seed, step = iteration), so iteration 0 has that driver's moments from the same seed.
+    Returns (meanEnergy, varEnergy), one entry per iteration 0..numsteps; the trained parameters are left in
+    train_tfim2d.last_params and keep the dtype of `params`."""
+    _check_shift(diag_shift)
+    _check_solver(solver)
+    if int(numsteps) < 0 or int(numsamples) < 2:
+        raise ValueError("numsteps must be >= 0 and numsamples >= 2, got %r and %r" % (numsteps, numsamples))
+    N = wf.N                                            # Nx Ny sites
+    if np.size(Jz) not in (1, N):
+        raise ValueError("Jz must be a scalar or have %d entries, got %d" % (N, np.size(Jz)))
+    jz = np.broadcast_to(np.asarray(Jz, dtype=np.float64).ravel(), (N,))
+    couplings = np.concatenate([jz, [float(Bx)]])
+    dtype = next(iter(params.values())).dtype
+    theta = flatten_params(wf, params, scope).astype(dtype).astype(np.float64)
+    wf.set_params_flat(theta)
+    meanEnergy, varEnergy = [], []
+    theta = _real_host_loop(wf, "_2d", theta, dtype, couplings, numsteps, numsamples, learningrate, diag_shift, seed, solver, meanEnergy, varEnergy)
+    train_tfim2d.last_params = unflatten_params(wf, theta, params, scope)
     return meanEnergy, varEnergy
