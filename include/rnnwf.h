@@ -415,6 +415,36 @@ int rnnwf_pauli_step_complex(rnnwf_handle* h, const int32_t* flip, const int32_t
                              const int32_t* samples, int64_t ns, uint64_t seed, uint64_t step, int64_t sample_offset,
                              double* term_sums, float* out_eloc_re_im, double* moments, double* out_log_ratio, int32_t* out_samples);
 
+/* rnnwf_pauli_train_steps / rnnwf_pauli_train_steps_complex: K whole Adam iterations (1 <= K <= 1024) on the Hamiltonian
+ * sum_k coeff_k O_k of the terms with ONE host synchronisation behind the last iteration: the counterpart of rnnwf_train_steps for the
+ * Hamiltonians of rnnwf_pauli_step / rnnwf_pauli_step_complex (docs/pauli_train.md).  The models are those of the two entries (the
+ * positive one-layer GRU1D and GRU1D_F64; the one-layer CRNN_U1).  The terms are checked, grouped and uploaded once per call.  Iteration
+ * k = 0 .. K-1, all on the handle's stream: numsamples samples drawn with step index step0 + k as rnnwf_sample draws them; the base
+ * pass, site terms and masked tails of the pauli entry; one amplitude ratio per (distinct flip mask, chain), read by E_loc and by the
+ * per-term sums; the moments into row k of `moments` ([K][4], as the pauli entry returns them); the gradient of the VMC cost with
+ * the mean energy read from those moments on the device; Adam with learning_rates[k] and bias correction number t + k + 1 (t the
+ * count of rnnwf_adam_get_state) on the flat float64 parameters, rounded to the model's type; every weight image rebuilt on the
+ * device.  The arithmetic is that of the host loop pauli entry -> rnnwf_vmc_gradient -> host Adam -> rnnwf_set_param, operation for
+ * operation: moments, parameters and Adam's state equal that loop's bit for bit.
+ * term_sums: NULL (the per-term kernels are then not launched), or [K][nterms][2] (complex: [K][nterms][4]): row k holds what the
+ * pauli entry's term_sums holds for iteration k's batch.  out_eloc: NULL, or [numsamples] E_loc (complex64 for the complex entry) of
+ * the LAST iteration's batch.
+ * Afterwards, as after rnnwf_train_steps: no batch is resident, rnnwf_get_param and rnnwf_commit_params see the device's parameters,
+ * Adam's step count has advanced by K.
+ * Refused before anything is launched or changed, leaving parameters, Adam's state and the resident batch as they were:
+ * RNNWF_ERR_INVALID "<entry>: <why>" for a model the pauli entry refuses, a handle with a communicator, K outside 1..1024, nterms < 1,
+ * numsamples < 1, null flip, sign, coeff, learning_rates or moments, sample_offset < 0, a learning_rates[k] that is not finite, a mask
+ * entry other than 0 / 1, more than 65535 distinct non-empty flip masks; RNNWF_ERR_STATE for uncommitted parameters; RNNWF_ERR_NOMEM
+ * "<entry>: ... exceed the state budget of one pass; split the batch" for numsamples beyond one pass of the pauli entry.
+ * Timing ids: 0 = base passes + site-term replay, 1 = masked-tail pass, 2 = ratios, [term sums,] E_loc and moments, 3 / 4 = gradient. */
+int rnnwf_pauli_train_steps(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff, int32_t nterms, int32_t K,
+                            int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset, const double* learning_rates,
+                            double beta1, double beta2, double epsilon, double* moments, double* term_sums, double* out_eloc);
+int rnnwf_pauli_train_steps_complex(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff_re_im, int32_t nterms,
+                                    int32_t K, int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset,
+                                    const double* learning_rates, double beta1, double beta2, double epsilon, double* moments,
+                                    double* term_sums, float* out_eloc_re_im);
+
 /* ---- stochastic reconfiguration (natural gradient, minSR; docs/sr.md) -------------------------------------------------------
  * psi = sqrt(P) real and positive:  O[s][k] = d log psi(sigma_s) / d theta_k = 1/2 d log P(sigma_s) / d theta_k, theta in the flat
  * order of rnnwf_set_params_flat;  dO = O - mean_s O;  eps_s = E_loc,s - mean E.  The minSR direction with diagonal shift lambda is

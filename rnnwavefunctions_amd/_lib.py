@@ -80,6 +80,10 @@ PROTOTYPES = {
                                       _I32P]),
     "rnnwf_pauli_step_complex": (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I32P, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F32P, _F64P,
                                            _F64P, _I32P]),
+    "rnnwf_pauli_train_steps": (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I32, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64, _F64, _F64,
+                                          _F64P, _F64P, _F64P]),
+    "rnnwf_pauli_train_steps_complex": (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I32, _I64, C.c_uint64, C.c_uint64, _I64, _F64P, _F64, _F64,
+                                                  _F64, _F64P, _F64P, _F32P]),
     "rnnwf_log_derivatives": (C.c_int, [_P, _F64P, _I64, _I64]),
     "rnnwf_sr_gram": (C.c_int, [_P, _F64P, _F64P]),
     "rnnwf_sr_apply": (C.c_int, [_P, _F64P, _F64P]),
@@ -794,6 +798,58 @@ class NativeWavefunction:
             out["log_ratio"] = lr
         if want_samples:
             out["samples"] = smp if smp is not None else s
+        return out
+
+    # -- device-resident Adam iterations on a Pauli-string Hamiltonian (docs/pauli_train.md) ---------
+    def pauli_train_steps(self, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1=0.9, beta2=0.999, epsilon=1e-8,
+                          sample_offset=0, want_term_sums=False, want_eloc=False):
+        """len(learning_rates) whole iterations (sample at step index step0 + k, local energies of the Hamiltonian sum_k coeff_k
+        (prod_sign sz)(prod_flip sx), gradient, Adam update with learning_rates[k], re-pack of the weight images) on the device with
+        one host synchronisation (rnnwf_pauli_train_steps).  flip, sign, coeff as pauli_step takes them.  Returns the (K, 4) moments
+        of the K batches, or - with want_term_sums or want_eloc - dict(moments=(K, 4), term_sums=(K, nterms, 2)?, eloc=(numsamples,)
+        of the last iteration's batch?).  No batch is resident afterwards; get_param returns the trained values."""
+        return self._pauli_train_call("rnnwf_pauli_train_steps", False, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1,
+                                      beta2, epsilon, sample_offset, want_term_sums, want_eloc)
+
+    def pauli_train_steps_complex(self, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1=0.9, beta2=0.999, epsilon=1e-8,
+                                  sample_offset=0, want_term_sums=False, want_eloc=False):
+        """pauli_train_steps for the complex RNN (rnnwf_pauli_train_steps_complex): coeff (nterms,) complex, term_sums (K, nterms, 4) as
+        pauli_step_complex returns a row, eloc complex64."""
+        return self._pauli_train_call("rnnwf_pauli_train_steps_complex", True, flip, sign, coeff, numsamples, seed, step0, learning_rates,
+                                      beta1, beta2, epsilon, sample_offset, want_term_sums, want_eloc)
+
+    def _pauli_train_call(self, entry, cplx, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1, beta2, epsilon,
+                          sample_offset, want_term_sums, want_eloc):
+        ns, N = int(numsamples), self.N
+        fl, sg = np.asarray(flip), np.asarray(sign)
+        if fl.ndim == 1:
+            fl, sg = fl[None, :], sg[None, :]
+        if fl.ndim != 2 or fl.shape[0] < 1 or fl.shape[1] != N or sg.shape != fl.shape:
+            raise ValueError("flip and sign must both have shape (nterms >= 1, %d), got %r and %r" % (N, fl.shape, sg.shape))
+        if not (np.all(fl == fl.astype(np.int32)) and np.all(sg == sg.astype(np.int32))):
+            raise ValueError("flip and sign must hold the integers 0 and 1")
+        fl, fp = _i32(fl)
+        sg, gp = _i32(sg)
+        nterms = fl.shape[0]
+        co = np.ascontiguousarray(np.atleast_1d(coeff), dtype=np.complex128 if cplx else np.float64)
+        if co.shape != (nterms,):
+            raise ValueError("coeff must have shape (%d,), got %r" % (nterms, co.shape))
+        lr, lrp = _f64(np.atleast_1d(learning_rates))
+        K = lr.size
+        mom = np.empty((K, 4), dtype=np.float64)
+        sums = np.empty((K, nterms, 4 if cplx else 2), dtype=np.float64) if want_term_sums else None
+        el = np.empty(max(ns, 0), dtype=np.complex64 if cplx else np.float64) if want_eloc else None
+        self._check(getattr(self.lib, entry)(self.h, fp, gp, co.ctypes.data_as(_F64P), nterms, K, ns, int(seed), int(step0), int(sample_offset),
+                                             lrp, float(beta1), float(beta2), float(epsilon), mom.ctypes.data_as(_F64P),
+                                             sums.ctypes.data_as(_F64P) if sums is not None else None,
+                                             el.ctypes.data_as(_F32P if cplx else _F64P) if el is not None else None))
+        if not (want_term_sums or want_eloc):
+            return mom
+        out = {"moments": mom}
+        if want_term_sums:
+            out["term_sums"] = sums
+        if want_eloc:
+            out["eloc"] = el
         return out
 
     # -- multi-GPU --------------------------------------------------------------------------------

@@ -171,6 +171,12 @@ int train_allreduce_grads_device(rnnwf_handle* h);           // 1: gradient all-
 int train_prepare(rnnwf_handle* h);                          // the tables built and the flat parameters current on the device
 // theta_i <- round_T(theta_i - lr (+-col[|gidx_i| - 1])) unless *hold != 0 (both on the device), then the re-pack of every image
 int train_apply_direction(rnnwf_handle* h, const double* col, size_t col_count, double lr, const long long* hold);
+// for the Adam iterations of another local energy (pauli_driver.h: pauli_train_steps), behind train_prepare: the rows of the pinned
+// moments table, iteration k's update as rnnwf_train_steps queues it, and the state that entry leaves after its one synchronisation
+constexpr int kTrainMaxSteps = 1024;                         // iterations of one call: the rows of the pinned moments table
+double* train_moments_row(rnnwf_handle* h, int k);           // device address of row k, for h->moments_direct
+int train_adam_update(rnnwf_handle* h, int k, double lr, double beta1, double beta2, double epsilon);
+void train_steps_done(rnnwf_handle* h, int K, double* moments);
 void grad_invalidate(rnnwf_handle* h);
 // bytes of per-site hidden states one pass may hold; RNNWF_STATE_BUDGET_MB (read at rnnwf_create) overrides the
 // default (tests use it to drive the multi-pass path at small sizes)

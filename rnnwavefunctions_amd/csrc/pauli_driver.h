@@ -11,8 +11,11 @@
 //                              arguments; site -> position map (empty: the same) and cell evaluations of a chain flipped from
 //                              position 0 on (pauli_terms.h); chains per pass
 //   pass(h, ns, g, sc, keep, sums_host)   the kernels of one pass over the chains in h->bits: log-ratios at sc.lr, E_loc in h->eloc
+// pauli_train_steps<P> below is the driver of the device-resident Adam iterations on the same terms (rnnwf_pauli_train_steps,
+// rnnwf_pauli_train_steps_complex).
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -109,6 +112,87 @@ int pauli_step(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const 
     if (moments) memcpy(moments, mom, sizeof mom);
     // one pass: bits, states and E_loc of the whole batch are on the device, as rnnwf_vmc_step leaves them
     keep_resident(h, ns <= chunk ? ns : 0);
+    return RNNWF_OK;
+}
+
+// K whole Adam iterations on the Hamiltonian of the terms with one host synchronisation behind the last (rnnwf_pauli_train_steps,
+// rnnwf_pauli_train_steps_complex; docs/pauli_train.md).  The policy adds to pauli_step's
+//   train_pass(h, ns, g, sc, sums_row)   the kernels of one iteration's pass over the chains drawn into h->bits: E_loc in h->eloc,
+//                                        the checkpoints kept, the per-term sums into sums_row on the device unless it is nullptr
+// Per call: the refusals, the terms derived and uploaded once, one scratch allocation (the tables, one pass, then the [K][nterms]
+// table of per-term sums), train.hip's tables and flat parameters.  Per iteration k, nothing waiting for the host: the family's base
+// pass drawing at step index step0 + k, train_pass, the moments into row k of train.hip's pinned table, the gradient reading them on
+// the device, Adam with learning_rates[k] and the re-pack of every weight image.  Neither the gradient nor the update touches
+// h->renyi, so the tables stay where they were uploaded.  out_eloc: [ns] E_loc of the last iteration's batch, or nullptr.
+template <class P>
+int pauli_train_steps(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const void* coeff, int32_t nterms, int32_t K, int64_t ns,
+                      uint64_t seed, uint64_t step0, int64_t sample_offset, const double* learning_rates, double beta1, double beta2,
+                      double epsilon, double* moments, double* term_sums, void* out_eloc) {
+    // everything is validated before anything is touched: a refused call leaves the resident batch, the parameters and Adam's state
+    if (!h) return RNNWF_ERR_INVALID;
+    if (int rc = P::refuse(h)) return rc;
+    if (int rc = refuse_uncommitted(h, P::kEntry, P::kUncommittedInvalid)) return rc;
+    if (h->comm) return h->fail(RNNWF_ERR_INVALID, "%s: runs in one process on one GPU, this handle has a communicator", P::kEntry);
+    if (int rc = require_gradient(h, P::kEntry)) return rc;
+    if (K < 1 || K > kTrainMaxSteps) return h->fail(RNNWF_ERR_INVALID, "%s: K must be 1..%d", P::kEntry, kTrainMaxSteps);
+    if (nterms < 1) return h->fail(RNNWF_ERR_INVALID, "%s: nterms must be >= 1", P::kEntry);
+    if (ns < 1) return h->fail(RNNWF_ERR_INVALID, "%s: numsamples must be >= 1", P::kEntry);
+    if (!flip || !sign || !coeff || !learning_rates || !moments)
+        return h->fail(RNNWF_ERR_INVALID, "%s: flip, sign, %s, learning_rates and moments must be non-null", P::kEntry, P::kCoeff);
+    if (sample_offset < 0) return h->fail(RNNWF_ERR_INVALID, "%s: sample_offset must be >= 0", P::kEntry);
+    for (int k = 0; k < K; ++k)
+        if (!std::isfinite(learning_rates[k])) return h->fail(RNNWF_ERR_INVALID, "%s: learning_rates[%d] must be finite", P::kEntry, k);
+    if (int rc = P::precheck(h, nullptr, ns)) return rc;
+    PauliTerms g;
+    const std::vector<int32_t> pos = P::positions(h);
+    if (int rc = prepare_pauli_terms(h, P::kEntry, flip, sign, nterms, pos.empty() ? nullptr : pos.data(), P::cells(h), g)) return rc;
+    const int N = h->N;
+    const size_t E = P::kElem;
+    if (ns > P::chunk(h, g.M))
+        return h->fail(RNNWF_ERR_NOMEM, "%s: %lld samples exceed the state budget of one pass; split the batch", P::kEntry, (long long)ns);
+    if ((int64_t)nterms * ((ns + P::kThreads - 1) / P::kThreads) > 0x7fffffffLL)
+        return h->fail(RNNWF_ERR_INVALID, "%s: nterms x ceil(ns / %d) exceeds the grid of the term kernel; split the batch", P::kEntry,
+                       P::kThreads);
+    RNNWF_HIP(h, hipSetDevice(h->cfg.device));
+    if (int rc = train_prepare(h)) return rc;
+    const PauliScratch sc(N, g, ns, E, P::kOwnLogP, P::kThreads);
+    const size_t row = (size_t)nterms * 2 * E;                // a (nterms, 2) real or (nterms, 4) complex row of per-term sums
+    if (int rc = ensure(h, h->renyi, sc.bytes + (term_sums ? (size_t)K * row : 0))) return rc;
+    if (int rc = ensure(h, h->bits, (size_t)(N + 31) / 32 * ns * 4)) return rc;
+    char* buf = (char*)h->renyi.p;
+    if (g.M) {
+        RNNWF_HIP(h, hipMemcpyAsync(buf + sc.mask, g.mask.data(), g.mask.size() * 4, hipMemcpyHostToDevice, h->stream));
+        RNNWF_HIP(h, hipMemcpyAsync(buf + sc.order, g.order.data(), (size_t)g.M * 4, hipMemcpyHostToDevice, h->stream));
+        RNNWF_HIP(h, hipMemcpyAsync(buf + sc.first, g.first.data(), (size_t)g.M * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    RNNWF_HIP(h, hipMemcpyAsync(buf + sc.sgn, g.sgn.data(), g.sgn.size() * 4, hipMemcpyHostToDevice, h->stream));
+    RNNWF_HIP(h, hipMemcpyAsync(buf + sc.tmask, g.tmask.data(), (size_t)nterms * 4, hipMemcpyHostToDevice, h->stream));
+    RNNWF_HIP(h, hipMemcpyAsync(buf + sc.coeff, coeff, (size_t)nterms * E, hipMemcpyHostToDevice, h->stream));
+    RNNWF_HIP(h, hipStreamSynchronize(h->stream));           // the set-up's: the tables leave the host's vectors before the iterations start
+    h->last_ns = 0;                                   // h->bits, h->hck and h->eloc are overwritten from here on
+    h->call_ns = ns;
+    int rc = 0;
+    for (int k = 0; k < K && !rc; ++k) {
+        const Draw d{seed, step0 + (uint64_t)k, sample_offset};
+        rc = h->family->base(h, ns, &d);
+        if (!rc) rc = P::train_pass(h, ns, g, sc, term_sums ? (double*)(buf + sc.bytes + (size_t)k * row) : nullptr);
+        if (rc) break;
+        h->moments_direct = train_moments_row(h, k);          // as rnnwf_train_steps: the moments kernel writes the pinned row itself
+        rc = run_moments(h, h->eloc.p, ns, P::kComplex, nullptr);
+        h->moments_direct = nullptr;
+        if (rc) break;
+        keep_resident(h, ns);                                 // the batch the gradient reads
+        rc = grad_device(h, 0.0, 0.0, 0.0, (const double*)h->moments.p, nullptr);
+        if (!rc) rc = train_adam_update(h, k, learning_rates[k], beta1, beta2, epsilon);
+    }
+    if (!rc && term_sums && hipMemcpyAsync(term_sums, buf + sc.bytes, (size_t)K * row, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+        rc = h->fail(RNNWF_ERR_HIP, "%s: download of the per-term sums failed", P::kEntry);
+    if (!rc && out_eloc && hipMemcpyAsync(out_eloc, h->eloc.p, (size_t)ns * 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
+        rc = h->fail(RNNWF_ERR_HIP, "%s: download of E_loc failed", P::kEntry);
+    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = h->fail(RNNWF_ERR_HIP, "%s: stream synchronisation failed", P::kEntry);
+    h->last_ns = 0;                       // the resident batch belongs to the weights before the last update
+    if (rc) return rc;
+    train_steps_done(h, K, moments);
     return RNNWF_OK;
 }
 

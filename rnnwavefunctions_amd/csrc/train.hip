@@ -26,7 +26,7 @@ using namespace rnnwf;
 
 namespace {
 
-constexpr int kMaxSteps = 1024;
+constexpr int kMaxSteps = kTrainMaxSteps;
 
 __device__ __forceinline__ void repack_entry(const PackEntry& t, const double* __restrict__ P, char* __restrict__ img) {
 #pragma clang fp contract(off)
@@ -323,6 +323,24 @@ int rnnwf::train_apply_direction(rnnwf_handle* h, const double* col, size_t col_
                                                                                       h->f64 ? 0 : 1, hold);
     RNNWF_HIP(h, hipGetLastError());
     return launch_repack(h);
+}
+
+double* rnnwf::train_moments_row(rnnwf_handle* h, int k) { return (double*)h->train.mom_host_dev + 4 * k; }
+
+// iteration k of a call: Adam from the gradient's dW image with the bias correction of update adam_t + k + 1, then the re-pack
+int rnnwf::train_adam_update(rnnwf_handle* h, int k, double lr, double beta1, double beta2, double epsilon) {
+    TrainState& t = h->train;
+    if (!t.supported || t.host_newer) return h->fail(RNNWF_ERR_STATE, "device training: train_adam_update without train_prepare");
+    if (int rc = ensure_bwd_image(h)) return rc;
+    return launch_update(h, adam_lr_t(lr, beta1, beta2, t.adam_t + k + 1), beta1, beta2, epsilon);
+}
+
+// behind the one synchronisation of K iterations: moments [K][4] from the pinned table, the state as rnnwf_train_steps leaves it
+void rnnwf::train_steps_done(rnnwf_handle* h, int K, double* moments) {
+    memcpy(moments, h->train.mom_host, (size_t)K * 4 * sizeof(double));
+    h->train.adam_t += K;
+    h->last_ns = 0;                       // the resident batch belongs to the weights before the last update
+    h->grads.clear();
 }
 
 void rnnwf::train_params_changed_on_host(rnnwf_handle* h) {

@@ -188,14 +188,19 @@ def structure_factor(corr, q):
     return out if np.ndim(q) else float(out[0])
 
 
-def minimize_hamiltonian(wf, ham, numsamples, steps, lr, params=None, seed=111, scope="RNNwavefunction", opt=None, verbose=False):
+def minimize_hamiltonian(wf, ham, numsamples, steps, lr, params=None, seed=111, scope="RNNwavefunction", opt=None, verbose=False,
+                         device_steps=None):
     """Minimise the energy of the complex RNN `wf` under `ham` (a ComplexHamiltonian) with training.minimize_hamiltonian's loop:
     pauli_step_complex (samples, complex local energies of `ham`, moments; the batch stays resident) -> vmc_gradient(mean_re,
     mean_im, n) of the complex cost -> training.Adam on the host -> set_params.  wf: the J1J2.ComplexRNNwavefunction facade (its own
     parameters and scope are used and updated) or a NativeWavefunction with `params` scoped by `scope`.  Returns (meanEnergy complex,
     varEnergy of the real part), one entry per iteration 0..steps; the trained parameters are left in
-    minimize_hamiltonian.last_params.  The batch must fit one pass of the state budget.  Single process, host optimizer."""
-    from .training import Adam, cost_gradient
+    minimize_hamiltonian.last_params.  The batch must fit one pass of the state budget.  Single process.
+    device_steps=K (an integer >= 1): the same iterations run on the device in chunks of at most K with one host synchronisation
+    each (pauli_train_steps_complex, docs/pauli_train.md) - the same energies, variances and parameters, bit for bit.  The device
+    runs Adam from a fresh state: opt= is refused with it."""
+    from .training import Adam, check_device_steps, cost_gradient, hamiltonian_steps_on_device
+    device_steps = check_device_steps(device_steps, opt, "minimize_hamiltonian")
     nat = _native_complex(wf)
     if ham.N != nat.N:
         raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, nat.N))
@@ -207,6 +212,15 @@ def minimize_hamiltonian(wf, ham, numsamples, steps, lr, params=None, seed=111, 
     opt = opt or Adam()
     params = {k: np.array(v) for k, v in params.items()}
     nat.set_params(params, scope=scope)
+    if device_steps:
+        nat.adam_set_state(None, None, 0)
+        meanEnergy, varEnergy = hamiltonian_steps_on_device(nat.pauli_train_steps_complex, ham, steps, numsamples, lr, seed, device_steps,
+                                                            verbose, lambda s1, si, n: complex(s1 / n, si / n))
+        params = nat.get_params_dict(params, scope)
+        if facade is not None:
+            facade.set_params(params)
+        minimize_hamiltonian.last_params = params
+        return meanEnergy, varEnergy
     meanEnergy, varEnergy = [], []
     for it in range(int(steps) + 1):
         s1, s2, n, si = nat.pauli_step_complex(ham.flip, ham.sign, ham.coeff, int(numsamples), seed=seed, step=it)["moments"]

@@ -383,14 +383,48 @@ def run_2DTFIM_1DRNN(numsteps=2 * 10 ** 4, systemsize_x=5, systemsize_y=5, Bx=+2
     return meanE, varE
 
 
+def check_device_steps(device_steps, opt, what):
+    """device_steps of the minimize_hamiltonian drivers: None (the host loop) or an integer >= 1 (iterations per device call); the
+    device runs Adam with the default state layout, so a caller's optimizer object cannot be combined with it"""
+    if device_steps is None:
+        return None
+    if isinstance(device_steps, bool) or not isinstance(device_steps, (int, np.integer)) or device_steps < 1:
+        raise ValueError("device_steps must be None or an integer >= 1, got %r" % (device_steps,))
+    if opt is not None:
+        raise ValueError("%s: device_steps runs Adam on the device; a custom optimizer (opt=%r) needs the host loop (device_steps=None)"
+                         % (what, opt))
+    return int(device_steps)
+
+
+def hamiltonian_steps_on_device(train_steps, ham, numsteps, numsamples, lr, seed, device_steps, verbose, mean_of):
+    """The numsteps + 1 iterations of a minimize_hamiltonian loop in chunks of at most device_steps (and at most 1024, one call's
+    limit) through train_steps (NativeWavefunction.pauli_train_steps or pauli_train_steps_complex): (meanEnergy, varEnergy) as the
+    host loop lists them, mean_of(s1, si, n) forming an entry of the first."""
+    meanEnergy, varEnergy = [], []
+    total, chunk = int(numsteps) + 1, min(device_steps, 1024)
+    for it in range(0, total, chunk):
+        K = min(chunk, total - it)
+        mom = train_steps(ham.flip, ham.sign, ham.coeff, int(numsamples), seed, it, [float(lr)] * K)
+        for j, (s1, s2, n, si) in enumerate(mom):
+            meanEnergy.append(mean_of(s1, si, n))
+            varEnergy.append(s2 / n - (s1 / n) ** 2)
+            if verbose and (it + j) % 10 == 0:
+                print("mean(E): {0}, var(E): {1}, #samples {2}, #Step {3} \n\n".format(meanEnergy[-1], varEnergy[-1], numsamples, it + j))
+    return meanEnergy, varEnergy
+
+
 def minimize_hamiltonian(wf, ham, params, numsteps=1000, numsamples=500, learningrate=5e-3, seed=111, scope="RNNwavefunction",
-                         opt=None, comm=None, verbose=False):
+                         opt=None, comm=None, verbose=False, device_steps=None):
     """Minimise the energy of `wf` (a NativeWavefunction of a positive one-layer GRU model holding `params`, scoped by `scope`)
     under `ham` (observables.Hamiltonian: any real-symmetric spin-1/2 Hamiltonian given as Pauli strings) with _train's host
     optimizer loop: pauli_step (samples, local energies of `ham`, moments; the batch stays resident) -> cost_gradient -> Adam ->
     set_params.  Returns (meanEnergy, varEnergy), one entry per iteration 0..numsteps like the run_* drivers; the trained
     parameters are left in minimize_hamiltonian.last_params.  The batch of numsamples must fit one pass of the state budget (the
-    gradient refuses otherwise).  Single process only: no device-resident variant, and a communicator is refused."""
+    gradient refuses otherwise).  Single process only: a communicator is refused.
+    device_steps=K (an integer >= 1): the same iterations run on the device in chunks of at most K with one host synchronisation
+    each (wf.pauli_train_steps, docs/pauli_train.md) - the same energies, variances and parameters, bit for bit.  The device runs
+    Adam from a fresh state: opt= is refused with it."""
+    device_steps = check_device_steps(device_steps, opt, "minimize_hamiltonian")
     if comm is not None:
         raise ValueError("minimize_hamiltonian runs in one process on one GPU: no communicator (comm=%r)" % (comm,))
     if ham.N != wf.N:
@@ -398,6 +432,12 @@ def minimize_hamiltonian(wf, ham, params, numsteps=1000, numsamples=500, learnin
     opt = opt or Adam()
     params = {k: np.array(v) for k, v in params.items()}
     wf.set_params(params, scope=scope)
+    if device_steps:
+        wf.adam_set_state(None, None, 0)
+        meanEnergy, varEnergy = hamiltonian_steps_on_device(wf.pauli_train_steps, ham, numsteps, numsamples, learningrate, seed,
+                                                            device_steps, verbose, lambda s1, si, n: s1 / n)
+        minimize_hamiltonian.last_params = wf.get_params_dict(params, scope)
+        return meanEnergy, varEnergy
     meanEnergy, varEnergy = [], []
     for it in range(numsteps + 1):
         s1, s2, n, _ = wf.pauli_step(ham.flip, ham.sign, ham.coeff, numsamples, seed=seed, step=it)["moments"]
