@@ -445,6 +445,21 @@ int rnnwf_pauli_train_steps_complex(rnnwf_handle* h, const int32_t* flip, const 
                                     const double* learning_rates, double beta1, double beta2, double epsilon, double* moments,
                                     double* term_sums, float* out_eloc_re_im);
 
+/* rnnwf_pauli_train_steps_2d: the same K iterations for the 2D RNN (RNNWF_MODEL_MDRNN2D, float64, 1..84 units) on the Hamiltonians of
+ * rnnwf_pauli_step_2d (docs/pauli_train.md, "2D RNN").  Arguments, layouts, outputs, refusals and the state afterwards are
+ * rnnwf_pauli_train_steps's, with N = Nx * Ny and that entry's one difference: the masks are indexed by the LATTICE index
+ * k = nx * Ny + ny; the driver maps them to visit order, and a bad mask entry is named by its lattice index.  The sampling base pass
+ * keeps every position's state and log P, so an iteration has no second pass in front of the site terms and masked tails.  moments
+ * [K][4], term_sums NULL or [K][nterms][2], out_eloc NULL or [numsamples] float64 of the last iteration's batch.  Moments, per-term
+ * sums, parameters and Adam's state equal the host loop rnnwf_pauli_step_2d -> rnnwf_vmc_gradient -> host Adam -> rnnwf_set_param bit
+ * for bit.  RNNWF_ERR_INVALID for any model but MDRNN2D (rnnwf_pauli_train_steps serves the GRU models,
+ * rnnwf_pauli_train_steps_complex the complex RNN, and both keep refusing this one); RNNWF_ERR_STATE for uncommitted parameters;
+ * RNNWF_ERR_NOMEM "... split the batch" for numsamples beyond one pass of rnnwf_pauli_step_2d.  Timing ids as above, 0 being the one
+ * sampling base pass + site-term replay.                                                                                         */
+int rnnwf_pauli_train_steps_2d(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff, int32_t nterms, int32_t K,
+                               int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset, const double* learning_rates,
+                               double beta1, double beta2, double epsilon, double* moments, double* term_sums, double* out_eloc);
+
 /* ---- stochastic reconfiguration (natural gradient, minSR; docs/sr.md) -------------------------------------------------------
  * psi = sqrt(P) real and positive:  O[s][k] = d log psi(sigma_s) / d theta_k = 1/2 d log P(sigma_s) / d theta_k, theta in the flat
  * order of rnnwf_set_params_flat;  dO = O - mean_s O;  eps_s = E_loc,s - mean E.  The minSR direction with diagonal shift lambda is

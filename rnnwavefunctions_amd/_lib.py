@@ -108,6 +108,7 @@ PROTOTYPES = {
     "rnnwf_synchronize": (C.c_int, [_P]),
     "rnnwf_device_info": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I64), C.c_char_p]),
 }
+PROTOTYPES["rnnwf_pauli_train_steps_2d"] = PROTOTYPES["rnnwf_pauli_train_steps"]       # the same argument list, one object
 
 _lib = None
 
@@ -817,6 +818,16 @@ class NativeWavefunction:
         pauli_step_complex returns a row, eloc complex64."""
         return self._pauli_train_call("rnnwf_pauli_train_steps_complex", True, flip, sign, coeff, numsamples, seed, step0, learning_rates,
                                       beta1, beta2, epsilon, sample_offset, want_term_sums, want_eloc)
+
+    def pauli_train_steps_2d(self, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1=0.9, beta2=0.999, epsilon=1e-8,
+                             sample_offset=0, want_term_sums=False, want_eloc=False):
+        """pauli_train_steps for the 2D RNN (rnnwf_pauli_train_steps_2d).  flip, sign: (nterms, Nx*Ny) masks indexed by the lattice
+        index nx*Ny + ny, or (nterms, Nx, Ny), as pauli_step_2d takes them.  Returns what pauli_train_steps returns."""
+        fl, sg = np.asarray(flip), np.asarray(sign)
+        if fl.ndim == 3 and fl.shape[1:] == (self.nx, self.ny) and sg.shape == fl.shape:
+            fl, sg = fl.reshape(fl.shape[0], self.N), sg.reshape(sg.shape[0], self.N)
+        return self._pauli_train_call("rnnwf_pauli_train_steps_2d", False, fl, sg, coeff, numsamples, seed, step0, learning_rates, beta1,
+                                      beta2, epsilon, sample_offset, want_term_sums, want_eloc)
 
     def _pauli_train_call(self, entry, cplx, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1, beta2, epsilon,
                           sample_offset, want_term_sums, want_eloc):

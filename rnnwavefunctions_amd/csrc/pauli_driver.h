@@ -12,7 +12,7 @@
 //                              position 0 on (pauli_terms.h); chains per pass
 //   pass(h, ns, g, sc, keep, sums_host)   the kernels of one pass over the chains in h->bits: log-ratios at sc.lr, E_loc in h->eloc
 // pauli_train_steps<P> below is the driver of the device-resident Adam iterations on the same terms (rnnwf_pauli_train_steps,
-// rnnwf_pauli_train_steps_complex).
+// rnnwf_pauli_train_steps_2d, rnnwf_pauli_train_steps_complex).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -116,9 +116,10 @@ int pauli_step(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const 
 }
 
 // K whole Adam iterations on the Hamiltonian of the terms with one host synchronisation behind the last (rnnwf_pauli_train_steps,
-// rnnwf_pauli_train_steps_complex; docs/pauli_train.md).  The policy adds to pauli_step's
+// rnnwf_pauli_train_steps_2d, rnnwf_pauli_train_steps_complex; docs/pauli_train.md).  The policy adds to pauli_step's
 //   train_pass(h, ns, g, sc, sums_row)   the kernels of one iteration's pass over the chains drawn into h->bits: E_loc in h->eloc,
 //                                        the checkpoints kept, the per-term sums into sums_row on the device unless it is nullptr
+//                                        (the 2D RNN's sampling base pass has kept every state and log P: its pass starts at the tails)
 // Per call: the refusals, the terms derived and uploaded once, one scratch allocation (the tables, one pass, then the [K][nterms]
 // table of per-term sums), train.hip's tables and flat parameters.  Per iteration k, nothing waiting for the host: the family's base
 // pass drawing at step index step0 + k, train_pass, the moments into row k of train.hip's pinned table, the gradient reading them on

@@ -1,4 +1,5 @@
-// pauli_train_kernels.h - the assembly of rnnwf_pauli_train_steps (pauli.hip, docs/pauli_train.md): the kernels of pauli_kernels.h
+// pauli_train_kernels.h - the assembly of rnnwf_pauli_train_steps (pauli.hip) and rnnwf_pauli_train_steps_2d (mdrnn_pauli.hip, whose
+// tails, site terms and log P have the same layout; docs/pauli_train.md), each instantiating it under its own flags: the kernels of pauli_kernels.h
 // with the amplitude ratio evaluated once per (flip mask, chain) instead of once per (term, chain) and per kernel.  Terms that share a
 // mask (XX and YY of a bond) and the two consumers (E_loc, per-term sums) read one table.
 //
@@ -8,7 +9,7 @@
 //                            e += coeff[k] * v.
 //   pauli_table_term_kernel: pauli_term_kernel with r read from the table; its partial sums are reduced by renyi_sums_kernel, which
 //                            writes the iteration's row of the call's table of per-term sums.
-// Every result equals the kernel's it replaces bit for bit (tests/test_gpu_pauli_train.py).  log r > 709 gives r = +inf as there.
+// Every result equals the kernel's it replaces bit for bit (tests/test_gpu_pauli_train.py, tests/test_gpu_pauli_train_2d.py).  log r > 709 gives r = +inf as there.
 #pragma once
 #include "pauli_kernels.h"
 

@@ -1,6 +1,7 @@
 """Pauli-string expectation values, energies of arbitrary real spin Hamiltonians and two-point functions for the 2D RNN (model
-MDRNN2D on the zig-zag path; rnnwf_pauli_step_2d, docs/pauli_2d.md), and the second Renyi entropy of arbitrary lattice regions
-(rnnwf_renyi2_regions_2d, docs/renyi_2d.md).
+MDRNN2D on the zig-zag path; rnnwf_pauli_step_2d, docs/pauli_2d.md), training on such a Hamiltonian (minimize_hamiltonian: the host
+loop, or rnnwf_pauli_train_steps_2d with device_steps=K, docs/pauli_train.md), and the second Renyi entropy of arbitrary lattice
+regions (rnnwf_renyi2_regions_2d, docs/renyi_2d.md).
 
 Sites are named by the LATTICE index k = site(Nx, Ny, nx, ny) = nx * Ny + ny, the C-order flattening of samples (ns, Nx, Ny): the
 convention of tfim_hamiltonian for a (Nx, Ny) Jz and of rnnwf_tfim2d_eloc.  The library maps k to the position along the path.  The
@@ -18,7 +19,7 @@ from . import _lib
 from .observables import (Hamiltonian, _disjoint_masks, _native, group_by_mask, mutual_information2_from_log_ratios,  # noqa: F401
                           pauli_from_sums, pauli_terms, renyi2_from_sums, tfim_hamiltonian)
 
-__all__ = ["site", "xxz_hamiltonian_2d", "tfim_hamiltonian", "Hamiltonian", "pauli_expectations", "energy", "correlations",
+__all__ = ["site", "xxz_hamiltonian_2d", "tfim_hamiltonian", "Hamiltonian", "pauli_expectations", "energy", "minimize_hamiltonian", "correlations",
            "rectangle_region", "row_cut_regions", "column_cut_regions", "renyi2_regions", "renyi2_mutual_information"]
 
 
@@ -89,6 +90,48 @@ def energy(wf, ham, numsamples, seed=111, step=0, samples=None, want_eloc=False)
     if want_eloc:
         res["eloc"] = out["eloc"]
     return res
+
+
+def minimize_hamiltonian(wf, ham, params, numsteps=1000, numsamples=500, learningrate=5e-3, seed=111, scope="RNNwavefunction",
+                         opt=None, comm=None, verbose=False, device_steps=None):
+    """training.minimize_hamiltonian for the 2D RNN: minimise the energy of `wf` (holding `params`, scoped by `scope`) under `ham`
+    (observables.Hamiltonian over the Nx Ny lattice indices) with the host optimizer loop pauli_step_2d (samples, local energies of
+    `ham`, moments; the batch stays resident) -> training.cost_gradient -> training.Adam -> set_params.  Returns (meanEnergy,
+    varEnergy), one entry per iteration 0..numsteps; the trained parameters are left in minimize_hamiltonian.last_params.  The batch
+    of numsamples must fit one pass of the state budget.  Single process only: a communicator is refused.
+    device_steps=K (an integer >= 1): the same iterations run on the device in chunks of at most K with one host synchronisation
+    each (NativeWavefunction.pauli_train_steps_2d, docs/pauli_train.md) - the same energies, variances and parameters, bit for bit.
+    The device runs Adam from a fresh state: opt= is refused with it."""
+    from . import training as T
+    device_steps = T.check_device_steps(device_steps, opt, "observables_2d.minimize_hamiltonian")
+    if comm is not None:
+        raise ValueError("minimize_hamiltonian runs in one process on one GPU: no communicator (comm=%r)" % (comm,))
+    nat = _native_2d(wf)
+    if ham.N != nat.N:
+        raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, nat.N))
+    opt = opt or T.Adam()
+    params = {k: np.array(v) for k, v in params.items()}
+    nat.set_params(params, scope=scope)
+    if device_steps:
+        nat.adam_set_state(None, None, 0)
+        meanEnergy, varEnergy = T.hamiltonian_steps_on_device(nat.pauli_train_steps_2d, ham, numsteps, numsamples, learningrate, seed,
+                                                              device_steps, verbose, lambda s1, si, n: s1 / n)
+        minimize_hamiltonian.last_params = nat.get_params_dict(params, scope)
+        return meanEnergy, varEnergy
+    meanEnergy, varEnergy = [], []
+    for it in range(numsteps + 1):
+        s1, s2, n, _ = nat.pauli_step_2d(ham.flip, ham.sign, ham.coeff, numsamples, seed=seed, step=it)["moments"]
+        meanE = s1 / n
+        varE = s2 / n - meanE ** 2
+        meanEnergy.append(meanE)
+        varEnergy.append(varE)
+        if verbose and it % 10 == 0:
+            print("mean(E): {0}, var(E): {1}, #samples {2}, #Step {3} \n\n".format(meanE, varE, numsamples, it))
+        grads = T.cost_gradient(nat, params, scope, meanE, n)
+        params = opt.step(params, grads, learningrate)
+        nat.set_params(params, scope=scope)
+    minimize_hamiltonian.last_params = params
+    return meanEnergy, varEnergy
 
 
 def correlations(wf, numsamples, pairs=None, seed=111, step=0, samples=None):
