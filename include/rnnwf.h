@@ -460,6 +460,22 @@ int rnnwf_pauli_train_steps_2d(rnnwf_handle* h, const int32_t* flip, const int32
                                int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset, const double* learning_rates,
                                double beta1, double beta2, double epsilon, double* moments, double* term_sums, double* out_eloc);
 
+/* rnnwf_pauli_step_stack, rnnwf_pauli_train_steps_stack: rnnwf_pauli_step and rnnwf_pauli_train_steps for STACKED GRU layers
+ * (RNNWF_MODEL_GRU1D float32 and RNNWF_MODEL_GRU1D_F64 float64 with 2..4 layers, every stack rnnwf_create accepts, layers of
+ * unequal width included; docs/pauli_stack.md).  Arguments, layouts, outputs, passes, fixed-order sums, the resident-batch rule,
+ * the state after the train entry and the refusals are those of the one-layer entries.  With f the first flipped site, the flipped
+ * chain restarts ALL layers from the chain's own checkpoint of site f - 1 (f = 0: from the zero states) and recomputes the sites
+ * f..N-1: N - f steps of the whole stack per chain and distinct mask, counted in work[0].  The checkpointed base pass always runs on
+ * the one-wave MFMA stack kernel, whatever kernel rnnwf_vmc_step takes for the handle.  RNNWF_ERR_INVALID, before any work: a
+ * one-layer handle (rnnwf_pauli_step / rnnwf_pauli_train_steps serve it, and keep refusing stacks); every other model, in
+ * rnnwf_pauli_step's words.  Timing ids as rnnwf_pauli_step / rnnwf_pauli_train_steps.                                          */
+int rnnwf_pauli_step_stack(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff, int32_t nterms,
+                           const int32_t* samples, int64_t ns, uint64_t seed, uint64_t step, int64_t sample_offset,
+                           double* term_sums, double* out_eloc, double* moments, double* out_log_ratio, int32_t* out_samples);
+int rnnwf_pauli_train_steps_stack(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff, int32_t nterms, int32_t K,
+                                  int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset, const double* learning_rates,
+                                  double beta1, double beta2, double epsilon, double* moments, double* term_sums, double* out_eloc);
+
 /* ---- stochastic reconfiguration (natural gradient, minSR; docs/sr.md) -------------------------------------------------------
  * psi = sqrt(P) real and positive:  O[s][k] = d log psi(sigma_s) / d theta_k = 1/2 d log P(sigma_s) / d theta_k, theta in the flat
  * order of rnnwf_set_params_flat;  dO = O - mean_s O;  eps_s = E_loc,s - mean E.  The minSR direction with diagonal shift lambda is

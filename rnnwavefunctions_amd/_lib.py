@@ -109,6 +109,8 @@ PROTOTYPES = {
     "rnnwf_device_info": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I64), C.c_char_p]),
 }
 PROTOTYPES["rnnwf_pauli_train_steps_2d"] = PROTOTYPES["rnnwf_pauli_train_steps"]       # the same argument list, one object
+PROTOTYPES["rnnwf_pauli_step_stack"] = PROTOTYPES["rnnwf_pauli_step"]                  # stacked layers (docs/pauli_stack.md): likewise
+PROTOTYPES["rnnwf_pauli_train_steps_stack"] = PROTOTYPES["rnnwf_pauli_train_steps"]
 
 _lib = None
 
@@ -173,6 +175,7 @@ class NativeWavefunction:
         self.model = model
         self.N = int(nx) * int(ny)
         self.nx, self.ny = int(nx), int(ny)
+        self.units = tuple(int(u) for u in units)
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _check(self, rc):
@@ -720,6 +723,13 @@ class NativeWavefunction:
         return self._pauli_call("rnnwf_pauli_step_2d", (max(int(ns), 0), self.nx, self.ny), fl, sg, coeff, ns, samples, seed, step,
                                 sample_offset, want_eloc, want_log_ratio, want_samples)
 
+    def pauli_step_stack(self, flip, sign, coeff, ns, samples=None, seed=0, step=0, sample_offset=0, want_eloc=False,
+                         want_log_ratio=False, want_samples=False):
+        """pauli_step for stacked GRU layers (rnnwf_pauli_step_stack, docs/pauli_stack.md): models GRU1D and GRU1D_F64 with 2..4
+        layers.  Arguments and the returned dict are pauli_step's."""
+        return self._pauli_call("rnnwf_pauli_step_stack", (max(int(ns), 0), self.N), flip, sign, coeff, ns, samples, seed, step,
+                                sample_offset, want_eloc, want_log_ratio, want_samples)
+
     def _pauli_call(self, entry, drawn_shape, flip, sign, coeff, ns, samples, seed, step, sample_offset, want_eloc, want_log_ratio,
                     want_samples):
         """the argument checks, buffers and result dict pauli_step and pauli_step_2d share"""
@@ -828,6 +838,13 @@ class NativeWavefunction:
             fl, sg = fl.reshape(fl.shape[0], self.N), sg.reshape(sg.shape[0], self.N)
         return self._pauli_train_call("rnnwf_pauli_train_steps_2d", False, fl, sg, coeff, numsamples, seed, step0, learning_rates, beta1,
                                       beta2, epsilon, sample_offset, want_term_sums, want_eloc)
+
+    def pauli_train_steps_stack(self, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1=0.9, beta2=0.999, epsilon=1e-8,
+                                sample_offset=0, want_term_sums=False, want_eloc=False):
+        """pauli_train_steps for stacked GRU layers (rnnwf_pauli_train_steps_stack, docs/pauli_stack.md).  Arguments and what it
+        returns are pauli_train_steps's."""
+        return self._pauli_train_call("rnnwf_pauli_train_steps_stack", False, flip, sign, coeff, numsamples, seed, step0, learning_rates,
+                                      beta1, beta2, epsilon, sample_offset, want_term_sums, want_eloc)
 
     def _pauli_train_call(self, entry, cplx, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1, beta2, epsilon,
                           sample_offset, want_term_sums, want_eloc):

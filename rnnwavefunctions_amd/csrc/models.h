@@ -117,6 +117,7 @@ int prnn_split_stream_pack(rnnwf_handle* h, std::vector<char>& simg);
 int prnn_teacher_base(rnnwf_handle* h, int64_t ns, bool reversed, double* out_lp);   // prnn.hip
 // prnn.hip, for the observable passes (observable.h): the base pass on the one-wave kernel only; its arguments; checkpoint bytes per 16 chains
 int prnn_plain_base(rnnwf_handle* h, const PrnnArgs& a);
+int prnn_stack_base(rnnwf_handle* h, const PrnnArgs& a);      // stacked layers (pauli_stack.hip): the one-wave MFMA stack kernel only
 PrnnArgs prnn_base_args(rnnwf_handle* h, int64_t ns);
 size_t prnn_hck_bytes_per_block(rnnwf_handle* h);
 // crnn.hip, for the complex RNN's Pauli pass (crnn_pauli.hip): the same three for the one-layer complex RNN

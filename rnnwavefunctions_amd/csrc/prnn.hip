@@ -49,6 +49,11 @@ struct Launch {
         if constexpr (NL > 1) return h->fail(RNNWF_ERR_INVALID, "stacked layers: no one-wave base pass");
         else return launch_persistent(h, kTimerBase, prnn_base_kernel<T, NFULL, WAVES>, WAVES * 64, S::LDS_BYTES, a.nsb, WAVES, a);
     }
+    // stacked layers: the one-wave MFMA kernel whatever the batch size and whatever `base` would take
+    static int stack_plain(rnnwf_handle* h, const PrnnArgs& a) {
+        if constexpr (NL > 1) return launch_shrinking<WAVES>(h, kTimerBase, prnn_ml_base_kernel<T, NFULL, NL, WAVES>, S::LDS_BYTES, a.nsb, a);
+        else return h->fail(RNNWF_ERR_INVALID, "one layer: its one-wave base pass is prnn_plain_base");
+    }
     static int flip(rnnwf_handle* h, const PrnnArgs& a) {
         if constexpr (NL > 1) return launch_persistent(h, kTimerFlip, prnn_ml_flip_kernel<T, NFULL, NL, WAVES>, WAVES * 64, S::LDS_BYTES, a.ntiles, WAVES, a);
         else return launch_persistent(h, kTimerFlip, prnn_flip_kernel<T, NFULL, WAVES>, WAVES * 64, S::LDS_BYTES, a.ntiles, WAVES, a);
@@ -257,6 +262,12 @@ int rnnwf::prnn_teacher_base(rnnwf_handle* h, int64_t ns, bool reversed, double*
 int rnnwf::prnn_plain_base(rnnwf_handle* h, const PrnnArgs& a) {
     int rc = 0;
     return with_launch(h, [&](auto k) { rc = decltype(k)::plain(h, a); }) ? rc : no_kernel(h);
+}
+// The same for stacked layers (pauli_stack.hip): the base pass on prnn_ml_base_kernel for every batch size, never the cooperative
+// kernel, whose accumulation order is its own - the stack's masked tails restart from these checkpoints and repeat this arithmetic.
+int rnnwf::prnn_stack_base(rnnwf_handle* h, const PrnnArgs& a) {
+    int rc = 0;
+    return with_launch(h, [&](auto k) { rc = decltype(k)::stack_plain(h, a); }) ? rc : no_kernel(h);
 }
 PrnnArgs rnnwf::prnn_base_args(rnnwf_handle* h, int64_t ns) { return base_args(h, ns); }
 size_t rnnwf::prnn_hck_bytes_per_block(rnnwf_handle* h) { return hck_bytes_per_block(h); }

@@ -1,0 +1,150 @@
+"""Pauli-string expectation values, energies of arbitrary real spin Hamiltonians, two-point functions and training on such a
+Hamiltonian for STACKED GRU layers: the positive models GRU1D (float32) and GRU1D_F64 (float64, raster path) with 2..4 layers - what
+units=[h] * num_layers builds (rnnwf_pauli_step_stack, rnnwf_pauli_train_steps_stack; docs/pauli_stack.md).
+
+The estimator, the strings and the Hamiltonians are observables.py's:  v(sigma) = prod_{i in S} s_i * exp(1/2 [log P(sigma ^ F) -
+log P(sigma)]),  E[v] = <psi|O|psi>;  sites in the model's order.  observables.pauli_expectations / energy / correlations and
+training.minimize_hamiltonian keep refusing stacks; these are the stacks' own entry points.  They accept a facade or a
+NativeWavefunction of one of the two models with more than one layer and raise ValueError for everything else - a one-layer wave
+function included, which observables.py serves - before the library is touched.
+"""
+import numpy as np
+
+from . import _lib
+from .observables import Hamiltonian, _native, group_by_mask, pauli_from_sums, pauli_terms, tfim_hamiltonian, xxz_hamiltonian  # noqa: F401
+
+__all__ = ["pauli_expectations", "energy", "correlations", "minimize_hamiltonian"]
+
+
+def _native_stack(wf):
+    nat = _native(wf)
+    if nat.model not in (_lib.MODEL_GRU1D, _lib.MODEL_GRU1D_F64):
+        raise ValueError("observables_stack serves stacked layers of the positive GRU models (GRU1D, GRU1D_F64) only")
+    if len(nat.units) < 2:
+        raise ValueError("observables_stack serves stacked layers (2..%d GRU layers), this wave function has one layer; observables.py "
+                         "and training.minimize_hamiltonian serve it" % _lib.MAX_LAYERS)
+    return nat
+
+
+def _samples(nat, samples, numsamples):
+    return None if samples is None else np.asarray(samples).reshape(int(numsamples), nat.N)
+
+
+def pauli_expectations(wf, strings, numsamples, seed=111, step=0, samples=None):
+    """<psi|P|psi> of every Pauli string P of `strings` (dense "XZIY..." or sparse [("X", i), ...]) with its standard error, from
+    `numsamples` samples: {"value": (K,), "err": (K,)}.  A string with an odd number of Y has expectation exactly 0 in the real state
+    psi = sqrt(P): 0 +- 0, without device work.  samples: (numsamples, N) spins; None draws them on the device from (seed, step)."""
+    nat = _native_stack(wf)
+    flip, sign, factor = pauli_terms(strings, nat.N)
+    value, err = np.zeros(len(factor)), np.zeros(len(factor))
+    real = np.flatnonzero(factor.imag == 0.0)
+    if real.size:
+        out = nat.pauli_step_stack(flip[real], sign[real], np.ones(real.size), int(numsamples), samples=_samples(nat, samples, numsamples),
+                                   seed=seed, step=step)
+        mean, e = pauli_from_sums(out["term_sums"], numsamples)
+        value[real], err[real] = factor.real[real] * mean, e
+    return {"value": value, "err": err}
+
+
+def energy(wf, ham, numsamples, seed=111, step=0, samples=None, want_eloc=False):
+    """Energy of `wf` under the Hamiltonian `ham` from `numsamples` samples: {"mean", "var" (population variance of E_loc), "err"
+    (sqrt(var / n)), "eloc" (numsamples,) when want_eloc}.  A batch that fits one pass stays resident: vmc_gradient then
+    differentiates the VMC cost of this Hamiltonian."""
+    nat = _native_stack(wf)
+    if ham.N != nat.N:
+        raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, nat.N))
+    out = nat.pauli_step_stack(ham.flip, ham.sign, ham.coeff, int(numsamples), samples=_samples(nat, samples, numsamples), seed=seed,
+                               step=step, want_eloc=want_eloc)
+    m = out["moments"]
+    mean = m[0] / m[2]
+    var = max(m[1] / m[2] - mean * mean, 0.0)
+    res = {"mean": mean, "var": var, "err": float(np.sqrt(var / m[2]))}
+    if want_eloc:
+        res["eloc"] = out["eloc"]
+    return res
+
+
+def minimize_hamiltonian(wf, ham, params, numsteps=1000, numsamples=500, learningrate=5e-3, seed=111, scope="RNNwavefunction",
+                         opt=None, comm=None, verbose=False, device_steps=None):
+    """training.minimize_hamiltonian for stacked layers: minimise the energy of `wf` (holding `params`, scoped by `scope`) under `ham`
+    (observables.Hamiltonian) with the host optimizer loop pauli_step_stack (samples, local energies of `ham`, moments; the batch
+    stays resident) -> training.cost_gradient -> training.Adam -> set_params.  Returns (meanEnergy, varEnergy), one entry per
+    iteration 0..numsteps; the trained parameters are left in minimize_hamiltonian.last_params.  The batch of numsamples must fit one
+    pass of the state budget.  Single process only: a communicator is refused.
+    device_steps=K (an integer >= 1): the same iterations run on the device in chunks of at most K with one host synchronisation
+    each (NativeWavefunction.pauli_train_steps_stack) - the same energies, variances and parameters, bit for bit.  The device runs
+    Adam from a fresh state: opt= is refused with it."""
+    from . import training as T
+    device_steps = T.check_device_steps(device_steps, opt, "observables_stack.minimize_hamiltonian")
+    if comm is not None:
+        raise ValueError("minimize_hamiltonian runs in one process on one GPU: no communicator (comm=%r)" % (comm,))
+    nat = _native_stack(wf)
+    if ham.N != nat.N:
+        raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, nat.N))
+    opt = opt or T.Adam()
+    params = {k: np.array(v) for k, v in params.items()}
+    nat.set_params(params, scope=scope)
+    if device_steps:
+        nat.adam_set_state(None, None, 0)
+        meanEnergy, varEnergy = T.hamiltonian_steps_on_device(nat.pauli_train_steps_stack, ham, numsteps, numsamples, learningrate, seed,
+                                                              device_steps, verbose, lambda s1, si, n: s1 / n)
+        minimize_hamiltonian.last_params = nat.get_params_dict(params, scope)
+        return meanEnergy, varEnergy
+    meanEnergy, varEnergy = [], []
+    for it in range(numsteps + 1):
+        s1, s2, n, _ = nat.pauli_step_stack(ham.flip, ham.sign, ham.coeff, numsamples, seed=seed, step=it)["moments"]
+        meanE = s1 / n
+        varE = s2 / n - meanE ** 2
+        meanEnergy.append(meanE)
+        varEnergy.append(varE)
+        if verbose and it % 10 == 0:
+            print("mean(E): {0}, var(E): {1}, #samples {2}, #Step {3} \n\n".format(meanE, varE, numsamples, it))
+        grads = T.cost_gradient(nat, params, scope, meanE, n)
+        params = opt.step(params, grads, learningrate)
+        nat.set_params(params, scope=scope)
+    minimize_hamiltonian.last_params = params
+    return meanEnergy, varEnergy
+
+
+def correlations(wf, numsamples, pairs=None, seed=111, step=0, samples=None):
+    """<sz_k>, <sx_k> of every site and, for the listed pairs of distinct sites, <sz_a sz_b>, <sx_a sx_b> and their connected parts,
+    with standard errors, from one pauli_step_stack call (one X mask per site, one XX mask per pair):
+
+        z, x (N,);  pairs (P, 2);  zz, xx, zz_c = zz - z_a z_b, xx_c = xx - x_a x_b (P,);  "<name>_err" for each.
+
+    pairs: None = every pair (c, k), k != c, with the centre site c = N // 2.  A pair (k, k) raises ValueError.  Errors: the plain
+    std / sqrt(n) (population variance) of the per-sample values s_k, r_k = exp(log r_k), s_a s_b, r_ab, which the call returns as
+    log-ratios and samples; connected parts to first order (delta method), as observables_2d.correlations."""
+    nat = _native_stack(wf)
+    N, n = nat.N, int(numsamples)
+    if pairs is None:
+        pairs = [(N // 2, k) for k in range(N) if k != N // 2]
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if np.any(pairs < 0) or np.any(pairs >= N) or np.any(pairs[:, 0] == pairs[:, 1]):
+        raise ValueError("pairs must name two distinct sites in 0..%d each" % (N - 1))
+    npair = len(pairs)
+    flip = np.zeros((N + npair, N), dtype=np.int32)
+    flip[np.arange(N), np.arange(N)] = 1
+    for k, (a, b) in enumerate(pairs):
+        flip[N + k, [a, b]] = 1
+    out = nat.pauli_step_stack(flip, np.zeros_like(flip), np.ones(len(flip)), n, samples=_samples(nat, samples, n), seed=seed, step=step,
+                               want_log_ratio=True, want_samples=True)
+    _, index = group_by_mask(flip)                       # (a, b) and (b, a) share a row
+    r = np.exp(out["log_ratio"])[index]                  # (N + P, n)
+    s = 2.0 * out["samples"].reshape(n, N).T - 1.0       # (N, n)
+
+    def stats(v):
+        return v.mean(axis=-1), v.std(axis=-1) / np.sqrt(n)
+
+    a, b = pairs[:, 0], pairs[:, 1]
+    res = {"pairs": pairs}
+    res["z"], res["z_err"] = stats(s)
+    res["x"], res["x_err"] = stats(r[:N])
+    res["zz"], res["zz_err"] = stats(s[a] * s[b])
+    res["xx"], res["xx_err"] = stats(r[N:])
+    z, x = res["z"], res["x"]
+    res["zz_c"] = res["zz"] - z[a] * z[b]
+    res["xx_c"] = res["xx"] - x[a] * x[b]
+    res["zz_c_err"] = stats(s[a] * s[b] - z[b][:, None] * s[a] - z[a][:, None] * s[b])[1]
+    res["xx_c_err"] = stats(r[N:] - x[b][:, None] * r[a] - x[a][:, None] * r[b])[1]
+    return res
