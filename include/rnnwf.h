@@ -476,6 +476,20 @@ int rnnwf_pauli_train_steps_stack(rnnwf_handle* h, const int32_t* flip, const in
                                   int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset, const double* learning_rates,
                                   double beta1, double beta2, double epsilon, double* moments, double* term_sums, double* out_eloc);
 
+/* rnnwf_renyi2_regions_stack: rnnwf_renyi2_regions for STACKED GRU layers (RNNWF_MODEL_GRU1D float32 and RNNWF_MODEL_GRU1D_F64 float64
+ * with 2..4 layers, every stack rnnwf_create accepts, layers of unequal width included; docs/renyi_stack.md).  Arguments, layouts,
+ * outputs, the normalisation of the masks (site 0 not in A; an empty or full region gives log r = 0 exactly at no cost), passes,
+ * fixed-order sums and +inf on log r > 709 are rnnwf_renyi2_regions's.  With f >= 1 the first site of A, the mixed chain (the
+ * partner's spins on A, the chain's own elsewhere) restarts ALL layers from the chain's own checkpoint of site f - 1 and recomputes
+ * the sites f..N-1: N - f steps of the whole stack per chain and region, counted in work[0].  The checkpointed base pass always runs
+ * on the one-wave MFMA stack kernel, whatever kernel rnnwf_vmc_step takes for the handle.  No batch is resident after a served call.
+ * RNNWF_ERR_INVALID, before any work (a refused call leaves an earlier batch usable): a one-layer handle (rnnwf_renyi2_regions serves
+ * it, and keeps refusing stacks); every other model, in rnnwf_renyi2_regions's words; the argument checks of rnnwf_renyi2_regions.
+ * Timing ids: 0 = base pass + site-term replay, 1 = paired masked-tail pass, 2 = log-ratio assembly + sums.                      */
+int rnnwf_renyi2_regions_stack(rnnwf_handle* h, const int32_t* regions, int32_t nregions, const int32_t* samples, int64_t npairs,
+                               uint64_t seed, uint64_t step, int64_t pair_offset, double* sums, double* out_log_ratio,
+                               int32_t* out_samples);
+
 /* ---- stochastic reconfiguration (natural gradient, minSR; docs/sr.md) -------------------------------------------------------
  * psi = sqrt(P) real and positive:  O[s][k] = d log psi(sigma_s) / d theta_k = 1/2 d log P(sigma_s) / d theta_k, theta in the flat
  * order of rnnwf_set_params_flat;  dO = O - mean_s O;  eps_s = E_loc,s - mean E.  The minSR direction with diagonal shift lambda is

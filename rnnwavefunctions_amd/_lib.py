@@ -111,6 +111,7 @@ PROTOTYPES = {
 PROTOTYPES["rnnwf_pauli_train_steps_2d"] = PROTOTYPES["rnnwf_pauli_train_steps"]       # the same argument list, one object
 PROTOTYPES["rnnwf_pauli_step_stack"] = PROTOTYPES["rnnwf_pauli_step"]                  # stacked layers (docs/pauli_stack.md): likewise
 PROTOTYPES["rnnwf_pauli_train_steps_stack"] = PROTOTYPES["rnnwf_pauli_train_steps"]
+PROTOTYPES["rnnwf_renyi2_regions_stack"] = PROTOTYPES["rnnwf_renyi2_regions"]          # docs/renyi_stack.md
 
 _lib = None
 
@@ -589,6 +590,14 @@ class NativeWavefunction:
         0 / 1 (or one mask of N entries), 1 = site in A, sites in the model's order.  samples: (2 numpairs, N) int32, pair p =
         rows 2p, 2p + 1; None: drawn on the device as sample(2 numpairs, seed, step, 2 pair_offset) draws them.  Returns
         dict(sums=(R, 2) [sum r_A, sum r_A^2], samples=(2 numpairs, N) when drawn, log_ratio=(R, numpairs) when asked)."""
+        return self._regions_call("rnnwf_renyi2_regions", regions, numpairs, samples, seed, step, pair_offset, log_ratio)
+
+    def renyi2_regions_stack(self, regions, numpairs, samples=None, seed=111, step=0, pair_offset=0, log_ratio=False):
+        """renyi2_regions for stacked GRU layers (rnnwf_renyi2_regions_stack, docs/renyi_stack.md): models GRU1D and GRU1D_F64 with
+        2..4 layers.  Arguments, shape checks and returns are renyi2_regions's."""
+        return self._regions_call("rnnwf_renyi2_regions_stack", regions, numpairs, samples, seed, step, pair_offset, log_ratio)
+
+    def _regions_call(self, entry, regions, numpairs, samples, seed, step, pair_offset, log_ratio):
         npairs = int(numpairs)
         reg = np.asarray(regions)
         if reg.ndim == 1:
@@ -603,9 +612,9 @@ class NativeWavefunction:
         sums = np.empty((R, 2), dtype=np.float64)
         lr = np.empty((R, max(npairs, 0)), dtype=np.float64) if log_ratio else None
         smp = np.empty((2 * max(npairs, 0), self.N), dtype=np.int32) if samples is None else None
-        self._check(self.lib.rnnwf_renyi2_regions(self.h, rp, R, sp, npairs, int(seed), int(step), int(pair_offset),
-                                                  sums.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
-                                                  smp.ctypes.data_as(_I32P) if smp is not None else None))
+        self._check(getattr(self.lib, entry)(self.h, rp, R, sp, npairs, int(seed), int(step), int(pair_offset),
+                                             sums.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
+                                             smp.ctypes.data_as(_I32P) if smp is not None else None))
         out = {"sums": sums}
         if smp is not None:
             out["samples"] = smp

@@ -4,9 +4,14 @@
 // checkpoints are the stack's, hck[N][nsb][NL][KT][64] (S::ROW values per lane and site, all N sites), as prnn_ml_base_kernel
 // writes them.
 //
-//   prnn_ml_masked_tail_kernel : tail of every chain and distinct flip mask - tile (mask, 16-chain block).  f >= 1: restores EVERY
+//   prnn_ml_masked_tail_kernel : tail of every chain and distinct mask - tile (mask, 16-chain block).  f >= 1: restores EVERY
 //                                layer's state from row f - 1, feeds the chain's own spin f - 1 and teacher-forces sites f..N-1 on
 //                                own_word ^ mask_word.  f = 0: zero states, input -1, all N sites.
+//                                PAIRED (renyi_stack.hip, docs/renyi_stack.md): chains (2p, 2p + 1) are a pair and a masked site
+//                                takes the partner's spin, (own_word & ~mask_word) | (partner_word & mask_word); the host
+//                                normalises the masks so that site 0 is never masked, 1 <= f <= N-1.  The start is the !PAIRED
+//                                form's, wave-uniform selects on f > 0 included: without them the checkpoint loads are hoisted
+//                                and <float, 1, 4, 4> needs 100 vector registers for 82 (5 -> 4 waves per SIMD).
 //   prnn_ml_site_terms_kernel  : log p(sigma_n | sigma_<n) of every chain and site 1..N-1: the head on the top layer's checkpoint
 //                                of site n - the stack keeps the state after the last site too, so no site takes a step here.
 // Both run the base pass's step form (S::BASE_BIAS_LAST) and head on the states prnn_ml_base_kernel stored, and pauli_log_ratio_kernel
@@ -16,7 +21,7 @@
 
 namespace rnnwf {
 
-template <typename T, int NFULL, int NL, int WAVES>
+template <typename T, int NFULL, int NL, int WAVES, bool PAIRED = false>
 __global__ void __launch_bounds__(WAVES * 64) prnn_ml_masked_tail_kernel(MaskArgs a) {
     using S = GruStack<T, NFULL, NL, 1>;
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -33,9 +38,22 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_ml_masked_tail_kernel(MaskArg
         const int64_t s = sb * kChains + w.c;
         const int64_t sc = s < a.ns ? s : a.ns - 1;
         const uint32_t* mrow = a.mask + (int64_t)r * a.W;
-        // 32 sites of the flipped chain at once, the mask word the same for the whole wave.  Bit 0 of `word` is the next site's spin.
-        auto changed_word = [&](int k) { return a.bits[(int64_t)k * a.ns + sc] ^ mrow[k]; };
-        // branch-free start (f is wave-uniform): for f = 0 the load of row 0 is discarded
+        // 32 sites of the changed chain at once, the mask word the same for the whole wave (PAIRED: ns is even, a valid chain's
+        // partner is valid).  Bit 0 of `word` is the next site's spin.
+        auto changed_word = [&](int k) {
+            if constexpr (PAIRED) {
+                // the partner s ^ 1 is the neighbouring lane of the quad (c ^ 1): its word by DPP quad_perm [1,0,3,2], no second
+                // load and no second address in vector registers.  A chain beyond ns has its partner beyond ns too (ns is even);
+                // both read chain ns - 1 and neither is stored.
+                const uint32_t m = mrow[k];
+                const uint32_t own = a.bits[(int64_t)k * a.ns + sc];
+                const uint32_t par = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)own, 0xB1, 0xF, 0xF, false);
+                return (own & ~m) | (par & m);
+            } else {
+                return a.bits[(int64_t)k * a.ns + sc] ^ mrow[k];
+            }
+        };
+        // branch-free start (f is wave-uniform): for f = 0 the load of row 0 is discarded (PAIRED: the host never emits f = 0)
         const int g = f > 0 ? f - 1 : 0;
         T h[S::NL][S::KT];
         {

@@ -7,13 +7,23 @@ log P(sigma)]),  E[v] = <psi|O|psi>;  sites in the model's order.  observables.p
 training.minimize_hamiltonian keep refusing stacks; these are the stacks' own entry points.  They accept a facade or a
 NativeWavefunction of one of the two models with more than one layer and raise ValueError for everything else - a one-layer wave
 function included, which observables.py serves - before the library is touched.
+
+The second Renyi entropy of arbitrary regions, block entropies and the Renyi-2 mutual information by the replica swap estimator of
+observables.py (rnnwf_renyi2_regions_stack; docs/renyi_stack.md): renyi2_regions, renyi2_entropy, renyi2_mutual_information, with
+observables.py's region builders re-exported.
 """
 import numpy as np
 
 from . import _lib
 from .observables import Hamiltonian, _native, group_by_mask, pauli_from_sums, pauli_terms, tfim_hamiltonian, xxz_hamiltonian  # noqa: F401
+from .observables import (_disjoint_masks, column_cut_regions, interval_region, mutual_information2_from_log_ratios,  # noqa: F401
+                          rectangle_region, renyi2_from_sums)
 
+# tests/test_pauli_stack_host.py pins this list; the Renyi functions and the re-exported region builders below are public all the same
+# (RENYI_API names them)
 __all__ = ["pauli_expectations", "energy", "correlations", "minimize_hamiltonian"]
+RENYI_API = ["renyi2_regions", "renyi2_entropy", "renyi2_mutual_information", "interval_region", "rectangle_region", "column_cut_regions",
+             "renyi2_from_sums"]
 
 
 def _native_stack(wf):
@@ -28,6 +38,41 @@ def _native_stack(wf):
 
 def _samples(nat, samples, numsamples):
     return None if samples is None else np.asarray(samples).reshape(int(numsamples), nat.N)
+
+
+def _pairs(nat, samples, numpairs):
+    return None if samples is None else np.asarray(samples).reshape(2 * int(numpairs), nat.N)
+
+
+# ---- second Renyi entropy (rnnwf_renyi2_regions_stack, docs/renyi_stack.md) ------------------------------------------------------
+
+def renyi2_regions(wf, regions, numpairs, seed=111, step=0, samples=None):
+    """Second Renyi entropy S2(A) (R,) and its standard error (R,) of the regions `regions` ((R, N) masks of 0 / 1, or one mask;
+    1 = site in A, sites in the model's order: raster ny * Nx + nx for the 2D raster model) from `numpairs` pairs of independent
+    samples.  samples: (2 numpairs, N) spins, pair p = rows 2p and 2p + 1; None draws them on the device from (seed, step)."""
+    nat = _native_stack(wf)
+    out = nat.renyi2_regions_stack(regions, int(numpairs), samples=_pairs(nat, samples, numpairs), seed=seed, step=step)
+    return renyi2_from_sums(out["sums"], numpairs)
+
+
+def renyi2_entropy(wf, numpairs, seed=111, step=0, samples=None):
+    """S2(l) of A = the first l sites (the model's order), l = 0..N, and its standard error, (N + 1,) each, in one call: the region
+    of cut l is given as its complement, the suffix {l..N-1} (r_A = r_complement).  Cuts 0 and N are exactly 0 +- 0."""
+    nat = _native_stack(wf)
+    suffixes = np.stack([interval_region(nat.N, l, nat.N) for l in range(nat.N + 1)])
+    out = nat.renyi2_regions_stack(suffixes, int(numpairs), samples=_pairs(nat, samples, numpairs), seed=seed, step=step)
+    return renyi2_from_sums(out["sums"], numpairs)
+
+
+def renyi2_mutual_information(wf, region_a, region_b, numpairs, seed=111, step=0, samples=None):
+    """Renyi-2 mutual information I2(A : B) = S2(A) + S2(B) - S2(A u B) of two DISJOINT regions (masks of N entries) and its standard
+    error (observables.mutual_information2_from_log_ratios), from `numpairs` pairs; A, B and A u B run in one call on the same
+    pairs."""
+    a, b = _disjoint_masks(region_a, region_b)
+    nat = _native_stack(wf)
+    out = nat.renyi2_regions_stack(np.stack([a, b, a | b]), int(numpairs), samples=_pairs(nat, samples, numpairs), seed=seed, step=step,
+                                   log_ratio=True)
+    return mutual_information2_from_log_ratios(*out["log_ratio"])
 
 
 def pauli_expectations(wf, strings, numsamples, seed=111, step=0, samples=None):
