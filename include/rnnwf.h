@@ -168,7 +168,8 @@ int rnnwf_vmc_step(rnnwf_handle* h, int64_t numsamples, uint64_t seed, uint64_t 
                    double* moments);
 
 /* ---- gradient of the VMC cost (models GRU1D, GRU1D_PARITY, CRNN_U1 (f32), GRU1D_F64, MDRNN2D (f64)) ----
- * (RNNWF_MODEL_LSTM1D_F64 has no gradient: these four and rnnwf_load_batch return RNNWF_ERR_INVALID for it.)
+ * (For RNNWF_MODEL_LSTM1D_F64 these four and rnnwf_load_batch return RNNWF_ERR_INVALID; its gradient has entries of its
+ * own, rnnwf_lstm_gradient and rnnwf_lstm_vmc_gradient_step below.)
  * rnnwf_vmc_gradient <- optimizer.compute_gradients(cost) with
  *   cost = mean(log_probs * Eloc) - mean(Eloc) * mean(log_probs)      (1DTFIM/TrainingRNN_1DTFIM.py:151-162)
  *   evaluated on the batch of the LAST rnnwf_vmc_step (its samples, per-site hidden states and E_loc are still
@@ -596,6 +597,21 @@ int rnnwf_comm_reduce_in_step(rnnwf_handle* h, int32_t on);
  * communicator exists.  Reports print it, so that N one-rank runs cannot be mistaken for one N-rank run.    */
 int rnnwf_comm_info(rnnwf_handle* h, int32_t* nranks, int32_t* rank, int32_t* device);
 int rnnwf_comm_destroy(rnnwf_handle* h);
+
+/* ---- gradient of the LSTM wave function (RNNWF_MODEL_LSTM1D_F64; docs/lstm.md, "Gradient") ------------------------
+ * The entries above keep refusing an LSTM handle; these two are its gradient.  Both leave the tensors where rnnwf_get_grad,
+ * rnnwf_get_grads_flat and rnnwf_allreduce_grads read them.  Any other model: RNNWF_ERR_INVALID; parameters not
+ * committed: RNNWF_ERR_STATE; more samples than the state budget of one pass holds: RNNWF_ERR_NOMEM ("split the batch").
+ *
+ * rnnwf_lstm_gradient: d/dtheta sum_s weights[s] log P(samples[s]) for B caller-supplied configurations (B, N) int32
+ *   (teacher-forced base pass with checkpoints, back-propagation through time, weight-gradient product).  With
+ *   weights[s] = (E_s - mean E) / n it is the gradient of the reference's cost; several processes centre with the global mean.
+ * rnnwf_lstm_vmc_gradient_step: rnnwf_vmc_step (same samples, E_loc and moments, bit for bit; couplings = Jz (Nx*Ny) then Bx)
+ *   followed by the gradient with weights (E_s - moments[0] / moments[2]) * (1 / moments[2]) on the states that step left on
+ *   the device: no second base pass, one host synchronisation.  Single process only (no communicator).              */
+int rnnwf_lstm_gradient(rnnwf_handle* h, const int32_t* samples, int64_t B, const double* weights);
+int rnnwf_lstm_vmc_gradient_step(rnnwf_handle* h, int64_t numsamples, uint64_t seed, uint64_t step, int64_t sample_offset,
+                                 const double* couplings, double* moments, int32_t* out_samples, double* out_eloc);
 
 /* ---- measurement ------------------------------------------------------------------------------
  * HIP-event timing of the kernels on the handle's stream (bench.py's roofline leg).

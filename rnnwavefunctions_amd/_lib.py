@@ -100,6 +100,8 @@ PROTOTYPES = {
     "rnnwf_sr_apply_2d": (C.c_int, [_P, _F64P, _F64P]),
     "rnnwf_sr_solve_2d": (C.c_int, [_P, _F64, _F64P]),
     "rnnwf_sr_direction_2d": (C.c_int, [_P, _F64, _F64P]),
+    "rnnwf_lstm_gradient": (C.c_int, [_P, _I32P, _I64, _F64P]),
+    "rnnwf_lstm_vmc_gradient_step": (C.c_int, [_P, _I64, _U64, _U64, _I64, _F64P, _F64P, _I32P, _F64P]),
     "rnnwf_resident_samples": (_I64, [_P]),
     "rnnwf_timing_enable": (C.c_int, [_P, _I32]),
     "rnnwf_timing_reset": (C.c_int, [_P]),
@@ -368,6 +370,55 @@ class NativeWavefunction:
             g = np.empty(shape, dtype=np.float64)
             self._check(self.lib.rnnwf_get_grad(self.h, name.encode(), g.ctypes.data_as(_P), g.size, F64))
             out[name] = g
+        return out
+
+    # -- gradient of the LSTM wave function (docs/lstm.md, "Gradient") ----------------------------
+    def _grads(self, shapes):
+        """{tf_name: float64 ndarray} of the gradient the library holds, every tensor of `shapes` in one call"""
+        lay = self._layout()
+        if not (len(shapes) == len(lay) and all(nm in shapes and int(np.prod(shapes[nm], dtype=np.int64)) == cnt for nm, cnt in lay)):
+            raise ValueError("shapes must name every tensor of the model with its shape: %r" % ([nm for nm, _ in lay],))
+        flat = np.empty(sum(cnt for _, cnt in lay), dtype=np.float64)
+        self._check(self.lib.rnnwf_get_grads_flat(self.h, flat.ctypes.data_as(_F64P), flat.size))
+        out, off = {}, 0
+        for nm, cnt in lay:
+            out[nm] = flat[off:off + cnt].reshape(shapes[nm])
+            off += cnt
+        return {name: out[name] for name in shapes}
+
+    def lstm_gradient(self, samples, weights, shapes, allreduce=False):
+        """d/dtheta sum_s weights[s] log P(samples[s]) of the LSTM wave function (rnnwf_lstm_gradient).  samples (B, N) or
+        (B, Nx, Ny), weights (B,); shapes: {tf_name (without scope): shape}; returns {tf_name: float64 ndarray}.  With
+        weights = (E - mean E) / B it is the gradient of the reference's cost; allreduce=True sums it over the communicator."""
+        s, sp = _i32(samples)
+        if s.ndim < 2 or s.shape[0] < 1 or int(np.prod(s.shape[1:])) != self.N:
+            raise ValueError("samples must be non-empty with %d sites per row, got shape %r" % (self.N, s.shape))
+        w, wp = _f64(weights)
+        if w.shape != (s.shape[0],):
+            raise ValueError("lstm_gradient: %d samples but weights of shape %r" % (s.shape[0], w.shape))
+        self._check(self.lib.rnnwf_lstm_gradient(self.h, sp, s.shape[0], wp))
+        if allreduce:
+            self._check(self.lib.rnnwf_allreduce_grads(self.h))
+        return self._grads(shapes)
+
+    def lstm_vmc_gradient_step(self, numsamples, seed, step, couplings, shapes, sample_offset=0, want_samples=False, want_eloc=False):
+        """vmc_step and the gradient of the reference's cost on its batch in one call with one host synchronisation
+        (rnnwf_lstm_vmc_gradient_step; single process).  couplings: Jz (N) then Bx.  Returns dict(moments=(4,), grads={tf_name:
+        float64 ndarray}, samples=?, eloc=?); moments, samples and eloc are vmc_step's bit for bit."""
+        c, cp = _f64(couplings)
+        if c.shape != (self.N + 1,):
+            raise ValueError("lstm_vmc_gradient_step: couplings must hold Jz (%d) then Bx, got shape %r" % (self.N, c.shape))
+        mom = np.zeros(4, dtype=np.float64)
+        smp = np.empty((numsamples, self.N), dtype=np.int32) if want_samples else None
+        el = np.empty(numsamples, dtype=np.float64) if want_eloc else None
+        self._check(self.lib.rnnwf_lstm_vmc_gradient_step(self.h, numsamples, seed, step, sample_offset, cp, mom.ctypes.data_as(_F64P),
+                                                          smp.ctypes.data_as(_I32P) if want_samples else None,
+                                                          el.ctypes.data_as(_F64P) if want_eloc else None))
+        out = {"moments": mom, "grads": self._grads(shapes)}
+        if want_samples:
+            out["samples"] = smp
+        if want_eloc:
+            out["eloc"] = el
         return out
 
     # -- stochastic reconfiguration: rnnwf_log_derivatives, rnnwf_sr_* (docs/sr.md) ---------------

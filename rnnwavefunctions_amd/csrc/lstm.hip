@@ -180,6 +180,16 @@ int pack_image(rnnwf_handle* h, std::vector<char>& img) {
 
 }  // namespace
 
+// base pass with checkpoints on the spins packed into h->bits, nothing else: the states the gradient's backward pass starts from
+int rnnwf::lstm_teacher_base(rnnwf_handle* h, int64_t ns) {
+    const int64_t nsb = (ns + kChains - 1) / kChains;
+    if (int rc = ensure(h, h->hck, (size_t)std::max(h->N - 1, 1) * nsb * hck_bytes_per_block(h))) return rc;
+    LstmArgs a = base_args(h, ns);
+    a.bits = (uint32_t*)h->bits.p;
+    a.hck = (double*)h->hck.p;
+    return launch_base(h, a);
+}
+
 const Family* rnnwf::lstm_family() {
     static const Family f = {
         "LSTM cell", pack_image, nullptr, log_prob_pass, nullptr, eloc_on_device, max_chains_per_pass, nullptr, nullptr,

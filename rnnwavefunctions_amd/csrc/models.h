@@ -120,6 +120,8 @@ int prnn_plain_base(rnnwf_handle* h, const PrnnArgs& a);
 int prnn_stack_base(rnnwf_handle* h, const PrnnArgs& a);      // stacked layers (pauli_stack.hip): the one-wave MFMA stack kernel only
 PrnnArgs prnn_base_args(rnnwf_handle* h, int64_t ns);
 size_t prnn_hck_bytes_per_block(rnnwf_handle* h);
+// lstm.hip, for the LSTM's gradient (lstm_grad.hip): teacher-forced base pass on h->bits that leaves the checkpoints in h->hck
+int lstm_teacher_base(rnnwf_handle* h, int64_t ns);
 // crnn.hip, for the complex RNN's Pauli pass (crnn_pauli.hip): the same three for the one-layer complex RNN
 int crnn_plain_base(rnnwf_handle* h, const CrnnArgs& a);
 CrnnArgs crnn_base_args(rnnwf_handle* h, int64_t ns);
