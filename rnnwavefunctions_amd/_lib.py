@@ -431,45 +431,65 @@ class NativeWavefunction:
         """samples of the batch the last vmc_step / load_batch left on the device, 0 without one (rnnwf_resident_samples)"""
         return int(self.lib.rnnwf_resident_samples(self.h))
 
+    def _sr_rows(self, suffix):
+        """rows of the minSR system on the resident batch: one per sample, two (real, imaginary) for the complex RNN"""
+        return (2 if suffix == "_complex" else 1) * self.resident_samples()
+
+    def _log_derivatives(self, suffix):
+        ns, n = self.resident_samples(), self.num_params()
+        out = np.empty((2, ns, n) if suffix == "_complex" else (ns, n), dtype=np.float64)
+        self._check(getattr(self.lib, "rnnwf_log_derivatives" + suffix)(self.h, out.ctypes.data_as(_F64P), ns, n))
+        return out[0] + 1j * out[1] if suffix == "_complex" else out
+
+    def _sr_gram(self, suffix):
+        n = self._sr_rows(suffix)
+        gram, eps = np.empty((n, n), dtype=np.float64), np.empty(n, dtype=np.float64)
+        self._check(getattr(self.lib, "rnnwf_sr_gram" + suffix)(self.h, gram.ctypes.data_as(_F64P), eps.ctypes.data_as(_F64P)))
+        return gram, eps
+
+    def _sr_apply(self, suffix, y):
+        yv, yp = _f64(y)
+        n = self._sr_rows(suffix)
+        if n > 0 and yv.shape != (n,):
+            raise ValueError("sr_apply%s: y must have shape (%d,), %s per sample of the resident batch, got %r"
+                             % (suffix, n, "two entries" if suffix == "_complex" else "one entry", yv.shape))
+        out = np.empty(self.num_params(), dtype=np.float64)
+        self._check(getattr(self.lib, "rnnwf_sr_apply" + suffix)(self.h, yp if n > 0 else None, out.ctypes.data_as(_F64P)))
+        return out
+
+    def _sr_solve(self, suffix, diag_shift):
+        y = np.empty(self._sr_rows(suffix), dtype=np.float64)
+        self._check(getattr(self.lib, "rnnwf_sr_solve" + suffix)(self.h, float(diag_shift), y.ctypes.data_as(_F64P)))
+        return y
+
+    def _sr_direction(self, suffix, diag_shift):
+        out = np.empty(self.num_params(), dtype=np.float64)
+        self._check(getattr(self.lib, "rnnwf_sr_direction" + suffix)(self.h, float(diag_shift), out.ctypes.data_as(_F64P)))
+        return out
+
     def log_derivatives(self):
         """(ns, num_params) float64: O[s, k] = d log psi(sigma_s) / d theta_k = 1/2 d log P / d theta_k on the resident batch of the
         last vmc_step / load_batch, theta in the flat order of _layout()."""
-        ns, n = self.resident_samples(), self.num_params()
-        out = np.empty((ns, n), dtype=np.float64)
-        self._check(self.lib.rnnwf_log_derivatives(self.h, out.ctypes.data_as(_F64P), ns, n))
-        return out
+        return self._log_derivatives("")
 
     def sr_gram(self):
         """(gram, eps): the centred Gram matrix dO dO^T (ns, ns) and eps = E_loc - mean E (ns,) of the resident batch, float64;
         gram is exactly symmetric."""
-        ns = self.resident_samples()
-        gram, eps = np.empty((ns, ns), dtype=np.float64), np.empty(ns, dtype=np.float64)
-        self._check(self.lib.rnnwf_sr_gram(self.h, gram.ctypes.data_as(_F64P), eps.ctypes.data_as(_F64P)))
-        return gram, eps
+        return self._sr_gram("")
 
     def sr_apply(self, y):
         """(num_params,) float64: dO^T y for y of one entry per sample of the resident batch, in the flat order of _layout()."""
-        yv, yp = _f64(y)
-        ns = self.resident_samples()
-        if ns > 0 and yv.shape != (ns,):
-            raise ValueError("sr_apply: y must have shape (%d,), one entry per sample of the resident batch, got %r" % (ns, yv.shape))
-        out = np.empty(self.num_params(), dtype=np.float64)
-        self._check(self.lib.rnnwf_sr_apply(self.h, yp if ns > 0 else None, out.ctypes.data_as(_F64P)))
-        return out
+        return self._sr_apply("", y)
 
     def sr_solve(self, diag_shift):
         """(ns,) float64: y of (dO dO^T + ns diag_shift I) y = eps on the resident batch, factorised and solved on the device
         (rnnwf_sr_solve); y is not centred."""
-        y = np.empty(self.resident_samples(), dtype=np.float64)
-        self._check(self.lib.rnnwf_sr_solve(self.h, float(diag_shift), y.ctypes.data_as(_F64P)))
-        return y
+        return self._sr_solve("", diag_shift)
 
     def sr_direction(self, diag_shift):
         """(num_params,) float64: the minSR direction dO^T (dO dO^T + ns diag_shift I)^-1 eps of the resident batch, everything on
         the device (rnnwf_sr_direction), in the flat order of _layout()."""
-        out = np.empty(self.num_params(), dtype=np.float64)
-        self._check(self.lib.rnnwf_sr_direction(self.h, float(diag_shift), out.ctypes.data_as(_F64P)))
-        return out
+        return self._sr_direction("", diag_shift)
 
     def sr_train_steps(self, K, numsamples, seed, step0, couplings, learning_rates, diag_shifts, sample_offset=0):
         """K whole minSR iterations (sample, local energies, Jacobian, Gram matrix, solve, theta -= lr delta, re-pack of the weight
@@ -488,82 +508,49 @@ class NativeWavefunction:
     def log_derivatives_complex(self):
         """(ns, num_params) complex128: O[s, k] = d log psi(sigma_s) / d theta_k = 1/2 d log P / d theta_k + i d phi / d theta_k on the
         resident batch, theta (real) in the flat order of _layout()."""
-        ns, n = self.resident_samples(), self.num_params()
-        out = np.empty((2, ns, n), dtype=np.float64)
-        self._check(self.lib.rnnwf_log_derivatives_complex(self.h, out.ctypes.data_as(_F64P), ns, n))
-        return out[0] + 1j * out[1]
+        return self._log_derivatives("_complex")
 
     def sr_gram_complex(self):
         """(gram, eps): Obar Obar^T (2 ns, 2 ns) for Obar = [Re dO ; Im dO] and eps = [Re (E_loc - mean E) ; Im (E_loc - mean E)]
         (2 ns,) of the resident batch, float64, each half centred with its own mean; gram is exactly symmetric."""
-        n = 2 * self.resident_samples()
-        gram, eps = np.empty((n, n), dtype=np.float64), np.empty(n, dtype=np.float64)
-        self._check(self.lib.rnnwf_sr_gram_complex(self.h, gram.ctypes.data_as(_F64P), eps.ctypes.data_as(_F64P)))
-        return gram, eps
+        return self._sr_gram("_complex")
 
     def sr_apply_complex(self, y):
         """(num_params,) float64: Obar^T y for y (2 ns,) = [weights of the real rows ; weights of the imaginary rows]."""
-        yv, yp = _f64(y)
-        ns = self.resident_samples()
-        if ns > 0 and yv.shape != (2 * ns,):
-            raise ValueError("sr_apply_complex: y must have shape (%d,), two entries per sample of the resident batch, got %r"
-                             % (2 * ns, yv.shape))
-        out = np.empty(self.num_params(), dtype=np.float64)
-        self._check(self.lib.rnnwf_sr_apply_complex(self.h, yp if ns > 0 else None, out.ctypes.data_as(_F64P)))
-        return out
+        return self._sr_apply("_complex", y)
 
     def sr_solve_complex(self, diag_shift):
         """(2 ns,) float64: y of (Obar Obar^T + ns diag_shift I) y = eps, factorised and solved on the device; y is not centred."""
-        y = np.empty(2 * self.resident_samples(), dtype=np.float64)
-        self._check(self.lib.rnnwf_sr_solve_complex(self.h, float(diag_shift), y.ctypes.data_as(_F64P)))
-        return y
+        return self._sr_solve("_complex", diag_shift)
 
     def sr_direction_complex(self, diag_shift):
         """(num_params,) float64: the minSR direction Obar^T (Obar Obar^T + ns diag_shift I)^-1 eps of the resident batch, everything
         on the device (rnnwf_sr_direction_complex), in the flat order of _layout()."""
-        out = np.empty(self.num_params(), dtype=np.float64)
-        self._check(self.lib.rnnwf_sr_direction_complex(self.h, float(diag_shift), out.ctypes.data_as(_F64P)))
-        return out
+        return self._sr_direction("_complex", diag_shift)
 
     # -- stochastic reconfiguration for the 2D RNN: rnnwf_*_2d (docs/sr_2d.md) ----------------------
     def log_derivatives_2d(self):
         """(ns, num_params) float64: O[s, k] = 1/2 d log P(sigma_s) / d theta_k on the resident batch of the 2D RNN, theta in the flat
         order of _layout()."""
-        ns, n = self.resident_samples(), self.num_params()
-        out = np.empty((ns, n), dtype=np.float64)
-        self._check(self.lib.rnnwf_log_derivatives_2d(self.h, out.ctypes.data_as(_F64P), ns, n))
-        return out
+        return self._log_derivatives("_2d")
 
     def sr_gram_2d(self):
         """(gram, eps): the centred Gram matrix dO dO^T (ns, ns) and eps = E_loc - mean E (ns,) of the resident batch of the 2D RNN,
         float64; gram is exactly symmetric."""
-        ns = self.resident_samples()
-        gram, eps = np.empty((ns, ns), dtype=np.float64), np.empty(ns, dtype=np.float64)
-        self._check(self.lib.rnnwf_sr_gram_2d(self.h, gram.ctypes.data_as(_F64P), eps.ctypes.data_as(_F64P)))
-        return gram, eps
+        return self._sr_gram("_2d")
 
     def sr_apply_2d(self, y):
         """(num_params,) float64: dO^T y for y of one entry per sample of the resident batch of the 2D RNN."""
-        yv, yp = _f64(y)
-        ns = self.resident_samples()
-        if ns > 0 and yv.shape != (ns,):
-            raise ValueError("sr_apply_2d: y must have shape (%d,), one entry per sample of the resident batch, got %r" % (ns, yv.shape))
-        out = np.empty(self.num_params(), dtype=np.float64)
-        self._check(self.lib.rnnwf_sr_apply_2d(self.h, yp if ns > 0 else None, out.ctypes.data_as(_F64P)))
-        return out
+        return self._sr_apply("_2d", y)
 
     def sr_solve_2d(self, diag_shift):
         """(ns,) float64: y of (dO dO^T + ns diag_shift I) y = eps, factorised and solved on the device; y is not centred."""
-        y = np.empty(self.resident_samples(), dtype=np.float64)
-        self._check(self.lib.rnnwf_sr_solve_2d(self.h, float(diag_shift), y.ctypes.data_as(_F64P)))
-        return y
+        return self._sr_solve("_2d", diag_shift)
 
     def sr_direction_2d(self, diag_shift):
         """(num_params,) float64: the minSR direction dO^T (dO dO^T + ns diag_shift I)^-1 eps of the resident batch of the 2D RNN,
         everything on the device (rnnwf_sr_direction_2d), in the flat order of _layout()."""
-        out = np.empty(self.num_params(), dtype=np.float64)
-        self._check(self.lib.rnnwf_sr_direction_2d(self.h, float(diag_shift), out.ctypes.data_as(_F64P)))
-        return out
+        return self._sr_direction("_2d", diag_shift)
 
     # -- device-resident training iteration (rnnwf_train_steps; single-layer float32 GRU models) ------------------
     def device_training_supported(self):
@@ -648,25 +635,42 @@ class NativeWavefunction:
         2..4 layers.  Arguments, shape checks and returns are renyi2_regions's."""
         return self._regions_call("rnnwf_renyi2_regions_stack", regions, numpairs, samples, seed, step, pair_offset, log_ratio)
 
-    def _regions_call(self, entry, regions, numpairs, samples, seed, step, pair_offset, log_ratio):
+    def _regions_call(self, entry, regions, numpairs, samples, seed, step, pair_offset, log_ratio, masks="any", lattice_draw=False, cplx=False):
+        """The argument checks, buffers and result dict of the four renyi2_regions methods.  masks: which shapes of `regions` besides
+        (R, N) and (N,) pass - "any": every (R, ...) with N entries per region; "lattice": (R, Nx, Ny); "flat": none.  lattice_draw:
+        drawn samples come back as (2 numpairs, Nx, Ny).  cplx: sums (R, 4), complex log_ratio and the in_sector output."""
         npairs = int(numpairs)
         reg = np.asarray(regions)
         if reg.ndim == 1:
             reg = reg[None, :]
-        if reg.ndim < 2 or reg.shape[0] < 1 or int(np.prod(reg.shape[1:])) != self.N:
+        if masks == "any":
+            ok = reg.ndim >= 2 and int(np.prod(reg.shape[1:])) == self.N
+        else:
+            if masks == "lattice" and reg.ndim == 3 and reg.shape[1:] == (self.nx, self.ny):
+                reg = reg.reshape(reg.shape[0], self.N)
+            ok = reg.ndim == 2 and reg.shape[1] == self.N
+        if not ok or reg.shape[0] < 1:
+            if masks == "lattice":
+                raise ValueError("regions must have shape (nregions >= 1, %d) or (nregions >= 1, %d, %d), got %r"
+                                 % (self.N, self.nx, self.ny, reg.shape))
             raise ValueError("regions must have shape (nregions >= 1, %d), got %r" % (self.N, reg.shape))
         if not np.all(reg == reg.astype(np.int32)):
             raise ValueError("regions must hold the integers 0 and 1")
         reg, rp = _i32(reg.reshape(reg.shape[0], self.N))
         R = reg.shape[0]
         s, sp = self._chain_samples(samples, 2 * npairs, "2*numpairs")
-        sums = np.empty((R, 2), dtype=np.float64)
-        lr = np.empty((R, max(npairs, 0)), dtype=np.float64) if log_ratio else None
-        smp = np.empty((2 * max(npairs, 0), self.N), dtype=np.int32) if samples is None else None
-        self._check(getattr(self.lib, entry)(self.h, rp, R, sp, npairs, int(seed), int(step), int(pair_offset),
-                                             sums.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
-                                             smp.ctypes.data_as(_I32P) if smp is not None else None))
+        sums = np.empty((R, 4 if cplx else 2), dtype=np.float64)
+        ins = np.empty(R, dtype=np.int64) if cplx else None
+        lr = np.empty((R, max(npairs, 0)), dtype=np.complex128 if cplx else np.float64) if log_ratio else None
+        smp = np.empty((2 * max(npairs, 0),) + ((self.nx, self.ny) if lattice_draw else (self.N,)), dtype=np.int32) if samples is None else None
+        outputs = [sums.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None]
+        if cplx:
+            outputs.append(ins.ctypes.data_as(C.POINTER(C.c_int64)))
+        outputs.append(smp.ctypes.data_as(_I32P) if smp is not None else None)
+        self._check(getattr(self.lib, entry)(self.h, rp, R, sp, npairs, int(seed), int(step), int(pair_offset), *outputs))
         out = {"sums": sums}
+        if cplx:
+            out["in_sector"] = ins
         if smp is not None:
             out["samples"] = smp
         if log_ratio:
@@ -679,32 +683,8 @@ class NativeWavefunction:
         (2 numpairs, Nx, Ny) or (2 numpairs, Nx*Ny) int32, pair p = rows 2p, 2p + 1; None: drawn on the device as sample(2 numpairs,
         seed, step, 2 pair_offset) draws them.  Returns dict(sums=(R, 2) [sum r_A, sum r_A^2], samples=(2 numpairs, Nx, Ny) when
         drawn, log_ratio=(R, numpairs) when asked)."""
-        npairs = int(numpairs)
-        reg = np.asarray(regions)
-        if reg.ndim == 1:
-            reg = reg[None, :]
-        if reg.ndim == 3 and reg.shape[1:] == (self.nx, self.ny):
-            reg = reg.reshape(reg.shape[0], self.N)
-        if reg.ndim != 2 or reg.shape[0] < 1 or reg.shape[1] != self.N:
-            raise ValueError("regions must have shape (nregions >= 1, %d) or (nregions >= 1, %d, %d), got %r"
-                             % (self.N, self.nx, self.ny, reg.shape))
-        if not np.all(reg == reg.astype(np.int32)):
-            raise ValueError("regions must hold the integers 0 and 1")
-        reg, rp = _i32(reg)
-        R = reg.shape[0]
-        s, sp = self._chain_samples(samples, 2 * npairs, "2*numpairs")
-        sums = np.empty((R, 2), dtype=np.float64)
-        lr = np.empty((R, max(npairs, 0)), dtype=np.float64) if log_ratio else None
-        smp = np.empty((2 * max(npairs, 0), self.nx, self.ny), dtype=np.int32) if samples is None else None
-        self._check(self.lib.rnnwf_renyi2_regions_2d(self.h, rp, R, sp, npairs, int(seed), int(step), int(pair_offset),
-                                                     sums.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
-                                                     smp.ctypes.data_as(_I32P) if smp is not None else None))
-        out = {"sums": sums}
-        if smp is not None:
-            out["samples"] = smp
-        if log_ratio:
-            out["log_ratio"] = lr
-        return out
+        return self._regions_call("rnnwf_renyi2_regions_2d", regions, numpairs, samples, seed, step, pair_offset, log_ratio, masks="lattice",
+                                  lattice_draw=True)
 
     def renyi2_regions_complex(self, regions, numpairs, samples=None, seed=111, step=0, pair_offset=0, log_ratio=False):
         """renyi2_regions for the complex RNN (rnnwf_renyi2_regions_complex).  regions: (R, N) masks of 0 / 1 (or one mask of N
@@ -712,31 +692,8 @@ class NativeWavefunction:
         drawn on the device as sample(2 numpairs, seed, step, 2 pair_offset) draws them.  Returns dict(sums=(R, 4) [sum Re r, sum
         Im r, sum (Re r)^2, sum (Im r)^2], in_sector=(R,) int64 surviving pairs, samples=(2 numpairs, N) when drawn,
         log_ratio=(R, numpairs) complex128 when asked, -inf + 0j for a pair whose mixed chains leave the sector)."""
-        npairs = int(numpairs)
-        reg = np.asarray(regions)
-        if reg.ndim == 1:
-            reg = reg[None, :]
-        if reg.ndim != 2 or reg.shape[0] < 1 or reg.shape[1] != self.N:
-            raise ValueError("regions must have shape (nregions >= 1, %d), got %r" % (self.N, reg.shape))
-        if not np.all(reg == reg.astype(np.int32)):
-            raise ValueError("regions must hold the integers 0 and 1")
-        reg, rp = _i32(reg)
-        R = reg.shape[0]
-        s, sp = self._chain_samples(samples, 2 * npairs, "2*numpairs")
-        sums = np.empty((R, 4), dtype=np.float64)
-        ins = np.empty(R, dtype=np.int64)
-        lr = np.empty((R, max(npairs, 0)), dtype=np.complex128) if log_ratio else None
-        smp = np.empty((2 * max(npairs, 0), self.N), dtype=np.int32) if samples is None else None
-        self._check(self.lib.rnnwf_renyi2_regions_complex(
-            self.h, rp, R, sp, npairs, int(seed), int(step), int(pair_offset), sums.ctypes.data_as(_F64P),
-            lr.ctypes.data_as(_F64P) if lr is not None else None, ins.ctypes.data_as(C.POINTER(C.c_int64)),
-            smp.ctypes.data_as(_I32P) if smp is not None else None))
-        out = {"sums": sums, "in_sector": ins}
-        if smp is not None:
-            out["samples"] = smp
-        if log_ratio:
-            out["log_ratio"] = lr
-        return out
+        return self._regions_call("rnnwf_renyi2_regions_complex", regions, numpairs, samples, seed, step, pair_offset, log_ratio, masks="flat",
+                                  cplx=True)
 
     # -- correlation functions --------------------------------------------------------------------
     def correlations(self, ns, samples=None, seed=0, step=0, sample_offset=0, want_log_ratio=False, want_samples=False):
@@ -769,7 +726,7 @@ class NativeWavefunction:
         sample_offset) draws them.  Returns dict(term_sums=(K, 2) [sum v_k, sum v_k^2], moments=(4,), eloc=(ns,)?,
         log_ratio=(distinct non-empty flip masks in order of first appearance, ns)?, samples=(ns, N)?).  A call that fits one pass
         leaves its batch resident for vmc_gradient."""
-        return self._pauli_call("rnnwf_pauli_step", (max(int(ns), 0), self.N), flip, sign, coeff, ns, samples, seed, step,
+        return self._pauli_call("rnnwf_pauli_step", False, (max(int(ns), 0), self.N), flip, sign, coeff, ns, samples, seed, step,
                                 sample_offset, want_eloc, want_log_ratio, want_samples)
 
     def pauli_step_2d(self, flip, sign, coeff, ns, samples=None, seed=0, step=0, sample_offset=0, want_eloc=False,
@@ -777,48 +734,58 @@ class NativeWavefunction:
         """pauli_step for the 2D RNN (rnnwf_pauli_step_2d).  flip, sign: (K, Nx*Ny) masks indexed by the lattice index nx*Ny + ny, the
         C-order flattening of samples (ns, Nx, Ny), or (K, Nx, Ny).  samples: (ns, Nx, Ny) or (ns, Nx*Ny) int32; None: drawn on the
         device as sample(ns, seed, step, sample_offset) draws them, and returned as (ns, Nx, Ny).  Returns what pauli_step returns."""
-        fl, sg = np.asarray(flip), np.asarray(sign)
-        if fl.ndim == 3 and fl.shape[1:] == (self.nx, self.ny) and sg.shape == fl.shape:
-            fl, sg = fl.reshape(fl.shape[0], self.N), sg.reshape(sg.shape[0], self.N)
-        return self._pauli_call("rnnwf_pauli_step_2d", (max(int(ns), 0), self.nx, self.ny), fl, sg, coeff, ns, samples, seed, step,
-                                sample_offset, want_eloc, want_log_ratio, want_samples)
+        return self._pauli_call("rnnwf_pauli_step_2d", False, (max(int(ns), 0), self.nx, self.ny), *self._lattice_masks(flip, sign), coeff, ns,
+                                samples, seed, step, sample_offset, want_eloc, want_log_ratio, want_samples)
 
     def pauli_step_stack(self, flip, sign, coeff, ns, samples=None, seed=0, step=0, sample_offset=0, want_eloc=False,
                          want_log_ratio=False, want_samples=False):
         """pauli_step for stacked GRU layers (rnnwf_pauli_step_stack, docs/pauli_stack.md): models GRU1D and GRU1D_F64 with 2..4
         layers.  Arguments and the returned dict are pauli_step's."""
-        return self._pauli_call("rnnwf_pauli_step_stack", (max(int(ns), 0), self.N), flip, sign, coeff, ns, samples, seed, step,
+        return self._pauli_call("rnnwf_pauli_step_stack", False, (max(int(ns), 0), self.N), flip, sign, coeff, ns, samples, seed, step,
                                 sample_offset, want_eloc, want_log_ratio, want_samples)
 
-    def _pauli_call(self, entry, drawn_shape, flip, sign, coeff, ns, samples, seed, step, sample_offset, want_eloc, want_log_ratio,
-                    want_samples):
-        """the argument checks, buffers and result dict pauli_step and pauli_step_2d share"""
-        ns = int(ns)
-        N = self.N
+    def _lattice_masks(self, flip, sign):
+        """flip and sign given as (K, Nx, Ny) flattened to (K, Nx*Ny); everything else as it came"""
+        fl, sg = np.asarray(flip), np.asarray(sign)
+        if fl.ndim == 3 and fl.shape[1:] == (self.nx, self.ny) and sg.shape == fl.shape:
+            fl, sg = fl.reshape(fl.shape[0], self.N), sg.reshape(sg.shape[0], self.N)
+        return fl, sg
+
+    def _term_masks(self, flip, sign, coeff, cplx):
+        """(flip, sign, coeff) as contiguous arrays - (K, N) int32 twice, (K,) float64 or, with cplx, complex128 - after the checks every
+        Pauli entry makes before the library is called"""
         fl, sg = np.asarray(flip), np.asarray(sign)
         if fl.ndim == 1:
             fl, sg = fl[None, :], sg[None, :]
-        if fl.ndim != 2 or fl.shape[0] < 1 or fl.shape[1] != N or sg.shape != fl.shape:
-            raise ValueError("flip and sign must both have shape (nterms >= 1, %d), got %r and %r" % (N, fl.shape, sg.shape))
+        if fl.ndim != 2 or fl.shape[0] < 1 or fl.shape[1] != self.N or sg.shape != fl.shape:
+            raise ValueError("flip and sign must both have shape (nterms >= 1, %d), got %r and %r" % (self.N, fl.shape, sg.shape))
         if not (np.all(fl == fl.astype(np.int32)) and np.all(sg == sg.astype(np.int32))):
             raise ValueError("flip and sign must hold the integers 0 and 1")
-        fl, fp = _i32(fl)
-        sg, gp = _i32(sg)
+        fl, sg = np.ascontiguousarray(fl, dtype=np.int32), np.ascontiguousarray(sg, dtype=np.int32)
+        co = np.ascontiguousarray(np.atleast_1d(coeff), dtype=np.complex128 if cplx else np.float64)
+        if co.shape != (fl.shape[0],):
+            raise ValueError("coeff must have shape (%d,), got %r" % (fl.shape[0], co.shape))
+        return fl, sg, co
+
+    def _pauli_call(self, entry, cplx, drawn_shape, flip, sign, coeff, ns, samples, seed, step, sample_offset, want_eloc, want_log_ratio,
+                    want_samples):
+        """the argument checks, buffers and result dict the four pauli_step methods share; cplx: complex coeff, eloc and log_ratio and
+        four sums per term"""
+        ns = int(ns)
+        fl, sg, co = self._term_masks(flip, sign, coeff, cplx)
         K = fl.shape[0]
-        co, cp = _f64(np.atleast_1d(coeff))
-        if co.shape != (K,):
-            raise ValueError("coeff must have shape (%d,), got %r" % (K, co.shape))
         s, sp = self._chain_samples(samples, ns, "ns")
-        sums = np.empty((K, 2), dtype=np.float64)
+        sums = np.empty((K, 4 if cplx else 2), dtype=np.float64)
         mom = np.zeros(4, dtype=np.float64)
-        el = np.empty(max(ns, 0), dtype=np.float64) if want_eloc else None
+        el = np.empty(max(ns, 0), dtype=np.complex64 if cplx else np.float64) if want_eloc else None
         nmasks = len({r.tobytes() for r in fl if r.any()})
-        lr = np.empty((nmasks, max(ns, 0)), dtype=np.float64) if want_log_ratio else None
+        lr = np.empty((nmasks, max(ns, 0)), dtype=np.complex128 if cplx else np.float64) if want_log_ratio else None
         smp = np.empty(drawn_shape, dtype=np.int32) if want_samples and samples is None else None
-        self._check(getattr(self.lib, entry)(self.h, fp, gp, cp, K, sp, ns, int(seed), int(step), int(sample_offset),
-                       sums.ctypes.data_as(_F64P), el.ctypes.data_as(_F64P) if el is not None else None,
-                       mom.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
-                       smp.ctypes.data_as(_I32P) if smp is not None else None))
+        self._check(getattr(self.lib, entry)(self.h, fl.ctypes.data_as(_I32P), sg.ctypes.data_as(_I32P), co.ctypes.data_as(_F64P), K, sp, ns,
+                                             int(seed), int(step), int(sample_offset), sums.ctypes.data_as(_F64P),
+                                             el.ctypes.data_as(_F32P if cplx else _F64P) if el is not None else None,
+                                             mom.ctypes.data_as(_F64P), lr.ctypes.data_as(_F64P) if lr is not None else None,
+                                             smp.ctypes.data_as(_I32P) if smp is not None else None))
         out = {"term_sums": sums, "moments": mom}
         if want_eloc:
             out["eloc"] = el
@@ -836,40 +803,8 @@ class NativeWavefunction:
         sum Im E], eloc=(ns,) complex64?, log_ratio=(distinct non-empty flip masks in order of first appearance, ns) complex128?
         (-inf + 0j where the flipped configuration leaves the zero-magnetisation sector), samples=(ns, N)?).  A call that fits one
         pass leaves its batch resident for vmc_gradient."""
-        ns = int(numsamples)
-        N = self.N
-        fl, sg = np.asarray(flip), np.asarray(sign)
-        if fl.ndim == 1:
-            fl, sg = fl[None, :], sg[None, :]
-        if fl.ndim != 2 or fl.shape[0] < 1 or fl.shape[1] != N or sg.shape != fl.shape:
-            raise ValueError("flip and sign must both have shape (nterms >= 1, %d), got %r and %r" % (N, fl.shape, sg.shape))
-        if not (np.all(fl == fl.astype(np.int32)) and np.all(sg == sg.astype(np.int32))):
-            raise ValueError("flip and sign must hold the integers 0 and 1")
-        fl, fp = _i32(fl)
-        sg, gp = _i32(sg)
-        K = fl.shape[0]
-        co = np.ascontiguousarray(np.atleast_1d(coeff), dtype=np.complex128)
-        if co.shape != (K,):
-            raise ValueError("coeff must have shape (%d,), got %r" % (K, co.shape))
-        s, sp = self._chain_samples(samples, ns, "ns")
-        sums = np.empty((K, 4), dtype=np.float64)
-        mom = np.zeros(4, dtype=np.float64)
-        el = np.empty(max(ns, 0), dtype=np.complex64) if want_eloc else None
-        nmasks = len({r.tobytes() for r in fl if r.any()})
-        lr = np.empty((nmasks, max(ns, 0)), dtype=np.complex128) if want_log_ratio else None
-        smp = np.empty((max(ns, 0), N), dtype=np.int32) if want_samples and samples is None else None
-        self._check(self.lib.rnnwf_pauli_step_complex(
-            self.h, fp, gp, co.ctypes.data_as(_F64P), K, sp, ns, int(seed), int(step), int(sample_offset), sums.ctypes.data_as(_F64P),
-            el.ctypes.data_as(_F32P) if el is not None else None, mom.ctypes.data_as(_F64P),
-            lr.ctypes.data_as(_F64P) if lr is not None else None, smp.ctypes.data_as(_I32P) if smp is not None else None))
-        out = {"term_sums": sums, "moments": mom}
-        if want_eloc:
-            out["eloc"] = el
-        if want_log_ratio:
-            out["log_ratio"] = lr
-        if want_samples:
-            out["samples"] = smp if smp is not None else s
-        return out
+        return self._pauli_call("rnnwf_pauli_step_complex", True, (max(int(numsamples), 0), self.N), flip, sign, coeff, numsamples, samples, seed,
+                                step, sample_offset, want_eloc, want_log_ratio, want_samples)
 
     # -- device-resident Adam iterations on a Pauli-string Hamiltonian (docs/pauli_train.md) ---------
     def pauli_train_steps(self, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1=0.9, beta2=0.999, epsilon=1e-8,
@@ -893,11 +828,8 @@ class NativeWavefunction:
                              sample_offset=0, want_term_sums=False, want_eloc=False):
         """pauli_train_steps for the 2D RNN (rnnwf_pauli_train_steps_2d).  flip, sign: (nterms, Nx*Ny) masks indexed by the lattice
         index nx*Ny + ny, or (nterms, Nx, Ny), as pauli_step_2d takes them.  Returns what pauli_train_steps returns."""
-        fl, sg = np.asarray(flip), np.asarray(sign)
-        if fl.ndim == 3 and fl.shape[1:] == (self.nx, self.ny) and sg.shape == fl.shape:
-            fl, sg = fl.reshape(fl.shape[0], self.N), sg.reshape(sg.shape[0], self.N)
-        return self._pauli_train_call("rnnwf_pauli_train_steps_2d", False, fl, sg, coeff, numsamples, seed, step0, learning_rates, beta1,
-                                      beta2, epsilon, sample_offset, want_term_sums, want_eloc)
+        return self._pauli_train_call("rnnwf_pauli_train_steps_2d", False, *self._lattice_masks(flip, sign), coeff, numsamples, seed, step0,
+                                      learning_rates, beta1, beta2, epsilon, sample_offset, want_term_sums, want_eloc)
 
     def pauli_train_steps_stack(self, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1=0.9, beta2=0.999, epsilon=1e-8,
                                 sample_offset=0, want_term_sums=False, want_eloc=False):
@@ -908,27 +840,16 @@ class NativeWavefunction:
 
     def _pauli_train_call(self, entry, cplx, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1, beta2, epsilon,
                           sample_offset, want_term_sums, want_eloc):
-        ns, N = int(numsamples), self.N
-        fl, sg = np.asarray(flip), np.asarray(sign)
-        if fl.ndim == 1:
-            fl, sg = fl[None, :], sg[None, :]
-        if fl.ndim != 2 or fl.shape[0] < 1 or fl.shape[1] != N or sg.shape != fl.shape:
-            raise ValueError("flip and sign must both have shape (nterms >= 1, %d), got %r and %r" % (N, fl.shape, sg.shape))
-        if not (np.all(fl == fl.astype(np.int32)) and np.all(sg == sg.astype(np.int32))):
-            raise ValueError("flip and sign must hold the integers 0 and 1")
-        fl, fp = _i32(fl)
-        sg, gp = _i32(sg)
+        ns = int(numsamples)
+        fl, sg, co = self._term_masks(flip, sign, coeff, cplx)
         nterms = fl.shape[0]
-        co = np.ascontiguousarray(np.atleast_1d(coeff), dtype=np.complex128 if cplx else np.float64)
-        if co.shape != (nterms,):
-            raise ValueError("coeff must have shape (%d,), got %r" % (nterms, co.shape))
         lr, lrp = _f64(np.atleast_1d(learning_rates))
         K = lr.size
         mom = np.empty((K, 4), dtype=np.float64)
         sums = np.empty((K, nterms, 4 if cplx else 2), dtype=np.float64) if want_term_sums else None
         el = np.empty(max(ns, 0), dtype=np.complex64 if cplx else np.float64) if want_eloc else None
-        self._check(getattr(self.lib, entry)(self.h, fp, gp, co.ctypes.data_as(_F64P), nterms, K, ns, int(seed), int(step0), int(sample_offset),
-                                             lrp, float(beta1), float(beta2), float(epsilon), mom.ctypes.data_as(_F64P),
+        self._check(getattr(self.lib, entry)(self.h, fl.ctypes.data_as(_I32P), sg.ctypes.data_as(_I32P), co.ctypes.data_as(_F64P), nterms, K, ns,
+                                             int(seed), int(step0), int(sample_offset), lrp, float(beta1), float(beta2), float(epsilon), mom.ctypes.data_as(_F64P),
                                              sums.ctypes.data_as(_F64P) if sums is not None else None,
                                              el.ctypes.data_as(_F32P if cplx else _F64P) if el is not None else None))
         if not (want_term_sums or want_eloc):

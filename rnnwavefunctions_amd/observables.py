@@ -21,6 +21,7 @@ import warnings
 import numpy as np
 
 from . import _lib
+from . import _observable_api as _api
 
 
 def _native(wf):
@@ -103,11 +104,7 @@ def renyi2_regions(wf, regions, numpairs, seed=111, step=0, samples=None):
     samples of `wf` (a facade or a NativeWavefunction).  samples: (2 numpairs, N) spins, pair p = rows 2p and 2p + 1; None draws
     them on the device from (seed, step).  Refused models (parity, complex RNN, 2D RNN, LSTM, stacked layers) raise ValueError
     with the library's reason."""
-    nat = _native(wf)
-    if samples is not None:
-        samples = np.asarray(samples).reshape(2 * int(numpairs), nat.N)
-    out = nat.renyi2_regions(regions, int(numpairs), samples=samples, seed=seed, step=step)
-    return renyi2_from_sums(out["sums"], numpairs)
+    return _api.renyi2_regions(_api.GRU, _native(wf), regions, numpairs, seed, step, samples)
 
 
 def mutual_information2_from_log_ratios(lr_a, lr_b, lr_ab):
@@ -143,11 +140,7 @@ def renyi2_mutual_information(wf, region_a, region_b, numpairs, seed=111, step=0
     error (mutual_information2_from_log_ratios), from `numpairs` pairs; A, B and A u B run in one call on the same pairs.
     samples, seed, step and the refused models as renyi2_regions."""
     a, b = _disjoint_masks(region_a, region_b)
-    nat = _native(wf)
-    if samples is not None:
-        samples = np.asarray(samples).reshape(2 * int(numpairs), nat.N)
-    out = nat.renyi2_regions(np.stack([a, b, a | b]), int(numpairs), samples=samples, seed=seed, step=step, log_ratio=True)
-    return mutual_information2_from_log_ratios(*out["log_ratio"])
+    return _api.renyi2_mutual_information(_api.GRU, _native(wf), a, b, numpairs, seed, step, samples)
 
 
 def correlations_from_sums(z_sums, zz_sums, x_sums, xx_sums, numsamples):
@@ -364,32 +357,10 @@ def pauli_expectations(wf, strings, numsamples, seed=111, step=0, samples=None):
     string with an odd number of Y has expectation exactly 0 in the real state psi = sqrt(P): 0 +- 0, without device work.  samples:
     (numsamples, N) spins; None draws them on the device from (seed, step).  Refused models (parity, complex RNN, 2D RNN, LSTM,
     stacked layers) raise ValueError with the library's reason."""
-    nat = _native(wf)
-    flip, sign, factor = pauli_terms(strings, nat.N)
-    value, err = np.zeros(len(factor)), np.zeros(len(factor))
-    real = np.flatnonzero(factor.imag == 0.0)
-    if real.size:
-        if samples is not None:
-            samples = np.asarray(samples).reshape(int(numsamples), nat.N)
-        out = nat.pauli_step(flip[real], sign[real], np.ones(real.size), int(numsamples), samples=samples, seed=seed, step=step)
-        mean, e = pauli_from_sums(out["term_sums"], numsamples)
-        value[real], err[real] = factor.real[real] * mean, e
-    return {"value": value, "err": err}
+    return _api.pauli_expectations(_api.GRU, _native(wf), strings, numsamples, seed, step, samples)
 
 
 def energy(wf, ham, numsamples, seed=111, step=0, samples=None, want_eloc=False):
     """Energy of `wf` under the Hamiltonian `ham` from `numsamples` samples: {"mean", "var" (population variance of E_loc), "err"
     (sqrt(var / n)), "eloc" (numsamples,) when want_eloc}.  samples, seed, step and the refused models as pauli_expectations."""
-    nat = _native(wf)
-    if ham.N != nat.N:
-        raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, nat.N))
-    if samples is not None:
-        samples = np.asarray(samples).reshape(int(numsamples), nat.N)
-    out = nat.pauli_step(ham.flip, ham.sign, ham.coeff, int(numsamples), samples=samples, seed=seed, step=step, want_eloc=want_eloc)
-    m = out["moments"]
-    mean = m[0] / m[2]
-    var = max(m[1] / m[2] - mean * mean, 0.0)
-    res = {"mean": mean, "var": var, "err": float(np.sqrt(var / m[2]))}
-    if want_eloc:
-        res["eloc"] = out["eloc"]
-    return res
+    return _api.energy(_api.GRU, _native(wf), ham, numsamples, seed, step, samples, want_eloc)

@@ -16,6 +16,7 @@ TFIM2D_2DRNN.RNNwavefunction facade or a NativeWavefunction of model MDRNN2D and
 import numpy as np
 
 from . import _lib
+from . import _observable_api as _api
 from .observables import (Hamiltonian, _disjoint_masks, _native, group_by_mask, mutual_information2_from_log_ratios,  # noqa: F401
                           pauli_from_sums, pauli_terms, renyi2_from_sums, tfim_hamiltonian)
 
@@ -53,43 +54,19 @@ def _native_2d(wf):
     return nat
 
 
-def _samples_2d(nat, samples, numsamples):
-    return None if samples is None else np.asarray(samples).reshape(int(numsamples), nat.nx, nat.ny)
-
-
 def pauli_expectations(wf, strings, numsamples, seed=111, step=0, samples=None):
     """<psi|P|psi> of every Pauli string P of `strings` (dense "XZIY..." over the lattice index, or sparse [("X", k), ...]) with its
     standard error, from `numsamples` samples: {"value": (K,), "err": (K,)}.  A string with an odd number of Y has expectation exactly
     0 in the real state psi = sqrt(P): 0 +- 0, without device work.  samples: (numsamples, Nx, Ny) or (numsamples, Nx * Ny) spins;
     None draws them on the device from (seed, step)."""
-    nat = _native_2d(wf)
-    flip, sign, factor = pauli_terms(strings, nat.N)
-    value, err = np.zeros(len(factor)), np.zeros(len(factor))
-    real = np.flatnonzero(factor.imag == 0.0)
-    if real.size:
-        out = nat.pauli_step_2d(flip[real], sign[real], np.ones(real.size), int(numsamples), samples=_samples_2d(nat, samples, numsamples),
-                                seed=seed, step=step)
-        mean, e = pauli_from_sums(out["term_sums"], numsamples)
-        value[real], err[real] = factor.real[real] * mean, e
-    return {"value": value, "err": err}
+    return _api.pauli_expectations(_api.LATTICE, _native_2d(wf), strings, numsamples, seed, step, samples)
 
 
 def energy(wf, ham, numsamples, seed=111, step=0, samples=None, want_eloc=False):
     """Energy of `wf` under the Hamiltonian `ham` (sites = lattice indices) from `numsamples` samples: {"mean", "var" (population
     variance of E_loc), "err" (sqrt(var / n)), "eloc" (numsamples,) when want_eloc}.  A batch that fits one pass stays resident:
     vmc_gradient then differentiates the VMC cost of this Hamiltonian."""
-    nat = _native_2d(wf)
-    if ham.N != nat.N:
-        raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, nat.N))
-    out = nat.pauli_step_2d(ham.flip, ham.sign, ham.coeff, int(numsamples), samples=_samples_2d(nat, samples, numsamples), seed=seed,
-                            step=step, want_eloc=want_eloc)
-    m = out["moments"]
-    mean = m[0] / m[2]
-    var = max(m[1] / m[2] - mean * mean, 0.0)
-    res = {"mean": mean, "var": var, "err": float(np.sqrt(var / m[2]))}
-    if want_eloc:
-        res["eloc"] = out["eloc"]
-    return res
+    return _api.energy(_api.LATTICE, _native_2d(wf), ham, numsamples, seed, step, samples, want_eloc)
 
 
 def minimize_hamiltonian(wf, ham, params, numsteps=1000, numsamples=500, learningrate=5e-3, seed=111, scope="RNNwavefunction",
@@ -102,35 +79,8 @@ def minimize_hamiltonian(wf, ham, params, numsteps=1000, numsamples=500, learnin
     device_steps=K (an integer >= 1): the same iterations run on the device in chunks of at most K with one host synchronisation
     each (NativeWavefunction.pauli_train_steps_2d, docs/pauli_train.md) - the same energies, variances and parameters, bit for bit.
     The device runs Adam from a fresh state: opt= is refused with it."""
-    from . import training as T
-    device_steps = T.check_device_steps(device_steps, opt, "observables_2d.minimize_hamiltonian")
-    if comm is not None:
-        raise ValueError("minimize_hamiltonian runs in one process on one GPU: no communicator (comm=%r)" % (comm,))
-    nat = _native_2d(wf)
-    if ham.N != nat.N:
-        raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, nat.N))
-    opt = opt or T.Adam()
-    params = {k: np.array(v) for k, v in params.items()}
-    nat.set_params(params, scope=scope)
-    if device_steps:
-        nat.adam_set_state(None, None, 0)
-        meanEnergy, varEnergy = T.hamiltonian_steps_on_device(nat.pauli_train_steps_2d, ham, numsteps, numsamples, learningrate, seed,
-                                                              device_steps, verbose, lambda s1, si, n: s1 / n)
-        minimize_hamiltonian.last_params = nat.get_params_dict(params, scope)
-        return meanEnergy, varEnergy
-    meanEnergy, varEnergy = [], []
-    for it in range(numsteps + 1):
-        s1, s2, n, _ = nat.pauli_step_2d(ham.flip, ham.sign, ham.coeff, numsamples, seed=seed, step=it)["moments"]
-        meanE = s1 / n
-        varE = s2 / n - meanE ** 2
-        meanEnergy.append(meanE)
-        varEnergy.append(varE)
-        if verbose and it % 10 == 0:
-            print("mean(E): {0}, var(E): {1}, #samples {2}, #Step {3} \n\n".format(meanE, varE, numsamples, it))
-        grads = T.cost_gradient(nat, params, scope, meanE, n)
-        params = opt.step(params, grads, learningrate)
-        nat.set_params(params, scope=scope)
-    minimize_hamiltonian.last_params = params
+    meanEnergy, varEnergy, minimize_hamiltonian.last_params = _api.minimize_family(
+        _api.LATTICE, _native_2d, wf, ham, params, numsteps, numsamples, learningrate, seed, scope, opt, comm, verbose, device_steps)
     return meanEnergy, varEnergy
 
 
@@ -145,40 +95,7 @@ def correlations(wf, numsamples, pairs=None, seed=111, step=0, samples=None):
     per-sample values s_k, r_k = exp(log r_k), s_a s_b, r_ab, which the call returns as log-ratios and samples - not the cross-moment
     formulas of observables.correlations_from_sums.  Connected parts to first order (delta method): the std / sqrt(n) of
     g = s_a s_b - z_b s_a - z_a s_b and of g = r_ab - x_b r_a - x_a r_b."""
-    nat = _native_2d(wf)
-    N, n = nat.N, int(numsamples)
-    if pairs is None:
-        c = site(nat.nx, nat.ny, nat.nx // 2, nat.ny // 2)
-        pairs = [(c, k) for k in range(N) if k != c]
-    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    if np.any(pairs < 0) or np.any(pairs >= N) or np.any(pairs[:, 0] == pairs[:, 1]):
-        raise ValueError("pairs must name two distinct lattice sites in 0..%d each" % (N - 1))
-    npair = len(pairs)
-    flip = np.zeros((N + npair, N), dtype=np.int32)
-    flip[np.arange(N), np.arange(N)] = 1
-    for k, (a, b) in enumerate(pairs):
-        flip[N + k, [a, b]] = 1
-    out = nat.pauli_step_2d(flip, np.zeros_like(flip), np.ones(len(flip)), n, samples=_samples_2d(nat, samples, n), seed=seed, step=step,
-                            want_log_ratio=True, want_samples=True)
-    _, index = group_by_mask(flip)                       # (a, b) and (b, a) share a row
-    r = np.exp(out["log_ratio"])[index]                  # (N + P, n)
-    s = 2.0 * out["samples"].reshape(n, N).T - 1.0       # (N, n)
-
-    def stats(v):
-        return v.mean(axis=-1), v.std(axis=-1) / np.sqrt(n)
-
-    a, b = pairs[:, 0], pairs[:, 1]
-    res = {"pairs": pairs}
-    res["z"], res["z_err"] = stats(s)
-    res["x"], res["x_err"] = stats(r[:N])
-    res["zz"], res["zz_err"] = stats(s[a] * s[b])
-    res["xx"], res["xx_err"] = stats(r[N:])
-    z, x = res["z"], res["x"]
-    res["zz_c"] = res["zz"] - z[a] * z[b]
-    res["xx_c"] = res["xx"] - x[a] * x[b]
-    res["zz_c_err"] = stats(s[a] * s[b] - z[b][:, None] * s[a] - z[a][:, None] * s[b])[1]
-    res["xx_c_err"] = stats(r[N:] - x[b][:, None] * r[a] - x[a][:, None] * r[b])[1]
-    return res
+    return _api.correlations(_api.LATTICE, _native_2d(wf), numsamples, pairs, seed, step, samples)
 
 
 def rectangle_region(Nx, Ny, x0, x1, y0, y1):
@@ -209,18 +126,12 @@ def column_cut_regions(Nx, Ny):
     return np.stack([rectangle_region(Nx, Ny, 0, c, 0, Ny) for c in range(1, Nx)])
 
 
-def _pairs_2d(nat, samples, numpairs):
-    return None if samples is None else np.asarray(samples).reshape(2 * int(numpairs), nat.nx, nat.ny)
-
-
 def renyi2_regions(wf, regions, numpairs, seed=111, step=0, samples=None):
     """Second Renyi entropy S2(A) (R,) and its standard error (R,) (observables.renyi2_from_sums) of the regions `regions`: (R, Nx Ny)
     masks of 0 / 1 over the lattice index, (R, Nx, Ny), or one mask of Nx Ny entries; 1 = site in A.  From `numpairs` pairs of
     independent samples; samples: (2 numpairs, Nx, Ny) or (2 numpairs, Nx Ny) spins, pair p = rows 2p and 2p + 1; None draws them on
     the device from (seed, step)."""
-    nat = _native_2d(wf)
-    out = nat.renyi2_regions_2d(regions, int(numpairs), samples=_pairs_2d(nat, samples, numpairs), seed=seed, step=step)
-    return renyi2_from_sums(out["sums"], numpairs)
+    return _api.renyi2_regions(_api.LATTICE, _native_2d(wf), regions, numpairs, seed, step, samples)
 
 
 def renyi2_mutual_information(wf, region_a, region_b, numpairs, seed=111, step=0, samples=None):
@@ -229,7 +140,4 @@ def renyi2_mutual_information(wf, region_a, region_b, numpairs, seed=111, step=0
     `numpairs` pairs; A, B and A u B run in one call on the same pairs.  Overlapping regions raise ValueError before the wave function
     is touched."""
     a, b = _disjoint_masks(np.asarray(region_a).reshape(-1), np.asarray(region_b).reshape(-1))
-    nat = _native_2d(wf)
-    out = nat.renyi2_regions_2d(np.stack([a, b, a | b]), int(numpairs), samples=_pairs_2d(nat, samples, numpairs), seed=seed, step=step,
-                                log_ratio=True)
-    return mutual_information2_from_log_ratios(*out["log_ratio"])
+    return _api.renyi2_mutual_information(_api.LATTICE, _native_2d(wf), a, b, numpairs, seed, step, samples)

@@ -19,6 +19,7 @@ import warnings
 import numpy as np
 
 from . import _lib
+from . import _observable_api as _api
 from .observables import _disjoint_masks, _native, group_by_mask, mutual_information2_from_values, pauli_terms
 
 __all__ = ["ComplexHamiltonian", "pauli_expectations", "energy", "j1j2_hamiltonian", "spin_correlation_terms", "spin_correlations",
@@ -35,10 +36,6 @@ def _native_complex(wf):
         raise ValueError("observables_complex serves the complex RNN (CRNN_U1) only; observables.py serves the GRU models, "
                          "observables_2d.py the 2D RNN")
     return nat
-
-
-def _samples(nat, samples, numsamples):
-    return None if samples is None else np.asarray(samples).reshape(int(numsamples), nat.N)
 
 
 class ComplexHamiltonian:
@@ -86,8 +83,8 @@ def pauli_expectations(wf, strings, numsamples, seed=111, step=0, samples=None):
     them on the device from (seed, step)."""
     nat = _native_complex(wf)
     flip, sign, factor = pauli_terms(strings, nat.N)
-    out = nat.pauli_step_complex(flip, sign, np.ones(len(factor)), int(numsamples), samples=_samples(nat, samples, numsamples), seed=seed,
-                                 step=step)
+    out = nat.pauli_step_complex(flip, sign, np.ones(len(factor)), int(numsamples), samples=_api.chains(_api.COMPLEX, nat, samples, numsamples),
+                                 seed=seed, step=step)
     mean, e_re, e_im = _from_sums(out["term_sums"], numsamples)
     # factor is one of 1, -i, -1, i: it rotates the value and, where imaginary, exchanges the two errors
     swap = factor.imag != 0.0
@@ -99,12 +96,10 @@ def energy(wf, ham, numsamples, seed=111, step=0, samples=None, want_eloc=False)
     of Re E_loc), "err" (sqrt(var / n)), "eloc" (numsamples,) complex64 when want_eloc}.  Warns when `ham` is not Hermitian.  A batch
     that fits one pass stays resident: vmc_gradient(mean, n) then differentiates the complex VMC cost of this Hamiltonian."""
     nat = _native_complex(wf)
-    if ham.N != nat.N:
-        raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, nat.N))
+    _api.check_sites(nat, ham)
     if not ham.is_hermitian():
         warnings.warn("energy: the Hamiltonian is not Hermitian; its expectation value is complex", stacklevel=2)
-    out = nat.pauli_step_complex(ham.flip, ham.sign, ham.coeff, int(numsamples), samples=_samples(nat, samples, numsamples), seed=seed,
-                                 step=step, want_eloc=want_eloc)
+    out = _api.local_energies(_api.COMPLEX, nat, ham, numsamples, seed, step, samples, want_eloc)
     m = out["moments"]
     re = m[0] / m[2]
     var = max(m[1] / m[2] - re * re, 0.0)
@@ -158,8 +153,8 @@ def spin_correlations(wf, numsamples, seed=111, step=0, samples=None):
     N, n = nat.N, int(numsamples)
     pairs, strings = spin_correlation_terms(N)
     flip, sign, factor = pauli_terms(strings, N)
-    out = nat.pauli_step_complex(flip, sign, 0.25 * factor, n, samples=_samples(nat, samples, n), seed=seed, step=step, want_log_ratio=True,
-                                 want_samples=True)
+    out = nat.pauli_step_complex(flip, sign, 0.25 * factor, n, samples=_api.chains(_api.COMPLEX, nat, samples, n), seed=seed, step=step,
+                                 want_log_ratio=True, want_samples=True)
     _, index = group_by_mask(flip)
     lr = out["log_ratio"]
     with np.errstate(invalid="ignore"):
@@ -199,40 +194,18 @@ def minimize_hamiltonian(wf, ham, numsamples, steps, lr, params=None, seed=111, 
     device_steps=K (an integer >= 1): the same iterations run on the device in chunks of at most K with one host synchronisation
     each (pauli_train_steps_complex, docs/pauli_train.md) - the same energies, variances and parameters, bit for bit.  The device
     runs Adam from a fresh state: opt= is refused with it."""
-    from .training import Adam, check_device_steps, cost_gradient, hamiltonian_steps_on_device
-    device_steps = check_device_steps(device_steps, opt, "minimize_hamiltonian")
+    from .training import check_device_steps
+    device_steps = check_device_steps(device_steps, opt, _api.COMPLEX.label)
     nat = _native_complex(wf)
-    if ham.N != nat.N:
-        raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, nat.N))
+    _api.check_sites(nat, ham)
     facade = wf if wf is not nat else None
     if facade is not None:
         params, scope = facade.get_params(), facade.scope
     if params is None:
         raise ValueError("minimize_hamiltonian on a NativeWavefunction needs its parameters (params=...)")
-    opt = opt or Adam()
-    params = {k: np.array(v) for k, v in params.items()}
-    nat.set_params(params, scope=scope)
-    if device_steps:
-        nat.adam_set_state(None, None, 0)
-        meanEnergy, varEnergy = hamiltonian_steps_on_device(nat.pauli_train_steps_complex, ham, steps, numsamples, lr, seed, device_steps,
-                                                            verbose, lambda s1, si, n: complex(s1 / n, si / n))
-        params = nat.get_params_dict(params, scope)
-        if facade is not None:
-            facade.set_params(params)
-        minimize_hamiltonian.last_params = params
-        return meanEnergy, varEnergy
-    meanEnergy, varEnergy = [], []
-    for it in range(int(steps) + 1):
-        s1, s2, n, si = nat.pauli_step_complex(ham.flip, ham.sign, ham.coeff, int(numsamples), seed=seed, step=it)["moments"]
-        meanE = complex(s1 / n, si / n)
-        varE = s2 / n - (s1 / n) ** 2
-        meanEnergy.append(meanE)
-        varEnergy.append(varE)
-        if verbose and it % 10 == 0:
-            print("mean(E): {0}, var(E): {1}, #samples {2}, #Step {3} \n\n".format(meanE, varE, numsamples, it))
-        grads = cost_gradient(nat, params, scope, meanE, n)
-        params = opt.step(params, grads, lr)
-        nat.set_params(params, scope=scope)
+    meanEnergy, varEnergy, params = _api.minimize_loop(nat.pauli_step_complex, nat.pauli_train_steps_complex,
+                                                       lambda s1, si, n: complex(s1 / n, si / n), nat, ham, params, scope, int(steps),
+                                                       int(numsamples), lr, seed, opt, device_steps, verbose)
     if facade is not None:
         facade.set_params(params)
     minimize_hamiltonian.last_params = params
@@ -261,10 +234,6 @@ def renyi2_from_sums(sums, numpairs):
     return {"S2": S2, "err": err, "imag": im, "err_imag": np.sqrt(var_im / n)}
 
 
-def _pairs(nat, samples, numpairs):
-    return None if samples is None else np.asarray(samples).reshape(2 * int(numpairs), nat.N)
-
-
 def renyi2_regions(wf, regions, numpairs, seed=111, step=0, samples=None, want_log_ratio=False):
     """Second Renyi entropy S2(A) of the regions `regions` ((R, N) masks of 0 / 1, or one mask; observables.interval_region builds
     them) from `numpairs` pairs of independent samples of the complex RNN `wf`: the dict of renyi2_from_sums plus "survivors" (R,),
@@ -272,8 +241,7 @@ def renyi2_regions(wf, regions, numpairs, seed=111, step=0, samples=None, want_l
     want_log_ratio, "log_ratio" (R, numpairs) complex128 (-inf + 0j outside the sector) and "samples" (2 numpairs, N).  samples:
     (2 numpairs, N) spins of the sector, pair p = rows 2p and 2p + 1; None draws them on the device from (seed, step)."""
     nat = _native_complex(wf)
-    s = _pairs(nat, samples, numpairs)
-    out = nat.renyi2_regions_complex(regions, int(numpairs), samples=s, seed=seed, step=step, log_ratio=want_log_ratio)
+    out, s = _api.regions(_api.COMPLEX, nat, regions, numpairs, seed, step, samples, log_ratio=want_log_ratio)
     res = renyi2_from_sums(out["sums"], numpairs)
     res["survivors"] = out["in_sector"] / float(numpairs)
     if want_log_ratio:
@@ -294,10 +262,8 @@ def renyi2_mutual_information(wf, region_a, region_b, numpairs, seed=111, step=0
     error by the delta method on the shared pairs (observables.mutual_information2_from_values on Re r); A, B and A u B run in one
     call.  Overlapping regions raise ValueError."""
     a, b = _disjoint_masks(region_a, region_b)
-    nat = _native_complex(wf)
-    out = nat.renyi2_regions_complex(np.stack([a, b, a | b]), int(numpairs), samples=_pairs(nat, samples, numpairs), seed=seed, step=step,
-                                     log_ratio=True)
-    return mutual_information2_from_values(*_ratio(out["log_ratio"]).real)
+    log_ratio = _api.mutual_log_ratios(_api.COMPLEX, _native_complex(wf), a, b, numpairs, seed, step, samples)
+    return mutual_information2_from_values(*_ratio(log_ratio).real)
 
 
 def _ratio(log_ratio):

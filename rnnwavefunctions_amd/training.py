@@ -424,31 +424,7 @@ def minimize_hamiltonian(wf, ham, params, numsteps=1000, numsamples=500, learnin
     device_steps=K (an integer >= 1): the same iterations run on the device in chunks of at most K with one host synchronisation
     each (wf.pauli_train_steps, docs/pauli_train.md) - the same energies, variances and parameters, bit for bit.  The device runs
     Adam from a fresh state: opt= is refused with it."""
-    device_steps = check_device_steps(device_steps, opt, "minimize_hamiltonian")
-    if comm is not None:
-        raise ValueError("minimize_hamiltonian runs in one process on one GPU: no communicator (comm=%r)" % (comm,))
-    if ham.N != wf.N:
-        raise ValueError("the Hamiltonian has %d sites, the wave function %d" % (ham.N, wf.N))
-    opt = opt or Adam()
-    params = {k: np.array(v) for k, v in params.items()}
-    wf.set_params(params, scope=scope)
-    if device_steps:
-        wf.adam_set_state(None, None, 0)
-        meanEnergy, varEnergy = hamiltonian_steps_on_device(wf.pauli_train_steps, ham, numsteps, numsamples, learningrate, seed,
-                                                            device_steps, verbose, lambda s1, si, n: s1 / n)
-        minimize_hamiltonian.last_params = wf.get_params_dict(params, scope)
-        return meanEnergy, varEnergy
-    meanEnergy, varEnergy = [], []
-    for it in range(numsteps + 1):
-        s1, s2, n, _ = wf.pauli_step(ham.flip, ham.sign, ham.coeff, numsamples, seed=seed, step=it)["moments"]
-        meanE = s1 / n
-        varE = s2 / n - meanE ** 2
-        meanEnergy.append(meanE)
-        varEnergy.append(varE)
-        if verbose and it % 10 == 0:
-            print("mean(E): {0}, var(E): {1}, #samples {2}, #Step {3} \n\n".format(meanE, varE, numsamples, it))
-        grads = cost_gradient(wf, params, scope, meanE, n)
-        params = opt.step(params, grads, learningrate)
-        wf.set_params(params, scope=scope)
-    minimize_hamiltonian.last_params = params
+    from . import _observable_api as _api
+    meanEnergy, varEnergy, minimize_hamiltonian.last_params = _api.minimize_family(
+        _api.GRU, lambda native: native, wf, ham, params, numsteps, numsamples, learningrate, seed, scope, opt, comm, verbose, device_steps)
     return meanEnergy, varEnergy
