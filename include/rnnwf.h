@@ -198,6 +198,12 @@ int rnnwf_get_grad(rnnwf_handle* h, const char* tf_name, void* data, int64_t cou
 /* One call per training iteration instead of one per tensor: every tensor in the reference's shapes, float64, concatenated in
  * the byte-wise order of the names (rnnwf_param_name(h, i, &count) lists them).  rnnwf_set_params_flat commits. */
 int rnnwf_set_params_flat(rnnwf_handle* h, const double* flat, int64_t count);
+/* Host only - needs no device and no handle: the two forms of the bf16x3 flip-pass image of a one-layer positive GRU of `units`
+ * hidden units (37..50: the ping-pong kernel's class) with the parameters `flat` (order of rnnwf_set_params_flat), as the packer
+ * builds them - img_h the form in h, img_g the form the kernel reads, whose state travels as g = (h + 1) / 2 - `cap` bytes each,
+ * and layout[10] = {NT, NQ, NUP, NOUT, OFF_ASP, OFF_CI, OFF_XC, OFF_WD, OFF_BD, BYTES} (csrc/pack_split.h: GstateLayout).  For tests
+ * of the packer on machines without a GPU.  Errors through rnnwf_last_error(NULL). */
+int rnnwf_host_split_images(int32_t units, const double* flat, int64_t count, void* img_h, void* img_g, int64_t cap, int32_t* layout);
 int rnnwf_get_grads_flat(rnnwf_handle* h, double* flat, int64_t count);
 const char* rnnwf_param_name(const rnnwf_handle* h, int32_t i, int64_t* count);
 int rnnwf_allreduce_grads(rnnwf_handle* h);

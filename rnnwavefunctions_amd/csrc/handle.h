@@ -117,6 +117,8 @@ struct rnnwf_handle {
     rnnwf::DevBuf gradDX[2];      // stacked layers: dL/dx of one layer's pass = dL/dh input of the pass below
     // bf16x3 engine (split_core.h): second weight image; engine_split = use it for the flip pass
     rnnwf::DevBuf wsplit;
+    rnnwf::DevBuf wsplit_g;       // positive RNN, one layer, 37..50 units: the g-state form of wsplit, which the ping-pong flip kernel reads
+                                  // (pack_split.h: gstate_word; rebuilt from wsplit wherever wsplit is)
     rnnwf::DevBuf wsplit16;       // image of the 16x16x32 form of the flip pass at 69..100 units (split16_core.h)
     rnnwf::DevBuf wbasebf;        // bf16x3 A fragments of the cooperative base pass (layout.h: BaseBfLayout); valid iff base_bf
     rnnwf::DevBuf wsplit_up[RNNWF_MAX_LAYERS - 1];   // stacked layers on the bf16x3 engine: image of layer l in [l - 1] (split_core.h: SplitUpperLayout)

@@ -109,7 +109,7 @@ struct PrnnArgs;
 struct CrnnArgs;
 int prnn_split_flip(rnnwf_handle* h, const PrnnArgs& a);
 double prnn_split_flops_per_step(rnnwf_handle* h);      // MFMA flops issued per 32-chain wave-step
-int prnn_split_pack(rnnwf_handle* h, std::vector<char>& simg);
+int prnn_split_pack(rnnwf_handle* h, std::vector<char>& simg, std::vector<char>& simg_g);   // simg_g: the g-state form (pack_split.h), empty: none at this width
 // split_stream.hip: the same pass at 53..100 units (the riders form; above 68 units the w3 fragments are read through L2)
 int prnn_split_flip_stream(rnnwf_handle* h, const PrnnArgs& a, int kt16);
 double prnn_split_stream_flops_per_step(rnnwf_handle* h);
@@ -150,6 +150,8 @@ int crnn_base_coop_bf(rnnwf_handle* h, const CrnnArgs& a);
 // device-resident training (train.hip): the tables of the engine's images over Lin into the active PackTrace, from the rows of
 // shapes.h their host packers take - h->wsplit of one layer; of a stack, layer 0 -> h->wsplit, l >= 1 -> h->wsplit_up[l - 1]; h->wbasebf
 int split_pack_table(rnnwf_handle* h);
+bool prnn_split_gstate_layout(const rnnwf_handle* h, int32_t* layout10);   // the ten fields of pack_split.h: GstateLayout; false: no g-state image at this width
+int split_gstate_refold(rnnwf_handle* h);      // behind a re-pack of h->wsplit: h->wsplit_g from it, on the stream (no-op without that image)
 int stack_pack_table(rnnwf_handle* h, int layer);
 int base_bf_pack_table(rnnwf_handle* h);
 

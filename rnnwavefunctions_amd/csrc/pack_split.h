@@ -268,6 +268,80 @@ std::vector<char> pack_split_image(const rnnwf_handle* h) {
     return img;
 }
 
+// ---- the g-state form of the MODE 2 image (split_pp.h: SplitPP<.., GSTATE>) ------------------------------------------------------
+// The ping-pong step that carries g = (h + 1) / 2 instead of h reads a second variant of the image.  With h = 2 g - 1 a row's
+// pre-activation b + sum_j W_j h_j is (b - sum_j W_j) + sum_j (2 W_j) g_j, so
+//   * every weight that multiplies the state is doubled - all bf16 parts of the K entries of the r, u, q and head rows (regular and
+//     special fragments) and the VALU head's table OFF_WD; doubling is exact in every part;
+//   * every constant such a row starts from - the table OFF_CI that preload reads, the VALU head's OFF_BD - is less the row's weight
+//     sum: float64, over the f32 weights w1 + w2 + w3 the image holds, in the order of the image, rounded to f32 once;
+//   * OFF_XC (the candidate's input side) never meets the state and stays.
+// The variant is a function of the h image alone, word by word (gstate_word), so the host packer and device-resident training
+// (split.hip: split_gstate_refold, behind train.hip's re-pack of the h image) run the same code and agree bit for bit; a sum over a
+// weight row is nothing an element table (pack_value.h: Lin) could hold.
+// Padded units (widths below 50) need no case: their weight columns, rows and constants are zero in the h image, so they add
+// nothing to a sum, and their own pre-activations stay 0 - then t = u = 0.5 and g' = t + u (g - t) keeps the g = 0.5 such a unit
+// enters with (h = 0 in the checkpoint); whatever it held would feed nothing.
+struct GstateLayout {
+    int NT, NQ, NUP, NOUT;
+    uint32_t OFF_ASP, OFF_CI, OFF_XC, OFF_WD, OFF_BD, BYTES;
+};
+template <class L>
+constexpr GstateLayout gstate_layout() {
+    static_assert(L::MODE == 2 && L::OFF_A == 0, "the g-state form exists for the K-packed layout of the ping-pong kernels");
+    return {L::NT, L::NQ, L::NUP, L::NOUT, (uint32_t)L::OFF_ASP, (uint32_t)L::OFF_CI, (uint32_t)L::OFF_XC, (uint32_t)L::OFF_WD, (uint32_t)L::OFF_BD,
+            (uint32_t)L::BYTES};
+}
+__host__ __device__ inline float gstate_bf16(uint16_t b) {
+    union { uint32_t u; float f; } x;
+    x.u = (uint32_t)b << 16;
+    return x.f;
+}
+__host__ __device__ inline uint32_t gstate_bits(float f) {
+    union { uint32_t u; float f; } x;
+    x.f = f;
+    return x.u;
+}
+// 32-bit word w of the g-state image, from the h image `img`
+__host__ __device__ inline uint32_t gstate_word(const GstateLayout& g, const char* img, uint32_t w) {
+    const uint32_t off = 4 * w, in = reinterpret_cast<const uint32_t*>(img)[w];
+    const uint16_t* A = reinterpret_cast<const uint16_t*>(img);
+    if (off < g.OFF_CI) {                                      // two bf16 weight parts, each doubled (x + x: exact, a bf16 again)
+        const float lo = gstate_bf16((uint16_t)(in & 0xffffu)), hi = gstate_bf16((uint16_t)(in >> 16));
+        return (gstate_bits(lo + lo) >> 16) | (gstate_bits(hi + hi) & 0xffff0000u);
+    }
+    if (off < g.OFF_XC) {                                      // CI[sigma][T][hh_row][rho]: less the weight sum of row (T, r32)
+        const int i = (int)((off - g.OFF_CI) / 4), rho = i & 15, hh_row = (i >> 4) & 1, T = (i >> 5) % g.NT;
+        const int r32 = (rho & 3) | (hh_row << 2) | ((rho >> 2) << 3);
+        double sum = 0.0;
+        for (int hhk = 0; hhk < 2; ++hhk) {
+            const int lane = 32 * hhk + r32;
+            for (int x = 0; x < g.NQ; ++x)
+                for (int jj = 0; jj < 8; ++jj) {
+                    float wv = 0.0f;                           // w3 + w2 + w1: exact, the split was
+                    for (int a = 2; a >= 0; --a) wv += gstate_bf16(A[((((size_t)T * 3 + a) * g.NQ + x) * 64 + lane) * 8 + jj]);
+                    sum += (double)wv;
+                }
+            const uint16_t* sp = A + g.OFF_ASP / 2 + ((size_t)T * 64 + lane) * 8;      // special unit: entries {w1, w1, w1, w2, w2, w3}
+            sum += (double)((gstate_bf16(sp[5]) + gstate_bf16(sp[3])) + gstate_bf16(sp[0]));
+        }
+        return gstate_bits((float)((double)reinterpret_cast<const float*>(img)[w] - sum));
+    }
+    if (off < g.OFF_WD) return in;                             // XC
+    const float* WD = reinterpret_cast<const float*>(img + g.OFF_WD);
+    if (off < g.OFF_BD) { const float v = reinterpret_cast<const float*>(img)[w]; return gstate_bits(v + v); }
+    const int o = (int)((off - g.OFF_BD) / 4);
+    if (o >= g.NOUT) return in;
+    double sum = 0.0;
+    for (int e = 0; e < 2 * g.NUP; ++e) sum += (double)WD[(size_t)e * g.NOUT + o];
+    return gstate_bits((float)((double)reinterpret_cast<const float*>(img)[w] - sum));
+}
+inline std::vector<char> gstate_image(const GstateLayout& g, const std::vector<char>& img) {
+    std::vector<char> out(img.size());
+    for (uint32_t w = 0; w < g.BYTES / 4; ++w) reinterpret_cast<uint32_t*>(out.data())[w] = gstate_word(g, img.data(), w);
+    return out;
+}
+
 // Image of GRU layer `layer` >= 1 on the bf16x3 engine (split_core.h: SplitUpperLayout): the X block (input = state of the layer
 // below) and the H block, each laid out as the MODE 2 image of the first layer, the biases as accumulator start values, and - for
 // the top layer - the head rows in the H block's spare mixed-tile slots plus the VALU head's tables.

@@ -231,10 +231,14 @@ int pack_image(rnnwf_handle* h, std::vector<char>& img) {
     if (h->engine_split && h->NL > 1) {
         if (int rc = stack_pack<1>(h)) return rc;
     } else if (h->engine_split) {
-        std::vector<char> simg;
-        if (int rc = prnn_split_pack(h, simg)) return rc;
+        std::vector<char> simg, simg_g;
+        if (int rc = prnn_split_pack(h, simg, simg_g)) return rc;
         if (int rc = ensure(h, h->wsplit, simg.size())) return rc;
         if (int rc = upload(h, h->wsplit.p, simg.data(), simg.size())) return rc;
+        if (!simg_g.empty()) {                                // 37..50 units: the ping-pong kernel's g-state form runs on its own image
+            if (int rc = ensure(h, h->wsplit_g, simg_g.size())) return rc;
+            if (int rc = upload(h, h->wsplit_g.p, simg_g.data(), simg_g.size())) return rc;
+        }
     }
     if (int rc = base_bf_pack(h)) return rc;
     return with_launch(h, [&](auto k) { img = decltype(k)::pack(h); }) ? 0 : no_kernel(h);

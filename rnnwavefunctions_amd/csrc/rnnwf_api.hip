@@ -246,7 +246,7 @@ extern "C" int rnnwf_destroy(rnnwf_handle* h) {
     rnnwf_comm_destroy(h);
     DevBuf* bufs[] = {&h->wimg, &h->samples_i32, &h->bits, &h->bits2, &h->hck, &h->lpq, &h->lpq2, &h->out_lp,
                       &h->out_lp2, &h->eloc, &h->moments, &h->coupl, &h->maps, &h->camp, &h->tiles,
-                      &h->tile_count, &h->cbase, &h->cout, &h->rowbuf, &h->wbwd, &h->gradP, &h->gradQ, &h->gradW, &h->gradPart, &h->gradHeadPart, &h->wsplit, &h->wsplit16, &h->wbasebf, &h->gradDX[0], &h->gradDX[1], &h->reduce_scratch, &h->renyi, &h->tck, &h->corr,
+                      &h->tile_count, &h->cbase, &h->cout, &h->rowbuf, &h->wbwd, &h->gradP, &h->gradQ, &h->gradW, &h->gradPart, &h->gradHeadPart, &h->wsplit, &h->wsplit_g, &h->wsplit16, &h->wbasebf, &h->gradDX[0], &h->gradDX[1], &h->reduce_scratch, &h->renyi, &h->tck, &h->corr,
                       &h->xrec[0], &h->xrec[1], &h->wsplit_up[0], &h->wsplit_up[1], &h->wsplit_up[2],
                       &h->train.P, &h->train.M, &h->train.V, &h->train.G, &h->train.gidx, &h->train.img[0].table, &h->train.img[1].table,
                       &h->train.img[2].table, &h->train.img[3].table, &h->train.img[4].table, &h->train.img[5].table, &h->train.img[6].table,
@@ -340,6 +340,39 @@ extern "C" int64_t rnnwf_num_params(const rnnwf_handle* h) {
     int64_t n = 0;
     if (h) for (auto& kv : h->params) n += (int64_t)kv.second.slot.size();
     return n;
+}
+
+// Host only, no device is touched: both forms of the bf16x3 flip-pass image of a one-layer positive GRU (rnnwf.h)
+extern "C" int rnnwf_host_split_images(int32_t units, const double* flat, int64_t count, void* img_h, void* img_g, int64_t cap, int32_t* layout) {
+    auto bad = [&](const std::string& m) {
+        g_create_error = "rnnwf_host_split_images: " + m;
+        return (int)RNNWF_ERR_INVALID;
+    };
+    if (!flat || !img_h || !img_g || !layout || units < 1) return bad("null or empty argument");
+    rnnwf_handle h;
+    h.cfg.model = h.model = RNNWF_MODEL_GRU1D;
+    h.cfg.nx = h.Nx = h.N = 2;
+    h.cfg.num_layers = 1;
+    h.cfg.units[0] = h.H = units;
+    h.family = gru_family();
+    h.NFULL = pick_nfull(units, false, false);
+    if (h.NFULL < 0) return bad("num_units too large");
+    declare_params(&h);
+    if (count != rnnwf_num_params(&h)) return bad("the model has " + std::to_string(rnnwf_num_params(&h)) + " parameters");
+    int64_t off = 0;
+    for (auto& kv : h.params) {
+        ParamSpec& p = kv.second;
+        for (size_t i = 0; i < p.slot.size(); ++i) p.value[p.slot[i]] = flat[off + (int64_t)i];
+        off += (int64_t)p.slot.size();
+        p.set = true;
+    }
+    std::vector<char> a, g;
+    if (prnn_split_pack(&h, a, g) != 0) return bad(h.err);
+    if (g.empty() || !prnn_split_gstate_layout(&h, layout)) return bad("this width has no g-state image (37..50 units)");
+    if ((int64_t)a.size() > cap) return bad("images of " + std::to_string(a.size()) + " bytes");
+    memcpy(img_h, a.data(), a.size());
+    memcpy(img_g, g.data(), g.size());
+    return RNNWF_OK;
 }
 
 extern "C" int rnnwf_init_params(rnnwf_handle* h, uint64_t seed) {

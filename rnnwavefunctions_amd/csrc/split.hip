@@ -5,6 +5,7 @@
 // serialise anyway, so half the VALU instructions is a straight gain: config 5 0.79 -> 0.86 of the f32 pipe).
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "crnn_split_kernels.h"
@@ -63,28 +64,35 @@ struct SLaunch {
         return launch_persistent(h, kTimerFlip, prnn_flip_split_kernel<NF32, RJ, WAVES, MODE>, WAVES * 64, L::LDS_BYTES, ntiles, WAVES, a,
                                  h->wsplit.p, kt16);
     }
-    // ping-pong form (8 waves per workgroup, two per SIMD, alternating MFMA / VALU segments): K-packed layouts only
+    // ping-pong form (8 waves per workgroup, two per SIMD, alternating MFMA / VALU segments): K-packed layouts only.  One layer runs
+    // the g-state form of the step on the g-state form of the image (h->wsplit_g; pack_split.h)
     static int flip_pp(rnnwf_handle* h, const PrnnArgs& a, int kt16) {
         if constexpr (MODE == 2) {
-            const auto kern = prnn_flip_pp_kernel<NF32, RJ>;
+            const auto kern = prnn_flip_pp_kernel<NF32, RJ, false, true>;
+            const void* img = h->wsplit_g.p;
             if (L::HP > 4 * kt16) return h->fail(RNNWF_ERR_INVALID, "bf16x3 layout wider than the checkpoint rows (%d > %d)", L::HP, 4 * kt16);
             const int64_t ntiles = (int64_t)(a.N - 1) * ((a.ns + 31) / 32);
             unsigned grid = 0;
             if (int rc = persistent_grid(h, kern, 512, L::BYTES, ntiles, 8, &grid)) return rc;
 #ifdef RNNWF_DIAGNOSTICS
             if (getenv("RNNWF_STAMPS")) {
-                return read_stamps(h, [&](unsigned long long* buf) { PrnnArgs b = a; b.stamps = buf; kern<<<grid, 512, L::BYTES, h->stream>>>(b, h->wsplit.p, kt16, StackArgs{}); },
+                return read_stamps(h, [&](unsigned long long* buf) { PrnnArgs b = a; b.stamps = buf; kern<<<grid, 512, L::BYTES, h->stream>>>(b, img, kt16, StackArgs{}); },
                                    (size_t)grid * 8, 16, "RNNWF_STAMPS", grid,
                                    {"mfma_seg", "barrier_after_mfma", "valu_seg_split_part", "barrier_after_valu", "tile_switch", "total_cycles",
                                     "realtime_ticks_100MHz", "iterations", "valu_seg_gates", "valu_seg_head_logsoftmax"});
             }
 #endif
-            return timed_launch(h, kTimerFlip, kern, grid, 512, L::BYTES, a, h->wsplit.p, kt16, StackArgs{});
+            return timed_launch(h, kTimerFlip, kern, grid, 512, L::BYTES, a, img, kt16, StackArgs{});
         } else {
             return flip(h, a, kt16);
         }
     }
     static std::vector<char> pack(const rnnwf_handle* h) { return pack_split_image<NF32, RJ, 1, MODE>(h); }
+    // the layout's g-state form (pack_split.h): false for a layout whose kernels have none
+    static bool gstate(GstateLayout* g) {
+        if constexpr (MODE == 2) { *g = gstate_layout<L>(); return true; }
+        else return false;
+    }
     static double mfma_flops_per_step() { return (double)L::NT * L::KS * 32768.0; }   // per 32-chain wave-step
 };
 
@@ -223,6 +231,35 @@ int rnnwf::split_pack_table(rnnwf_handle* h) {               // h->wsplit of one
     }) ? 0 : 1;
 }
 
+// the positive RNN's g-state image (h->wsplit_g) once more from h->wsplit as the re-pack kernel has just left it, on the stream: the
+// host packer's own fold (pack_split.h: gstate_word), one thread per word.  Nothing to do for a handle without that image.
+namespace {
+__global__ void gstate_refold_kernel(GstateLayout g, const char* __restrict__ img, uint32_t* __restrict__ out) {
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w < g.BYTES / 4) out[w] = gstate_word(g, img, w);
+}
+}  // namespace
+static bool gstate_of(const rnnwf_handle* h, GstateLayout* g) {
+    bool has = false;
+    if (h->model != RNNWF_MODEL_CRNN_U1 && h->NL == 1 && !riders(h)) with_layout<SLaunch>(h, [&](auto k) { has = decltype(k)::gstate(g); });
+    return has;
+}
+bool rnnwf::prnn_split_gstate_layout(const rnnwf_handle* h, int32_t* layout10) {
+    GstateLayout g{};
+    static_assert(sizeof(GstateLayout) == 40, "ten 32-bit fields");
+    if (!gstate_of(h, &g)) return false;
+    memcpy(layout10, &g, sizeof g);
+    return true;
+}
+int rnnwf::split_gstate_refold(rnnwf_handle* h) {
+    GstateLayout g{};
+    if (!h->wsplit_g.p || !gstate_of(h, &g)) return 0;
+    if (g.BYTES > h->wsplit.cap || g.BYTES > h->wsplit_g.cap) return h->fail(RNNWF_ERR_STATE, "g-state image larger than its buffers");
+    gstate_refold_kernel<<<(g.BYTES / 4 + 255) / 256, 256, 0, h->stream>>>(g, (const char*)h->wsplit.p, (uint32_t*)h->wsplit_g.p);
+    RNNWF_HIP(h, hipGetLastError());
+    return 0;
+}
+
 // ---- stacked layers on the bf16x3 engine: a pipeline of one kernel per layer (split_core.h: SplitUpperLayout) -----------------
 namespace {
 constexpr int kStackNF32 = 1, kStackRJ = 9;                  // the K-packed layout of 37..50 units (SplitLayout MODE 2)
@@ -342,9 +379,14 @@ double rnnwf::prnn_split_flops_per_step(rnnwf_handle* h) {
 }
 
 
-int rnnwf::prnn_split_pack(rnnwf_handle* h, std::vector<char>& simg) {
+int rnnwf::prnn_split_pack(rnnwf_handle* h, std::vector<char>& simg, std::vector<char>& simg_g) {
+    simg_g.clear();
     if (riders(h)) return prnn_split_stream_pack(h, simg);
-    if (with_layout<SLaunch>(h, [&](auto k) { simg = decltype(k)::pack(h); })) return 0;
+    if (with_layout<SLaunch>(h, [&](auto k) {
+            simg = decltype(k)::pack(h);
+            GstateLayout g;
+            if (decltype(k)::gstate(&g)) simg_g = gstate_image(g, simg);
+        })) return 0;
     return h->fail(RNNWF_ERR_INVALID, "no bf16x3 layout for NFULL=%d", h->NFULL);
 }
 

@@ -18,7 +18,12 @@ namespace rnnwf {
 
 #define RNNWF_STAGE() __builtin_amdgcn_sched_barrier(0)
 
-template <int NF32, int RJ, int NOUT>
+// GSTATE: the state travels as g = (h + 1) / 2 instead of h.  The candidate is c = 2 t - 1 with t = rcp(1 + exp2(..)) (tanh through the
+// sigmoid), so h' = c + u (h - c) is g' = t + u (g - t): the fma(2, t, -1) per unit is never issued.  h = 2 g - 1 is affine and
+// folds into the image (pack_split.h: gstate_word - every weight that multiplies the state doubled, every constant that meets
+// such a row less the row's weight sum), so split, MFMA segment and head run on g unchanged; the kernel turns a
+// checkpoint (h, as the base pass wrote it) into g once per tile.
+template <int NF32, int RJ, int NOUT, bool GSTATE = false>
 struct SplitPP {
     using C = SplitCore<NF32, RJ, NOUT, 2>;
     using L = typename C::L;
@@ -132,7 +137,11 @@ struct SplitPP {
         for (int o = 0; o < NOUT; ++o) z[o] = acc[3 * NF32 + (L::HEAD_SLOT + o) / 16][(L::HEAD_SLOT + o) % 16];
     }
 
+    // checkpointed state -> the form the step carries: h, or g = (h + 1) / 2 (once per tile)
+    static __device__ __forceinline__ float enter(float hck) { return GSTATE ? fmaf(0.5f, hck, 0.5f) : hck; }
+
     // gate arithmetic of units [E0, E1), one stage at a time: r = sigmoid, u = sigmoid, c = tanh(xc + r q), h' = c + u (h - c)
+    // (GSTATE: t = (c + 1) / 2 as it leaves the rcp, g' = t + u (g - t))
     template <int E0, int E1>
     static __device__ __forceinline__ void gate_batch(const f32x16 (&acc)[NT], const float* xcp, float (&h)[NU]) {
         constexpr int n = E1 - E0;
@@ -163,9 +172,11 @@ struct SplitPP {
 #pragma unroll
         for (int j = 0; j < n; ++j) ac[j] = __builtin_amdgcn_rcpf(ac[j]);
         RNNWF_STAGE();
+        if constexpr (!GSTATE) {
 #pragma unroll
-        for (int j = 0; j < n; ++j) ac[j] = fmaf(2.0f, ac[j], -1.0f);
-        RNNWF_STAGE();
+            for (int j = 0; j < n; ++j) ac[j] = fmaf(2.0f, ac[j], -1.0f);
+            RNNWF_STAGE();
+        }
 #pragma unroll
         for (int j = 0; j < n; ++j) ar[j] = h[E0 + j] - ac[j];
         RNNWF_STAGE();

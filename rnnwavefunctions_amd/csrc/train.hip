@@ -270,7 +270,7 @@ int launch_repack(rnnwf_handle* h) {
         RNNWF_HIP(h, hipGetLastError());
     }
     t.dev_newer = true;
-    return 0;
+    return split_gstate_refold(h);         // the g-state image follows h->wsplit: its constants are row sums, which no table entry holds
 }
 
 double adam_lr_t(double lr, double b1, double b2, int64_t t) {
