@@ -204,6 +204,10 @@ int rnnwf_set_params_flat(rnnwf_handle* h, const double* flat, int64_t count);
  * and layout[10] = {NT, NQ, NUP, NOUT, OFF_ASP, OFF_CI, OFF_XC, OFF_WD, OFF_BD, BYTES} (csrc/pack_split.h: GstateLayout).  For tests
  * of the packer on machines without a GPU.  Errors through rnnwf_last_error(NULL). */
 int rnnwf_host_split_images(int32_t units, const double* flat, int64_t count, void* img_h, void* img_g, int64_t cap, int32_t* layout);
+/* Host only, beside it: *bound = the image's range bound - the largest sum, over the units, of the bounds of the update gate's and the
+ * candidate's exponent arguments over every state and both input spins (csrc/pack_split.h: gstate_range) - and *in_range = the word
+ * the packer writes into img_g from it: 1 (bound <= 120, the flip kernel may take one reciprocal for update gate and candidate) or 0. */
+int rnnwf_host_split_range(int32_t units, const double* flat, int64_t count, double* bound, int32_t* in_range);
 int rnnwf_get_grads_flat(rnnwf_handle* h, double* flat, int64_t count);
 const char* rnnwf_param_name(const rnnwf_handle* h, int32_t i, int64_t* count);
 int rnnwf_allreduce_grads(rnnwf_handle* h);

@@ -54,6 +54,7 @@ PROTOTYPES = {
     "rnnwf_get_grad": (C.c_int, [_P, C.c_char_p, _P, _I64, _I32]),
     "rnnwf_set_params_flat": (C.c_int, [_P, _F64P, _I64]),
     "rnnwf_host_split_images": (C.c_int, [C.c_int32, _F64P, _I64, _P, _P, _I64, _I32P]),
+    "rnnwf_host_split_range": (C.c_int, [C.c_int32, _F64P, _I64, _F64P, _I32P]),
     "rnnwf_get_grads_flat": (C.c_int, [_P, _F64P, _I64]),
     "rnnwf_param_name": (C.c_char_p, [_P, _I32, C.POINTER(_I64)]),
     "rnnwf_allreduce_grads": (C.c_int, [_P]),

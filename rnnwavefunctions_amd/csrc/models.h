@@ -151,6 +151,7 @@ int crnn_base_coop_bf(rnnwf_handle* h, const CrnnArgs& a);
 // shapes.h their host packers take - h->wsplit of one layer; of a stack, layer 0 -> h->wsplit, l >= 1 -> h->wsplit_up[l - 1]; h->wbasebf
 int split_pack_table(rnnwf_handle* h);
 bool prnn_split_gstate_layout(const rnnwf_handle* h, int32_t* layout10);   // the ten fields of pack_split.h: GstateLayout; false: no g-state image at this width
+bool prnn_split_gstate_range(const rnnwf_handle* h, const std::vector<char>& simg, const std::vector<char>& simg_g, double* bound, uint32_t* word);   // host: pack_split.h's gstate_range of the h image, the range word as the g image holds it
 int split_gstate_refold(rnnwf_handle* h);      // behind a re-pack of h->wsplit: h->wsplit_g from it, on the stream (no-op without that image)
 int stack_pack_table(rnnwf_handle* h, int layer);
 int base_bf_pack_table(rnnwf_handle* h);

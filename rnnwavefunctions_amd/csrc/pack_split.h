@@ -284,13 +284,15 @@ std::vector<char> pack_split_image(const rnnwf_handle* h) {
 // enters with (h = 0 in the checkpoint); whatever it held would feed nothing.
 struct GstateLayout {
     int NT, NQ, NUP, NOUT;
-    uint32_t OFF_ASP, OFF_CI, OFF_XC, OFF_WD, OFF_BD, BYTES;
+    uint32_t OFF_ASP, OFF_CI, OFF_XC, OFF_WD, OFF_BD, BYTES;   // the ten fields rnnwf_host_split_images returns
+    int NF32, RJ;                                              // where a unit's gate rows lie (gstate_range_unit)
 };
 template <class L>
 constexpr GstateLayout gstate_layout() {
     static_assert(L::MODE == 2 && L::OFF_A == 0, "the g-state form exists for the K-packed layout of the ping-pong kernels");
+    static_assert(L::NOUT <= (int)kGstateRangeSlot, "the range word takes a head-bias word no head row uses");
     return {L::NT, L::NQ, L::NUP, L::NOUT, (uint32_t)L::OFF_ASP, (uint32_t)L::OFF_CI, (uint32_t)L::OFF_XC, (uint32_t)L::OFF_WD, (uint32_t)L::OFF_BD,
-            (uint32_t)L::BYTES};
+            (uint32_t)L::BYTES, L::NF32, L::RJ};   // (the range word: split_core.h, kGstateRangeSlot)
 }
 __host__ __device__ inline float gstate_bf16(uint16_t b) {
     union { uint32_t u; float f; } x;
@@ -336,9 +338,65 @@ __host__ __device__ inline uint32_t gstate_word(const GstateLayout& g, const cha
     for (int e = 0; e < 2 * g.NUP; ++e) sum += (double)WD[(size_t)e * g.NOUT + o];
     return gstate_bits((float)((double)reinterpret_cast<const float*>(img)[w] - sum));
 }
+// ---- the range word: may the step take ONE reciprocal for update gate and candidate? (split_pp.h: gate_batch, MERGED) -------------
+// With Eu = exp2(a_u) and Ec = exp2(a_c) the merged form divides by (1 + Eu)(1 + Ec), which must stay finite in f32:
+// (1 + 2^a)(1 + 2^b) <= 2^(a + b + 2) < 2^128 needs a + b <= 125 for a, b >= 0.  gstate_range_unit bounds that sum for the unit at
+// entry e of lane half hh over EVERY state and both input spins, in the exponent units the image is scaled to:
+//     A_u >= |a_u|             = max over sigma of |start-table entry of the u row| + sum of |w1 + w2 + w3| over the row's K entries,
+//     A_c >= |xc + r q|, r in [0, 1]:  max over sigma of |xc| + max over sigma of |start-table entry of the q row| + the q row's sum.
+// (|h| <= 1 in the h form is g in [0, 1] in the g form: the same interval of pre-activations, so the h image gives the bound for the g
+// image's step.)  Absolute values throughout, so both bounds are >= 0 and a gate that underflows counts like one that overflows: the
+// bound errs to the safe side.  The image is in range iff the largest sum is <= kGstateRangeLimit = 120: five exponents are left for
+// the f32 rounding of the accumulated pre-activations (each below 2^-17 of A) and of g itself.  float64, additions and comparisons only,
+// in the order of the image: host and device agree bit for bit, as gstate_word's sums do.  Padded units give 0.
+constexpr double kGstateRangeLimit = 120.0;
+__host__ __device__ inline double gstate_max(double a, double b) { return (a > b || a != a) ? a : b; }      // a NaN stays (then: out of range)
+__host__ __device__ inline double gstate_row_abs_sum(const GstateLayout& g, const char* img, int T, int r32) {
+    const uint16_t* A = reinterpret_cast<const uint16_t*>(img);
+    double sum = 0.0;
+    for (int hhk = 0; hhk < 2; ++hhk) {
+        const int lane = 32 * hhk + r32;
+        for (int x = 0; x < g.NQ; ++x)
+            for (int jj = 0; jj < 8; ++jj) {
+                float wv = 0.0f;                               // w3 + w2 + w1: exact
+                for (int a = 2; a >= 0; --a) wv += gstate_bf16(A[((((size_t)T * 3 + a) * g.NQ + x) * 64 + lane) * 8 + jj]);
+                sum += fabs((double)wv);
+            }
+        const uint16_t* sp = A + g.OFF_ASP / 2 + ((size_t)T * 64 + lane) * 8;
+        sum += fabs((double)((gstate_bf16(sp[5]) + gstate_bf16(sp[3])) + gstate_bf16(sp[0])));
+    }
+    return sum;
+}
+__host__ __device__ inline double gstate_range_unit(const GstateLayout& g, const char* img, int e, int hh) {
+    const float* CI = reinterpret_cast<const float*>(img + g.OFF_CI);
+    const float* XC = reinterpret_cast<const float*>(img + g.OFF_XC);
+    double A = 0.0;
+    for (int gate = 1; gate <= 2; ++gate) {                    // 1: u row, 2: q row of the unit (split_pp.h: slots)
+        const int s = gate * g.RJ + (e - 16 * g.NF32);
+        const int T = e < 16 * g.NF32 ? 3 * (e / 16) + gate : 3 * g.NF32 + s / 16, rho = e < 16 * g.NF32 ? e % 16 : s % 16;
+        const int r32 = (rho & 3) | (hh << 2) | ((rho >> 2) << 3);
+        double c = 0.0;
+        for (int sgm = 0; sgm < 2; ++sgm) c = gstate_max(c, fabs((double)CI[(((size_t)sgm * g.NT + T) * 2 + hh) * 16 + rho]));
+        A += c + gstate_row_abs_sum(g, img, T, r32);
+    }
+    double xc = 0.0;
+    for (int sgm = 0; sgm < 2; ++sgm) xc = gstate_max(xc, fabs((double)XC[(size_t)(sgm * 2 + hh) * g.NUP + e]));
+    return A + xc;
+}
+// the largest bound of the image (host; device-resident training: split.hip, gstate_range_kernel) and the word that says "in range"
+inline double gstate_range(const GstateLayout& g, const char* img) {
+    double m = 0.0;
+    for (int hh = 0; hh < 2; ++hh)
+        for (int e = 0; e < 16 * g.NF32 + g.RJ; ++e) m = gstate_max(m, gstate_range_unit(g, img, e, hh));
+    return m;
+}
+__host__ __device__ inline uint32_t gstate_range_word(double bound) { return bound <= kGstateRangeLimit ? 1u : 0u; }
+__host__ __device__ inline uint32_t gstate_range_word_index(const GstateLayout& g) { return g.OFF_BD / 4 + kGstateRangeSlot; }
+
 inline std::vector<char> gstate_image(const GstateLayout& g, const std::vector<char>& img) {
     std::vector<char> out(img.size());
     for (uint32_t w = 0; w < g.BYTES / 4; ++w) reinterpret_cast<uint32_t*>(out.data())[w] = gstate_word(g, img.data(), w);
+    reinterpret_cast<uint32_t*>(out.data())[gstate_range_word_index(g)] = gstate_range_word(gstate_range(g, img.data()));
     return out;
 }
 

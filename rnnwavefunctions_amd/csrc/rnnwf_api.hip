@@ -342,23 +342,20 @@ extern "C" int64_t rnnwf_num_params(const rnnwf_handle* h) {
     return n;
 }
 
-// Host only, no device is touched: both forms of the bf16x3 flip-pass image of a one-layer positive GRU (rnnwf.h)
-extern "C" int rnnwf_host_split_images(int32_t units, const double* flat, int64_t count, void* img_h, void* img_g, int64_t cap, int32_t* layout) {
-    auto bad = [&](const std::string& m) {
-        g_create_error = "rnnwf_host_split_images: " + m;
-        return (int)RNNWF_ERR_INVALID;
-    };
-    if (!flat || !img_h || !img_g || !layout || units < 1) return bad("null or empty argument");
-    rnnwf_handle h;
+// Host only, no device is touched: the bf16x3 flip-pass image of a one-layer positive GRU (rnnwf.h)
+namespace {
+// a handle on the host alone with the parameters `flat`; "" or what is wrong with the arguments
+std::string host_gru_handle(rnnwf_handle& h, int32_t units, const double* flat, int64_t count) {
+    if (!flat || units < 1) return "null or empty argument";
     h.cfg.model = h.model = RNNWF_MODEL_GRU1D;
     h.cfg.nx = h.Nx = h.N = 2;
     h.cfg.num_layers = 1;
     h.cfg.units[0] = h.H = units;
     h.family = gru_family();
     h.NFULL = pick_nfull(units, false, false);
-    if (h.NFULL < 0) return bad("num_units too large");
+    if (h.NFULL < 0) return "num_units too large";
     declare_params(&h);
-    if (count != rnnwf_num_params(&h)) return bad("the model has " + std::to_string(rnnwf_num_params(&h)) + " parameters");
+    if (count != rnnwf_num_params(&h)) return "the model has " + std::to_string(rnnwf_num_params(&h)) + " parameters";
     int64_t off = 0;
     for (auto& kv : h.params) {
         ParamSpec& p = kv.second;
@@ -366,12 +363,44 @@ extern "C" int rnnwf_host_split_images(int32_t units, const double* flat, int64_
         off += (int64_t)p.slot.size();
         p.set = true;
     }
+    return "";
+}
+}  // namespace
+
+// both forms of the image
+extern "C" int rnnwf_host_split_images(int32_t units, const double* flat, int64_t count, void* img_h, void* img_g, int64_t cap, int32_t* layout) {
+    auto bad = [&](const std::string& m) {
+        g_create_error = "rnnwf_host_split_images: " + m;
+        return (int)RNNWF_ERR_INVALID;
+    };
+    if (!img_h || !img_g || !layout) return bad("null or empty argument");
+    rnnwf_handle h;
+    const std::string err = host_gru_handle(h, units, flat, count);
+    if (!err.empty()) return bad(err);
     std::vector<char> a, g;
     if (prnn_split_pack(&h, a, g) != 0) return bad(h.err);
     if (g.empty() || !prnn_split_gstate_layout(&h, layout)) return bad("this width has no g-state image (37..50 units)");
     if ((int64_t)a.size() > cap) return bad("images of " + std::to_string(a.size()) + " bytes");
     memcpy(img_h, a.data(), a.size());
     memcpy(img_g, g.data(), g.size());
+    return RNNWF_OK;
+}
+
+// the range bound of the image and the verdict the packer writes into its g-state form
+extern "C" int rnnwf_host_split_range(int32_t units, const double* flat, int64_t count, double* bound, int32_t* in_range) {
+    auto bad = [&](const std::string& m) {
+        g_create_error = "rnnwf_host_split_range: " + m;
+        return (int)RNNWF_ERR_INVALID;
+    };
+    if (!bound || !in_range) return bad("null or empty argument");
+    rnnwf_handle h;
+    const std::string err = host_gru_handle(h, units, flat, count);
+    if (!err.empty()) return bad(err);
+    std::vector<char> a, g;
+    if (prnn_split_pack(&h, a, g) != 0) return bad(h.err);
+    uint32_t word = 0;
+    if (g.empty() || !prnn_split_gstate_range(&h, a, g, bound, &word)) return bad("this width has no g-state image (37..50 units)");
+    *in_range = (int32_t)word;
     return RNNWF_OK;
 }
 

@@ -4,6 +4,7 @@
 // SIMD partner's - whereas the f32-input-MFMA kernels of prnn.hip / crnn.hip WANT the packed forms (their MFMA and VALU
 // serialise anyway, so half the VALU instructions is a straight gain: config 5 0.79 -> 0.86 of the f32 pipe).
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
@@ -238,6 +239,19 @@ __global__ void gstate_refold_kernel(GstateLayout g, const char* __restrict__ im
     const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w < g.BYTES / 4) out[w] = gstate_word(g, img, w);
 }
+// the range word of that image (pack_split.h: gstate_range): one thread per owned unit of the two lane halves, the largest bound through
+// LDS, one vector store.  One block, launched behind the refold on the same stream - the flip pass that reads the word is behind both.
+__global__ void __launch_bounds__(128) gstate_range_kernel(GstateLayout g, const char* __restrict__ img, uint32_t* __restrict__ out) {
+    __shared__ double bound[128];
+    const int NU = 16 * g.NF32 + g.RJ, t = threadIdx.x;
+    bound[t] = t < 2 * NU ? gstate_range_unit(g, img, t % NU, t / NU) : 0.0;
+    __syncthreads();
+    for (int s = 64; s > 0; s >>= 1) {
+        if (t < s) bound[t] = gstate_max(bound[t], bound[t + s]);
+        __syncthreads();
+    }
+    if (t == 0) out[gstate_range_word_index(g)] = gstate_range_word(bound[0]);
+}
 }  // namespace
 static bool gstate_of(const rnnwf_handle* h, GstateLayout* g) {
     bool has = false;
@@ -246,16 +260,26 @@ static bool gstate_of(const rnnwf_handle* h, GstateLayout* g) {
 }
 bool rnnwf::prnn_split_gstate_layout(const rnnwf_handle* h, int32_t* layout10) {
     GstateLayout g{};
-    static_assert(sizeof(GstateLayout) == 40, "ten 32-bit fields");
+    static_assert(offsetof(GstateLayout, NF32) == 40, "ten 32-bit fields, then the packer's own");
     if (!gstate_of(h, &g)) return false;
-    memcpy(layout10, &g, sizeof g);
+    memcpy(layout10, &g, 40);
+    return true;
+}
+bool rnnwf::prnn_split_gstate_range(const rnnwf_handle* h, const std::vector<char>& simg, const std::vector<char>& simg_g, double* bound, uint32_t* word) {
+    GstateLayout g{};
+    if (!gstate_of(h, &g) || simg.size() < g.BYTES || simg_g.size() < g.BYTES) return false;
+    *bound = gstate_range(g, simg.data());
+    *word = reinterpret_cast<const uint32_t*>(simg_g.data())[gstate_range_word_index(g)];
     return true;
 }
 int rnnwf::split_gstate_refold(rnnwf_handle* h) {
     GstateLayout g{};
     if (!h->wsplit_g.p || !gstate_of(h, &g)) return 0;
     if (g.BYTES > h->wsplit.cap || g.BYTES > h->wsplit_g.cap) return h->fail(RNNWF_ERR_STATE, "g-state image larger than its buffers");
+    if (2 * (16 * g.NF32 + g.RJ) > 128) return h->fail(RNNWF_ERR_STATE, "g-state range kernel: more than 128 owned units");
     gstate_refold_kernel<<<(g.BYTES / 4 + 255) / 256, 256, 0, h->stream>>>(g, (const char*)h->wsplit.p, (uint32_t*)h->wsplit_g.p);
+    RNNWF_HIP(h, hipGetLastError());
+    gstate_range_kernel<<<1, 128, 0, h->stream>>>(g, (const char*)h->wsplit.p, (uint32_t*)h->wsplit_g.p);
     RNNWF_HIP(h, hipGetLastError());
     return 0;
 }

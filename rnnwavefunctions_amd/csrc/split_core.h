@@ -103,6 +103,10 @@ struct SplitLayout {
     }
 };
 
+// MODE 2, g-state form of the image (pack_split.h): the last of the four head-bias words, which a head of up to three rows leaves spare,
+// says whether the image is in the range of the ping-pong step's one-reciprocal gate tail (pack_split.h: gstate_range; 1: in range).
+constexpr unsigned kGstateRangeSlot = 3;
+
 // Stacked GRU layers above the first on the bf16x3 engine (tf.nn.rnn_cell.MultiRNNCell, 1DTFIM/RNNwavefunction.py:32; the complex
 // wave function's default is two layers, J1J2/ComplexRNNwavefunction.py:16,40), K-packed layout MODE 2 (37..50 units).
 // The input x of layer l is the new state of layer l - 1: an h-wide f32 vector instead of a one-hot, so a step is TWO blocks of

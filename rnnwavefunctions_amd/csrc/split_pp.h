@@ -23,8 +23,14 @@ namespace rnnwf {
 // folds into the image (pack_split.h: gstate_word - every weight that multiplies the state doubled, every constant that meets
 // such a row less the row's weight sum), so split, MFMA segment and head run on g unchanged; the kernel turns a
 // checkpoint (h, as the base pass wrote it) into g once per tile.
-template <int NF32, int RJ, int NOUT, bool GSTATE = false>
+// MERGED (GSTATE only): update gate and candidate share ONE reciprocal.  With Eu = exp2(a_u), Ec = exp2(a_c), u = 1 / (1 + Eu) and
+// t = 1 / (1 + Ec), g' = t + u (g - t) is [g (1 + Ec) + Eu] / [(1 + Eu)(1 + Ec)]: five transcendentals per unit instead of six, the
+// same six plain instructions.  Unlike the two-reciprocal form it does not survive an exp2 that overflows (inf x 0) or a denominator
+// beyond the f32 range (g' = 0, silently), so a kernel may take it only for an image whose range word says that neither can happen
+// (pack_split.h: gstate_range; split_kernels.h chooses once per launch).
+template <int NF32, int RJ, int NOUT, bool GSTATE = false, bool MERGED = false>
 struct SplitPP {
+    static_assert(GSTATE || !MERGED, "the one-reciprocal gate tail is written for the g-state form");
     using C = SplitCore<NF32, RJ, NOUT, 2>;
     using L = typename C::L;
     static constexpr int NT = C::NT, NU = C::NU, NUA = C::NUA, NQ = C::NQ;
@@ -155,11 +161,15 @@ struct SplitPP {
         for (int j = 0; j < n; ++j) { ar[j] = __builtin_amdgcn_exp2f(ar[j]); au[j] = __builtin_amdgcn_exp2f(au[j]); }
         RNNWF_STAGE();
 #pragma unroll
-        for (int j = 0; j < n; ++j) { ar[j] = 1.0f + ar[j]; au[j] = 1.0f + au[j]; }
+        for (int j = 0; j < n; ++j) { ar[j] = 1.0f + ar[j]; if constexpr (!MERGED) au[j] = 1.0f + au[j]; }
         RNNWF_STAGE();
 #pragma unroll
-        for (int j = 0; j < n; ++j) { ar[j] = __builtin_amdgcn_rcpf(ar[j]); au[j] = __builtin_amdgcn_rcpf(au[j]); }
+        for (int j = 0; j < n; ++j) { ar[j] = __builtin_amdgcn_rcpf(ar[j]); if constexpr (!MERGED) au[j] = __builtin_amdgcn_rcpf(au[j]); }
         RNNWF_STAGE();
+        if constexpr (MERGED) {
+            gate_tail_merged<E0, E1>(ar, au, ac, xc, h);
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < n; ++j) ac[j] = fmaf(ar[j], ac[j], xc[j]);
         RNNWF_STAGE();
@@ -184,6 +194,35 @@ struct SplitPP {
         // v_fmac (25 v_mov per wave-step).  Plain VALU producer, VALU consumers (head, re-split): no software hazard.
 #pragma unroll
         for (int j = 0; j < n; ++j) asm("v_fma_f32 %0, %1, %2, %3" : "=v"(h[E0 + j]) : "v"(au[j]), "v"(ar[j]), "v"(ac[j]));
+        RNNWF_STAGE();
+    }
+
+    // MERGED: the rest of gate_batch behind r = rcp(1 + Er), with au = Eu as it left exp2:
+    //   D2 = 1 + Ec, num = g D2 + Eu (into the register r has left), D = Eu D2 + D2 = (1 + Eu)(1 + Ec), g' = num rcp(D)
+    template <int E0, int E1>
+    static __device__ __forceinline__ void gate_tail_merged(float (&ar)[E1 - E0], float (&au)[E1 - E0], float (&ac)[E1 - E0], const float (&xc)[E1 - E0],
+                                                            float (&h)[NU]) {
+        constexpr int n = E1 - E0;
+#pragma unroll
+        for (int j = 0; j < n; ++j) ac[j] = fmaf(ar[j], ac[j], xc[j]);
+        RNNWF_STAGE();
+#pragma unroll
+        for (int j = 0; j < n; ++j) ac[j] = __builtin_amdgcn_exp2f(ac[j]);
+        RNNWF_STAGE();
+#pragma unroll
+        for (int j = 0; j < n; ++j) ac[j] = 1.0f + ac[j];
+        RNNWF_STAGE();
+#pragma unroll
+        for (int j = 0; j < n; ++j) ar[j] = fmaf(h[E0 + j], ac[j], au[j]);
+        RNNWF_STAGE();
+#pragma unroll
+        for (int j = 0; j < n; ++j) au[j] = fmaf(au[j], ac[j], ac[j]);
+        RNNWF_STAGE();
+#pragma unroll
+        for (int j = 0; j < n; ++j) au[j] = __builtin_amdgcn_rcpf(au[j]);
+        RNNWF_STAGE();
+#pragma unroll
+        for (int j = 0; j < n; ++j) h[E0 + j] = ar[j] * au[j];
         RNNWF_STAGE();
     }
 
