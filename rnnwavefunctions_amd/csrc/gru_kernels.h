@@ -284,6 +284,10 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_ml_flip_kernel(PrnnArgs a) {
 //     last wave  : head, draw / read the spin, publish it, log-probabilities
 // The arithmetic per unit is the instruction sequence of prnn_base_kernel (GruCore::step<BIAS_LAST>), so both kernels
 // agree bit for bit, draws included - a batch and its shards may take different kernels.
+// The per-site body (tile products; bias rows last, gates, publish, checkpoint) stands here, in coop_base_pass_bf and in
+// ml_coop.h, written out: moved into shared force-inlined templates, all 26 cooperative kernels compiled to other assembly
+// and register counts (profiles/coop_core_isa_attempt.txt).  An edit to it goes to every copy; tools/forward_bits.py --coop
+// lists the bits of all of them.
 // The cooperative site loop shared by the positive and the complex RNN: `begin(sb)` on every wave at the start of a
 // block of 16 chains, `site(n, h) -> spin` on the remainder wave once the state after site n is complete (head, draw,
 // bookkeeping), `end(sb)` on the remainder wave after the last site.
