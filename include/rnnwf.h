@@ -623,6 +623,30 @@ int rnnwf_lstm_gradient(rnnwf_handle* h, const int32_t* samples, int64_t B, cons
 int rnnwf_lstm_vmc_gradient_step(rnnwf_handle* h, int64_t numsamples, uint64_t seed, uint64_t step, int64_t sample_offset,
                                  const double* couplings, double* moments, int32_t* out_samples, double* out_eloc);
 
+/* ---- Pauli strings and generic Hamiltonians for the LSTM wave function (RNNWF_MODEL_LSTM1D_F64; docs/pauli_lstm.md) ----------
+ * rnnwf_pauli_step_lstm: rnnwf_pauli_step for the LSTM cell (one layer, 1..68 units, float64).  Arguments, layouts, outputs, passes
+ *   under RNNWF_STATE_BUDGET_MB, fixed-order sums, +inf on log r > 709 and the argument refusals (a mask entry that is not 0 or 1,
+ *   nterms < 1, ns < 1, a negative sample_offset, more than 65 535 distinct flip masks, the grid of the term kernel) are
+ *   rnnwf_pauli_step's; masks are indexed by the chain position, the column of `samples` (raster order).  A mask whose first flipped
+ *   site is f >= 1 restarts the chain from its own checkpoint (h, c) of site f - 1: N - f cell evaluations per chain and mask,
+ *   counted in work[0].  Terms without a flip alone run no recurrent kernel.  No batch is resident after a served call (the LSTM has
+ *   no hook in rnnwf_vmc_gradient).  RNNWF_ERR_INVALID, before any work: every other model, by name, with the entry that serves it.
+ *   rnnwf_pauli_step, _stack, _2d and _complex keep refusing the LSTM.  Timing ids: 0 = base pass with site terms, 1 = masked-tail
+ *   pass, 2 = log-ratio assembly + sums.
+ * rnnwf_lstm_pauli_gradient_step: rnnwf_lstm_vmc_gradient_step for the Hamiltonian sum_k coeff[k] (prod_sign sz)(prod_flip sx):
+ *   one pass of rnnwf_pauli_step_lstm on numsamples drawn samples (same samples, E_loc, moments and term_sums, bit for bit), then
+ *   the gradient with weights (E_s - moments[0] / moments[2]) * (1 / moments[2]) on the checkpoints that pass left on the device: no
+ *   second base pass, one host synchronisation.  term_sums (nterms, 2), out_samples, out_eloc may be NULL.  Leaves the tensors where
+ *   rnnwf_get_grad and rnnwf_get_grads_flat read them.  Refused before anything is touched (an earlier batch, the parameters and
+ *   the gradient stay as they were): the refusals above; a handle with a communicator (single process only); RNNWF_ERR_NOMEM
+ *   "... exceed the state budget of one pass; split the batch" for more samples than one pass holds.                           */
+int rnnwf_pauli_step_lstm(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff, int32_t nterms,
+                          const int32_t* samples, int64_t ns, uint64_t seed, uint64_t step, int64_t sample_offset,
+                          double* term_sums, double* out_eloc, double* moments, double* out_log_ratio, int32_t* out_samples);
+int rnnwf_lstm_pauli_gradient_step(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff, int32_t nterms,
+                                   int64_t numsamples, uint64_t seed, uint64_t step, int64_t sample_offset, double* moments,
+                                   double* term_sums, int32_t* out_samples, double* out_eloc);
+
 /* ---- measurement ------------------------------------------------------------------------------
  * HIP-event timing of the kernels on the handle's stream (bench.py's roofline leg).
  * kernel ids: 0 = base pass (sample / teacher-forced + checkpoints), 1 = flip pass (dominant),

@@ -116,6 +116,8 @@ PROTOTYPES["rnnwf_pauli_train_steps_2d"] = PROTOTYPES["rnnwf_pauli_train_steps"]
 PROTOTYPES["rnnwf_pauli_step_stack"] = PROTOTYPES["rnnwf_pauli_step"]                  # stacked layers (docs/pauli_stack.md): likewise
 PROTOTYPES["rnnwf_pauli_train_steps_stack"] = PROTOTYPES["rnnwf_pauli_train_steps"]
 PROTOTYPES["rnnwf_renyi2_regions_stack"] = PROTOTYPES["rnnwf_renyi2_regions"]          # docs/renyi_stack.md
+PROTOTYPES["rnnwf_pauli_step_lstm"] = PROTOTYPES["rnnwf_pauli_step"]                   # the LSTM cell (docs/pauli_lstm.md): likewise
+PROTOTYPES["rnnwf_lstm_pauli_gradient_step"] = (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I64, _U64, _U64, _I64, _F64P, _F64P, _I32P, _F64P])
 
 _lib = None
 
@@ -745,6 +747,40 @@ class NativeWavefunction:
         layers.  Arguments and the returned dict are pauli_step's."""
         return self._pauli_call("rnnwf_pauli_step_stack", False, (max(int(ns), 0), self.N), flip, sign, coeff, ns, samples, seed, step,
                                 sample_offset, want_eloc, want_log_ratio, want_samples)
+
+    def pauli_step_lstm(self, flip, sign, coeff, ns, samples=None, seed=0, step=0, sample_offset=0, want_eloc=False,
+                        want_log_ratio=False, want_samples=False):
+        """pauli_step for the LSTM wave function (rnnwf_pauli_step_lstm, docs/pauli_lstm.md): model LSTM1D_F64.  flip, sign: (K, N)
+        masks indexed by the chain position, the column of samples (ns, N), or (K, Nx, Ny) in the shape lstm_gradient accepts samples
+        in.  samples: (ns, N) or (ns, Nx, Ny) int32; None: drawn on the device as sample(ns, seed, step, sample_offset) draws them.
+        Returns what pauli_step returns; no batch stays resident."""
+        return self._pauli_call("rnnwf_pauli_step_lstm", False, (max(int(ns), 0), self.N), *self._lattice_masks(flip, sign), coeff, ns,
+                                samples, seed, step, sample_offset, want_eloc, want_log_ratio, want_samples)
+
+    def lstm_pauli_gradient_step(self, flip, sign, coeff, numsamples, seed, step, shapes, sample_offset=0, want_samples=False,
+                                 want_eloc=False):
+        """One pass of pauli_step_lstm on numsamples drawn samples and the gradient of the VMC cost of the Hamiltonian
+        sum_k coeff_k (prod_sign sz)(prod_flip sx) on its batch, in one call with one host synchronisation
+        (rnnwf_lstm_pauli_gradient_step; single process).  Returns dict(moments=(4,), grads={tf_name: float64 ndarray},
+        term_sums=(K, 2), samples=(numsamples, N)?, eloc=(numsamples,)?); moments, term_sums, samples and eloc are pauli_step_lstm's
+        bit for bit, grads is lstm_gradient(samples, (eloc - s1 / n) * (1.0 / n))'s."""
+        numsamples = int(numsamples)
+        fl, sg, co = self._term_masks(*self._lattice_masks(flip, sign), coeff, False)
+        K = fl.shape[0]
+        mom = np.zeros(4, dtype=np.float64)
+        sums = np.empty((K, 2), dtype=np.float64)
+        smp = np.empty((max(numsamples, 0), self.N), dtype=np.int32) if want_samples else None
+        el = np.empty(max(numsamples, 0), dtype=np.float64) if want_eloc else None
+        self._check(self.lib.rnnwf_lstm_pauli_gradient_step(self.h, fl.ctypes.data_as(_I32P), sg.ctypes.data_as(_I32P), co.ctypes.data_as(_F64P), K,
+                                                            numsamples, int(seed), int(step), int(sample_offset), mom.ctypes.data_as(_F64P),
+                                                            sums.ctypes.data_as(_F64P), smp.ctypes.data_as(_I32P) if want_samples else None,
+                                                            el.ctypes.data_as(_F64P) if want_eloc else None))
+        out = {"moments": mom, "grads": self._grads(shapes), "term_sums": sums}
+        if want_samples:
+            out["samples"] = smp
+        if want_eloc:
+            out["eloc"] = el
+        return out
 
     def _lattice_masks(self, flip, sign):
         """flip and sign given as (K, Nx, Ny) flattened to (K, Nx*Ny); everything else as it came"""

@@ -1,5 +1,5 @@
 """The one implementation behind the Pauli, Renyi and minimize wrappers of observables.py, observables_stack.py, observables_2d.py,
-observables_complex.py and training.minimize_hamiltonian.  A Family names what differs between the wave-function families - the
+observables_complex.py, observables_lstm.py and training.minimize_hamiltonian.  A Family names what differs between the wave-function families - the
 NativeWavefunction methods, the shape caller samples take, the centre site, two wordings -; the functions below take one and a
 NativeWavefunction that the calling module's guard (_native, _native_stack, ...) has already accepted.  Private: the public names,
 signatures and docstrings live in the calling modules."""
@@ -11,8 +11,10 @@ from . import observables as O
 from . import training as T
 
 # step, train_steps, regions: names of the NativeWavefunction methods; chain_shape(nat): the shape of one chain of caller samples;
-# centre(nat): the default centre site of correlations; label: what check_device_steps calls the driver; sites: the pairs error's noun
-Family = namedtuple("Family", "step train_steps regions chain_shape centre label sites")
+# centre(nat): the default centre site of correlations; label: what check_device_steps calls the driver; sites: the pairs error's noun;
+# fused: name of a method that runs step AND the gradient of the cost in one call (dict with "moments" and "grads"), for a family whose
+# batch vmc_gradient does not serve; None: step, then training.cost_gradient
+Family = namedtuple("Family", "step train_steps regions chain_shape centre label sites fused", defaults=(None,))
 
 
 def _chain(nat):
@@ -25,6 +27,9 @@ STACK = Family("pauli_step_stack", "pauli_train_steps_stack", "renyi2_regions_st
 LATTICE = Family("pauli_step_2d", "pauli_train_steps_2d", "renyi2_regions_2d", lambda nat: (nat.nx, nat.ny),
                  lambda nat: (nat.nx // 2) * nat.ny + nat.ny // 2, "observables_2d.minimize_hamiltonian", "lattice sites")
 COMPLEX = Family("pauli_step_complex", "pauli_train_steps_complex", "renyi2_regions_complex", _chain, None, "minimize_hamiltonian", None)
+# the LSTM cell (observables_lstm.py): no device-resident Adam and no region pass; its minimize loop takes the fused step
+LSTM = Family("pauli_step_lstm", None, None, _chain, lambda nat: nat.N // 2, "observables_lstm.minimize_hamiltonian", "sites",
+              "lstm_pauli_gradient_step")
 
 
 def chains(fam, nat, samples, rows):
@@ -122,10 +127,13 @@ def renyi2_mutual_information(fam, nat, a, b, numpairs, seed, step, samples):
     return O.mutual_information2_from_log_ratios(*mutual_log_ratios(fam, nat, a, b, numpairs, seed, step, samples))
 
 
-def minimize_loop(step, train_steps, mean_of, nat, ham, params, scope, numsteps, numsamples, learningrate, seed, opt, device_steps, verbose):
+def minimize_loop(step, train_steps, mean_of, nat, ham, params, scope, numsteps, numsamples, learningrate, seed, opt, device_steps, verbose,
+                  fused=None, lr_of_it=None):
     """Iterations 0..numsteps of  step (samples, local energies of `ham`, moments; the batch stays resident) -> training.cost_gradient ->
     opt.step -> set_params,  or - with device_steps - the same iterations through train_steps in chunks.  step, train_steps: bound
-    NativeWavefunction methods; mean_of(s1, si, n): an entry of meanEnergy from the moments.  Returns (meanEnergy, varEnergy, params)."""
+    NativeWavefunction methods; mean_of(s1, si, n): an entry of meanEnergy from the moments.  Returns (meanEnergy, varEnergy, params).
+    fused: a bound method that takes step's place and training.cost_gradient's in one call (shapes= the tensors' shapes; its dict holds
+    "moments" and the unscoped "grads").  lr_of_it(learningrate, it): the learning rate of iteration it; None: learningrate."""
     opt = opt or T.Adam()
     params = {k: np.array(v) for k, v in params.items()}
     nat.set_params(params, scope=scope)
@@ -135,26 +143,36 @@ def minimize_loop(step, train_steps, mean_of, nat, ham, params, scope, numsteps,
                                                               mean_of)
         return meanEnergy, varEnergy, nat.get_params_dict(params, scope)
     meanEnergy, varEnergy = [], []
+    shapes = {k[len(scope) + 1:]: v.shape for k, v in params.items()}
     for it in range(numsteps + 1):
-        s1, s2, n, si = step(ham.flip, ham.sign, ham.coeff, numsamples, seed=seed, step=it)["moments"]
+        if fused is not None:
+            out = fused(ham.flip, ham.sign, ham.coeff, numsamples, seed=seed, step=it, shapes=shapes)
+        else:
+            out = step(ham.flip, ham.sign, ham.coeff, numsamples, seed=seed, step=it)
+        s1, s2, n, si = out["moments"]
         meanE = mean_of(s1, si, n)
         varE = s2 / n - (s1 / n) ** 2
         meanEnergy.append(meanE)
         varEnergy.append(varE)
         if verbose and it % 10 == 0:
             print("mean(E): {0}, var(E): {1}, #samples {2}, #Step {3} \n\n".format(meanE, varE, numsamples, it))
-        grads = T.cost_gradient(nat, params, scope, meanE, n)
-        params = opt.step(params, grads, learningrate)
+        grads = T.cost_gradient(nat, params, scope, meanE, n) if fused is None else {scope + "/" + k: v for k, v in out["grads"].items()}
+        params = opt.step(params, grads, learningrate if lr_of_it is None else lr_of_it(learningrate, it))
         nat.set_params(params, scope=scope)
     return meanEnergy, varEnergy, params
 
 
-def minimize_family(fam, guard, wf, ham, params, numsteps, numsamples, learningrate, seed, scope, opt, comm, verbose, device_steps):
+def minimize_family(fam, guard, wf, ham, params, numsteps, numsamples, learningrate, seed, scope, opt, comm, verbose, device_steps,
+                    lr_of_it=None):
     """the drivers of the real families: their refusals in their order, then minimize_loop; guard(wf) gives the NativeWavefunction"""
     device_steps = T.check_device_steps(device_steps, opt, fam.label)
+    if device_steps is not None and fam.train_steps is None:
+        raise ValueError("%s: device_steps is not available for this family: it has no device-resident Adam (docs/lstm.md, \"Out of "
+                         "scope\"); use the host loop (device_steps=None)" % fam.label)
     if comm is not None:
         raise ValueError("minimize_hamiltonian runs in one process on one GPU: no communicator (comm=%r)" % (comm,))
     nat = guard(wf)
     check_sites(nat, ham)
-    return minimize_loop(getattr(nat, fam.step), getattr(nat, fam.train_steps), lambda s1, si, n: s1 / n, nat, ham, params, scope, numsteps,
-                         numsamples, learningrate, seed, opt, device_steps, verbose)
+    return minimize_loop(getattr(nat, fam.step), getattr(nat, fam.train_steps) if fam.train_steps else None, lambda s1, si, n: s1 / n, nat, ham,
+                         params, scope, numsteps, numsamples, learningrate, seed, opt, device_steps, verbose,
+                         fused=getattr(nat, fam.fused) if fam.fused else None, lr_of_it=lr_of_it)

@@ -116,10 +116,13 @@ int require_lstm(rnnwf_handle* h, const char* what) {
                    model_name(h->model));
 }
 
+}  // namespace
+
 // The one driver: the backward pass on the ns chains whose spins (h->bits) and checkpoints (h->hck) the base pass just left, with
 // the weights in w_dev, or (w_dev == nullptr) formed from h->eloc and the step's moments still on the device; the dW image and the
-// head row are queued for download into h->staging.  The caller synchronises once and calls lstm_grad_finish.
-int lstm_grad_queue(rnnwf_handle* h, const char* what, int64_t ns, const double* w_dev) {
+// head row are queued for download into h->staging.  The caller synchronises once and calls lstm_grad_finish.  (Declared in models.h:
+// rnnwf_lstm_pauli_gradient_step, lstm_pauli.hip, runs it on the batch of its Pauli pass.)
+int rnnwf::lstm_grad_queue(rnnwf_handle* h, const char* what, int64_t ns, const double* w_dev) {
     return with_lstm_grad(h, what, [&](auto k) -> int {
         using K = decltype(k);
         if (!h->wbwd_valid) {
@@ -147,9 +150,11 @@ int lstm_grad_queue(rnnwf_handle* h, const char* what, int64_t ns, const double*
         return 0;
     });
 }
-void lstm_grad_finish(rnnwf_handle* h) {
+void rnnwf::lstm_grad_finish(rnnwf_handle* h) {
     with_lstm_grad(h, "", [&](auto k) -> int { decltype(k)::unpack(h, (const double*)h->staging); return 0; });
 }
+
+namespace {
 
 int check_ready(rnnwf_handle* h, const char* what) {
     if (int rc = require_lstm(h, what)) return rc;

@@ -122,6 +122,11 @@ PrnnArgs prnn_base_args(rnnwf_handle* h, int64_t ns);
 size_t prnn_hck_bytes_per_block(rnnwf_handle* h);
 // lstm.hip, for the LSTM's gradient (lstm_grad.hip): teacher-forced base pass on h->bits that leaves the checkpoints in h->hck
 int lstm_teacher_base(rnnwf_handle* h, int64_t ns);
+// lstm_grad.hip, for the fused Pauli gradient step (lstm_pauli.hip): the LSTM's backward pass on the batch in h->bits / h->hck, weights
+// from w_dev or (nullptr) from h->eloc and h->moments, the result queued into h->staging; after the caller's synchronisation
+// lstm_grad_finish leaves the TF-named tensors in h->grads
+int lstm_grad_queue(rnnwf_handle* h, const char* what, int64_t ns, const double* w_dev);
+void lstm_grad_finish(rnnwf_handle* h);
 // crnn.hip, for the complex RNN's Pauli pass (crnn_pauli.hip): the same three for the one-layer complex RNN
 int crnn_plain_base(rnnwf_handle* h, const CrnnArgs& a);
 CrnnArgs crnn_base_args(rnnwf_handle* h, int64_t ns);

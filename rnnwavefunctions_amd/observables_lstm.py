@@ -1,0 +1,83 @@
+"""Pauli-string expectation values, energies of arbitrary real spin Hamiltonians, two-point functions and training on such a
+Hamiltonian for the LSTM wave function over the raster path: model LSTM1D_F64, one layer of 1..68 units, float64 - the default cell of
+the reference's 2D raster constructor (rnnwf_pauli_step_lstm, rnnwf_lstm_pauli_gradient_step; docs/pauli_lstm.md).
+
+The estimator, the strings and the Hamiltonians are observables.py's:  v(sigma) = prod_{i in S} s_i * exp(1/2 [log P(sigma ^ F) -
+log P(sigma)]),  E[v] = <psi|O|psi>;  sites in the model's order, the raster index ny * Nx + nx = the column of a (ns, Nx * Ny)
+sample.  observables.pauli_expectations / energy / correlations and training.minimize_hamiltonian keep refusing the LSTM; these are
+its own entry points.  They accept a facade or a NativeWavefunction of the LSTM model and raise ValueError for everything else,
+naming the module that serves that model, before the library is touched.
+
+Not here (docs/lstm.md, "Out of scope"): Renyi-2 regions, minSR and device-resident Adam for the LSTM.
+"""
+from . import _lib
+from . import _observable_api as _api
+from .observables import Hamiltonian, _native, pauli_terms, tfim_hamiltonian, xxz_hamiltonian  # noqa: F401
+
+__all__ = ["pauli_expectations", "energy", "correlations", "minimize_hamiltonian"]
+
+_SERVED_BY = {
+    _lib.MODEL_GRU1D: "observables.py serves the GRU models (observables_stack.py their stacked layers)",
+    _lib.MODEL_GRU1D_F64: "observables.py serves the GRU models (observables_stack.py their stacked layers)",
+    _lib.MODEL_GRU1D_PARITY: "no Pauli pass serves the parity model",
+    _lib.MODEL_CRNN_U1: "observables_complex.py serves the complex RNN",
+    _lib.MODEL_MDRNN2D: "observables_2d.py serves the 2D RNN",
+}
+
+
+def _native_lstm(wf):
+    try:
+        nat = _native(wf)
+    except TypeError as e:
+        raise ValueError(str(e))
+    if nat.model != _lib.MODEL_LSTM1D_F64:
+        raise ValueError("observables_lstm serves the LSTM wave function (LSTM1D_F64) only; %s" % _SERVED_BY.get(nat.model, "this model has no module"))
+    return nat
+
+
+def lr_schedule(learningrate, it):
+    """the learning rate of iteration `it` in training_lstm.run_2DTFIM_1DRNN_LSTM: 1 / (1 / lr + it / 10)"""
+    return 1.0 / ((1.0 / learningrate) + it / 10)
+
+
+def pauli_expectations(wf, strings, numsamples, seed=111, step=0, samples=None):
+    """<psi|P|psi> of every Pauli string P of `strings` (dense "XZIY..." or sparse [("X", i), ...]) with its standard error, from
+    `numsamples` samples: {"value": (K,), "err": (K,)}.  A string with an odd number of Y has expectation exactly 0 in the real state
+    psi = sqrt(P): 0 +- 0, without device work.  samples: (numsamples, N) or (numsamples, Nx, Ny) spins as lstm_gradient takes them;
+    None draws them on the device from (seed, step)."""
+    return _api.pauli_expectations(_api.LSTM, _native_lstm(wf), strings, numsamples, seed, step, samples)
+
+
+def energy(wf, ham, numsamples, seed=111, step=0, samples=None, want_eloc=False):
+    """Energy of `wf` under the Hamiltonian `ham` from `numsamples` samples: {"mean", "var" (population variance of E_loc), "err"
+    (sqrt(var / n)), "eloc" (numsamples,) when want_eloc}.  No batch stays resident: the gradient of this energy is
+    NativeWavefunction.lstm_pauli_gradient_step's."""
+    return _api.energy(_api.LSTM, _native_lstm(wf), ham, numsamples, seed, step, samples, want_eloc)
+
+
+def minimize_hamiltonian(wf, ham, params, numsteps=1000, numsamples=500, learningrate=5e-3, seed=111, scope="RNNwavefunction",
+                         opt=None, comm=None, verbose=False, device_steps=None):
+    """training.minimize_hamiltonian for the LSTM wave function: minimise the energy of `wf` (holding `params`, scoped by `scope`)
+    under `ham` (observables.Hamiltonian) with the host optimizer loop  lstm_pauli_gradient_step (samples, local energies of `ham`,
+    moments and the gradient of the cost, one library call with one host synchronisation) -> training.Adam -> set_params,  the loop
+    of training_lstm.run_2DTFIM_1DRNN_LSTM with its learning rate 1 / (1 / learningrate + it / 10) in iteration it.  Returns
+    (meanEnergy, varEnergy), one entry per iteration 0..numsteps; the trained parameters are left in
+    minimize_hamiltonian.last_params.  The batch of numsamples must fit one pass of the state budget.  Single process only: a
+    communicator is refused.  device_steps is refused: the LSTM has no device-resident Adam (docs/lstm.md, "Out of scope")."""
+    _native_lstm(wf)                                  # another model is told its module before it is told about device_steps
+    meanEnergy, varEnergy, minimize_hamiltonian.last_params = _api.minimize_family(
+        _api.LSTM, _native_lstm, wf, ham, params, numsteps, numsamples, learningrate, seed, scope, opt, comm, verbose, device_steps,
+        lr_of_it=lr_schedule)
+    return meanEnergy, varEnergy
+
+
+def correlations(wf, numsamples, pairs=None, seed=111, step=0, samples=None):
+    """<sz_k>, <sx_k> of every site and, for the listed pairs of distinct sites, <sz_a sz_b>, <sx_a sx_b> and their connected parts,
+    with standard errors, from one pauli_step_lstm call (one X mask per site, one XX mask per pair):
+
+        z, x (N,);  pairs (P, 2);  zz, xx, zz_c = zz - z_a z_b, xx_c = xx - x_a x_b (P,);  "<name>_err" for each.
+
+    pairs: None = every pair (c, k), k != c, with the centre site c = N // 2.  A pair (k, k) raises ValueError.  Errors: the plain
+    std / sqrt(n) (population variance) of the per-sample values s_k, r_k = exp(log r_k), s_a s_b, r_ab, which the call returns as
+    log-ratios and samples; connected parts to first order (delta method), as observables_2d.correlations."""
+    return _api.correlations(_api.LSTM, _native_lstm(wf), numsamples, pairs, seed, step, samples)
