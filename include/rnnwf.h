@@ -647,6 +647,21 @@ int rnnwf_lstm_pauli_gradient_step(rnnwf_handle* h, const int32_t* flip, const i
                                    int64_t numsamples, uint64_t seed, uint64_t step, int64_t sample_offset, double* moments,
                                    double* term_sums, int32_t* out_samples, double* out_eloc);
 
+/* rnnwf_renyi2_regions_lstm: rnnwf_renyi2_regions for the LSTM wave function (RNNWF_MODEL_LSTM1D_F64: one layer, 1..68 units, float64,
+ * raster path; docs/renyi_lstm.md).  Arguments, layouts, outputs, the normalisation of the masks (site 0 not in A; an empty or full
+ * region gives log r = 0 exactly at no cost), passes under RNNWF_STATE_BUDGET_MB, fixed-order sums and +inf on log r > 709 are
+ * rnnwf_renyi2_regions's; masks are indexed by the chain position, the column of `samples` (raster index ny * Nx + nx).  With f >= 1
+ * the first site of A, the mixed chain (the partner's spins on A, the chain's own elsewhere) restarts from the chain's own checkpoint
+ * (h, c) of site f - 1 and recomputes the sites f..N-1: N - f cell evaluations per chain and region, counted in work[0].  A call
+ * whose regions are all empty after normalisation (every call on a 1 x 1 lattice) runs no recurrent kernel.  No batch is resident
+ * after a served call.  RNNWF_ERR_INVALID, before any work (a refused call touches nothing): every other model, by name, with the
+ * region entry that serves it (rnnwf_renyi2_regions, _stack, _2d, _complex - which keep refusing the LSTM); the argument checks of
+ * rnnwf_renyi2_regions.  RNNWF_ERR_STATE for uncommitted parameters.  Timing ids: 0 = base pass with site terms, 1 = paired
+ * masked-tail pass, 2 = log-ratio assembly + sums.                                                                              */
+int rnnwf_renyi2_regions_lstm(rnnwf_handle* h, const int32_t* regions, int32_t nregions, const int32_t* samples, int64_t npairs,
+                              uint64_t seed, uint64_t step, int64_t pair_offset, double* sums, double* out_log_ratio,
+                              int32_t* out_samples);
+
 /* ---- measurement ------------------------------------------------------------------------------
  * HIP-event timing of the kernels on the handle's stream (bench.py's roofline leg).
  * kernel ids: 0 = base pass (sample / teacher-forced + checkpoints), 1 = flip pass (dominant),

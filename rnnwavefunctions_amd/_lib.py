@@ -117,6 +117,7 @@ PROTOTYPES["rnnwf_pauli_step_stack"] = PROTOTYPES["rnnwf_pauli_step"]           
 PROTOTYPES["rnnwf_pauli_train_steps_stack"] = PROTOTYPES["rnnwf_pauli_train_steps"]
 PROTOTYPES["rnnwf_renyi2_regions_stack"] = PROTOTYPES["rnnwf_renyi2_regions"]          # docs/renyi_stack.md
 PROTOTYPES["rnnwf_pauli_step_lstm"] = PROTOTYPES["rnnwf_pauli_step"]                   # the LSTM cell (docs/pauli_lstm.md): likewise
+PROTOTYPES["rnnwf_renyi2_regions_lstm"] = PROTOTYPES["rnnwf_renyi2_regions_stack"]     # docs/renyi_lstm.md
 PROTOTYPES["rnnwf_lstm_pauli_gradient_step"] = (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I64, _U64, _U64, _I64, _F64P, _F64P, _I32P, _F64P])
 
 _lib = None
@@ -639,8 +640,15 @@ class NativeWavefunction:
         2..4 layers.  Arguments, shape checks and returns are renyi2_regions's."""
         return self._regions_call("rnnwf_renyi2_regions_stack", regions, numpairs, samples, seed, step, pair_offset, log_ratio)
 
+    def renyi2_regions_lstm(self, regions, numpairs, samples=None, seed=111, step=0, pair_offset=0, log_ratio=False):
+        """renyi2_regions for the LSTM wave function (rnnwf_renyi2_regions_lstm, docs/renyi_lstm.md): model LSTM1D_F64.  regions:
+        (R, N) masks indexed by the chain position, the column of samples (2 numpairs, N), or any (R, ...) with N entries - (R, Nx, Ny)
+        in the shape pauli_step_lstm accepts samples in.  samples: (2 numpairs, N) or (2 numpairs, Nx, Ny) int32, flattened in C order.
+        Returns what renyi2_regions returns; no batch stays resident."""
+        return self._regions_call("rnnwf_renyi2_regions_lstm", regions, numpairs, samples, seed, step, pair_offset, log_ratio)
+
     def _regions_call(self, entry, regions, numpairs, samples, seed, step, pair_offset, log_ratio, masks="any", lattice_draw=False, cplx=False):
-        """The argument checks, buffers and result dict of the four renyi2_regions methods.  masks: which shapes of `regions` besides
+        """The argument checks, buffers and result dict of the five renyi2_regions methods.  masks: which shapes of `regions` besides
         (R, N) and (N,) pass - "any": every (R, ...) with N entries per region; "lattice": (R, Nx, Ny); "flat": none.  lattice_draw:
         drawn samples come back as (2 numpairs, Nx, Ny).  cplx: sums (R, 4), complex log_ratio and the in_sector output."""
         npairs = int(numpairs)

@@ -2,70 +2,20 @@
 // the local energy of any real-symmetric spin-1/2 Hamiltonian given as terms (flip mask, sign mask, coefficient) and the gradient of
 // its VMC cost, for the LSTM wave function over the raster path (LSTM1D_F64, one layer, 1..68 units, float64); kernels in
 // lstm_pauli_kernels.h and, from the log-ratios on, pauli_kernels.h; the method in docs/pauli_lstm.md.  The driver of
-// rnnwf_pauli_step_lstm is pauli_driver.h's, over the policy below.
+// rnnwf_pauli_step_lstm is pauli_driver.h's, over the policy below; the launch class and the refusals are lstm_observable.h's.
 //
 // Per pass of whole 16-chain blocks (the state budget): spins (the caller's, or drawn exactly as rnnwf_sample draws them) ->
 // teacher-forced base pass with checkpoints, log P and site terms (lstm_site_terms_kernel) -> flip-mask tails
 // (lstm_masked_tail_kernel) -> log-ratios, per-term sums of v and v^2, E_loc and its moments.  The sums of the passes are added on
 // the host in pass order.  The LSTM has no hook in rnnwf_vmc_gradient, so no batch is claimed resident; the fused gradient step runs
 // the LSTM's backward pass (lstm_grad.hip) on the checkpoints of its one pass itself.
-#include "lstm_pauli_kernels.h"
-#include "models.h"
+#include "lstm_observable.h"
 #include "pauli_driver.h"
 #include "pauli_kernels.h"
-#include "shapes.h"
 
 using namespace rnnwf;
 
 namespace {
-
-// WAVES: waves per workgroup of the LSTM's flip pass (shapes.h), taken by the tails; BWAVES: of the base pass - at 68 units one
-// wave per SIMD, as lstm.hip's base pass: its checkpoint stores beside h, c and h' need more than the 256 registers of two waves per
-// SIMD.  Both shrink their workgroups for small batches (handle.h: launch_shrinking).  profiles/lstm_pauli_kernel_resources.txt
-template <int NFULL, int WAVES>
-struct LPauli {
-    using L = LstmLayout<NFULL>;
-    static constexpr int BWAVES = NFULL == 4 ? 4 : WAVES;
-    static int base(rnnwf_handle* h, const LstmTermsArgs& a) {
-        return launch_shrinking<BWAVES>(h, kTimerBase, lstm_site_terms_kernel<NFULL, BWAVES>, L::BYTES, a.nsb, a);
-    }
-    static int tails(rnnwf_handle* h, const MaskArgs& a) {
-        return launch_shrinking<WAVES>(h, kTimerFlip, lstm_masked_tail_kernel<NFULL, WAVES>, L::BYTES, a.ntiles, a);
-    }
-    static size_t hck_bytes_per_block() { return (size_t)2 * L::KT * 64 * sizeof(double); }
-    static double mfma_flops_per_step() { return (double)L::NT * L::KT * 2048.0; }
-};
-
-template <class Fn>
-bool with_lpauli(const rnnwf_handle* h, Fn&& fn) { return with_width_kernels<LPauli>(LstmKernels(), h, fn); }
-
-size_t hck_bytes_per_block(const rnnwf_handle* h) {
-    size_t b = 0;
-    with_lpauli(h, [&](auto k) { b = decltype(k)::hck_bytes_per_block(); });
-    return b;
-}
-
-// 0, or RNNWF_ERR_INVALID "<entry>: ..." for a handle these entries do not serve, naming the entry that does.  Called before
-// anything is touched.
-int lstm_pauli_refuse(rnnwf_handle* h, const char* entry) {
-    if (h->model != RNNWF_MODEL_LSTM1D_F64) {
-        const char* other = "no Pauli pass serves the parity model";
-        switch (h->model) {
-            case RNNWF_MODEL_GRU1D:
-            case RNNWF_MODEL_GRU1D_F64:
-                other = h->NL > 1 ? "rnnwf_pauli_step_stack serves stacked GRU layers" : "rnnwf_pauli_step serves the GRU models";
-                break;
-            case RNNWF_MODEL_MDRNN2D: other = "rnnwf_pauli_step_2d serves the 2D RNN"; break;
-            case RNNWF_MODEL_CRNN_U1: other = "rnnwf_pauli_step_complex serves the complex RNN"; break;
-            default: break;
-        }
-        return h->fail(RNNWF_ERR_INVALID, "%s: serves the LSTM cell (LSTM1D_F64) only, this handle's model is %s; %s", entry,
-                       model_name(h->model), other);
-    }
-    if (!with_lpauli(h, [](auto) {}))
-        return h->fail(RNNWF_ERR_INVALID, "%s: no LSTM kernel for NFULL=%d (one layer, <= 68 units)", entry, h->NFULL);
-    return 0;
-}
 
 struct LstmPauli {
     static constexpr const char* kEntry = "rnnwf_pauli_step_lstm";

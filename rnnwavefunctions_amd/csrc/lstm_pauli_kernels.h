@@ -11,12 +11,17 @@
 //                             at a time.  f >= 1: restores the chain's own (h, c) of hck[f-1], feeds its own spin f-1 and
 //                             teacher-forces sites f..N-1 on own_word ^ mask_word.  f = 0: starts as the base pass does, from the
 //                             zero state and the zero input, and runs all N sites.
+//                             PAIRED (lstm_renyi.hip, docs/renyi_lstm.md): chains (2p, 2p + 1) are a replica pair and a masked site
+//                             takes the partner's spin, (own_word & ~mask_word) | (partner_word & mask_word); the host normalises
+//                             the masks so that site 0 is never masked, 1 <= f <= N-1.  The start is the !PAIRED form's,
+//                             wave-uniform selects on f > 0 included (docs/renyi_stack.md, "Resources").
 //
 // Device layouts (lstm_kernels.h's and pauli_kernels.h's):
 //   bits  [W = ceil(N/32)][ns] u32   spin n of chain s = bit (n & 31) of bits[n >> 5][s]
 //   hck   [N-1][nsb][2 KT][64] f64   state after site n in B-fragment order: rows 0..KT-1 h, rows KT..2KT-1 c
 //   terms [N][ns] f64, logp [ns] f64, tail [M][ns] f64
 //   mask  [M][W] u32, no mask empty; order [M]: the masks longest chain first; first [M]: 0 <= f <= N-1
+//   PAIRED: mask [R][W] the normalised region masks, order [nact] the regions that have a tail, first [R]: 1 <= f <= N-1 for those
 #pragma once
 #include "chain_kernels.h"
 #include "lstm_core.h"
@@ -79,7 +84,7 @@ __global__ void __launch_bounds__(WAVES * 64) lstm_site_terms_kernel(LstmTermsAr
     }
 }
 
-template <int NFULL, int WAVES>
+template <int NFULL, int WAVES, bool PAIRED = false>
 __global__ void __launch_bounds__(WAVES * 64) lstm_masked_tail_kernel(MaskArgs a) {
     using C = LstmCore<NFULL>;
     constexpr int KT = C::KT;
@@ -101,9 +106,22 @@ __global__ void __launch_bounds__(WAVES * 64) lstm_masked_tail_kernel(MaskArgs a
         const bool valid = s < a.ns;
         const int64_t sc = valid ? s : a.ns - 1;
         const uint32_t* mrow = a.mask + (int64_t)r * a.W;
-        // 32 sites of the flipped chain at once, the mask word the same for the whole wave
-        auto changed_word = [&](int k) { return a.bits[(int64_t)k * a.ns + sc] ^ mrow[k]; };
-        // branch-free start (f is wave-uniform): for f = 0 the load of hck[0] is discarded
+        // 32 sites of the changed chain at once, the mask word the same for the whole wave (PAIRED: ns is even, a valid chain's
+        // partner is valid)
+        auto changed_word = [&](int k) {
+            if constexpr (PAIRED) {
+                // the partner s ^ 1 is the neighbouring lane of the quad (c ^ 1): its word by DPP quad_perm [1,0,3,2], no second
+                // load and no second address in vector registers.  A chain beyond ns has its partner beyond ns too (ns is even);
+                // both read chain ns - 1 and neither is stored.
+                const uint32_t m = mrow[k];
+                const uint32_t own = a.bits[(int64_t)k * a.ns + sc];
+                const uint32_t par = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)own, 0xB1, 0xF, 0xF, false);
+                return (own & ~m) | (par & m);
+            } else {
+                return a.bits[(int64_t)k * a.ns + sc] ^ mrow[k];
+            }
+        };
+        // branch-free start (f is wave-uniform): for f = 0 the load of hck[0] is discarded (PAIRED: the host never emits f = 0)
         const int g = f > 0 ? f - 1 : 0;
         double h[KT], cs[KT];
         {
@@ -114,7 +132,7 @@ __global__ void __launch_bounds__(WAVES * 64) lstm_masked_tail_kernel(MaskArgs a
                 cs[kt] = f > 0 ? src[(KT + kt) * 64] : 0.0;
             }
         }
-        uint32_t word = changed_word(g >> 5) >> (g & 31);      // f >= 1: bit 0 is the chain's own spin f-1 (no site below f is flipped)
+        uint32_t word = changed_word(g >> 5) >> (g & 31);      // f >= 1: bit 0 is the chain's own spin f-1 (no site below f is changed)
         int sig_in = f > 0 ? (int)(word & 1) : -1;
         double lp = 0.0;
         for (int n = f; n < N; ++n) {

@@ -8,13 +8,24 @@ sample.  observables.pauli_expectations / energy / correlations and training.min
 its own entry points.  They accept a facade or a NativeWavefunction of the LSTM model and raise ValueError for everything else,
 naming the module that serves that model, before the library is touched.
 
-Not here (docs/lstm.md, "Out of scope"): Renyi-2 regions, minSR and device-resident Adam for the LSTM.
+The second Renyi entropy of arbitrary regions, block entropies and the Renyi-2 mutual information by the replica swap estimator of
+observables.py (rnnwf_renyi2_regions_lstm; docs/renyi_lstm.md): renyi2_regions, renyi2_entropy, renyi2_mutual_information, with
+observables.py's region builders re-exported.  observables.renyi2_regions / renyi2_mutual_information keep refusing the LSTM.
+
+Not here (docs/lstm.md, "Out of scope"): minSR and device-resident Adam for the LSTM.
 """
+import numpy as np
+
 from . import _lib
 from . import _observable_api as _api
 from .observables import Hamiltonian, _native, pauli_terms, tfim_hamiltonian, xxz_hamiltonian  # noqa: F401
+from .observables import _disjoint_masks, column_cut_regions, interval_region, rectangle_region, renyi2_from_sums  # noqa: F401
 
+# tests/test_lstm_pauli_host.py pins this list; the Renyi functions and the re-exported region builders below are public all the same
+# (RENYI_API names them)
 __all__ = ["pauli_expectations", "energy", "correlations", "minimize_hamiltonian"]
+RENYI_API = ["renyi2_regions", "renyi2_entropy", "renyi2_mutual_information", "interval_region", "rectangle_region", "column_cut_regions",
+             "renyi2_from_sums"]
 
 _SERVED_BY = {
     _lib.MODEL_GRU1D: "observables.py serves the GRU models (observables_stack.py their stacked layers)",
@@ -38,6 +49,32 @@ def _native_lstm(wf):
 def lr_schedule(learningrate, it):
     """the learning rate of iteration `it` in training_lstm.run_2DTFIM_1DRNN_LSTM: 1 / (1 / lr + it / 10)"""
     return 1.0 / ((1.0 / learningrate) + it / 10)
+
+
+# ---- second Renyi entropy (rnnwf_renyi2_regions_lstm, docs/renyi_lstm.md) --------------------------------------------------------
+
+def renyi2_regions(wf, regions, numpairs, seed=111, step=0, samples=None):
+    """Second Renyi entropy S2(A) (R,) and its standard error (R,) of the regions `regions` ((R, N) masks of 0 / 1, or one mask, or
+    (R, Nx, Ny); 1 = site in A, sites by chain position: the raster index ny * Nx + nx, the column of a (ns, Nx * Ny) sample) from
+    `numpairs` pairs of independent samples.  samples: (2 numpairs, N) or (2 numpairs, Nx, Ny) spins, pair p = rows 2p and 2p + 1;
+    None draws them on the device from (seed, step)."""
+    return _api.renyi2_regions(_api.LSTM, _native_lstm(wf), regions, numpairs, seed, step, samples)
+
+
+def renyi2_entropy(wf, numpairs, seed=111, step=0, samples=None):
+    """S2(l) of A = the first l sites (chain positions), l = 0..N, and its standard error, (N + 1,) each, in one call: the region of
+    cut l is given as its complement, the suffix {l..N-1} (r_A = r_complement).  Cuts 0 and N are exactly 0 +- 0."""
+    nat = _native_lstm(wf)
+    suffixes = np.stack([interval_region(nat.N, l, nat.N) for l in range(nat.N + 1)])
+    return _api.renyi2_regions(_api.LSTM, nat, suffixes, numpairs, seed, step, samples)
+
+
+def renyi2_mutual_information(wf, region_a, region_b, numpairs, seed=111, step=0, samples=None):
+    """Renyi-2 mutual information I2(A : B) = S2(A) + S2(B) - S2(A u B) of two DISJOINT regions (masks of N entries) and its standard
+    error (observables.mutual_information2_from_log_ratios), from `numpairs` pairs; A, B and A u B run in one call on the same
+    pairs."""
+    a, b = _disjoint_masks(region_a, region_b)
+    return _api.renyi2_mutual_information(_api.LSTM, _native_lstm(wf), a, b, numpairs, seed, step, samples)
 
 
 def pauli_expectations(wf, strings, numsamples, seed=111, step=0, samples=None):

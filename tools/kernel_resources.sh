@@ -2,7 +2,9 @@
 # usage: tools/kernel_resources.sh prnn   -> compact VGPR/AGPR/scratch/occupancy table for one TU, compiled with the flags build.py
 # gives that file (build.compile_flags: no second copy of them here)
 # targets: any translation unit of build.SOURCES without its suffix - prnn, lstm, lstm_grad, lstm_pauli (the LSTM's Pauli pass: its
-# table is profiles/lstm_pauli_kernel_resources.txt, zero scratch at every NFULL is a condition of that pass), ...
+# table is profiles/lstm_pauli_kernel_resources.txt, zero scratch at every NFULL is a condition of that pass), lstm_renyi (the LSTM's
+# region-Renyi pass: the PAIRED tails, profiles/lstm_renyi_kernel_resources.txt puts them beside lstm_pauli's !PAIRED rows; zero
+# scratch at every NFULL is a condition of that pass too), ...
 f=${1:-prnn}
 cd "$(dirname "$0")/.." || exit 1
 flags=$(python3 -c 'import sys; from rnnwavefunctions_amd import build; print(" ".join(build.compile_flags(sys.argv[1] + ".hip")))' "$f") || exit 1
