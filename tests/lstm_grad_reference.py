@@ -26,6 +26,53 @@ NS = 40                    # two full 16-chain blocks and a ragged one of 8
 WIDTHS = (10, 16, 17, 20, 21, 33, 36, 37, 50, 52, 53, 67, 68)
 LATTICES = ((11, 3), (17, 2), (7, 5), (2, 1))      # 33 to 35 sites: the spin-word boundary is crossed; 2 x 1: a single checkpoint
 SHARP = 3.0
+# one to five spin words: where lstm_bwd_kernel's word walk (wcur, wlow, spin_in) swaps, refetches and hands a spin over
+BIG_LATTICES = (
+    (8, 4),       # 32 sites: one full word; wlow never loaded
+    (16, 4),      # 64 sites: two full words; the swap at 32, no refetch
+    (13, 5),      # 65 sites: one site in the third word; the refetch at n = 64 reads word 0
+    (12, 8),      # 96 sites: three full words
+    (10, 10),     # 100 sites: the benchmarked size
+    (12, 12),     # 144 sites: five words; refetches at 128, 96 and 64
+)
+BIG_NFULL_LATTICES = ((13, 5), (10, 10), (12, 12))       # each of these also at one width of every NFULL
+BIG_NFULL_WIDTHS = (20, 36, 52, 68)
+# (lattice, units): sharp where it is not SHARP.  17 units with kernels x 3 is nearly polarised (float64 sampler, 400 draws: 92 to 98 %
+# ones at sites 31 and 63 on 13 x 5 and 10 x 10, 90 % at x 2, 84 % at x 1.5), so 40 rows would often hold one spin value at a word
+# boundary; with the kernels as initialised it is 70 to 75 %.  No other case is above 87 % at either site.  13 x 5 / 17 is a GPU case
+# (big_cases), 10 x 10 / 17 the second fixture of tests/test_lstm_grad_reference.py.
+BIG_SHARP = {((13, 5), 17): 1.0, ((10, 10), 17): 1.0}
+WIDE = dict(shape=(10, 10), ns=1000, configs=NS, widths=(21, 50, 68))      # 62 full blocks and a ragged one of 8
+
+
+def big_cases():
+    """[(lattice, units)]: every width on BIG_LATTICES in rotation, then BIG_NFULL_WIDTHS on each of BIG_NFULL_LATTICES"""
+    return [(BIG_LATTICES[k % len(BIG_LATTICES)], u) for k, u in enumerate(WIDTHS)] + \
+           [(s, u) for s in BIG_NFULL_LATTICES for u in BIG_NFULL_WIDTHS]
+
+
+def big_sharp(shape, units):
+    return BIG_SHARP.get((tuple(shape), units), SHARP)
+
+
+def word_boundaries_mixed(samples, w):
+    """both spin values at site 63, and at site 31 where the lattice has them, among the rows with non-zero weight: the spins the word
+    walk hands over from bit 31 of the word below"""
+    s = np.asarray(samples).reshape(len(samples), -1)[np.asarray(w) != 0.0]
+    return all(len(np.unique(s[:, n])) == 2 for n in (31, 63) if n < s.shape[1])
+
+
+def wide_batch(configs, ns):
+    """(ns, N) rows repeating the distinct configurations, and the index of each row's configuration: row r holds configuration
+    (7 r + 3 (r // 16)) mod m, so the 16 rows of a block differ from one another and the blocks from their neighbours"""
+    c = np.asarray(configs).reshape(len(configs), -1)
+    m = len(c)
+    assert m >= 16 and m % 7 and len(np.unique(c, axis=0)) == m
+    r = np.arange(ns)
+    idx = (7 * r + 3 * (r // 16)) % m
+    for b in range(0, ns, 16):
+        assert len(set(idx[b:b + 16])) == len(idx[b:b + 16])
+    return np.ascontiguousarray(c[idx]), idx
 
 
 def nfull(units):

@@ -5,8 +5,10 @@ EVERY element of every tensor of lstm_gradient against one float64 reverse-mode 
 (33 to 35 sites: the spin-word boundary is crossed) and 2 x 1 (a single checkpoint), 40 samples (two full 16-chain blocks and a ragged
 one of 8) drawn with vmc_step on sharpened weights, weights with both signs and exact zeros.  The bound is the float64 families' of
 tests/test_gpu_gradient_classes.py: autograd_reference.verdict with unit_roundoff_ratio 2^-29, FACTOR 16 and that module's rounding
-floor; tests/test_lstm_grad_reference.py shows on the reference alone what it rejects.  Then: a long batch whose blocks outnumber the
-persistent grid's waves; exact zero for zero weights, bit-identical repeats, additivity in the weights; the fused step against
+floor; tests/test_lstm_grad_reference.py shows on the reference alone what it rejects.  The same on lattices of one to five spin words (LG.BIG_LATTICES: 32, 64, 65, 96, 100
+and 144 sites, every width in rotation and every NFULL at 65, 100 and 144 sites), where the backward pass's word walk swaps and
+refetches; a wide batch at 10 x 10 (1 000 rows, NFULL 2 to 4) that fills many workgroups and gives the weight-gradient product blocks
+longer than its floor.  Then: a long batch whose blocks outnumber the persistent grid's waves, at every NFULL; exact zero for zero weights, bit-identical repeats, additivity in the weights; the fused step against
 vmc_step + lstm_gradient bit for bit; every gradient along five iterations of the driver's loop; training against the float64 GRU;
 the refusals.
 """
@@ -78,10 +80,77 @@ def test_every_gradient_element(shape, units):
     assert not failures, "tensors beyond %g x the bound: %s" % (A.FACTOR, failures)
 
 
-def test_long_batch_wraps_the_persistent_grid():
-    """2 x 2, 10 units, 40 000 samples = 2 500 blocks of 16 chains: more than the grid's waves (four per workgroup, two workgroups
-    per CU by registers: profiles/lstm_grad_kernel_resources.txt), so waves walk several blocks and sum their head rows over them."""
-    shape, units, ns = (2, 2), 10, 40000
+BIG_CASES = LG.big_cases()
+
+
+@pytest.mark.parametrize("shape,units", BIG_CASES, ids=["%dx%d-%d" % (s[0], s[1], u) for s, u in BIG_CASES])
+def test_every_gradient_element_on_one_to_five_spin_words(shape, units):
+    """test_every_gradient_element on LG.BIG_LATTICES (32, 64, 65, 96, 100 and 144 sites): the backward pass's spin-word walk swaps at
+    every multiple of 32 and refetches from site 64 down.  The drawn rows with non-zero weight hold both spin values at sites 31 and
+    63, so a spin handed over from the wrong word changes the gradient (tests/test_lstm_grad_reference.py: by 1e12 bounds)."""
+    t0 = time.time()
+    prm = LG.parameters(units, sharp=LG.big_sharp(shape, units))
+    wf = handle(shape, units, prm)
+    s, _, _ = drawn(wf, shape, LG.NS)
+    w = LG.weights(LG.NS)
+    wf.timing_enable(True)
+    wf.timing_reset()
+    grads = native_gradient(wf, prm, s, w)
+    launches = wf.timing_get(3)["launches"], wf.timing_get(4)["launches"]
+    wf.close()
+    ones = s.reshape(LG.NS, -1)[w != 0.0].mean(axis=0)
+    print("LSTMGRAD [lstm-%dx%d-%d] sharp %g: ones among the weighted rows %.2f at site 31%s, %.2f overall"
+          % (shape[0], shape[1], units, LG.big_sharp(shape, units), ones[31], ", %.2f at site 63" % ones[63] if len(ones) > 63 else "",
+             ones.mean()))
+    assert LG.word_boundaries_mixed(s, w)
+    ref = LG.reference(prm, s, w)
+    label = "[lstm-%dx%d-%d]" % (shape[0], shape[1], units)
+    worst, failures = checked(label, prm, grads, ref)
+    print("LSTMGRAD %s NFULL %d: launches %d + %d, worst deviation / bound %.3f (limit %g), reference %.2f s, case %.2f s"
+          % (label, LG.nfull(units), launches[0], launches[1], worst, A.FACTOR, ref.seconds, time.time() - t0))
+    assert launches == (1, 1)
+    assert not failures, "tensors beyond %g x the bound: %s" % (A.FACTOR, failures)
+
+
+@pytest.mark.parametrize("units", LG.WIDE["widths"])
+def test_wide_batch_fills_many_workgroups_and_long_gemm_blocks(units):
+    """10 x 10, 1 000 rows = 62 full 16-chain blocks and a ragged one of 8: more than one workgroup of four waves, so head_reduce_kernel
+    sums head rows over several workgroups, and N ns = 100 000 rows > 256 cu_count, so tn_gemm_launch_cols gives every block of the
+    weight-gradient product more than its floor of 64 rows.  The rows repeat 40 device-drawn configurations, the 16 of a block all
+    different, each row with a weight of its own (LG.wide_batch); the floor comes from the 40 configurations' terms."""
+    t0 = time.time()
+    shape, ns = LG.WIDE["shape"], LG.WIDE["ns"]
+    N = shape[0] * shape[1]
+    prm = LG.parameters(units)
+    wf = handle(shape, units, prm)
+    configs, _, _ = drawn(wf, shape, LG.WIDE["configs"])
+    s, _ = LG.wide_batch(configs, ns)
+    w = LG.weights(ns)
+    wf.timing_enable(True)
+    wf.timing_reset()
+    grads = native_gradient(wf, prm, s, w)
+    launches = wf.timing_get(3)["launches"], wf.timing_get(4)["launches"]
+    cus = wf.device_info()["cu_count"]
+    wf.close()
+    assert N * ns > 256 * cus                                       # rows per block of the product: ceil(N ns / (4 cu_count)) > 64
+    assert (ns + 15) // 16 > 4 and ns % 16 == 8                     # more than one workgroup of four waves; a ragged last block
+    assert LG.word_boundaries_mixed(s, w)
+    ref = LG.reference(prm, s, w, keep_terms=False)
+    label = "[lstm-10x10-%d-%d]" % (units, ns)
+    worst, failures = checked(label, prm, grads, ref)
+    print("LSTMGRAD %s NFULL %d: launches %d + %d, worst deviation / bound %.3f (limit %g), reference %.2f s, case %.2f s"
+          % (label, LG.nfull(units), launches[0], launches[1], worst, A.FACTOR, ref.seconds, time.time() - t0))
+    assert launches == (1, 1)
+    assert not failures, "tensors beyond %g x the bound: %s" % (A.FACTOR, failures)
+
+
+@pytest.mark.parametrize("units", [10, 36, 52, 68])
+def test_long_batch_wraps_the_persistent_grid(units):
+    """2 x 2, 40 000 samples = 2 500 blocks of 16 chains: more than the grid's waves (four per workgroup, at most two workgroups per
+    CU by registers: profiles/lstm_grad_kernel_resources.txt), so waves walk several blocks and sum their head rows over them - at 52
+    and 68 units (NFULL 3 and 4, one workgroup per CU) with the backward operand streamed through L2."""
+    t0 = time.time()
+    shape, ns = (2, 2), 40000
     prm = LG.parameters(units)
     wf = handle(shape, units, prm)
     s, _, _ = drawn(wf, shape, ns)
@@ -91,8 +160,10 @@ def test_long_batch_wraps_the_persistent_grid():
     wf.close()
     assert (ns + 15) // 16 > 2 * 4 * cus
     ref = LG.reference(prm, s, w, keep_terms=False)
-    worst, failures = checked("[lstm-2x2-10-40000]", prm, grads, ref)
-    print("LSTMGRAD long batch: worst deviation / bound %.3f (limit %g), reference %.2f s" % (worst, A.FACTOR, ref.seconds))
+    label = "[lstm-2x2-%d-%d]" % (units, ns)
+    worst, failures = checked(label, prm, grads, ref)
+    print("LSTMGRAD long batch %s NFULL %d: worst deviation / bound %.3f (limit %g), reference %.2f s, case %.2f s"
+          % (label, LG.nfull(units), worst, A.FACTOR, ref.seconds, time.time() - t0))
     assert not failures, "tensors beyond %g x the bound: %s" % (A.FACTOR, failures)
 
 
@@ -116,8 +187,9 @@ def test_identities():
         assert not failures, (label, failures)
 
 
-def test_fused_step_is_vmc_step_plus_lstm_gradient_bit_for_bit():
-    shape, units, ns = (7, 5), 37, 200
+@pytest.mark.parametrize("shape,units", [((7, 5), 37), ((10, 10), 50)], ids=["7x5-37", "10x10-50"])
+def test_fused_step_is_vmc_step_plus_lstm_gradient_bit_for_bit(shape, units):
+    ns = 200
     prm = LG.parameters(units, sharp=1.5)
     wf = handle(shape, units, prm)
     fused = wf.lstm_vmc_gradient_step(ns, seed=111, step=3, couplings=couplings(shape), shapes=LG.shapes(prm), want_samples=True,

@@ -318,9 +318,10 @@ def test_refusals_through_the_c_call_and_the_module():
 
 # ---- 5. the fused gradient step ---------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("units", [20, 53])
-def test_fused_step_is_pauli_step_plus_lstm_gradient_bit_for_bit(units):
-    shape, ns = (4, 3), 200
+# 13 x 5: 65 sites, the backward pass's spin-word walk refetches word 0 at n = 64 (tests/test_gpu_lstm_grad.py)
+@pytest.mark.parametrize("shape,units", [((4, 3), 20), ((4, 3), 53), ((13, 5), 37)], ids=["20", "53", "13x5-37"])
+def test_fused_step_is_pauli_step_plus_lstm_gradient_bit_for_bit(shape, units):
+    ns = 200
     prm = LG.parameters(units, sharp=1.5)
     ham = xxz_lattice(*shape)
     wf = handle(shape, units, prm)

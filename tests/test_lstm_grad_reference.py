@@ -6,10 +6,14 @@
   ragged block's last chain dropped, the last site's term dropped, the forget bias left out of sigmoid(f), dc_carry without its factor
   f, the one-hot fed into site 32 taken from site 31, or any one tensor x 1.001 - and ACCEPTS the float64 gradient summed in another
   order.
+* Beyond two spin words (13 x 5 at 37 units, 10 x 10 at 17 units) it REJECTS the one-hot fed into site 64 taken from site 31 (bit 31
+  of the wrong word), word 0 read as zeros (the refetch at n = 64 skipped) and the wide batch without its ragged block's last chain,
+  and ACCEPTS the other summation order; the wide batch's grouped floor is the row-by-row one; BIG_LATTICES holds what it must.
 * The new C entries are declared, exported and bound, and the Python wrappers validate shapes and the weights' length before any
   library call.
 """
 import ctypes
+import functools
 import os
 import re
 
@@ -110,6 +114,93 @@ def test_case_table_covers_every_width_class():
     assert sorted({LG.nfull(u) for u in LG.WIDTHS}) == [1, 2, 3, 4]
     assert {16 * nf + 4 for nf in (1, 2, 3, 4)} <= set(LG.WIDTHS)                    # full mixed tile at every NFULL
     assert all(33 <= a * b <= 35 for a, b in LG.LATTICES[:3]) and LG.LATTICES[3] == (2, 1)
+
+
+# ---- beyond two spin words and one workgroup (BIG_LATTICES, the wide batch) ------------------------------------------------------------
+
+BIG = [((13, 5), 37), ((10, 10), 17)]
+
+
+@functools.lru_cache(maxsize=None)
+def big(shape, units):
+    """40 lstm_sample draws at the case table's sharp (10 x 10 / 17: 1, where the draw is not polarised), both spin values at sites 31
+    and 63 among the rows with non-zero weight"""
+    prm = LG.parameters(units, sharp=LG.big_sharp(shape, units))
+    u = np.random.RandomState(5).random_sample((LG.NS, shape[0] * shape[1]))
+    s = LR.lstm_sample(prm, shape[0], shape[1], u)[0]
+    w = LG.weights(LG.NS)
+    assert LG.word_boundaries_mixed(s, w)
+    return prm, s, w, LG.reference(prm, s, w)
+
+
+@pytest.fixture(scope="module", params=BIG, ids=["%dx%d-%d" % (s[0], s[1], u) for s, u in BIG])
+def big_case(request):
+    return big(*request.param)
+
+
+def test_the_bound_rejects_a_wrong_word_walk(big_case):
+    prm, s, w, ref = big_case
+    fed = s.copy()
+    fed[:, 63] = s[:, 31]                               # what site 64 is fed: site 63's spin, taken from bit 31 of word 0 instead of word 1
+    assert ((fed[:, 63] != s[:, 63]) & (w != 0.0)).sum() >= 2
+    assert rejected("one-hot fed into site 64 taken from site 31", big_case, LG.gradient(prm, s, w, inputs=fed))
+    low = s.copy()
+    low[:, :32] = 0                                     # the refetch at n = 64 skipped: wlow stays 0 and becomes wcur at n = 32
+    assert (np.any(low != s, axis=1) & (w != 0.0)).sum() >= 2
+    assert rejected("word 0 read as zeros", big_case, LG.gradient(prm, low, w))
+
+
+def test_the_bound_accepts_another_summation_order_at_these_sizes(big_case):
+    prm, s, w, ref = big_case
+    g = {k: np.add.reduce(t[::-1], axis=0) for k, t in ref.terms.items()}
+    assert any(not np.array_equal(g[k], ref.g64[k]) for k in g)
+    worst, failures = LG.judge("[reversed order]", g, ref, echo=lambda *_: None)
+    print("reversed order: worst deviation / bound %.3g" % worst)
+    assert not failures and worst <= A.FACTOR
+
+
+def test_the_bound_rejects_the_wide_batch_without_its_last_chain():
+    """the wide batch of tests/test_gpu_lstm_grad.py (1 000 rows of 40 configurations, 62 full blocks and a ragged one of 8) on the
+    10 x 10 fixture's draws: the ragged block's last chain dropped"""
+    prm, configs, _, _ = big(*BIG[1])
+    ns = LG.WIDE["ns"]
+    s, idx = LG.wide_batch(configs, ns)
+    w = LG.weights(ns)
+    assert s.shape == (ns, 100) and ns % 16 == 8 and w[-1] != 0.0 and sorted(set(idx)) == list(range(LG.NS))
+    wide = prm, s, w, LG.reference(prm, s, w, keep_terms=False)
+    assert rejected("last chain of the wide batch's ragged block dropped", wide, LG.gradient(prm, s[:-1], w[:-1]))
+    worst, failures = LG.judge("[reference itself]", wide[3].g64, wide[3], echo=lambda *_: None)
+    assert worst == 0.0 and not failures
+
+
+def test_wide_batch_floor_equals_the_per_sample_one():
+    """the wide batch's floor sums the terms per distinct configuration, rows with independent weights: the same sums as row by row"""
+    prm = LG.parameters(10)
+    configs = np.unique(np.random.RandomState(9).randint(0, 2, size=(60, 9)), axis=0)[:20]
+    s, idx = LG.wide_batch(configs, 200)
+    w = LG.weights(200)
+    assert len(configs) == 20 and len(set(idx)) == 20 and np.array_equal(s, configs[idx])
+    assert all(len(np.unique(s[b:b + 16], axis=0)) == len(s[b:b + 16]) for b in range(0, 200, 16))
+    direct = {k: np.abs(t).sum(axis=0) for k, t in LG.per_sample_terms(prm, s, w).items()}
+    grouped = LG.abs_term_sums(prm, s, w)
+    for k in direct:
+        assert np.allclose(grouped[k], direct[k], rtol=1e-12, atol=0.0), k
+    a, b = LG.reference(prm, s, w), LG.reference(prm, s, w, keep_terms=False)
+    assert all(np.isclose(a.floor[k], b.floor[k], rtol=1e-12) for k in a.floor)
+    assert all(np.array_equal(a.g64[k], b.g64[k]) for k in a.g64)
+
+
+def test_big_case_table_covers_the_word_walk_at_every_nfull():
+    sites = [a * b for a, b in LG.BIG_LATTICES]
+    assert {32, 64, 65} <= set(sites)
+    assert any(n > 64 and n % 32 == 0 for n in sites)                                # full words above the first refetch
+    assert any((n + 31) // 32 >= 5 for n in sites)                                   # refetches at 128, 96 and 64
+    cases = LG.big_cases()
+    assert len(cases) == len(set(cases)) and {u for _, u in cases} == set(LG.WIDTHS) and {s for s, _ in cases} == set(LG.BIG_LATTICES)
+    for n in (65, 100, 144):
+        assert {LG.nfull(u) for s, u in cases if s[0] * s[1] == n} == {1, 2, 3, 4}, n
+    assert all(key in cases or key == BIG[1] for key in LG.BIG_SHARP)                # no override without its case
+    assert {LG.nfull(u) for u in LG.WIDE["widths"]} == {2, 3, 4} and LG.WIDE["ns"] % 16 == 8
 
 
 # ---- host side of the new entries -------------------------------------------------------------------------------------------------
