@@ -662,6 +662,30 @@ int rnnwf_renyi2_regions_lstm(rnnwf_handle* h, const int32_t* regions, int32_t n
                               uint64_t seed, uint64_t step, int64_t pair_offset, double* sums, double* out_log_ratio,
                               int32_t* out_samples);
 
+/* ---- device-resident Adam training of the LSTM wave function (RNNWF_MODEL_LSTM1D_F64; docs/lstm.md, "Device-resident training") ----
+ * rnnwf_adam_step, rnnwf_train_steps, rnnwf_pauli_train_steps* and rnnwf_device_training_supported keep refusing an LSTM handle;
+ * these two are its K iterations (1 <= K <= 1024) with ONE host synchronisation behind the last.  Both run, per iteration and
+ * without a host visit, the kernels of the host loop's fused call, Adam in f64 on the device-resident flat parameters and the
+ * re-pack of the forward image and of the backward operand from the recorded tables of their host packers: a trajectory equals the
+ * host loop's (the fused call, the optimizer's arithmetic on the host, rnnwf_set_params_flat) bit for bit.
+ * rnnwf_lstm_train_steps: rnnwf_train_steps's arguments and outputs; iteration k is rnnwf_lstm_vmc_gradient_step at step index
+ *   step0 + k followed by the update with learning_rates[k].
+ * rnnwf_lstm_pauli_train_steps: rnnwf_pauli_train_steps's arguments and outputs; iteration k is rnnwf_lstm_pauli_gradient_step.
+ * Afterwards, as after rnnwf_train_steps: no batch is resident, rnnwf_get_param and rnnwf_commit_params see the device's
+ * parameters, rnnwf_set_param / rnnwf_set_params_flat replace them, and Adam's moments and step count are read and set with
+ * rnnwf_adam_get_state / rnnwf_adam_set_state (which serve an LSTM handle).  Refused before anything is touched: RNNWF_ERR_INVALID
+ * for any other model ("needs an LSTM1D_F64 handle"), a handle with a communicator ("single process only"), K outside 1..1024, a
+ * non-finite learning rate and the argument refusals of the entries they mirror; RNNWF_ERR_STATE for uncommitted parameters;
+ * RNNWF_ERR_NOMEM "... exceed the state budget of one pass; split the batch".  An error inside the loop: the updates already
+ * applied count in Adam's step count, and no batch or gradient is left.                                                          */
+int rnnwf_lstm_train_steps(rnnwf_handle* h, int32_t K, int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset,
+                           const double* couplings, int64_t n_couplings, const double* learning_rates, double beta1, double beta2,
+                           double epsilon, double* moments);
+int rnnwf_lstm_pauli_train_steps(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff, int32_t nterms,
+                                 int32_t K, int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset,
+                                 const double* learning_rates, double beta1, double beta2, double epsilon, double* moments,
+                                 double* term_sums, double* out_eloc);
+
 /* ---- measurement ------------------------------------------------------------------------------
  * HIP-event timing of the kernels on the handle's stream (bench.py's roofline leg).
  * kernel ids: 0 = base pass (sample / teacher-forced + checkpoints), 1 = flip pass (dominant),

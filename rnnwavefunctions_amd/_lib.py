@@ -119,6 +119,8 @@ PROTOTYPES["rnnwf_renyi2_regions_stack"] = PROTOTYPES["rnnwf_renyi2_regions"]   
 PROTOTYPES["rnnwf_pauli_step_lstm"] = PROTOTYPES["rnnwf_pauli_step"]                   # the LSTM cell (docs/pauli_lstm.md): likewise
 PROTOTYPES["rnnwf_renyi2_regions_lstm"] = PROTOTYPES["rnnwf_renyi2_regions_stack"]     # docs/renyi_lstm.md
 PROTOTYPES["rnnwf_lstm_pauli_gradient_step"] = (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I64, _U64, _U64, _I64, _F64P, _F64P, _I32P, _F64P])
+PROTOTYPES["rnnwf_lstm_train_steps"] = PROTOTYPES["rnnwf_train_steps"]                 # the LSTM's device-resident Adam (docs/lstm.md): likewise
+PROTOTYPES["rnnwf_lstm_pauli_train_steps"] = PROTOTYPES["rnnwf_pauli_train_steps"]
 
 _lib = None
 
@@ -571,6 +573,18 @@ class NativeWavefunction:
                                                float(beta1), float(beta2), float(epsilon), mom.ctypes.data_as(_F64P)))
         return mom
 
+    def lstm_train_steps(self, numsamples, seed, step0, couplings, learning_rates, beta1=0.9, beta2=0.999, epsilon=1e-8, sample_offset=0):
+        """train_steps for the LSTM wave function (rnnwf_lstm_train_steps; model LSTM1D_F64, single process): len(learning_rates)
+        whole iterations of the host loop - lstm_vmc_gradient_step at step index step0 + k, training.Adam with learning_rates[k],
+        set_params - on the device with one host synchronisation, bit for bit.  Returns the (K, 4) moments of the K batches; get_param
+        returns the trained values, adam_get_state / adam_set_state the optimizer's."""
+        c, cp = _f64(couplings)
+        lr, lrp = _f64(np.atleast_1d(learning_rates))
+        mom = np.empty((lr.size, 4), dtype=np.float64)
+        self._check(self.lib.rnnwf_lstm_train_steps(self.h, lr.size, int(numsamples), int(seed), int(step0), int(sample_offset), cp, c.size, lrp,
+                                                    float(beta1), float(beta2), float(epsilon), mom.ctypes.data_as(_F64P)))
+        return mom
+
     def adam_step(self, learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8):
         """One Adam update on the device from the gradient of the last vmc_gradient, then the images' re-pack."""
         self._check(self.lib.rnnwf_adam_step(self.h, float(learning_rate), float(beta1), float(beta2), float(epsilon)))
@@ -883,6 +897,15 @@ class NativeWavefunction:
         returns are pauli_train_steps's."""
         return self._pauli_train_call("rnnwf_pauli_train_steps_stack", False, flip, sign, coeff, numsamples, seed, step0, learning_rates,
                                       beta1, beta2, epsilon, sample_offset, want_term_sums, want_eloc)
+
+    def lstm_pauli_train_steps(self, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1=0.9, beta2=0.999, epsilon=1e-8,
+                               sample_offset=0, want_term_sums=False, want_eloc=False):
+        """pauli_train_steps for the LSTM wave function (rnnwf_lstm_pauli_train_steps; single process): iteration k is
+        lstm_pauli_gradient_step at step index step0 + k, training.Adam with learning_rates[k] and set_params, bit for bit.  flip,
+        sign: (nterms, N) masks by chain position or (nterms, Nx, Ny), as pauli_step_lstm takes them.  Returns what pauli_train_steps
+        returns."""
+        return self._pauli_train_call("rnnwf_lstm_pauli_train_steps", False, *self._lattice_masks(flip, sign), coeff, numsamples, seed, step0,
+                                      learning_rates, beta1, beta2, epsilon, sample_offset, want_term_sums, want_eloc)
 
     def _pauli_train_call(self, entry, cplx, flip, sign, coeff, numsamples, seed, step0, learning_rates, beta1, beta2, epsilon,
                           sample_offset, want_term_sums, want_eloc):

@@ -27,7 +27,8 @@ STACK = Family("pauli_step_stack", "pauli_train_steps_stack", "renyi2_regions_st
 LATTICE = Family("pauli_step_2d", "pauli_train_steps_2d", "renyi2_regions_2d", lambda nat: (nat.nx, nat.ny),
                  lambda nat: (nat.nx // 2) * nat.ny + nat.ny // 2, "observables_2d.minimize_hamiltonian", "lattice sites")
 COMPLEX = Family("pauli_step_complex", "pauli_train_steps_complex", "renyi2_regions_complex", _chain, None, "minimize_hamiltonian", None)
-# the LSTM cell (observables_lstm.py): no device-resident Adam; its minimize loop takes the fused step
+# the LSTM cell (observables_lstm.py): its minimize loop takes the fused step and keeps refusing device_steps (the device-resident loop
+# is training_lstm.minimize_hamiltonian_device)
 LSTM = Family("pauli_step_lstm", None, "renyi2_regions_lstm", _chain, lambda nat: nat.N // 2, "observables_lstm.minimize_hamiltonian", "sites",
               "lstm_pauli_gradient_step")
 

@@ -16,14 +16,17 @@ namespace {
 const char* kLstmPre = "multi_rnn_cell/cell_0/lstm_cell/";
 
 // Packs LSTMCell + Dense(2) into LstmLayout<NFULL>.  TF's kernel is [2 + H, 4H]: rows 0..1 the one-hot input, rows 2.. the
-// hidden state; columns i | j | f | o in blocks of H.
-template <int NFULL>
+// hidden state; columns i | j | f | o in blocks of H.  S = double: the image; S = Lin: its table for device-resident training
+// (pack_value.h), every element with the operations the double run performs, in their order
+template <int NFULL, class S = double>
 std::vector<char> pack_lstm_image(const rnnwf_handle* h) {
     using L = LstmLayout<NFULL>;
+    using Out = PackSink<S>;
     const int H = h->H;
     std::vector<char> img(L::BYTES, 0);
-    const std::vector<double>& K = pv(h, std::string(kLstmPre) + "kernel");
-    const std::vector<double>& b = pv(h, std::string(kLstmPre) + "bias");
+    Out::begin(img);
+    const auto K = pvs<S>(h, std::string(kLstmPre) + "kernel");
+    const auto b = pvs<S>(h, std::string(kLstmPre) + "bias");
     const size_t W = (size_t)4 * H;
     auto decode = [&](int tile, int q, int r, int& gate, int& unit) -> bool {
         if (tile < 4 * NFULL) {
@@ -35,8 +38,8 @@ std::vector<char> pack_lstm_image(const rnnwf_handle* h) {
         }
         return unit < H;
     };
-    auto wt = [&](int gate, int unit, int k) -> double {      // W^T[row(gate, unit)][k] over the hidden rows of K
-        return k < H ? K[(size_t)(2 + k) * W + (size_t)gate * H + unit] : 0.0;
+    auto wt = [&](int gate, int unit, int k) -> S {           // W^T[row(gate, unit)][k] over the hidden rows of K
+        return k < H ? K[(size_t)(2 + k) * W + (size_t)gate * H + unit] : S(0.0);
     };
     double* avec = reinterpret_cast<double*>(img.data() + L::OFF_AVEC);
     double* arem = reinterpret_cast<double*>(img.data() + L::OFF_AREM);
@@ -49,8 +52,8 @@ std::vector<char> pack_lstm_image(const rnnwf_handle* h) {
                 const int lane = (kq << 4) | row;
                 for (int g = 0; g < L::NG; ++g)
                     for (int j = 0; j < L::VW; ++j)
-                        avec[(((size_t)tile * L::NG + g) * 64 + lane) * L::VW + j] = wt(gate, unit, 4 * (g * L::VW + j) + kq);
-                arem[(size_t)tile * 64 + lane] = wt(gate, unit, 4 * (L::KT - 1) + kq);
+                        Out::put(&avec[(((size_t)tile * L::NG + g) * 64 + lane) * L::VW + j], wt(gate, unit, 4 * (g * L::VW + j) + kq));
+                Out::put(&arem[(size_t)tile * 64 + lane], wt(gate, unit, 4 * (L::KT - 1) + kq));
             }
         }
     for (int v = 0; v < 3; ++v) {  // v = 0: zero input; v = 1, 2: one-hot of spin 0, 1
@@ -61,21 +64,22 @@ std::vector<char> pack_lstm_image(const rnnwf_handle* h) {
                     int gate, unit;
                     if (!decode(tile, q, r, gate, unit)) continue;
                     const size_t col = (size_t)gate * H + unit;
-                    double x = b[col] + (v ? K[(size_t)(v - 1) * W + col] : 0.0);
-                    if (gate == 2) x += 1.0;         // forget_bias = 1.0, folded into the f rows (lstm_core.h)
-                    binit[tile * 16 + q * 4 + r] = x;
+                    // v = 0 adds the zero input's 0.0 (a bias of -0.0 becomes +0.0): recorded as such, not skipped
+                    S x = v ? b[col] + K[(size_t)(v - 1) * W + col] : add_const(b[col], 0.0);
+                    if (gate == 2) x = add_const(x, 1.0);   // forget_bias = 1.0, folded into the f rows (lstm_core.h)
+                    Out::put(&binit[tile * 16 + q * 4 + r], x);
                 }
     }
     double* wd = reinterpret_cast<double*>(img.data() + L::OFF_WD);
     double* bd = reinterpret_cast<double*>(img.data() + L::OFF_BD);
-    const std::vector<double>& Wd = pv(h, "wf_dense/kernel");   // [H, 2]
-    const std::vector<double>& bdv = pv(h, "wf_dense/bias");    // [2]
+    const auto Wd = pvs<S>(h, "wf_dense/kernel");   // [H, 2]
+    const auto bdv = pvs<S>(h, "wf_dense/bias");    // [2]
     for (int kt = 0; kt < L::KT; ++kt)
         for (int q = 0; q < 4; ++q) {
             const int unit = 4 * kt + q;
-            if (unit < H) wd[q * L::WD_Q + kt] = Wd[(size_t)unit * 2 + 1] - Wd[(size_t)unit * 2];
+            if (unit < H) Out::put(&wd[q * L::WD_Q + kt], Wd[(size_t)unit * 2 + 1] - Wd[(size_t)unit * 2]);
         }
-    bd[0] = bdv[1] - bdv[0];
+    Out::put(&bd[0], bdv[1] - bdv[0]);
     return img;
 }
 
@@ -95,6 +99,7 @@ struct LLaunch {
         return launch_shrinking<WAVES>(h, kTimerFlip, lstm_flip_kernel<NFULL, WAVES>, L::BYTES, a.ntiles, a);
     }
     static std::vector<char> pack(const rnnwf_handle* h) { return pack_lstm_image<NFULL>(h); }
+    static void pack_table(const rnnwf_handle* h) { pack_lstm_image<NFULL, Lin>(h); }
     static size_t hck_bytes_per_block() { return (size_t)2 * L::KT * 64 * sizeof(double); }
     static double mfma_flops_per_step() { return (double)L::NT * L::KT * 2048.0; }
 };
@@ -179,6 +184,12 @@ int pack_image(rnnwf_handle* h, std::vector<char>& img) {
 }
 
 }  // namespace
+
+// the table of h->wimg over Lin into the active PackTrace (train.hip: the LSTM's builder; lstm_family()'s pack_table stays nullptr, so
+// the entries that ask the family keep refusing an LSTM handle)
+int rnnwf::lstm_pack_table(rnnwf_handle* h) {
+    return with_launch(h, [&](auto k) { decltype(k)::pack_table(h); }) ? 0 : no_kernel(h);
+}
 
 // base pass with checkpoints on the spins packed into h->bits, nothing else: the states the gradient's backward pass starts from
 int rnnwf::lstm_teacher_base(rnnwf_handle* h, int64_t ns) {

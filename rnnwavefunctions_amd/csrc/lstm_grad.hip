@@ -4,6 +4,7 @@
 // The existing gradient entries keep refusing an LSTM handle (lstm_family()'s `gradient` stays nullptr): these entries carry their
 // own hooks, as rnnwf_pauli_step_stack does for stacks.
 #include <algorithm>
+#include <cmath>
 
 #include "lstm_grad_kernels.h"
 #include "tn_gemm.h"
@@ -29,12 +30,15 @@ struct LGrad {
     static constexpr size_t COUNT = DW + G::HEAD_ROW;
 
     // pack_bwd_side's operand (grad.hip) with four gates: in the A fragment of output tile t (hidden unit kout receives dL/dh),
-    // k-step 4 kt + gate holds K[2 + kout][gate H + u], u = 4 kt + lane quarter
+    // k-step 4 kt + gate holds K[2 + kout][gate H + u], u = 4 kt + lane quarter.  S = Lin: the operand's table (pack_value.h)
+    template <class S = double>
     static std::vector<char> pack_bwd(const rnnwf_handle* h) {
+        using Out = PackSink<S>;
         const int H = h->H;
         std::vector<char> img(G::BWD_BYTES, 0);
+        Out::begin(img);
         double* A = reinterpret_cast<double*>(img.data());
-        const std::vector<double>& K = pv(h, std::string(kLstmPre) + "kernel");      // [2 + H, 4H], columns i | j | f | o
+        const auto K = pvs<S>(h, std::string(kLstmPre) + "kernel");      // [2 + H, 4H], columns i | j | f | o
         for (int t = 0; t < G::NTO; ++t)
             for (int row = 0; row < 16; ++row) {
                 int q, r;
@@ -47,7 +51,8 @@ struct LGrad {
                     for (int kk = 0; kk < G::KB; ++kk) {
                         const int kt = kk / 4, gate = kk % 4, u = 4 * kt + kq;
                         if (u >= H) continue;
-                        A[(((size_t)t * G::KBG + kk / G::VW) * 64 + lane) * G::VW + (kk % G::VW)] = K[(size_t)(2 + kout) * 4 * H + (size_t)gate * H + u];
+                        Out::put(&A[(((size_t)t * G::KBG + kk / G::VW) * 64 + lane) * G::VW + (kk % G::VW)],
+                                 K[(size_t)(2 + kout) * 4 * H + (size_t)gate * H + u]);
                     }
                 }
             }
@@ -118,19 +123,57 @@ int require_lstm(rnnwf_handle* h, const char* what) {
 
 }  // namespace
 
+// the backward operand in h->wbwd, packed from the host's parameters and uploaded when a commit has left it stale (a device re-pack
+// keeps it current: train.hip)
+int rnnwf::lstm_bwd_image(rnnwf_handle* h, const char* what) {
+    if (h->wbwd_valid) return 0;
+    return with_lstm_grad(h, what, [&](auto k) -> int {
+        const std::vector<char> img = decltype(k)::pack_bwd(h);
+        if (int rc = ensure(h, h->wbwd, img.size())) return rc;
+        if (int rc = upload(h, h->wbwd.p, img.data(), img.size())) return rc;
+        h->wbwd_valid = true;
+        return 0;
+    });
+}
+// its table over Lin into the active PackTrace
+int rnnwf::lstm_bwd_pack_table(rnnwf_handle* h) {
+    return with_lstm_grad(h, "device training", [&](auto k) -> int { decltype(k)::template pack_bwd<Lin>(h); return 0; });
+}
+// grad_flat_probe (grad.hip) for the LSTM: LGrad::unpack on an image whose element k holds k + 1 - sidx[i] = +-(1 + the h->gradW
+// element flat parameter i is read from; the sign: the head's two columns), *count = LGrad::COUNT.  h->grads is left as it was
+int rnnwf::lstm_grad_flat_probe(rnnwf_handle* h, std::vector<int32_t>& sidx, size_t* count) {
+    return with_lstm_grad(h, "device training", [&](auto k) -> int {
+        using K = decltype(k);
+        *count = K::COUNT;
+        static_assert(K::COUNT < ((size_t)1 << 31), "the indices must fit int32_t");
+        std::vector<double> img(K::COUNT);
+        for (size_t i = 0; i < K::COUNT; ++i) img[i] = (double)(i + 1);
+        const auto saved = h->grads;
+        K::unpack(h, img.data());
+        sidx.clear();
+        int rc = 0;
+        for (auto& kv : h->params) {
+            auto it = h->grads.find(kv.first);
+            if (it == h->grads.end() || it->second.size() != kv.second.value.size()) {
+                rc = h->fail(RNNWF_ERR_STATE, "device training: no gradient for '%s'", kv.first.c_str());
+                break;
+            }
+            for (int64_t s : kv.second.slot) sidx.push_back((int32_t)std::llround(it->second[(size_t)s]));
+        }
+        h->grads = saved;
+        return rc;
+    });
+}
+
 // The one driver: the backward pass on the ns chains whose spins (h->bits) and checkpoints (h->hck) the base pass just left, with
 // the weights in w_dev, or (w_dev == nullptr) formed from h->eloc and the step's moments still on the device; the dW image and the
 // head row are queued for download into h->staging.  The caller synchronises once and calls lstm_grad_finish.  (Declared in models.h:
 // rnnwf_lstm_pauli_gradient_step, lstm_pauli.hip, runs it on the batch of its Pauli pass.)
-int rnnwf::lstm_grad_queue(rnnwf_handle* h, const char* what, int64_t ns, const double* w_dev) {
+// download = false (device-resident training, rnnwf_lstm_train_steps): the result stays in h->gradW, where Adam reads it.
+int rnnwf::lstm_grad_queue(rnnwf_handle* h, const char* what, int64_t ns, const double* w_dev, bool download) {
     return with_lstm_grad(h, what, [&](auto k) -> int {
         using K = decltype(k);
-        if (!h->wbwd_valid) {
-            const std::vector<char> img = K::pack_bwd(h);
-            if (int rc = ensure(h, h->wbwd, img.size())) return rc;
-            if (int rc = upload(h, h->wbwd.p, img.data(), img.size())) return rc;
-            h->wbwd_valid = true;
-        }
+        if (int rc = lstm_bwd_image(h, what)) return rc;
         if (int rc = ensure(h, h->gradW, K::COUNT * 8)) return rc;
         RNNWF_HIP(h, hipMemsetAsync(h->gradW.p, 0, K::COUNT * 8, h->stream));
         LstmGradArgs a{};
@@ -145,6 +188,7 @@ int rnnwf::lstm_grad_queue(rnnwf_handle* h, const char* what, int64_t ns, const 
         a.eloc = (const double*)h->eloc.p;
         a.mom = (const double*)h->moments.p;
         if (int rc = K::run(h, a)) return rc;
+        if (!download) return 0;
         if (int rc = ensure_staging(h, K::COUNT * 8)) return rc;      // pinned: the copy is a plain DMA, the one wait is the caller's
         RNNWF_HIP(h, hipMemcpyAsync(h->staging, h->gradW.p, K::COUNT * 8, hipMemcpyDeviceToHost, h->stream));
         return 0;
@@ -199,5 +243,50 @@ extern "C" int rnnwf_lstm_vmc_gradient_step(rnnwf_handle* h, int64_t ns, uint64_
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));
     memcpy(moments, h->pinned, 4 * sizeof(double));
     lstm_grad_finish(h);
+    return RNNWF_OK;
+}
+
+// K whole Adam iterations with one host synchronisation: rnnwf_train_steps for the LSTM (docs/lstm.md, "Device-resident training").
+// Per iteration, nothing waiting for the host: rnnwf_lstm_vmc_gradient_step's kernels - the fused step with its moments written into
+// row k of train.hip's pinned table, the backward pass and P^T Q with the dW image left in h->gradW -, then train.hip's Adam and the
+// re-pack of h->wimg and h->wbwd from the tables the LSTM's builder recorded (train_prepare_lstm).
+extern "C" int rnnwf_lstm_train_steps(rnnwf_handle* h, int32_t K, int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset,
+                                      const double* couplings, int64_t n_couplings, const double* learning_rates, double beta1,
+                                      double beta2, double epsilon, double* moments) {
+    constexpr const char* kEntry = "rnnwf_lstm_train_steps";
+    // everything is validated before anything is touched: a refused call leaves the parameters and Adam's state
+    if (!h) return RNNWF_ERR_INVALID;
+    if (h->model != RNNWF_MODEL_LSTM1D_F64)
+        return h->fail(RNNWF_ERR_INVALID, "%s: needs an LSTM1D_F64 handle, this one is %s (its device-resident training: rnnwf_train_steps)",
+                       kEntry, model_name(h->model));
+    if (!h->committed) return h->fail(RNNWF_ERR_STATE, "%s: parameters not committed (call rnnwf_commit_params)", kEntry);
+    if (h->comm || h->nranks > 1 || h->reduce_in_step)
+        return h->fail(RNNWF_ERR_INVALID, "%s: single process only (the weights are centred with this handle's moments), this handle has "
+                                          "a communicator", kEntry);
+    if (K < 1 || K > kTrainMaxSteps) return h->fail(RNNWF_ERR_INVALID, "%s: K must be 1..%d", kEntry, kTrainMaxSteps);
+    if (numsamples < 1 || !couplings || !learning_rates || !moments)
+        return h->fail(RNNWF_ERR_INVALID, "%s: bad arguments (numsamples >= 1; couplings, learning_rates and moments non-null)", kEntry);
+    if (n_couplings != (int64_t)h->family->coupl_per_site * h->N + h->family->coupl_tail)
+        return h->fail(RNNWF_ERR_INVALID, "%s: wrong number of couplings", kEntry);
+    for (int k = 0; k < K; ++k)
+        if (!std::isfinite(learning_rates[k])) return h->fail(RNNWF_ERR_INVALID, "%s: learning_rates[%d] must be finite", kEntry, k);
+    if (int rc = refuse_past_budget(h, numsamples, kEntry)) return rc;
+    RNNWF_HIP(h, hipSetDevice(h->cfg.device));
+    if (int rc = train_prepare_lstm(h)) return rc;
+    int rc = 0, applied = 0;
+    for (int k = 0; k < K && !rc; ++k) {
+        h->moments_direct = train_moments_row(h, k);          // as rnnwf_train_steps: the moments kernel writes the pinned row itself
+        rc = vmc_step(h, numsamples, Draw{seed, step0 + (uint64_t)k, sample_offset}, couplings, nullptr, nullptr, nullptr);
+        h->moments_direct = nullptr;
+        if (!rc) rc = lstm_grad_queue(h, kEntry, numsamples, nullptr, false);
+        if (!rc) rc = train_adam_update(h, k, learning_rates[k], beta1, beta2, epsilon);
+        if (!rc) ++applied;
+    }
+    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = h->fail(RNNWF_ERR_HIP, "%s: stream synchronisation failed", kEntry);
+    if (rc) {                                                 // the updates that were applied count; no batch belongs to the new weights
+        train_steps_failed(h, applied);
+        return rc;
+    }
+    train_steps_done(h, K, moments);
     return RNNWF_OK;
 }

@@ -34,7 +34,30 @@ struct LstmPauli {
         return std::max<int64_t>(1, (int64_t)(state_budget_bytes(h, kDefaultStateBudget) / per_block)) * kChains;
     }
     static int tails(rnnwf_handle* h, int64_t ns, const PauliTerms& g, const PauliScratch& sc, bool keep);
+    static int assemble(rnnwf_handle* h, int64_t ns, const PauliTerms& g, const PauliScratch& sc, bool keep, double* sums_dev);
     static int pass(rnnwf_handle* h, int64_t ns, const PauliTerms& g, const PauliScratch& sc, bool keep, double* sums_host);
+};
+
+// rnnwf_lstm_pauli_train_steps: the model, terms, pass size and kernels of rnnwf_lstm_pauli_gradient_step's pass, the per-term sums
+// written into the call's table on the device; the gradient and train.hip's state through the LSTM's own road (pauli_driver.h:
+// OwnGradient)
+struct LstmPauliTrain : LstmPauli {
+    static constexpr const char* kEntry = "rnnwf_lstm_pauli_train_steps";
+    static int refuse(rnnwf_handle* h) {
+        if (h->model != RNNWF_MODEL_LSTM1D_F64)
+            return h->fail(RNNWF_ERR_INVALID, "%s: needs an LSTM1D_F64 handle, this one is %s (its device-resident training on Pauli terms: "
+                                              "rnnwf_pauli_train_steps and its siblings)", kEntry, model_name(h->model));
+        if (int rc = lstm_pauli_refuse(h, kEntry)) return rc;
+        if (h->comm || h->nranks > 1 || h->reduce_in_step)
+            return h->fail(RNNWF_ERR_INVALID, "%s: single process only (the weights are centred with this handle's moments), this handle "
+                                              "has a communicator", kEntry);
+        return 0;
+    }
+    static int train_pass(rnnwf_handle* h, int64_t ns, const PauliTerms& g, const PauliScratch& sc, double* sums_row) {
+        return assemble(h, ns, g, sc, true, sums_row);
+    }
+    static int train_prepare(rnnwf_handle* h) { return train_prepare_lstm(h); }
+    static int train_gradient(rnnwf_handle* h, int64_t ns) { return lstm_grad_queue(h, kEntry, ns, nullptr, false); }
 };
 
 // the front of a pass over the ns chains packed in h->bits: base pass with checkpoints (log P at sc.logp, site terms at sc.terms) and
@@ -80,9 +103,10 @@ int LstmPauli::tails(rnnwf_handle* h, int64_t ns, const PauliTerms& g, const Pau
     return 0;
 }
 
-// one pass over the ns chains packed in h->bits: the log-ratios stay in h->renyi, E_loc in h->eloc; sums_host (K, 2) of this pass, or
-// nullptr - then the per-term kernels are not launched.  keep: the checkpoints are wanted whatever the terms (the fused gradient step)
-int LstmPauli::pass(rnnwf_handle* h, int64_t ns, const PauliTerms& g, const PauliScratch& sc, bool keep, double* sums_host) {
+// one pass over the ns chains packed in h->bits: the log-ratios stay in h->renyi, E_loc in h->eloc; sums_dev: where on the device the
+// (K, 2) sums of this pass go, or nullptr - then the per-term kernels are not launched.  keep: the checkpoints are wanted whatever the
+// terms (the fused gradient step, the training iterations)
+int LstmPauli::assemble(rnnwf_handle* h, int64_t ns, const PauliTerms& g, const PauliScratch& sc, bool keep, double* sums_dev) {
     const int N = h->N, K = g.K, M = g.M;
     if (int rc = tails(h, ns, g, sc, keep)) return rc;
     char* buf = (char*)h->renyi.p;
@@ -97,18 +121,25 @@ int LstmPauli::pass(rnnwf_handle* h, int64_t ns, const PauliTerms& g, const Paul
         TimedLaunch tl(h, kTimerAssembly);
         const uint32_t* sgn = (const uint32_t*)(buf + sc.sgn);
         const int32_t* tmask = (const int32_t*)(buf + sc.tmask);
-        if (sums_host) {
+        if (sums_dev) {
             pauli_term_kernel<<<(unsigned)(K * sc.nblk), kPauliThreads, 0, h->stream>>>(bits, sgn, tmask, lr, g.W, ns, sc.nblk,
                                                                                        (double*)(buf + sc.part));
             RNNWF_HIP(h, hipGetLastError());
-            renyi_sums_kernel<<<(unsigned)K, kPauliThreads, 0, h->stream>>>((const double*)(buf + sc.part), sc.nblk, (double*)(buf + sc.sums));
+            renyi_sums_kernel<<<(unsigned)K, kPauliThreads, 0, h->stream>>>((const double*)(buf + sc.part), sc.nblk, sums_dev);
             RNNWF_HIP(h, hipGetLastError());
         }
         pauli_eloc_kernel<<<(unsigned)sc.nblk, kPauliThreads, 0, h->stream>>>(bits, sgn, tmask, (const double*)(buf + sc.coeff), lr, K, g.W,
                                                                              ns, (double*)h->eloc.p);
         RNNWF_HIP(h, hipGetLastError());
     }
-    if (sums_host) RNNWF_HIP(h, hipMemcpyAsync(sums_host, buf + sc.sums, (size_t)K * 16, hipMemcpyDeviceToHost, h->stream));
+    return 0;
+}
+
+// the same with the sums copied to the host: sums_host (K, 2) of this pass, or nullptr
+int LstmPauli::pass(rnnwf_handle* h, int64_t ns, const PauliTerms& g, const PauliScratch& sc, bool keep, double* sums_host) {
+    char* buf = (char*)h->renyi.p;
+    if (int rc = assemble(h, ns, g, sc, keep, sums_host ? (double*)(buf + sc.sums) : nullptr)) return rc;
+    if (sums_host) RNNWF_HIP(h, hipMemcpyAsync(sums_host, buf + sc.sums, (size_t)g.K * 16, hipMemcpyDeviceToHost, h->stream));
     return 0;
 }
 
@@ -184,4 +215,14 @@ extern "C" int rnnwf_lstm_pauli_gradient_step(rnnwf_handle* h, const int32_t* fl
     memcpy(moments, h->pinned, 4 * sizeof(double));
     lstm_grad_finish(h);
     return RNNWF_OK;
+}
+
+// K whole Adam iterations on the Hamiltonian of the terms with one host synchronisation: rnnwf_pauli_train_steps for the LSTM
+// (pauli_driver.h: pauli_train_steps over LstmPauliTrain; docs/lstm.md, "Device-resident training")
+extern "C" int rnnwf_lstm_pauli_train_steps(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const double* coeff, int32_t nterms,
+                                            int32_t K, int64_t numsamples, uint64_t seed, uint64_t step0, int64_t sample_offset,
+                                            const double* learning_rates, double beta1, double beta2, double epsilon, double* moments,
+                                            double* term_sums, double* out_eloc) {
+    return pauli_train_steps<LstmPauliTrain>(h, flip, sign, coeff, nterms, K, numsamples, seed, step0, sample_offset, learning_rates, beta1,
+                                             beta2, epsilon, moments, term_sums, out_eloc);
 }

@@ -125,8 +125,16 @@ int lstm_teacher_base(rnnwf_handle* h, int64_t ns);
 // lstm_grad.hip, for the fused Pauli gradient step (lstm_pauli.hip): the LSTM's backward pass on the batch in h->bits / h->hck, weights
 // from w_dev or (nullptr) from h->eloc and h->moments, the result queued into h->staging; after the caller's synchronisation
 // lstm_grad_finish leaves the TF-named tensors in h->grads
-int lstm_grad_queue(rnnwf_handle* h, const char* what, int64_t ns, const double* w_dev);
+// download = false (device-resident training): the result stays in h->gradW and nothing is queued into h->staging
+int lstm_grad_queue(rnnwf_handle* h, const char* what, int64_t ns, const double* w_dev, bool download = true);
 void lstm_grad_finish(rnnwf_handle* h);
+// for the LSTM's builder of device-resident training (train.hip: train_prepare_lstm): the tables of h->wimg (lstm.hip) and of the
+// backward operand h->wbwd (lstm_grad.hip) over Lin into the active PackTrace; the operand packed on the host when stale; and
+// grad_flat_probe's table from the LSTM's own unpacker, *count the elements of its h->gradW image
+int lstm_pack_table(rnnwf_handle* h);
+int lstm_bwd_pack_table(rnnwf_handle* h);
+int lstm_bwd_image(rnnwf_handle* h, const char* what);
+int lstm_grad_flat_probe(rnnwf_handle* h, std::vector<int32_t>& sidx, size_t* count);
 // crnn.hip, for the complex RNN's Pauli pass (crnn_pauli.hip): the same three for the one-layer complex RNN
 int crnn_plain_base(rnnwf_handle* h, const CrnnArgs& a);
 CrnnArgs crnn_base_args(rnnwf_handle* h, int64_t ns);
@@ -180,6 +188,9 @@ int train_sync_params_to_host(rnnwf_handle* h);               // before the host
 int train_allreduce_grads_device(rnnwf_handle* h);           // 1: gradient all-reduced in-stream on the device, 0: not available
 // for rnnwf_sr_train_steps (sr.hip), whose iterations update the same flat parameters and re-pack the same images:
 int train_prepare(rnnwf_handle* h);                          // the tables built and the flat parameters current on the device
+// the same for an LSTM1D_F64 handle, through a builder of its own (the LSTM has no hook table: train_prepare keeps refusing it), for
+// rnnwf_lstm_train_steps (lstm_grad.hip) and rnnwf_lstm_pauli_train_steps (lstm_pauli.hip)
+int train_prepare_lstm(rnnwf_handle* h);
 // theta_i <- round_T(theta_i - lr (+-col[|gidx_i| - 1])) unless *hold != 0 (both on the device), then the re-pack of every image
 int train_apply_direction(rnnwf_handle* h, const double* col, size_t col_count, double lr, const long long* hold);
 // for the Adam iterations of another local energy (pauli_driver.h: pauli_train_steps), behind train_prepare: the rows of the pinned
@@ -188,6 +199,9 @@ constexpr int kTrainMaxSteps = 1024;                         // iterations of on
 double* train_moments_row(rnnwf_handle* h, int k);           // device address of row k, for h->moments_direct
 int train_adam_update(rnnwf_handle* h, int k, double lr, double beta1, double beta2, double epsilon);
 void train_steps_done(rnnwf_handle* h, int K, double* moments);
+// an error inside the LSTM entries' loop, behind their synchronisation: the `applied` updates count in Adam's bias correction and no
+// batch or gradient is left claiming to belong to the new weights
+void train_steps_failed(rnnwf_handle* h, int applied);
 void grad_invalidate(rnnwf_handle* h);
 // bytes of per-site hidden states one pass may hold; RNNWF_STATE_BUDGET_MB (read at rnnwf_create) overrides the
 // default (tests use it to drive the multi-pass path at small sizes)

@@ -5,6 +5,8 @@
 //                  value = c * ((P[a] + s * P[b]) + P[d])   (b, d optional; a bias plus an input row, a head column difference, the 2D
 //                                                            cell's b + Uh[x_h] + Uv[x_v], ...)
 //              followed by the store's conversion (f32, f64, or part k of the exact three-way bf16 split of the f32 value).
+//              Behind the sum an unscaled value may carry a packer's additive constant (add_const): + 0.0 (which turns a -0.0 into
+//              +0.0), then + 1.0 - the LSTM's bias rows  b + 0.0  and  (b + K) + 1.0  (lstm.hip: forget_bias).
 //              The record - a PackTable - is what the device-side re-pack kernel (train.hip: repack_kernel) replays on the
 //              device-resident parameters after every optimizer step, so that a training iteration never visits the host
 //              (the reference runs `sess.run(optstep)` on the device, 1DTFIM/TrainingRNN_1DTFIM.py:113,162,221).
@@ -49,13 +51,14 @@ struct Lin {
     int32_t a = -1, b = -1, d = -1;
     double c = 1.0;
     int32_t s = 0;
+    int32_t k = 0;                                            // constants added behind the sum: PACK_ADD0, PACK_ADD1 (add_const)
     Lin() = default;
     Lin(double k) : v(k) {}                                   // a constant (0.0 for padded units)
 };
 inline Lin operator+(const Lin& x, const Lin& y) {
     if (x.a < 0 && x.v == 0.0) return y;
     if (y.a < 0 && y.v == 0.0) return x;
-    if (x.a < 0 || y.a < 0 || x.d >= 0 || y.b >= 0 || y.d >= 0 || x.c != 1.0 || y.c != 1.0) throw std::logic_error("pack_value.h: unsupported sum in a packer");
+    if (x.a < 0 || y.a < 0 || x.d >= 0 || y.b >= 0 || y.d >= 0 || x.c != 1.0 || y.c != 1.0 || x.k || y.k) throw std::logic_error("pack_value.h: unsupported sum in a packer");
     Lin r = x;
     r.v = x.v + y.v;
     if (x.b < 0) { r.b = y.a; r.s = 1; }
@@ -64,13 +67,14 @@ inline Lin operator+(const Lin& x, const Lin& y) {
 }
 inline Lin operator-(const Lin& x, const Lin& y) {
     if (y.a < 0 && y.v == 0.0) return x;
-    if (x.a < 0 || y.a < 0 || x.b >= 0 || y.b >= 0 || x.d >= 0 || y.d >= 0 || x.c != 1.0 || y.c != 1.0) throw std::logic_error("pack_value.h: unsupported difference in a packer");
+    if (x.a < 0 || y.a < 0 || x.b >= 0 || y.b >= 0 || x.d >= 0 || y.d >= 0 || x.c != 1.0 || y.c != 1.0 || x.k || y.k) throw std::logic_error("pack_value.h: unsupported difference in a packer");
     Lin r;
     r.v = x.v - y.v; r.a = x.a; r.b = y.a; r.s = -1;
     return r;
 }
 inline Lin operator*(double k, const Lin& x) {
     if (x.c != 1.0) throw std::logic_error("pack_value.h: a packer scales a value twice");
+    if (x.k) throw std::logic_error("pack_value.h: a packer scales a value behind its additive constant");
     Lin r = x;
     r.v = k * x.v;
     r.c = k;
@@ -81,7 +85,8 @@ inline Lin operator*(double k, const Lin& x) {
 struct PackEntry {
     uint32_t off;        // byte offset in the image
     int32_t a, b;        // flat parameter indices (order of rnnwf_set_params_flat), b < 0: none
-    int32_t kind;        // 0: f32, 1: f64, 2 + k: bf16 part k of the f32 value; bit 8: s = -1 (difference instead of sum)
+    int32_t kind;        // 0: f32, 1: f64, 2 + k: bf16 part k of the f32 value; bit 8: s = -1 (difference instead of sum); bits 9, 10:
+                         // + 0.0, then + 1.0 behind the sum (add_const)
     int32_t d;           // third term (added after a +- b), < 0: none
     double c;            // scale (1.0: none)
 };
@@ -89,7 +94,20 @@ struct PackTable {
     std::vector<PackEntry> entries;
     size_t image_bytes = 0;
 };
-enum { PACK_F32 = 0, PACK_F64 = 1, PACK_BF16 = 2, PACK_MINUS = 256 };
+enum { PACK_F32 = 0, PACK_F64 = 1, PACK_BF16 = 2, PACK_MINUS = 256, PACK_ADD0 = 512, PACK_ADD1 = 1024 };
+
+// x + k behind a packer's sum, k = 0.0 or 1.0, each at most once and 0.0 first: the flag bits of PackEntry::kind.  No entry of a
+// packer that does not call this gains an operation, and nothing is added to an entry without its bit (an unconditional + 0.0
+// would turn a -0.0 into +0.0)
+inline double add_const(double x, double k) { return x + k; }
+inline Lin add_const(const Lin& x, double k) {
+    const int32_t bit = k == 0.0 ? PACK_ADD0 : PACK_ADD1;
+    if ((k != 0.0 && k != 1.0) || x.c != 1.0 || x.k >= bit) throw std::logic_error("pack_value.h: unsupported additive constant in a packer");
+    Lin r = x;
+    r.v = x.v + k;
+    if (x.a >= 0) r.k |= bit;                                 // (a constant stays one)
+    return r;
+}
 
 // where Lin stores go while a packer runs in recording mode (one packer at a time per thread)
 struct PackTrace {
@@ -129,7 +147,7 @@ template <> struct PackSink<Lin> {
         PackEntry e;
         e.off = (uint32_t)((const char*)dst - t.base + t.shift);
         e.a = x.a; e.b = x.b; e.d = x.d;
-        e.kind = kind | (x.b >= 0 && x.s < 0 ? PACK_MINUS : 0);
+        e.kind = kind | (x.b >= 0 && x.s < 0 ? PACK_MINUS : 0) | x.k;
         e.c = x.c;
         t.table->entries.push_back(e);
     }

@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "observable.h"
@@ -120,11 +121,19 @@ int pauli_step(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const 
 //   train_pass(h, ns, g, sc, sums_row)   the kernels of one iteration's pass over the chains drawn into h->bits: E_loc in h->eloc,
 //                                        the checkpoints kept, the per-term sums into sums_row on the device unless it is nullptr
 //                                        (the 2D RNN's sampling base pass has kept every state and log P: its pass starts at the tails)
+// A family without a hook table in rnnwf_vmc_gradient (the LSTM, lstm_pauli.hip) brings the steps that go through it - detected by
+// their presence (OwnGradient):
+//   train_prepare(h)                     train.hip's tables and flat parameters for this model, in train_prepare's place
+//   train_gradient(h, ns)                the backward pass on the batch of train_pass, the dW image left in h->gradW
+// and, on an error inside its loop, has the applied updates counted (train_steps_failed).
 // Per call: the refusals, the terms derived and uploaded once, one scratch allocation (the tables, one pass, then the [K][nterms]
 // table of per-term sums), train.hip's tables and flat parameters.  Per iteration k, nothing waiting for the host: the family's base
 // pass drawing at step index step0 + k, train_pass, the moments into row k of train.hip's pinned table, the gradient reading them on
 // the device, Adam with learning_rates[k] and the re-pack of every weight image.  Neither the gradient nor the update touches
 // h->renyi, so the tables stay where they were uploaded.  out_eloc: [ns] E_loc of the last iteration's batch, or nullptr.
+template <class P, class = void> struct OwnGradient : std::false_type {};
+template <class P> struct OwnGradient<P, std::void_t<decltype(&P::train_gradient)>> : std::true_type {};
+
 template <class P>
 int pauli_train_steps(rnnwf_handle* h, const int32_t* flip, const int32_t* sign, const void* coeff, int32_t nterms, int32_t K, int64_t ns,
                       uint64_t seed, uint64_t step0, int64_t sample_offset, const double* learning_rates, double beta1, double beta2,
@@ -134,7 +143,8 @@ int pauli_train_steps(rnnwf_handle* h, const int32_t* flip, const int32_t* sign,
     if (int rc = P::refuse(h)) return rc;
     if (int rc = refuse_uncommitted(h, P::kEntry, P::kUncommittedInvalid)) return rc;
     if (h->comm) return h->fail(RNNWF_ERR_INVALID, "%s: runs in one process on one GPU, this handle has a communicator", P::kEntry);
-    if (int rc = require_gradient(h, P::kEntry)) return rc;
+    if constexpr (!OwnGradient<P>::value)
+        if (int rc = require_gradient(h, P::kEntry)) return rc;
     if (K < 1 || K > kTrainMaxSteps) return h->fail(RNNWF_ERR_INVALID, "%s: K must be 1..%d", P::kEntry, kTrainMaxSteps);
     if (nterms < 1) return h->fail(RNNWF_ERR_INVALID, "%s: nterms must be >= 1", P::kEntry);
     if (ns < 1) return h->fail(RNNWF_ERR_INVALID, "%s: numsamples must be >= 1", P::kEntry);
@@ -155,7 +165,11 @@ int pauli_train_steps(rnnwf_handle* h, const int32_t* flip, const int32_t* sign,
         return h->fail(RNNWF_ERR_INVALID, "%s: nterms x ceil(ns / %d) exceeds the grid of the term kernel; split the batch", P::kEntry,
                        P::kThreads);
     RNNWF_HIP(h, hipSetDevice(h->cfg.device));
-    if (int rc = train_prepare(h)) return rc;
+    if constexpr (OwnGradient<P>::value) {
+        if (int rc = P::train_prepare(h)) return rc;
+    } else {
+        if (int rc = train_prepare(h)) return rc;
+    }
     const PauliScratch sc(N, g, ns, E, P::kOwnLogP, P::kThreads);
     const size_t row = (size_t)nterms * 2 * E;                // a (nterms, 2) real or (nterms, 4) complex row of per-term sums
     if (int rc = ensure(h, h->renyi, sc.bytes + (term_sums ? (size_t)K * row : 0))) return rc;
@@ -172,7 +186,7 @@ int pauli_train_steps(rnnwf_handle* h, const int32_t* flip, const int32_t* sign,
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));           // the set-up's: the tables leave the host's vectors before the iterations start
     h->last_ns = 0;                                   // h->bits, h->hck and h->eloc are overwritten from here on
     h->call_ns = ns;
-    int rc = 0;
+    int rc = 0, applied = 0;
     for (int k = 0; k < K && !rc; ++k) {
         const Draw d{seed, step0 + (uint64_t)k, sample_offset};
         rc = h->family->base(h, ns, &d);
@@ -182,9 +196,14 @@ int pauli_train_steps(rnnwf_handle* h, const int32_t* flip, const int32_t* sign,
         rc = run_moments(h, h->eloc.p, ns, P::kComplex, nullptr);
         h->moments_direct = nullptr;
         if (rc) break;
-        keep_resident(h, ns);                                 // the batch the gradient reads
-        rc = grad_device(h, 0.0, 0.0, 0.0, (const double*)h->moments.p, nullptr);
+        if constexpr (OwnGradient<P>::value) {
+            rc = P::train_gradient(h, ns);
+        } else {
+            keep_resident(h, ns);                             // the batch the gradient reads
+            rc = grad_device(h, 0.0, 0.0, 0.0, (const double*)h->moments.p, nullptr);
+        }
         if (!rc) rc = train_adam_update(h, k, learning_rates[k], beta1, beta2, epsilon);
+        if (!rc) ++applied;
     }
     if (!rc && term_sums && hipMemcpyAsync(term_sums, buf + sc.bytes, (size_t)K * row, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
         rc = h->fail(RNNWF_ERR_HIP, "%s: download of the per-term sums failed", P::kEntry);
@@ -192,7 +211,10 @@ int pauli_train_steps(rnnwf_handle* h, const int32_t* flip, const int32_t* sign,
         rc = h->fail(RNNWF_ERR_HIP, "%s: download of E_loc failed", P::kEntry);
     if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = h->fail(RNNWF_ERR_HIP, "%s: stream synchronisation failed", P::kEntry);
     h->last_ns = 0;                       // the resident batch belongs to the weights before the last update
-    if (rc) return rc;
+    if (rc) {
+        if constexpr (OwnGradient<P>::value) train_steps_failed(h, applied);
+        return rc;
+    }
     train_steps_done(h, K, moments);
     return RNNWF_OK;
 }

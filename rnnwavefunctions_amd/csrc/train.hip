@@ -33,6 +33,8 @@ __device__ __forceinline__ void repack_entry(const PackEntry& t, const double* _
     double v = P[t.a];
     if (t.b >= 0) v = (t.kind & PACK_MINUS) ? __dsub_rn(v, P[t.b]) : __dadd_rn(v, P[t.b]);
     if (t.d >= 0) v = __dadd_rn(v, P[t.d]);
+    if (t.kind & PACK_ADD0) v = __dadd_rn(v, 0.0);             // the LSTM's bias rows alone carry these bits (pack_value.h: add_const)
+    if (t.kind & PACK_ADD1) v = __dadd_rn(v, 1.0);
     if (t.c != 1.0) v = __dmul_rn(t.c, v);
     const int kind = t.kind & 255;
     if (kind == PACK_F32) {
@@ -145,9 +147,10 @@ int add_image(rnnwf_handle* h, DevBuf* target, Fn&& run_packer) {
     return 0;
 }
 
-int build(rnnwf_handle* h) {
+// the state every builder fills: P/M/V/G, the pinned moments table, gidx from `probe(sidx, count, f64)`, the image tables from `images()`
+template <class Probe, class Images>
+int build_state(rnnwf_handle* h, Probe&& probe, Images&& images) {
     TrainState& t = h->train;
-    if (int rc = require_gradient(h, "device-resident training")) return rc;
     if (t.built) return t.supported ? 0 : h->fail(RNNWF_ERR_INVALID, "device-resident training is not available for this model: %s", t.why.c_str());
     t.built = true;
     t.nparams = rnnwf_num_params(h);
@@ -159,32 +162,63 @@ int build(rnnwf_handle* h) {
     RNNWF_HIP(h, hipHostGetDevicePointer(&t.mom_host_dev, t.mom_host, 0));
     // gradient: dW image -> flat
     std::vector<int32_t> sidx;
-    GradImage im;
-    if (int rc = grad_flat_probe(h, sidx, &im)) return rc;
-    t.dw_count = im.count;
-    t.dw_f64 = im.f64;
+    if (int rc = probe(sidx, t.dw_count, t.dw_f64)) return rc;
     if ((int64_t)sidx.size() != t.nparams) return h->fail(RNNWF_ERR_STATE, "device training: gradient probe size mismatch");
     for (int32_t k : sidx)
         if ((size_t)(k < 0 ? -k : k) > t.dw_count) return h->fail(RNNWF_ERR_STATE, "device training: gradient probe index out of range");
     if (int rc = ensure(h, t.gidx, sidx.size() * 4)) return rc;
     RNNWF_HIP(h, hipMemcpy(t.gidx.p, sidx.data(), sidx.size() * 4, hipMemcpyHostToDevice));
-    // images (the backward image's table is added on first use: its buffer exists once the gradient has packed it on the host)
     t.nimg = 0;
-    if (int rc = add_image(h, &h->wimg, [&] { return h->family->pack_table(h); })) return rc;
-    if (h->engine_split && h->NL > 1) {
-        // a stack on the bf16x3 engine: the layer pipeline's images (split.hip: stack_pack)
-        for (int l = 0; l < h->NL; ++l)
-            if (int rc = add_image(h, l ? &h->wsplit_up[l - 1] : &h->wsplit, [&] { return stack_pack_table(h, l); })) return rc;
-    } else if (h->engine_split) {
-        if (int rc = add_image(h, &h->wsplit, [&] { return split_pack_table(h); })) return rc;
-        if (h->wsplit16.p)                                     // the positive RNN's 16x16x32 form (split_stream.hip)
-            if (int rc = add_image(h, &h->wsplit16, [&] { pack_split16_image<1, Lin>(h); return 0; })) return rc;
-    }
-    if (h->base_bf)
-        if (int rc = add_image(h, &h->wbasebf, [&] { return base_bf_pack_table(h); })) return rc;
+    if (int rc = images()) return rc;
     t.supported = true;
     return 0;
 }
+
+int build(rnnwf_handle* h) {
+    if (int rc = require_gradient(h, "device-resident training")) return rc;
+    auto probe = [&](std::vector<int32_t>& sidx, size_t& count, bool& f64) {
+        GradImage im;
+        if (int rc = grad_flat_probe(h, sidx, &im)) return rc;
+        count = im.count;
+        f64 = im.f64;
+        return 0;
+    };
+    // images (the backward image's table is added on first use: its buffer exists once the gradient has packed it on the host)
+    return build_state(h, probe, [&]() -> int {
+        if (int rc = add_image(h, &h->wimg, [&] { return h->family->pack_table(h); })) return rc;
+        if (h->engine_split && h->NL > 1) {
+            // a stack on the bf16x3 engine: the layer pipeline's images (split.hip: stack_pack)
+            for (int l = 0; l < h->NL; ++l)
+                if (int rc = add_image(h, l ? &h->wsplit_up[l - 1] : &h->wsplit, [&] { return stack_pack_table(h, l); })) return rc;
+        } else if (h->engine_split) {
+            if (int rc = add_image(h, &h->wsplit, [&] { return split_pack_table(h); })) return rc;
+            if (h->wsplit16.p)                                     // the positive RNN's 16x16x32 form (split_stream.hip)
+                if (int rc = add_image(h, &h->wsplit16, [&] { pack_split16_image<1, Lin>(h); return 0; })) return rc;
+        }
+        if (h->base_bf)
+            if (int rc = add_image(h, &h->wbasebf, [&] { return base_bf_pack_table(h); })) return rc;
+        return 0;
+    });
+}
+
+// The LSTM's road into the same state (docs/lstm.md, "Device-resident training"): lstm_family() has neither a gradient hook table nor a
+// pack_table hook, so build() - and with it rnnwf_adam_step, rnnwf_train_steps, rnnwf_device_training_supported, train_prepare - keeps
+// refusing the model; this builder is reached from the LSTM's own entries and from rnnwf_adam_get_state / rnnwf_adam_set_state.
+// gidx comes from a probe of the LSTM's unpacker, the tables of h->wimg and h->wbwd from its two packers over Lin.  Both images are in
+// the list from the start, so every re-pack keeps h->wbwd current and h->wbwd_valid true; a host commit clears it as ever.
+int build_lstm(rnnwf_handle* h) {
+    if (h->model != RNNWF_MODEL_LSTM1D_F64) return h->fail(RNNWF_ERR_INVALID, "device-resident LSTM training: needs an LSTM1D_F64 handle");
+    auto probe = [&](std::vector<int32_t>& sidx, size_t& count, bool& f64) {
+        f64 = true;
+        return lstm_grad_flat_probe(h, sidx, &count);
+    };
+    return build_state(h, probe, [&]() -> int {
+        if (int rc = add_image(h, &h->wimg, [&] { return lstm_pack_table(h); })) return rc;
+        if (int rc = lstm_bwd_image(h, "device training")) return rc;      // (the host's parameters are current: nothing has been trained yet)
+        return add_image(h, &h->wbwd, [&] { return lstm_bwd_pack_table(h); });
+    });
+}
+int build_for(rnnwf_handle* h) { return h->model == RNNWF_MODEL_LSTM1D_F64 ? build_lstm(h) : build(h); }
 
 // the backward image's table needs the image's buffer: added on first use, when the gradient has packed it once on the host
 int ensure_bwd_image(rnnwf_handle* h) {
@@ -284,7 +318,7 @@ double adam_lr_t(double lr, double b1, double b2, int64_t t) {
 // the call, 0 when the caller must take the staged road, < 0 on error.
 int rnnwf::train_allreduce_grads_device(rnnwf_handle* h) {
     TrainState& t = h->train;
-    if (!h->comm || !h->gradW.p) return 0;
+    if (!h->comm || !h->gradW.p || !h->family->gradient) return 0;      // (the LSTM's gradient entries keep the staged road)
     if (!t.built) { if (build(h) != 0) { h->err.clear(); return 0; } }
     if (!t.supported) return 0;
     const unsigned blocks = (unsigned)((t.nparams + 255) / 256);
@@ -325,6 +359,13 @@ int rnnwf::train_apply_direction(rnnwf_handle* h, const double* col, size_t col_
     return launch_repack(h);
 }
 
+int rnnwf::train_prepare_lstm(rnnwf_handle* h) {
+    if (int rc = build_lstm(h)) return rc;
+    // a commit since the last call: the operand is packed from the host's parameters, which are the current ones then
+    if (int rc = lstm_bwd_image(h, "device training")) return rc;
+    return params_to_device(h);
+}
+
 double* rnnwf::train_moments_row(rnnwf_handle* h, int k) { return (double*)h->train.mom_host_dev + 4 * k; }
 
 // iteration k of a call: Adam from the gradient's dW image with the bias correction of update adam_t + k + 1, then the re-pack
@@ -340,6 +381,12 @@ void rnnwf::train_steps_done(rnnwf_handle* h, int K, double* moments) {
     memcpy(moments, h->train.mom_host, (size_t)K * 4 * sizeof(double));
     h->train.adam_t += K;
     h->last_ns = 0;                       // the resident batch belongs to the weights before the last update
+    h->grads.clear();
+}
+
+void rnnwf::train_steps_failed(rnnwf_handle* h, int applied) {
+    h->train.adam_t += applied;
+    h->last_ns = 0;
     h->grads.clear();
 }
 
@@ -375,7 +422,7 @@ extern "C" int rnnwf_device_training_supported(rnnwf_handle* h) {
 extern "C" int rnnwf_adam_set_state(rnnwf_handle* h, const double* m_flat, const double* v_flat, int64_t count, int64_t t_steps) {
     if (!h || !h->committed) return RNNWF_ERR_INVALID;
     RNNWF_HIP(h, hipSetDevice(h->cfg.device));
-    if (int rc = build(h)) return rc;
+    if (int rc = build_for(h)) return rc;
     TrainState& t = h->train;
     if (count != t.nparams || t_steps < 0) return h->fail(RNNWF_ERR_INVALID, "rnnwf_adam_set_state: the model has %lld parameters, caller passed %lld", (long long)t.nparams, (long long)count);
     if (m_flat && v_flat) {
@@ -392,7 +439,7 @@ extern "C" int rnnwf_adam_set_state(rnnwf_handle* h, const double* m_flat, const
 extern "C" int rnnwf_adam_get_state(rnnwf_handle* h, double* m_flat, double* v_flat, int64_t count, int64_t* t_steps) {
     if (!h || !h->committed) return RNNWF_ERR_INVALID;
     RNNWF_HIP(h, hipSetDevice(h->cfg.device));
-    if (int rc = build(h)) return rc;
+    if (int rc = build_for(h)) return rc;
     TrainState& t = h->train;
     if (count != t.nparams) return h->fail(RNNWF_ERR_INVALID, "rnnwf_adam_get_state: the model has %lld parameters, caller passed %lld", (long long)t.nparams, (long long)count);
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));

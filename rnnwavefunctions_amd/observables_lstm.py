@@ -12,7 +12,8 @@ The second Renyi entropy of arbitrary regions, block entropies and the Renyi-2 m
 observables.py (rnnwf_renyi2_regions_lstm; docs/renyi_lstm.md): renyi2_regions, renyi2_entropy, renyi2_mutual_information, with
 observables.py's region builders re-exported.  observables.renyi2_regions / renyi2_mutual_information keep refusing the LSTM.
 
-Not here (docs/lstm.md, "Out of scope"): minSR and device-resident Adam for the LSTM.
+Not here: minSR (docs/lstm.md, "Out of scope").  Device-resident Adam on a Hamiltonian is training_lstm.minimize_hamiltonian_device
+(docs/lstm.md, "Device-resident training"); minimize_hamiltonian below keeps refusing device_steps.
 """
 import numpy as np
 
@@ -100,7 +101,8 @@ def minimize_hamiltonian(wf, ham, params, numsteps=1000, numsamples=500, learnin
     of training_lstm.run_2DTFIM_1DRNN_LSTM with its learning rate 1 / (1 / learningrate + it / 10) in iteration it.  Returns
     (meanEnergy, varEnergy), one entry per iteration 0..numsteps; the trained parameters are left in
     minimize_hamiltonian.last_params.  The batch of numsamples must fit one pass of the state budget.  Single process only: a
-    communicator is refused.  device_steps is refused: the LSTM has no device-resident Adam (docs/lstm.md, "Out of scope")."""
+    communicator is refused.  device_steps is refused here, in the words it always was: the same loop with its iterations on the device is
+    training_lstm.minimize_hamiltonian_device (docs/lstm.md, "Device-resident training")."""
     _native_lstm(wf)                                  # another model is told its module before it is told about device_steps
     meanEnergy, varEnergy, minimize_hamiltonian.last_params = _api.minimize_family(
         _api.LSTM, _native_lstm, wf, ham, params, numsteps, numsamples, learningrate, seed, scope, opt, comm, verbose, device_steps,
