@@ -586,6 +586,29 @@ int rnnwf_sr_apply_2d(rnnwf_handle* h, const double* y, double* out_direction);
 int rnnwf_sr_solve_2d(rnnwf_handle* h, double diag_shift, double* y);
 int rnnwf_sr_direction_2d(rnnwf_handle* h, double diag_shift, double* out_direction);
 
+/* ---- stochastic reconfiguration for the LSTM wave function (LSTM1D_F64; docs/sr_lstm.md) -----------------------------------------
+ * psi = sqrt(P) real and positive: the conventions, arguments, state rules, workspace check (ns <= 4096), pivot status and error
+ * codes of the positive model's five calls, on the resident batch of an LSTM1D_F64 handle (one layer, up to 68 units).  O[s][k] =
+ * 1/2 d log P(sigma_s) / d theta_k in the flat order of rnnwf_set_params_flat; sum_s 2 w_s O_s is what rnnwf_lstm_gradient returns
+ * for the weights w.
+ * An LSTM handle has a resident batch only after one of two entries (rnnwf_vmc_step leaves it none and rnnwf_load_batch refuses it);
+ * without one the five calls return RNNWF_ERR_STATE "<entry>: call rnnwf_lstm_load_batch or rnnwf_sr_step_lstm first".
+ * rnnwf_lstm_load_batch: samples (ns, N) int32 and their local energies eloc (ns,) f64 become the resident batch (teacher-forced
+ *     base pass); validates before it touches anything.
+ * rnnwf_sr_step_lstm: one minSR iteration's device work with one host synchronisation - rnnwf_vmc_step's fused TFIM step at (seed,
+ *     step, sample_offset) with couplings = [Jz (N) | Bx], moments (4,) as rnnwf_vmc_step returns them bit for bit, then the
+ *     direction of rnnwf_sr_direction_lstm on that batch into out_direction (nparams,).  The batch and its Jacobian stay resident.
+ * RNNWF_ERR_INVALID "<entry>: only for the LSTM wave function (RNNWF_MODEL_LSTM1D_F64)" for every other model; a handle with a
+ * communicator is refused.  The other families' entries, rnnwf_sr_train_steps among them, keep refusing this model.              */
+int rnnwf_log_derivatives_lstm(rnnwf_handle* h, double* out, int64_t ns, int64_t nparams);
+int rnnwf_sr_gram_lstm(rnnwf_handle* h, double* gram, double* eps);
+int rnnwf_sr_apply_lstm(rnnwf_handle* h, const double* y, double* out_direction);
+int rnnwf_sr_solve_lstm(rnnwf_handle* h, double diag_shift, double* y);
+int rnnwf_sr_direction_lstm(rnnwf_handle* h, double diag_shift, double* out_direction);
+int rnnwf_lstm_load_batch(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* eloc);
+int rnnwf_sr_step_lstm(rnnwf_handle* h, int64_t numsamples, uint64_t seed, uint64_t step, int64_t sample_offset, const double* couplings,
+                       int64_t n_couplings, double diag_shift, double* moments, double* out_direction, int64_t nparams);
+
 /* ---- multi-GPU: one RCCL all-reduce of the energy moments -------------------------------------
  * The reference is single-process; these add the one data-parallel collective of SURVEY.md 8e.
  * One process per GPU: rank 0 calls rnnwf_comm_unique_id and ships the 128 bytes to the other

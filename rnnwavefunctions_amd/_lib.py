@@ -121,6 +121,10 @@ PROTOTYPES["rnnwf_renyi2_regions_lstm"] = PROTOTYPES["rnnwf_renyi2_regions_stack
 PROTOTYPES["rnnwf_lstm_pauli_gradient_step"] = (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I64, _U64, _U64, _I64, _F64P, _F64P, _I32P, _F64P])
 PROTOTYPES["rnnwf_lstm_train_steps"] = PROTOTYPES["rnnwf_train_steps"]                 # the LSTM's device-resident Adam (docs/lstm.md): likewise
 PROTOTYPES["rnnwf_lstm_pauli_train_steps"] = PROTOTYPES["rnnwf_pauli_train_steps"]
+for _name in ("rnnwf_log_derivatives", "rnnwf_sr_gram", "rnnwf_sr_apply", "rnnwf_sr_solve", "rnnwf_sr_direction"):
+    PROTOTYPES[_name + "_lstm"] = PROTOTYPES[_name]                                    # the LSTM's minSR (docs/sr_lstm.md): likewise
+PROTOTYPES["rnnwf_lstm_load_batch"] = (C.c_int, [_P, _I32P, _I64, _F64P])
+PROTOTYPES["rnnwf_sr_step_lstm"] = (C.c_int, [_P, _I64, _U64, _U64, _I64, _F64P, _I64, _F64, _F64P, _F64P, _I64])
 
 _lib = None
 
@@ -558,6 +562,53 @@ class NativeWavefunction:
         """(num_params,) float64: the minSR direction dO^T (dO dO^T + ns diag_shift I)^-1 eps of the resident batch of the 2D RNN,
         everything on the device (rnnwf_sr_direction_2d), in the flat order of _layout()."""
         return self._sr_direction("_2d", diag_shift)
+
+    # -- stochastic reconfiguration for the LSTM wave function: rnnwf_*_lstm (docs/sr_lstm.md) ------
+    def lstm_load_batch(self, samples, eloc):
+        """load_batch for the LSTM wave function (rnnwf_lstm_load_batch): samples (ns, N) or (ns, Nx, Ny) and their local energies
+        (ns,) float64 become the resident batch the *_lstm calls below work on."""
+        s, sp = _i32(samples)
+        if s.ndim < 2 or s.shape[0] < 1 or int(np.prod(s.shape[1:])) != self.N:
+            raise ValueError("samples must be non-empty with %d sites per row, got shape %r" % (self.N, s.shape))
+        e, ep = _f64(eloc)
+        if e.shape != (s.shape[0],):
+            raise ValueError("lstm_load_batch: %d samples but local energies of shape %r" % (s.shape[0], e.shape))
+        self._check(self.lib.rnnwf_lstm_load_batch(self.h, sp, s.shape[0], ep))
+
+    def sr_step_lstm(self, numsamples, seed, step, couplings, diag_shift, sample_offset=0):
+        """One minSR iteration's device work with one host synchronisation (rnnwf_sr_step_lstm; single process): vmc_step's fused
+        step - couplings: Jz (N) then Bx - and the minSR direction of sr_direction_lstm on its batch, which stays resident with its
+        Jacobian.  Returns dict(moments=(4,), direction=(num_params,)): moments are vmc_step's bit for bit, direction is what
+        lstm_load_batch of that step's samples and energies followed by sr_direction_lstm returns, bit for bit."""
+        c, cp = _f64(couplings)
+        mom = np.zeros(4, dtype=np.float64)
+        out = np.empty(self.num_params(), dtype=np.float64)
+        self._check(self.lib.rnnwf_sr_step_lstm(self.h, int(numsamples), int(seed), int(step), int(sample_offset), cp, c.size,
+                                                float(diag_shift), mom.ctypes.data_as(_F64P), out.ctypes.data_as(_F64P), out.size))
+        return {"moments": mom, "direction": out}
+
+    def log_derivatives_lstm(self):
+        """(ns, num_params) float64: O[s, k] = 1/2 d log P(sigma_s) / d theta_k on the resident batch of the LSTM wave function
+        (lstm_load_batch / sr_step_lstm), theta in the flat order of _layout()."""
+        return self._log_derivatives("_lstm")
+
+    def sr_gram_lstm(self):
+        """(gram, eps): the centred Gram matrix dO dO^T (ns, ns) and eps = E_loc - mean E (ns,) of the resident batch of the LSTM
+        wave function, float64; gram is exactly symmetric."""
+        return self._sr_gram("_lstm")
+
+    def sr_apply_lstm(self, y):
+        """(num_params,) float64: dO^T y for y of one entry per sample of the resident batch of the LSTM wave function."""
+        return self._sr_apply("_lstm", y)
+
+    def sr_solve_lstm(self, diag_shift):
+        """(ns,) float64: y of (dO dO^T + ns diag_shift I) y = eps, factorised and solved on the device; y is not centred."""
+        return self._sr_solve("_lstm", diag_shift)
+
+    def sr_direction_lstm(self, diag_shift):
+        """(num_params,) float64: the minSR direction dO^T (dO dO^T + ns diag_shift I)^-1 eps of the resident batch of the LSTM wave
+        function, everything on the device (rnnwf_sr_direction_lstm), in the flat order of _layout()."""
+        return self._sr_direction("_lstm", diag_shift)
 
     # -- device-resident training iteration (rnnwf_train_steps; single-layer float32 GRU models) ------------------
     def device_training_supported(self):

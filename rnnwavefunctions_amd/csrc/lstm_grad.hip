@@ -73,6 +73,19 @@ struct LGrad {
         return tn_gemm_launch<double, G::PCOLS / 16, G::QCOLS / 16>(h, a.P, a.Q, R, (double*)h->gradW.p);
     }
 
+    // the unit-weight pass of stochastic reconfiguration (sr.hip): the same P and Q rows, every chain's head row into head_rows
+    // [ns][HEAD_ROW]; no reduction follows, so the launch is the persistent one without head_reduce_kernel
+    static int sr_run(rnnwf_handle* h, LstmGradArgs a, double* head_rows) {
+        const int64_t R = a.ns * a.N;
+        if (int rc = ensure(h, h->gradP, (size_t)R * G::PCOLS * 8)) return rc;
+        if (int rc = ensure(h, h->gradQ, (size_t)R * G::QCOLS * 8)) return rc;
+        a.P = (double*)h->gradP.p;
+        a.Q = (double*)h->gradQ.p;
+        a.head_part = head_rows;
+        return launch_persistent(h, kTimerBackprop, lstm_bwd_kernel<NFULL, kLstmGradWaves, true>, kLstmGradWaves * 64, G::LDS, a.nsb,
+                                 kLstmGradWaves, a);
+    }
+
     // dW image [PCOLS][QCOLS] + head row -> TF-named gradient arrays
     static void unpack(rnnwf_handle* h, const double* dW) {
         const int H = h->H;
@@ -170,20 +183,28 @@ int rnnwf::lstm_grad_flat_probe(rnnwf_handle* h, std::vector<int32_t>& sidx, siz
 // head row are queued for download into h->staging.  The caller synchronises once and calls lstm_grad_finish.  (Declared in models.h:
 // rnnwf_lstm_pauli_gradient_step, lstm_pauli.hip, runs it on the batch of its Pauli pass.)
 // download = false (device-resident training, rnnwf_lstm_train_steps): the result stays in h->gradW, where Adam reads it.
+namespace {
+// what every backward pass reads of the batch in h->bits / h->hck
+LstmGradArgs batch_args(rnnwf_handle* h, int64_t ns) {
+    LstmGradArgs a{};
+    a.wimg = h->wimg.p;
+    a.wbwd = h->wbwd.p;
+    a.N = h->N;
+    a.ns = ns;
+    a.nsb = (ns + kChains - 1) / kChains;
+    a.bits = (const uint32_t*)h->bits.p;
+    a.hck = (const double*)h->hck.p;
+    return a;
+}
+}  // namespace
+
 int rnnwf::lstm_grad_queue(rnnwf_handle* h, const char* what, int64_t ns, const double* w_dev, bool download) {
     return with_lstm_grad(h, what, [&](auto k) -> int {
         using K = decltype(k);
         if (int rc = lstm_bwd_image(h, what)) return rc;
         if (int rc = ensure(h, h->gradW, K::COUNT * 8)) return rc;
         RNNWF_HIP(h, hipMemsetAsync(h->gradW.p, 0, K::COUNT * 8, h->stream));
-        LstmGradArgs a{};
-        a.wimg = h->wimg.p;
-        a.wbwd = h->wbwd.p;
-        a.N = h->N;
-        a.ns = ns;
-        a.nsb = (ns + kChains - 1) / kChains;
-        a.bits = (const uint32_t*)h->bits.p;
-        a.hck = (const double*)h->hck.p;
+        LstmGradArgs a = batch_args(h, ns);
         a.weights = w_dev;
         a.eloc = (const double*)h->eloc.p;
         a.mom = (const double*)h->moments.p;
@@ -192,6 +213,14 @@ int rnnwf::lstm_grad_queue(rnnwf_handle* h, const char* what, int64_t ns, const 
         if (int rc = ensure_staging(h, K::COUNT * 8)) return rc;      // pinned: the copy is a plain DMA, the one wait is the caller's
         RNNWF_HIP(h, hipMemcpyAsync(h->staging, h->gradW.p, K::COUNT * 8, hipMemcpyDeviceToHost, h->stream));
         return 0;
+    });
+}
+// stochastic reconfiguration (sr.hip): the backward pass in its unit-weight mode over the resident batch (h->last_ns chains in
+// h->bits / h->hck); the rows of P and Q into h->gradP / h->gradQ, every chain's head row into head_rows.  h->wbwd is current
+// (lstm_bwd_image: sr_build_shape)
+int rnnwf::lstm_sr_backward(rnnwf_handle* h, double* head_rows) {
+    return with_lstm_grad(h, "stochastic reconfiguration", [&](auto k) -> int {
+        return decltype(k)::sr_run(h, batch_args(h, h->last_ns), head_rows);
     });
 }
 void rnnwf::lstm_grad_finish(rnnwf_handle* h) {

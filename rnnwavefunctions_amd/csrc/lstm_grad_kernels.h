@@ -56,10 +56,14 @@ struct LstmGradArgs {
     double* P;                 // [N*ns][PCOLS]
     double* Q;                 // [N*ns][QCOLS]
     double* head_grad;         // [HEAD_ROW], written by head_reduce_kernel
-    double* head_part;         // [waves of the grid][HEAD_ROW]
+    double* head_part;         // [waves of the grid][HEAD_ROW]; SR: [ns][HEAD_ROW], every chain's
 };
 
-template <int NFULL, int WAVES>
+// SR (sr.hip: the per-sample log-derivatives, docs/sr_lstm.md): unit weights w_s = 1 - weights, eloc and mom are not read - and the
+// head row of every chain kept on its own, head_part = [ns][HEAD_ROW] (slot 4 k + q a unit, 4 KT the bias: store_head_part's
+// layout), instead of one sum per wave: lane (c, q) holds the units 4 k + q of chain c in hg[0][k], so the row is stored without a
+// reduction.  The P and Q rows are the same rows.
+template <int NFULL, int WAVES, bool SR = false>
 __global__ void __launch_bounds__(WAVES * 64) lstm_bwd_kernel(LstmGradArgs a) {
     using C = LstmCore<NFULL>;
     using L = LstmLayout<NFULL>;
@@ -105,7 +109,14 @@ __global__ void __launch_bounds__(WAVES * 64) lstm_bwd_kernel(LstmGradArgs a) {
         const bool valid = s < a.ns;
         const int64_t sc = valid ? s : a.ns - 1;
         double w = 0.0;
-        if (valid) w = a.weights ? a.weights[sc] : (a.eloc[sc] - a.mom[0] / a.mom[2]) * (1.0 / a.mom[2]);
+        if constexpr (SR) {
+            if (valid) w = 1.0;
+            gb[0] = 0.0;
+#pragma unroll
+            for (int k = 0; k < KT; ++k) hg[0][k] = 0.0;
+        } else {
+            if (valid) w = a.weights ? a.weights[sc] : (a.eloc[sc] - a.mom[0] / a.mom[2]) * (1.0 / a.mom[2]);
+        }
         auto word = [&](int wi) { return a.bits[(int64_t)wi * a.ns + sc]; };
         // the spin words of sites n and n - 1 sit in registers; the word below is fetched 32 sites ahead (gru_bwd_kernel)
         uint32_t wcur = word((N - 1) >> 5), wlow = N > 32 ? word(((N - 1) >> 5) - 1) : 0u;
@@ -283,8 +294,16 @@ __global__ void __launch_bounds__(WAVES * 64) lstm_bwd_kernel(LstmGradArgs a) {
 #pragma unroll
             for (int k = 0; k < KT; ++k) hcur[k] = hin[k];          // h' of site n - 1
         }
+        if constexpr (SR) {
+            if (valid) {
+                double* row = a.head_part + s * G::HEAD_ROW;
+#pragma unroll
+                for (int k = 0; k < KT; ++k) row[4 * k + q] = hg[0][k];
+                row[4 * KT + q] = q == 0 ? gb[0] : 0.0;
+            }
+        }
     }
-    store_head_part<double, 1, KT>(a.head_part + (size_t)gw * G::HEAD_ROW, G::HEAD_ROW, hg, gb, c, q);
+    if constexpr (!SR) store_head_part<double, 1, KT>(a.head_part + (size_t)gw * G::HEAD_ROW, G::HEAD_ROW, hg, gb, c, q);
 }
 
 }  // namespace rnnwf

@@ -135,6 +135,9 @@ int lstm_pack_table(rnnwf_handle* h);
 int lstm_bwd_pack_table(rnnwf_handle* h);
 int lstm_bwd_image(rnnwf_handle* h, const char* what);
 int lstm_grad_flat_probe(rnnwf_handle* h, std::vector<int32_t>& sidx, size_t* count);
+// lstm_grad.hip, for stochastic reconfiguration (sr.hip): lstm_bwd_kernel's unit-weight mode over the resident batch - the rows of P
+// and Q into h->gradP / h->gradQ, every chain's head row into head_rows [ns][HEAD_ROW]
+int lstm_sr_backward(rnnwf_handle* h, double* head_rows);
 // crnn.hip, for the complex RNN's Pauli pass (crnn_pauli.hip): the same three for the one-layer complex RNN
 int crnn_plain_base(rnnwf_handle* h, const CrnnArgs& a);
 CrnnArgs crnn_base_args(rnnwf_handle* h, int64_t ns);

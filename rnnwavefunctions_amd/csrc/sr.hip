@@ -8,6 +8,9 @@
 // = [Re O ; Im O], each half centred with its own mean, and the same solve path on a system of order 2 ns.
 // The 2D RNN (MDRNN2D, float64, up to 84 units) has them as rnnwf_*_2d (docs/sr_2d.md): J[ns][D_2] in the order of its gradient image,
 // from mdrnn_bwd_kernel's unit-weight mode (mdrnn.hip: mdrnn_sr_backward); one row block, everything behind J as for the positive GRU.
+// The LSTM wave function (LSTM1D_F64, up to 68 units) has them as rnnwf_*_lstm (docs/sr_lstm.md): J[ns][D_l] from lstm_bwd_kernel's
+// unit-weight mode (lstm_grad.hip: lstm_sr_backward).  Its resident batch comes from two entries of its own, rnnwf_lstm_load_batch and
+// rnnwf_sr_step_lstm (the fused step and the whole direction in one call): rnnwf_vmc_step leaves an LSTM handle none.
 #include <cmath>
 #include <cstring>
 
@@ -27,9 +30,9 @@ constexpr int kSrMaxNFULL = 4;             // up to 68 units
 constexpr int kSrMaxSteps = 1024;          // iterations of one rnnwf_sr_train_steps call: the rows of train.hip's pinned moments table (kMaxSteps)
 
 // An entry point: its name, and the family it belongs to - the positive GRU's, the complex RNN's (rnnwf_*_complex, docs/sr_complex.md)
-// or the 2D RNN's (rnnwf_*_2d, docs/sr_2d.md).  Which handles an entry serves depends on the entry; once it has accepted a handle, the
+// the 2D RNN's (rnnwf_*_2d, docs/sr_2d.md) or the LSTM's (rnnwf_*_lstm, docs/sr_lstm.md).  Which handles an entry serves depends on the entry; once it has accepted a handle, the
 // handle's model decides everything else (sr_halves, with_sr_shape).
-enum SrFamily { kSrPositive, kSrComplex, kSr2D };
+enum SrFamily { kSrPositive, kSrComplex, kSr2D, kSrLstm };
 struct SrEntry {
     const char* name;
     SrFamily family;
@@ -45,6 +48,11 @@ int sr_refuse(rnnwf_handle* h, const SrEntry& e) {
     const char* why = nullptr;
     if (e.family == kSr2D) {
         if (h->model != RNNWF_MODEL_MDRNN2D) why = "only for the 2D RNN (RNNWF_MODEL_MDRNN2D)";
+        else if (h->comm) why = "not implemented for a handle with a communicator";
+        return why ? h->fail(RNNWF_ERR_INVALID, "%s: %s", entry, why) : 0;
+    }
+    if (e.family == kSrLstm) {                             // (one layer, up to 68 units: every LSTM handle there is)
+        if (h->model != RNNWF_MODEL_LSTM1D_F64) why = "only for the LSTM wave function (RNNWF_MODEL_LSTM1D_F64)";
         else if (h->comm) why = "not implemented for a handle with a communicator";
         return why ? h->fail(RNNWF_ERR_INVALID, "%s: %s", entry, why) : 0;
     }
@@ -69,13 +77,16 @@ int sr_refuse(rnnwf_handle* h, const SrEntry& e) {
 }
 
 // fn(SrShape<T, NFULL, NOUT>()) for the handle's row among the one-layer rows of its family's table up to kSrMaxNFULL (shapes.h):
-// the positive GRU's (NOUT 1) or the complex RNN's (NOUT 3); fn(MdSrShape<NFULL>()) for every row of the 2D RNN's table
+// the positive GRU's (NOUT 1) or the complex RNN's (NOUT 3); fn(MdSrShape<NFULL>()) for every row of the 2D RNN's table,
+// fn(LstmSrShape<NFULL>()) for every row of the LSTM's
 template <class R> struct SrRow : std::bool_constant<R::NL == 1 && R::NFULL <= kSrMaxNFULL> {};
 template <class Fn>
 int with_sr_shape(rnnwf_handle* h, Fn&& fn) {
     int rc = 0;
     const bool hit = h->model == RNNWF_MODEL_MDRNN2D
         ? with_row<OneLayer>(MdKernels(), h, [&](auto r) { rc = fn(MdSrShape<decltype(r)::NFULL>()); })
+        : h->model == RNNWF_MODEL_LSTM1D_F64
+        ? with_row<SrRow>(LstmKernels(), h, [&](auto r) { rc = fn(LstmSrShape<decltype(r)::NFULL>()); })
         : h->model == RNNWF_MODEL_CRNN_U1
         ? with_row<SrRow>(CrnnKernels(), h, [&](auto r) { rc = fn(SrShape<typename decltype(r)::T, decltype(r)::NFULL, 3>()); })
         : with_row<SrRow>(GruKernels(), h, [&](auto r) { rc = fn(SrShape<typename decltype(r)::T, decltype(r)::NFULL>()); });
@@ -112,7 +123,10 @@ int sr_ready(rnnwf_handle* h, const SrEntry& e, bool factor = false) {
     const char* entry = e.name;
     if (int rc = sr_refuse(h, e)) return rc;
     if (int rc = sr_committed(h, entry)) return rc;
-    if (h->last_ns <= 0) return h->fail(RNNWF_ERR_STATE, "%s: call rnnwf_vmc_step first (its samples, states and E_loc are reused)", entry);
+    if (h->last_ns <= 0)
+        return e.family == kSrLstm
+            ? h->fail(RNNWF_ERR_STATE, "%s: call rnnwf_lstm_load_batch or rnnwf_sr_step_lstm first (their samples, states and E_loc are reused)", entry)
+            : h->fail(RNNWF_ERR_STATE, "%s: call rnnwf_vmc_step first (its samples, states and E_loc are reused)", entry);
     if (int rc = sr_workspace(h, entry, h->last_ns, factor)) return rc;
     RNNWF_HIP(h, hipSetDevice(h->cfg.device));
     return 0;
@@ -122,8 +136,13 @@ int sr_ready(rnnwf_handle* h, const SrEntry& e, bool factor = false) {
 int sr_table(rnnwf_handle* h, int64_t D) {
     if (!h->sr_sidx.empty()) return 0;
     std::vector<int32_t> sidx;
-    GradImage im;
-    if (int rc = grad_flat_probe(h, sidx, &im)) return rc;
+    GradImage im{};
+    if (h->model == RNNWF_MODEL_LSTM1D_F64) {              // no hook table: the probe of its own unpacker (lstm_grad.hip), +- for the head's two columns
+        im.f64 = true;
+        if (int rc = lstm_grad_flat_probe(h, sidx, &im.count)) return rc;
+    } else if (int rc = grad_flat_probe(h, sidx, &im)) {
+        return rc;
+    }
     if ((int64_t)im.count != D || im.f64 != h->f64) return h->fail(RNNWF_ERR_INVALID, "stochastic reconfiguration: gradient image of %zu elements, expected %lld", im.count, (long long)D);
     std::vector<uint8_t> used((size_t)D, 0);
     for (int32_t v : sidx)
@@ -157,6 +176,11 @@ template <int NFULL>
 int sr_backward(rnnwf_handle* h, MdSrShape<NFULL>, int) {
     return mdrnn_sr_backward(h, (double*)h->srHead.p);
 }
+// LSTM: lstm_bwd_kernel<SR> behind the arguments of its gradient launch
+template <int NFULL>
+int sr_backward(rnnwf_handle* h, LstmSrShape<NFULL>, int) {
+    return lstm_sr_backward(h, (double*)h->srHead.p);
+}
 
 template <class S>
 int sr_build_shape(rnnwf_handle* h) {
@@ -165,7 +189,7 @@ int sr_build_shape(rnnwf_handle* h) {
     const int N = h->N;
     const int64_t ns = h->last_ns;
     if (int rc = sr_table(h, S::D)) return rc;
-    if (int rc = grad_bwd_image(h)) return rc;
+    if (int rc = h->model == RNNWF_MODEL_LSTM1D_F64 ? lstm_bwd_image(h, "stochastic reconfiguration") : grad_bwd_image(h)) return rc;
     if (int rc = ensure(h, h->srHead, (size_t)ns * S::NOUT * G::HEAD_ROW * sizeof(T))) return rc;
     if (int rc = ensure(h, h->srJ, (size_t)sr_halves(h) * ns * S::D * sizeof(T))) return rc;
     // complex RNN: one backward pass and one outer-product pass per seed, Re O into the rows [0, ns) and Im O into [ns, 2 ns).  Both
@@ -306,8 +330,8 @@ void sr_gather(const std::vector<int32_t>& sidx, const T* img, double* flat) {
 
 extern "C" int64_t rnnwf_resident_samples(const rnnwf_handle* h) { return h ? h->last_ns : 0; }
 
-// ---- the five calls on the resident batch, each behind the positive GRU's entry, the complex RNN's (docs/sr_complex.md) and the 2D
-// RNN's (docs/sr_2d.md).  Below the refusal the three run the same code on sr_halves(h) row blocks of ns rows: n = sr_order(h) rows of J, a Gram matrix and a
+// ---- the five calls on the resident batch, each behind the positive GRU's entry, the complex RNN's (docs/sr_complex.md), the 2D
+// RNN's (docs/sr_2d.md) and the LSTM's (docs/sr_lstm.md).  Below the refusal the four run the same code on sr_halves(h) row blocks of ns rows: n = sr_order(h) rows of J, a Gram matrix and a
 // solve of order n, y and eps of n entries ([Re ; Im] for the complex RNN).
 
 static int sr_log_derivatives(rnnwf_handle* h, const SrEntry& e, double* out, int64_t ns, int64_t nparams) {
@@ -398,11 +422,8 @@ static int sr_solve(rnnwf_handle* h, const SrEntry& e, double diag_shift, double
     return RNNWF_OK;
 }
 
-static int sr_direction(rnnwf_handle* h, const SrEntry& e, double diag_shift, double* out_direction) {
-    if (!h) return RNNWF_ERR_INVALID;
-    if (!out_direction) return h->fail(RNNWF_ERR_INVALID, "%s: bad arguments", e.name);
-    if (int rc = sr_solve_common(h, e, diag_shift)) return rc;
-    if (int rc = sr_direction_queue(h)) return rc;
+// behind sr_direction_queue: the one synchronisation, the pivot status, the gather into flat order
+static int sr_direction_finish(rnnwf_handle* h, const char* entry, double diag_shift, double* out_direction) {
     const int64_t D = sr_image_size(h);
     const double* col = sr_direction_image(h);
     if (int rc = ensure_staging(h, (size_t)(D + 1) * 8)) return rc;
@@ -410,9 +431,17 @@ static int sr_direction(rnnwf_handle* h, const SrEntry& e, double diag_shift, do
     RNNWF_HIP(h, hipMemcpyAsync((double*)h->staging + D, sr_status(h), 8, hipMemcpyDeviceToHost, h->stream));
     RNNWF_HIP(h, hipStreamSynchronize(h->stream));
     const long long status = ((const long long*)h->staging)[D];
-    if (status) return sr_pivot_error(h, e.name, status, diag_shift);
+    if (status) return sr_pivot_error(h, entry, status, diag_shift);
     sr_gather(h->sr_sidx, (const double*)h->staging, out_direction);
     return RNNWF_OK;
+}
+
+static int sr_direction(rnnwf_handle* h, const SrEntry& e, double diag_shift, double* out_direction) {
+    if (!h) return RNNWF_ERR_INVALID;
+    if (!out_direction) return h->fail(RNNWF_ERR_INVALID, "%s: bad arguments", e.name);
+    if (int rc = sr_solve_common(h, e, diag_shift)) return rc;
+    if (int rc = sr_direction_queue(h)) return rc;
+    return sr_direction_finish(h, e.name, diag_shift, out_direction);
 }
 
 extern "C" int rnnwf_log_derivatives(rnnwf_handle* h, double* out, int64_t ns, int64_t nparams) {
@@ -453,6 +482,80 @@ extern "C" int rnnwf_sr_apply_2d(rnnwf_handle* h, const double* y, double* out_d
 extern "C" int rnnwf_sr_solve_2d(rnnwf_handle* h, double diag_shift, double* y) { return sr_solve(h, {"rnnwf_sr_solve_2d", kSr2D}, diag_shift, y); }
 extern "C" int rnnwf_sr_direction_2d(rnnwf_handle* h, double diag_shift, double* out_direction) {
     return sr_direction(h, {"rnnwf_sr_direction_2d", kSr2D}, diag_shift, out_direction);
+}
+
+extern "C" int rnnwf_log_derivatives_lstm(rnnwf_handle* h, double* out, int64_t ns, int64_t nparams) {
+    return sr_log_derivatives(h, {"rnnwf_log_derivatives_lstm", kSrLstm}, out, ns, nparams);
+}
+extern "C" int rnnwf_sr_gram_lstm(rnnwf_handle* h, double* gram, double* eps) { return sr_gram(h, {"rnnwf_sr_gram_lstm", kSrLstm}, gram, eps); }
+extern "C" int rnnwf_sr_apply_lstm(rnnwf_handle* h, const double* y, double* out_direction) {
+    return sr_apply(h, {"rnnwf_sr_apply_lstm", kSrLstm}, y, out_direction);
+}
+extern "C" int rnnwf_sr_solve_lstm(rnnwf_handle* h, double diag_shift, double* y) {
+    return sr_solve(h, {"rnnwf_sr_solve_lstm", kSrLstm}, diag_shift, y);
+}
+extern "C" int rnnwf_sr_direction_lstm(rnnwf_handle* h, double diag_shift, double* out_direction) {
+    return sr_direction(h, {"rnnwf_sr_direction_lstm", kSrLstm}, diag_shift, out_direction);
+}
+
+// ---- the LSTM's resident batch (docs/sr_lstm.md, "The resident batch").  lstm_family() has no gradient hook, so rnnwf_vmc_step
+// leaves an LSTM handle no batch and rnnwf_load_batch refuses it; these two entries are the only ones that set h->last_ns on one.
+// Every place that overwrites h->bits, h->hck or h->eloc clears it (rnnwf_api.hip), and so does a commit.
+
+// rnnwf_load_batch for the LSTM: the caller's samples packed into h->bits, the teacher-forced base pass with its (h, c) checkpoints,
+// the caller's E_loc (float64) into h->eloc.  Everything is validated before anything is touched.
+extern "C" int rnnwf_lstm_load_batch(rnnwf_handle* h, const int32_t* samples, int64_t ns, const double* eloc) {
+    if (!h) return RNNWF_ERR_INVALID;
+    const char* entry = "rnnwf_lstm_load_batch";
+    if (int rc = sr_refuse(h, SrEntry{entry, kSrLstm})) return rc;
+    if (int rc = sr_committed(h, entry)) return rc;
+    if (ns < 1 || !samples || !eloc) return h->fail(RNNWF_ERR_INVALID, "%s: bad arguments", entry);
+    if (int rc = refuse_past_budget(h, ns, entry)) return rc;
+    RNNWF_HIP(h, hipSetDevice(h->cfg.device));
+    h->last_ns = 0;
+    h->call_ns = ns;
+    if (int rc = upload_and_pack(h, samples, ns, h->bits, 0, nullptr)) return rc;
+    if (int rc = lstm_teacher_base(h, ns)) return rc;
+    if (int rc = ensure(h, h->eloc, (size_t)ns * 8)) return rc;
+    RNNWF_HIP(h, hipMemcpyAsync(h->eloc.p, eloc, (size_t)ns * 8, hipMemcpyHostToDevice, h->stream));
+    RNNWF_HIP(h, hipStreamSynchronize(h->stream));
+    h->last_ns = ns;
+    h->sr_valid = false;
+    return RNNWF_OK;
+}
+
+// One minSR iteration's device work with one host synchronisation: the fused VMC step (its moments written into the step's pinned row,
+// as rnnwf_lstm_vmc_gradient_step has them), then on its batch the Jacobian, the Gram matrix, the solve and dO^T y as
+// rnnwf_sr_direction_lstm queues them.  The batch and its Jacobian stay resident.
+extern "C" int rnnwf_sr_step_lstm(rnnwf_handle* h, int64_t numsamples, uint64_t seed, uint64_t step, int64_t sample_offset,
+                                  const double* couplings, int64_t n_couplings, double diag_shift, double* moments, double* out_direction,
+                                  int64_t nparams) {
+    if (!h) return RNNWF_ERR_INVALID;
+    const char* entry = "rnnwf_sr_step_lstm";
+    if (int rc = sr_refuse(h, SrEntry{entry, kSrLstm})) return rc;
+    if (int rc = sr_committed(h, entry)) return rc;
+    if (numsamples < 1 || !couplings || !moments || !out_direction) return h->fail(RNNWF_ERR_INVALID, "%s: bad arguments", entry);
+    if (n_couplings != (int64_t)h->family->coupl_per_site * h->N + h->family->coupl_tail)
+        return h->fail(RNNWF_ERR_INVALID, "%s: wrong number of couplings", entry);
+    if (nparams != rnnwf_num_params(h))
+        return h->fail(RNNWF_ERR_INVALID, "%s: the model has %lld parameters, caller passed %lld", entry, (long long)rnnwf_num_params(h),
+                       (long long)nparams);
+    if (h->nranks > 1 || h->reduce_in_step) return h->fail(RNNWF_ERR_INVALID, "%s: single process only", entry);
+    if (int rc = sr_check_shift(h, entry, diag_shift)) return rc;
+    if (int rc = sr_workspace(h, entry, numsamples, true)) return rc;
+    if (int rc = refuse_past_budget(h, numsamples, entry)) return rc;
+    // nothing was touched so far: a refused call leaves the resident batch and its Jacobian as they were
+    RNNWF_HIP(h, hipSetDevice(h->cfg.device));
+    h->moments_direct = (double*)h->pinned_dev;
+    const int rc_step = vmc_step(h, numsamples, Draw{seed, step, sample_offset}, couplings, nullptr, nullptr, nullptr);
+    h->moments_direct = nullptr;
+    if (rc_step) return rc_step;
+    h->last_ns = numsamples;                                  // (vmc_step cleared sr_valid: keep_resident)
+    if (int rc = sr_solve_queue(h, diag_shift)) return rc;
+    if (int rc = sr_direction_queue(h)) return rc;
+    if (int rc = sr_direction_finish(h, entry, diag_shift, out_direction)) return rc;
+    memcpy(moments, h->pinned, 4 * sizeof(double));
+    return RNNWF_OK;
 }
 
 // K whole minSR iterations with one host synchronisation (docs/sr.md, "Iterations on the device"): per iteration the fused VMC step,

@@ -5,6 +5,7 @@
 //   Complex RNN (docs/sr_complex.md): J[2 ns][D_c], D_c = PCOLS QCOLS + 3 HEAD_ROW, row s = Re O_s, row ns + s = Im O_s; the rows
 //   [0, ns) and [ns, 2 ns) are centred with their own column means (HALVES).
 //   2D RNN (docs/sr_2d.md): J[ns][D_2], D_2 = PCOLS QCOLS + 2 HEAD_ROW of MdGradLayout, from the rows mdrnn_bwd_kernel<SR> left.
+//   LSTM (docs/sr_lstm.md): J[ns][D_l], D_l = PCOLS QCOLS + HEAD_ROW of LstmGradLayout, from the rows lstm_bwd_kernel<SR> left.
 //
 //   sr_outer_kernel  : O_s = 1/2 sum_n p_{n ns + s} (x) q_{n ns + s} from the rows gru_bwd_kernel<SR> left in P and Q (unit weights),
 //                      plus 1/2 of the sample's head row; image elements that no parameter reads (padding) are written as zeros.
@@ -14,6 +15,7 @@
 // Every sum has a fixed order (no atomics): the same batch gives the same bits.
 #pragma once
 #include "grad_kernels.h"
+#include "lstm_grad_kernels.h"
 #include "mdrnn_grad_kernels.h"
 
 namespace rnnwf {
@@ -55,6 +57,14 @@ struct SrShape : SrTiles<T, GradLayout<NFULL, T>, NOUT_, kSrGruWaves<T, NFULL>, 
 // two (up to 52 units) or four (53..84 units: eight waves) columns of waves.
 template <int NFULL>
 struct MdSrShape : SrTiles<double, MdGradLayout<NFULL>, 2, NFULL <= 3 ? 4 : 8, NFULL <= 3 ? 2 : 4, true> {
+    static constexpr int NF = NFULL;
+};
+
+// The LSTM (docs/sr_lstm.md): (4 NFULL + 1) x (NFULL + 1) tiles of 8 registers, a P-heavy image - the P tiles go round four (up to 20
+// units) or eight waves and no wave splits the Q tiles: 2 x 2, 2 x 3 and 2 x 4 tiles per wave in one pass, 3 x 5 in three passes of
+// 2, 2 and 1 Q tiles at 53..68 units.
+template <int NFULL>
+struct LstmSrShape : SrTiles<double, LstmGradLayout<NFULL>, 1, NFULL == 1 ? 4 : 8, 1, true> {
     static constexpr int NF = NFULL;
 };
 

@@ -240,3 +240,60 @@ def train_tfim2d(wf, Jz, Bx, params, numsteps=100, numsamples=500, learningrate=
     theta = _real_host_loop(wf, "_2d", theta, dtype, couplings, numsteps, numsamples, learningrate, diag_shift, seed, solver, meanEnergy, varEnergy)
     train_tfim2d.last_params = unflatten_params(wf, theta, params, scope)
     return meanEnergy, varEnergy
+
+
+# ---- the LSTM wave function (docs/sr_lstm.md) -------------------------------------------------------------------------------------
+# psi = sqrt(P) real and positive on the raster path: the positive model's formulas and solve, on the rnnwf_*_lstm entries of an
+# LSTM1D_F64 handle.  Its resident batch comes from wf.lstm_load_batch or wf.sr_step_lstm: vmc_step leaves an LSTM handle none.
+
+def minsr_direction_lstm(wf, diag_shift, solver="host"):
+    """delta (num_params,) float64 on the resident batch of the LSTM wave function `wf` (lstm_load_batch / sr_step_lstm), flat
+    order of wf._layout().  solver "host": the Gram matrix to the host, LAPACK Cholesky, sr_apply_lstm; "device": wf.sr_direction_lstm."""
+    return _real_direction(wf, "_lstm", diag_shift, solver)
+
+
+def qgt_lstm(wf):
+    """S = dO^T dO / ns (num_params, num_params) float64 from the per-sample log-derivatives of the resident batch of the LSTM wave
+    function.  For diagnostics and small models."""
+    return _real_qgt(wf.log_derivatives_lstm())
+
+
+def train_tfim_lstm(wf, Jz, Bx, params, numsteps=100, numsamples=500, learningrate=1e-2, diag_shift=1e-3, seed=111, scope="RNNwavefunction",
+                    solver="device"):
+    """Minimise the square-lattice TFIM energy of `wf` (a NativeWavefunction of LSTM1D_F64 holding `params`) by minSR, with
+    train_tfim2d's semantics: per iteration 0..numsteps a batch drawn at (seed, step = iteration), the minSR direction on it,
+    theta -= lr delta, set_params_flat.  solver "device": one wf.sr_step_lstm per iteration (the fused step and the whole direction
+    with one host synchronisation).  solver "host": wf.vmc_step with its samples and energies returned, wf.lstm_load_batch, the
+    Gram matrix to the host, LAPACK Cholesky, sr_apply_lstm.  Both see the same batches.  Jz: a scalar or one entry per site in the
+    order of vmc_step's couplings.  Returns (meanEnergy, varEnergy), one entry per iteration; the trained parameters are left in
+    train_tfim_lstm.last_params and keep the dtype of `params`.  Whole iterations without the host (sr_train_steps) are not
+    implemented for the LSTM: there is no device_steps argument."""
+    lam = _check_shift(diag_shift)
+    _check_solver(solver)
+    if int(numsteps) < 0 or int(numsamples) < 2:
+        raise ValueError("numsteps must be >= 0 and numsamples >= 2, got %r and %r" % (numsteps, numsamples))
+    N = wf.N                                            # Nx Ny sites
+    if np.size(Jz) not in (1, N):
+        raise ValueError("Jz must be a scalar or have %d entries, got %d" % (N, np.size(Jz)))
+    jz = np.broadcast_to(np.asarray(Jz, dtype=np.float64).ravel(), (N,))
+    couplings = np.concatenate([jz, [float(Bx)]])
+    dtype = next(iter(params.values())).dtype
+    theta = flatten_params(wf, params, scope).astype(dtype).astype(np.float64)
+    wf.set_params_flat(theta)
+    meanEnergy, varEnergy = [], []
+    for it in range(int(numsteps) + 1):
+        if solver == "device":
+            out = wf.sr_step_lstm(int(numsamples), seed, it, couplings, lam)
+            delta = out["direction"]
+        else:
+            out = wf.vmc_step(int(numsamples), seed, it, couplings, want_samples=True, want_eloc=True)
+            wf.lstm_load_batch(out["samples"], out["eloc"])
+            delta = _real_direction(wf, "_lstm", lam, "host")
+        s1, s2, n, _ = out["moments"]
+        meanE = s1 / n
+        meanEnergy.append(meanE)
+        varEnergy.append(s2 / n - meanE ** 2)
+        theta = (theta - learningrate * delta).astype(dtype).astype(np.float64)
+        wf.set_params_flat(theta)
+    train_tfim_lstm.last_params = unflatten_params(wf, theta, params, scope)
+    return meanEnergy, varEnergy
