@@ -346,6 +346,25 @@ int rnnwf_correlations(rnnwf_handle* h, const int32_t* samples, int64_t ns, uint
                        int64_t sample_offset, double* z_sums, double* zz_sums, double* x_sums, double* xx_sums,
                        double* out_log_ratio, int32_t* out_samples);
 
+/* ---- correlation functions of the LSTM wave function ----------------------------------------------------
+ * rnnwf_correlations for the LSTM cell over the raster path (LSTM1D_F64, one layer, 1..68 units, float64; every other model:
+ * RNNWF_ERR_INVALID naming the entry that serves it, if one does) - docs/correlations_lstm.md.  The estimators, the arguments,
+ * the layouts and shapes of the outputs, the pass rule (whole 16-chain blocks under the state budget, per-chain results
+ * independent of the pass size, sums of the passes added on the host in pass order), the fixed-order reductions and the overflow
+ * rule (a chain with log r > 709 makes the sums it enters +inf) are rnnwf_correlations'.  Sites are the chain position: the
+ * column of `samples`, the raster index ny * Nx + nx.  Trunk i (spin i flipped) restarts from the base pass's state (h, c)
+ * after site i and keeps its own states; branch (i, j) restarts from trunk i's state after site j:
+ * N(N-1)/2 + N(N-1)(N-2)/6 cell evaluations per chain.  N = 1 runs no trunk kernel, N <= 2 no branch kernel.
+ * Everything is validated before anything is touched: a refused call (another model, uncommitted parameters - RNNWF_ERR_STATE -,
+ * ns < 1, a null sums array, sample_offset < 0 with drawn samples) leaves a batch of rnnwf_lstm_load_batch resident; a served
+ * call overwrites it, and rnnwf_resident_samples is 0 afterwards.
+ * Timing ids: 0 = base passes (the draw and the teacher-forced pass with checkpoints and both outcomes of every site),
+ * 1 = trunk + branch passes, 2 = log-ratio assembly + sums.  work[0] += ns (N(N-1)/2 + N(N-1)(N-2)/6); work[1] += the MFMA flops
+ * of those evaluations (per 16-chain block, padding included). */
+int rnnwf_correlations_lstm(rnnwf_handle* h, const int32_t* samples, int64_t ns, uint64_t seed, uint64_t step,
+                            int64_t sample_offset, double* z_sums, double* zz_sums, double* x_sums, double* xx_sums,
+                            double* out_log_ratio, int32_t* out_samples);
+
 /* ---- Pauli strings and arbitrary spin Hamiltonians ---------------------------------------------------
  * Expectation values of products of Pauli matrices and the local energy of any real-symmetric spin-1/2 Hamiltonian, for the
  * positive one-layer GRU models (GRU1D, GRU1D_F64; every other model and stacked layers: RNNWF_ERR_INVALID), psi = sqrt(P),

@@ -118,6 +118,7 @@ PROTOTYPES["rnnwf_pauli_train_steps_stack"] = PROTOTYPES["rnnwf_pauli_train_step
 PROTOTYPES["rnnwf_renyi2_regions_stack"] = PROTOTYPES["rnnwf_renyi2_regions"]          # docs/renyi_stack.md
 PROTOTYPES["rnnwf_pauli_step_lstm"] = PROTOTYPES["rnnwf_pauli_step"]                   # the LSTM cell (docs/pauli_lstm.md): likewise
 PROTOTYPES["rnnwf_renyi2_regions_lstm"] = PROTOTYPES["rnnwf_renyi2_regions_stack"]     # docs/renyi_lstm.md
+PROTOTYPES["rnnwf_correlations_lstm"] = PROTOTYPES["rnnwf_correlations"]               # docs/correlations_lstm.md
 PROTOTYPES["rnnwf_lstm_pauli_gradient_step"] = (C.c_int, [_P, _I32P, _I32P, _F64P, _I32, _I64, _U64, _U64, _I64, _F64P, _F64P, _I32P, _F64P])
 PROTOTYPES["rnnwf_lstm_train_steps"] = PROTOTYPES["rnnwf_train_steps"]                 # the LSTM's device-resident Adam (docs/lstm.md): likewise
 PROTOTYPES["rnnwf_lstm_pauli_train_steps"] = PROTOTYPES["rnnwf_pauli_train_steps"]
@@ -777,6 +778,17 @@ class NativeWavefunction:
         """Sums of the diagonal and off-diagonal two-point functions over ns chains (rnnwf_correlations).  samples: (ns, N) int32;
         None: drawn on the device as sample(ns, seed, step, sample_offset) draws them.  Returns dict(z_sums=(N,), zz_sums=(N, N),
         x_sums=(N, 2), xx_sums=(N, N, 5), log_ratio=(N + N(N-1)/2, ns)?, samples=(ns, N)?); see include/rnnwf.h for the entries."""
+        return self._correlations_call("rnnwf_correlations", ns, samples, seed, step, sample_offset, want_log_ratio, want_samples)
+
+    def correlations_lstm(self, ns, samples=None, seed=0, step=0, sample_offset=0, want_log_ratio=False, want_samples=False):
+        """correlations for the LSTM wave function (rnnwf_correlations_lstm, docs/correlations_lstm.md): model LSTM1D_F64.  Sites are
+        the chain position, the column of samples (ns, N).  samples: (ns, N) or (ns, Nx, Ny) int32, as pauli_step_lstm takes them;
+        None: drawn on the device as sample(ns, seed, step, sample_offset) draws them.  Returns what correlations returns; a batch of
+        lstm_load_batch does not survive the call."""
+        return self._correlations_call("rnnwf_correlations_lstm", ns, samples, seed, step, sample_offset, want_log_ratio, want_samples)
+
+    def _correlations_call(self, entry, ns, samples, seed, step, sample_offset, want_log_ratio, want_samples):
+        """the buffers and result dict the two correlations methods share"""
         ns = int(ns)
         N = self.N
         s, sp = self._chain_samples(samples, ns, "ns")
@@ -784,10 +796,10 @@ class NativeWavefunction:
         x, xx = np.empty((N, 2), dtype=np.float64), np.empty((N, N, 5), dtype=np.float64)
         lr = np.empty((N + N * (N - 1) // 2, max(ns, 0)), dtype=np.float64) if want_log_ratio else None
         smp = np.empty((max(ns, 0), N), dtype=np.int32) if want_samples and samples is None else None
-        self._check(self.lib.rnnwf_correlations(self.h, sp, ns, int(seed), int(step), int(sample_offset), z.ctypes.data_as(_F64P),
-                                                zz.ctypes.data_as(_F64P), x.ctypes.data_as(_F64P), xx.ctypes.data_as(_F64P),
-                                                lr.ctypes.data_as(_F64P) if lr is not None else None,
-                                                smp.ctypes.data_as(_I32P) if smp is not None else None))
+        self._check(getattr(self.lib, entry)(self.h, sp, ns, int(seed), int(step), int(sample_offset), z.ctypes.data_as(_F64P),
+                                             zz.ctypes.data_as(_F64P), x.ctypes.data_as(_F64P), xx.ctypes.data_as(_F64P),
+                                             lr.ctypes.data_as(_F64P) if lr is not None else None,
+                                             smp.ctypes.data_as(_I32P) if smp is not None else None))
         out = {"z_sums": z, "zz_sums": zz, "x_sums": x, "xx_sums": xx}
         if want_log_ratio:
             out["log_ratio"] = lr

@@ -21,6 +21,8 @@
 //   corr_sums_kernel      : one block per row (site or pair): the sums over the chains, each thread a fixed stride, then a tree
 //                           (no atomics: a repeated call is bit-identical).
 //   corr_diag_kernel      : sum s_i s_j from the packed spins, in integers (exact).
+// The four kernels from the suffix sums on read CorrArgs' arrays of doubles and the packed spins alone: lstm_corr.hip runs them
+// behind the LSTM's recurrent kernels (lstm_corr_kernels.h), hence `inline`.
 // Trunk and branch run the base pass's step form (step<true>, bias last) and head on states the base pass or the trunk stored, so
 // what should cancel (zero weights; a branch whose flips do not reach the tail) cancels to rounding of the f64 sums only.
 #pragma once
@@ -153,7 +155,7 @@ __global__ void __launch_bounds__(WAVES * 64) prnn_branch_kernel(CorrArgs a) {
 }
 
 // suf [N][ns]: suf[j] = sum_{n>j} bsel[n], added from site N-1 down.  One thread per chain.
-__global__ void __launch_bounds__(kCorrThreads) corr_suffix_kernel(const double* bsel, int N, int64_t ns, double* suf) {
+inline __global__ void __launch_bounds__(kCorrThreads) corr_suffix_kernel(const double* bsel, int N, int64_t ns, double* suf) {
     const int64_t s = (int64_t)blockIdx.x * kCorrThreads + threadIdx.x;
     if (s >= ns) return;
     double acc = 0.0;
@@ -167,7 +169,7 @@ __global__ void __launch_bounds__(kCorrThreads) corr_suffix_kernel(const double*
 // log r_ij.  With x = both[i] and mid_j = sum_{i<n<j} (tsel[(i,n)] - bsel[n]), added with n ascending:
 //     log r_ij = 1/2 (((x + mid_j) + (toth[(i,j)] - bsel[j])) + (tail[(i,j)] - suf[j]))       (j = N-1: no tail term)
 //     log r_i  = 1/2 (x + mid_N)
-__global__ void __launch_bounds__(kCorrThreads) corr_assemble_kernel(CorrArgs a, const double* suf, double* lr) {
+inline __global__ void __launch_bounds__(kCorrThreads) corr_assemble_kernel(CorrArgs a, const double* suf, double* lr) {
     const int N = a.N, i = blockIdx.y;
     const int64_t ns = a.ns, s = (int64_t)blockIdx.x * kCorrThreads + threadIdx.x;
     if (s >= ns) return;
@@ -187,7 +189,7 @@ __global__ void __launch_bounds__(kCorrThreads) corr_assemble_kernel(CorrArgs a,
 // one block per row of lr.  Row i < N: x_sums[i] = {sum r_i, sum r_i^2}.  Row N + pair_index(i, j): xx_sums[i][j] = {sum r_ij,
 // sum r_ij^2, sum r_ij r_i, sum r_ij r_j, sum r_i r_j}.  Thread t adds chains t, t + 256, ... in that order, then a binary tree over
 // the 256 threads.  exp of log r > 709 is +inf, and so are the sums it enters (docs/correlations.md).
-__global__ void __launch_bounds__(kCorrThreads) corr_sums_kernel(const double* lr, int N, int64_t ns, double* x_sums, double* xx_sums) {
+inline __global__ void __launch_bounds__(kCorrThreads) corr_sums_kernel(const double* lr, int N, int64_t ns, double* x_sums, double* xx_sums) {
     __shared__ double red[5][kCorrThreads];
     const int64_t row = blockIdx.x;
     double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
@@ -235,7 +237,7 @@ __global__ void __launch_bounds__(kCorrThreads) corr_sums_kernel(const double* l
 
 // grid (N, N): block (j, i), j >= i (the others return): zz[i][j] = zz[j][i] = sum_s s_i s_j = ns - 2 #{s: sigma_i != sigma_j}, and
 // from the diagonal block z[i] = 2 #{s: sigma_i = 1} - ns.  Integer counts: exact, whatever the order.
-__global__ void __launch_bounds__(kCorrThreads) corr_diag_kernel(const uint32_t* bits, int N, int64_t ns, double* z, double* zz) {
+inline __global__ void __launch_bounds__(kCorrThreads) corr_diag_kernel(const uint32_t* bits, int N, int64_t ns, double* z, double* zz) {
     __shared__ long long red[kCorrThreads];
     const int j = blockIdx.x, i = blockIdx.y;
     if (j < i) return;

@@ -1,5 +1,6 @@
 // lstm_observable.h - what the host drivers of the observable passes of the LSTM wave function share: rnnwf_pauli_step_lstm and
-// rnnwf_lstm_pauli_gradient_step (lstm_pauli.hip), rnnwf_renyi2_regions_lstm (lstm_renyi.hip).  The launch class of a width, the walk
+// rnnwf_lstm_pauli_gradient_step (lstm_pauli.hip), rnnwf_renyi2_regions_lstm (lstm_renyi.hip), rnnwf_correlations_lstm (lstm_corr.hip,
+// which derives its own launch class from this one).  The launch class of a width, the walk
 // over the LSTM's table, the size of a checkpoint row and the refusals.  All serve LSTM1D_F64 (one layer, 1..68 units, float64, raster
 // path); kernels in lstm_pauli_kernels.h.  Each .hip instantiates its own kernels, under its own flags.
 #pragma once
@@ -43,12 +44,21 @@ inline size_t hck_bytes_per_block(const rnnwf_handle* h) {
 }
 
 // which entries a refusal names to a handle of another model
-enum class LstmEntryKind { Pauli, Renyi };
+enum class LstmEntryKind { Pauli, Renyi, Corr };
 
 // 0, or RNNWF_ERR_INVALID "<entry>: ..." for a handle these entries do not serve, naming the entry that does.  Called before
 // anything is touched.
 inline int lstm_pauli_refuse(rnnwf_handle* h, const char* entry, LstmEntryKind kind = LstmEntryKind::Pauli) {
     const bool renyi = kind == LstmEntryKind::Renyi;
+    if (h->model != RNNWF_MODEL_LSTM1D_F64 && kind == LstmEntryKind::Corr) {
+        // rnnwf_correlations is the one other all-pair pass: it serves the positive GRU models with one layer
+        const bool gru = h->model == RNNWF_MODEL_GRU1D || h->model == RNNWF_MODEL_GRU1D_F64;
+        const char* other = gru ? (h->NL > 1 ? "no all-pair correlation pass serves stacked GRU layers (rnnwf_correlations: one GRU layer)"
+                                             : "rnnwf_correlations serves the one-layer GRU models")
+                                : "no all-pair correlation pass serves this model (rnnwf_correlations: the one-layer GRU models)";
+        return h->fail(RNNWF_ERR_INVALID, "%s: serves the LSTM cell (LSTM1D_F64) only, this handle's model is %s; %s", entry,
+                       model_name(h->model), other);
+    }
     if (h->model != RNNWF_MODEL_LSTM1D_F64) {
         const char* other = renyi ? "no region-Renyi pass serves the parity model" : "no Pauli pass serves the parity model";
         switch (h->model) {

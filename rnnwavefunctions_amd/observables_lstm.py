@@ -12,6 +12,10 @@ The second Renyi entropy of arbitrary regions, block entropies and the Renyi-2 m
 observables.py (rnnwf_renyi2_regions_lstm; docs/renyi_lstm.md): renyi2_regions, renyi2_entropy, renyi2_mutual_information, with
 observables.py's region builders re-exported.  observables.renyi2_regions / renyi2_mutual_information keep refusing the LSTM.
 
+Every site and every pair at once (rnnwf_correlations_lstm; docs/correlations_lstm.md): correlation_matrix, the trunk / branch pass
+that observables.correlations runs for the GRU, and structure_factor of one of its matrices.  `correlations` below stays the
+pair-list form on pauli_step_lstm.
+
 Not here: minSR (docs/lstm.md, "Out of scope").  Device-resident Adam on a Hamiltonian is training_lstm.minimize_hamiltonian_device
 (docs/lstm.md, "Device-resident training"); minimize_hamiltonian below keeps refusing device_steps.
 """
@@ -20,6 +24,7 @@ import numpy as np
 from . import _lib
 from . import _observable_api as _api
 from .observables import Hamiltonian, _native, pauli_terms, tfim_hamiltonian, xxz_hamiltonian  # noqa: F401
+from .observables import correlations_from_sums  # noqa: F401
 from .observables import _disjoint_masks, column_cut_regions, interval_region, rectangle_region, renyi2_from_sums  # noqa: F401
 
 # tests/test_lstm_pauli_host.py pins this list; the Renyi functions and the re-exported region builders below are public all the same
@@ -27,6 +32,8 @@ from .observables import _disjoint_masks, column_cut_regions, interval_region, r
 __all__ = ["pauli_expectations", "energy", "correlations", "minimize_hamiltonian"]
 RENYI_API = ["renyi2_regions", "renyi2_entropy", "renyi2_mutual_information", "interval_region", "rectangle_region", "column_cut_regions",
              "renyi2_from_sums"]
+# likewise outside __all__: the all-pair correlation pass (docs/correlations_lstm.md)
+CORRELATION_API = ["correlation_matrix", "structure_factor", "correlations_from_sums"]
 
 _SERVED_BY = {
     _lib.MODEL_GRU1D: "observables.py serves the GRU models (observables_stack.py their stacked layers)",
@@ -120,3 +127,33 @@ def correlations(wf, numsamples, pairs=None, seed=111, step=0, samples=None):
     std / sqrt(n) (population variance) of the per-sample values s_k, r_k = exp(log r_k), s_a s_b, r_ab, which the call returns as
     log-ratios and samples; connected parts to first order (delta method), as observables_2d.correlations."""
     return _api.correlations(_api.LSTM, _native_lstm(wf), numsamples, pairs, seed, step, samples)
+
+
+# ---- every site and pair at once (rnnwf_correlations_lstm, docs/correlations_lstm.md) --------------------------------------------
+
+def correlation_matrix(wf, numsamples, seed=111, step=0, samples=None):
+    """<sz_i>, <sz_i sz_j>, <sx_i>, <sx_i sx_j> of every site and every pair and the connected two-point functions, with standard
+    errors (the connected ones' by the delta method, from cross moments reduced on the device), from `numsamples` samples in one
+    correlations_lstm call: the dict of observables.correlations_from_sums - z, x (N,); zz, xx, zz_c, xx_c (N, N); "<name>_err" for
+    each.  Sites by chain position: the raster index ny * Nx + nx, the column of a (ns, Nx * Ny) sample.  samples: (numsamples, N) or
+    (numsamples, Nx, Ny) spins; None draws them on the device from (seed, step)."""
+    nat = _native_lstm(wf)
+    out = nat.correlations_lstm(int(numsamples), samples=samples, seed=seed, step=step)
+    return correlations_from_sums(out["z_sums"], out["zz_sums"], out["x_sums"], out["xx_sums"], numsamples)
+
+
+def structure_factor(corr, qx, qy, Nx, Ny):
+    """S(q) = (1 / N) sum_{jk} exp(i q . (r_j - r_k)) C_jk of an (N, N) matrix `corr` over the sites of correlation_matrix (for
+    instance its "zz_c" or "xx_c"), N = Nx Ny, site n at (nx, ny) = (n mod Nx, n div Nx).  qx, qy: one wave vector or arrays of
+    them (broadcast against each other).  Returns S(q) in their shape: real for a real symmetric `corr`, complex otherwise."""
+    c = np.asarray(corr)
+    N = int(Nx) * int(Ny)
+    if c.shape != (N, N):
+        raise ValueError("corr must have shape (%d, %d) = (Nx Ny, Nx Ny), got %r" % (N, N, c.shape))
+    qx, qy = np.broadcast_arrays(np.asarray(qx, dtype=np.float64), np.asarray(qy, dtype=np.float64))
+    n = np.arange(N)
+    phase = np.exp(1j * (qx[..., None] * (n % int(Nx)) + qy[..., None] * (n // int(Nx))))      # (..., N): exp(i q . r_n)
+    sq = np.einsum("...j,jk,...k->...", phase, c, phase.conj()) / N
+    if np.isrealobj(c) and np.array_equal(c, c.T):
+        sq = sq.real
+    return sq[()] if sq.ndim == 0 else sq
